@@ -2,7 +2,7 @@
 """Headline benchmark: full-batch R-GCN epoch time (ms) + stacked-CSR SpMM HBM GB/s on the
 AM-shaped synthetic graph (BASELINE.json `metric`).
 
-    python bench.py --gpus 1 --steps 20 --warmup 3
+    python bench.py --gpus 1 --steps 20 --warmup 3 [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -10,6 +10,11 @@ One "step" = one epoch = forward (2 R-GCN layers), cross-entropy on the labelled
 backward, clip_grad_norm_(1.0), Adam — mrgcn/tasks/node_classification.py:166-193 — with all
 inputs resident in HBM.  N > 1 runs N independent replicas of the same epoch (the AM graph
 and its optimizer state fit one MI355X several times over; see DESIGN.md "multi-GPU").
+
+A plain run sets up, warms up, times the K steps and prints the line: `value` = `ms_per_step` = the epoch time of
+those K steps.  `--full` adds every other measurement of the line (SpMM roofline, seeds 0-2 whose median then becomes
+`value`, side workloads, reference loops, yardsticks, CPU baseline, the partitioned probes of N > 1).
+`--dump-outputs DIR` writes what the last timed step left its caller (loss, trained parameters) as .npy files.
 """
 from __future__ import annotations
 
@@ -88,7 +93,46 @@ def parse():
     ap.add_argument("--no-side-workloads", dest="side_workloads", action="store_false",
                     help="skip extra.workloads (fb15k, synth10m, aifb, mutag, AM ref_int8, AM bf16 as compact records; "
                          "default AM run only)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the timed steps as well: roofline, seeds 0-2 (their median becomes `value`), "
+                         "side workloads, reference loops, yardsticks, CPU baseline, partitioned probes (the --no-* "
+                         "switches above select among them).  Off: the line carries the timed steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one left its caller (the loss and the trained "
+                         "parameters; a fixed, seeded sample of a large one) as DIR/<name>.npy in float32")
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return a
+
+
+DUMP_SAMPLE = 1 << 20           # elements written of a larger parameter (a fixed, seeded choice of positions)
+DUMP_BUDGET = 64 << 20          # bytes written by --dump-outputs at most
+
+
+def dump_outputs(out_dir, loss, named_params):
+    """--dump-outputs: the loss of the last timed step and the parameters it left, as float32 .npy files.  A parameter
+    of more than DUMP_SAMPLE elements is written as DUMP_SAMPLE draws of its flattened positions (sorted, duplicates
+    dropped) from a generator seeded by its name and size: the same positions in every run and every build."""
+    import zlib
+
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"loss": loss.detach().float().reshape(1)}
+    for name, p in named_params:
+        flat = p.detach().reshape(-1)
+        if flat.numel() > DUMP_SAMPLE:
+            rng = np.random.default_rng(zlib.crc32(f"{name}:{flat.numel()}".encode()))
+            pos = np.unique(rng.integers(0, flat.numel(), DUMP_SAMPLE, dtype=np.int64))
+            flat = flat[torch.from_numpy(pos).to(flat.device)]
+        arrays["param." + name] = flat.float()
+    total = 0
+    for name, t in arrays.items():
+        a = t.cpu().numpy()
+        total += a.nbytes
+        if total > DUMP_BUDGET:
+            raise RuntimeError(f"--dump-outputs: more than {DUMP_BUDGET >> 20} MB at {name}")
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def event_time_ms(fn, iters, stream_ptr):
@@ -903,13 +947,17 @@ def main_lp(args, emit=True):
     mdist.barrier(dev)
     dt = mdist.max_over_ranks(time.perf_counter() - t0, dev)
     ms_per_step = dt / args.steps * 1e3
+    if args.dump_outputs and rank == 0 and emit:
+        dump_outputs(args.dump_outputs, loss, model.named_parameters())
     out = None
     if rank == 0:
-        # the encoder's stacked-CSR product at this shape: rows of 800 bytes, the wide-row kernel (k_spmm<G = 64>)
-        roofline = spmm_roofline(plan, H, "f32", args.spmm_iters, dev, "fb15k", args.scale)
-        ach = roofline["achieved"]
+        roofline = ach = None
+        if args.full:
+            # the encoder's stacked-CSR product at this shape: rows of 800 bytes, the wide-row kernel (k_spmm<G = 64>)
+            roofline = spmm_roofline(plan, H, "f32", args.spmm_iters, dev, "fb15k", args.scale)
+            ach = roofline["achieved"]
         extra = {}
-        if not partitioned:
+        if not partitioned and args.full:
             with torch.no_grad():
                 emb = model(None, A)
                 rel = model.relations
@@ -927,7 +975,7 @@ def main_lp(args, emit=True):
                          rank_raw_tflops=flop / (t2 - t1) / 1e12, mrr_raw=lp.mrr_hits(raw)[0],
                          mrr_filtered=lp.mrr_hits(flt)[0])
         cpu = None
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             try:
                 cpu = lp_cpu_baseline(args, sh, train_frac)
             except Exception as e:  # noqa: BLE001
@@ -1291,6 +1339,8 @@ def main():
     dt = mdist.max_over_ranks(time.perf_counter() - t0, dev)  # replicas: the slowest rank's time
     ms_per_step = dt / args.steps * 1e3
     final_loss = float(loss)
+    if args.dump_outputs and rank == 0:   # (before --full's legs: some of them train the live model further)
+        dump_outputs(args.dump_outputs, loss, live["model"].named_parameters())
 
     def measure_roofline():
         # ---- roofline of the dominant sparse kernel: the stacked-CSR SpMM of layer 0 ----
@@ -1309,14 +1359,14 @@ def main():
             rf = lo
         return rf
     # (with several ranks the replica's model is dropped before the big partition probe: rank 0 measures first)
-    early_roofline = measure_roofline() if (rank == 0 and world > 1 and "plan" in live) else None
+    early_roofline = measure_roofline() if (args.full and rank == 0 and world > 1 and "plan" in live) else None
     if world > 1:
         barrier()
 
     # --gpus N on a replica workload: the node-partitioned engine on the same graph (and on the 10 M-node graph),
     # every rank takes part; a failure (RCCL, memory) leaves its message and the replica line still prints
     part_records = None
-    if world > 1 and not partitioned and os.environ.get("MRGCN_BENCH_PARTITION_PROBE", "1") != "0":
+    if args.full and world > 1 and not partitioned and os.environ.get("MRGCN_BENCH_PARTITION_PROBE", "1") != "0":
         part_records = {}
         probes = [name] + (["synth10m"] if name == "am" and args.scale == 1.0 else [])
         # the probes share ONE time budget (what a hung first contact with a multi-GPU node may add to the run: the
@@ -1346,13 +1396,13 @@ def main():
         A, X, idx, tgt = live.get("A"), live.get("X"), live.get("idx"), live.get("tgt")
         if early_roofline is not None:
             roofline = early_roofline
-        elif have_model:
+        elif have_model and args.full:
             roofline = measure_roofline()
         else:
             roofline = None
         ach = roofline["achieved"] if roofline else None
         stream = torch.cuda.current_stream(dev).cuda_stream
-        if have_model and world == 1:
+        if have_model and world == 1 and args.full:
             bytes_alg_f32 = plan.spmm_bytes(F)
             dY = torch.randn((plan.num_rows, F), device=dev)
             dM = torch.empty((plan.ncols, (F + 3) // 4 * 4), device=dev)
@@ -1417,28 +1467,29 @@ def main():
                     extra["spmm_literal_error"] = str(e)[:200]
         # the roofline denominator next to what a plain device copy reaches on this
         # box, and the bytes the parameter tail of an epoch has to move
-        src = torch.empty(1 << 28, dtype=torch.float32, device=dev)  # 1 GiB
-        dst = torch.empty_like(src)
-        t_cp = event_time_ms(lambda: dst.copy_(src), 5, stream)
-        extra["device_copy_gbps"] = 2 * src.numel() * 4 / (t_cp * 1e-3) / 1e9  # read + write
-        # the same as hand-written kernels of this library, ONE-SHOT grids: a float4 copy and a 3-read / 3-write pass (Adam's
-        # shape) — the yardsticks the streaming kernels of the epoch are held against
-        lib_ = L.load()
-        t_cp = event_time_ms(lambda: L.check(lib_.mrgcn_probe_copy_f32(src.data_ptr(), dst.data_ptr(), src.numel(), stream),
-                                             "mrgcn_probe_copy_f32"), 5, stream)
-        extra["device_copy_gbps_hip"] = 2 * src.numel() * 4 / (t_cp * 1e-3) / 1e9
-        third = torch.zeros_like(src)
-        t_tr = event_time_ms(lambda: L.check(lib_.mrgcn_probe_triad_f32(src.data_ptr(), dst.data_ptr(), third.data_ptr(),
-                                                                       src.numel(), stream), "mrgcn_probe_triad_f32"), 5, stream)
-        extra["triad_gbps"] = 6 * src.numel() * 4 / (t_tr * 1e-3) / 1e9
-        # the same two as persistent grid-stride loops (round 5's yardsticks): the shape of a kernel with per-block state
-        t_cp = event_time_ms(lambda: L.check(lib_.mrgcn_probe_copy_persistent_f32(src.data_ptr(), dst.data_ptr(), src.numel(), stream),
-                                             "mrgcn_probe_copy_persistent_f32"), 5, stream)
-        extra["device_copy_gbps_hip_persistent"] = 2 * src.numel() * 4 / (t_cp * 1e-3) / 1e9
-        t_tr = event_time_ms(lambda: L.check(lib_.mrgcn_probe_triad_persistent_f32(src.data_ptr(), dst.data_ptr(), third.data_ptr(),
-                                                                                  src.numel(), stream), "mrgcn_probe_triad_persistent_f32"), 5, stream)
-        extra["triad_gbps_persistent"] = 6 * src.numel() * 4 / (t_tr * 1e-3) / 1e9
-        del src, dst, third
+        if args.full:
+            src = torch.empty(1 << 28, dtype=torch.float32, device=dev)  # 1 GiB
+            dst = torch.empty_like(src)
+            t_cp = event_time_ms(lambda: dst.copy_(src), 5, stream)
+            extra["device_copy_gbps"] = 2 * src.numel() * 4 / (t_cp * 1e-3) / 1e9  # read + write
+            # the same as hand-written kernels of this library, ONE-SHOT grids: a float4 copy and a 3-read / 3-write pass (Adam's
+            # shape) — the yardsticks the streaming kernels of the epoch are held against
+            lib_ = L.load()
+            t_cp = event_time_ms(lambda: L.check(lib_.mrgcn_probe_copy_f32(src.data_ptr(), dst.data_ptr(), src.numel(), stream),
+                                                 "mrgcn_probe_copy_f32"), 5, stream)
+            extra["device_copy_gbps_hip"] = 2 * src.numel() * 4 / (t_cp * 1e-3) / 1e9
+            third = torch.zeros_like(src)
+            t_tr = event_time_ms(lambda: L.check(lib_.mrgcn_probe_triad_f32(src.data_ptr(), dst.data_ptr(), third.data_ptr(),
+                                                                           src.numel(), stream), "mrgcn_probe_triad_f32"), 5, stream)
+            extra["triad_gbps"] = 6 * src.numel() * 4 / (t_tr * 1e-3) / 1e9
+            # the same two as persistent grid-stride loops (round 5's yardsticks): the shape of a kernel with per-block state
+            t_cp = event_time_ms(lambda: L.check(lib_.mrgcn_probe_copy_persistent_f32(src.data_ptr(), dst.data_ptr(), src.numel(), stream),
+                                                 "mrgcn_probe_copy_persistent_f32"), 5, stream)
+            extra["device_copy_gbps_hip_persistent"] = 2 * src.numel() * 4 / (t_cp * 1e-3) / 1e9
+            t_tr = event_time_ms(lambda: L.check(lib_.mrgcn_probe_triad_persistent_f32(src.data_ptr(), dst.data_ptr(), third.data_ptr(),
+                                                                                      src.numel(), stream), "mrgcn_probe_triad_persistent_f32"), 5, stream)
+            extra["triad_gbps_persistent"] = 6 * src.numel() * 4 / (t_tr * 1e-3) / 1e9
+            del src, dst, third
         if have_model:
             n_params = sum(p.numel() for p in model.parameters())
             extra["param_bytes"] = 4 * n_params * (1 + 1 + 6)  # grad write, clip read, Adam 3 reads + 3 writes
@@ -1452,7 +1503,7 @@ def main():
         torch.cuda.synchronize(dev)
         # seeds 0-2 (report the median): the headline is the seed of --seed, the others run the same
         # K steps on their own graph / labels / parameters
-        if (world == 1 and name == "am" and args.scale == 1.0 and args.seeds and not partitioned):
+        if (args.full and world == 1 and name == "am" and args.scale == 1.0 and args.seeds and not partitioned):
             seeds = {str(args.seed): ms_per_step}
             import gc
             step = plan = model = A = X = idx = tgt = None
@@ -1472,7 +1523,7 @@ def main():
             vals = sorted(v for v in seeds.values() if v is not None)
             extra["seeds_ms_per_step"] = seeds
             extra["seeds_median_ms"] = vals[len(vals) // 2] if vals else None
-        if world == 1 and name == "am" and args.scale == 1.0 and args.side_workloads and not partitioned:
+        if args.full and world == 1 and name == "am" and args.scale == 1.0 and args.side_workloads and not partitioned:
             step = plan = model = A = X = idx = tgt = None
             drop_live()
             extra["workloads"] = side_workloads(args, dev)
@@ -1483,7 +1534,7 @@ def main():
             gc.collect()
             torch.cuda.empty_cache()
         cpu = None
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             try:
                 cpu = cpu_baseline(args, name)
             except Exception as e:  # noqa: BLE001

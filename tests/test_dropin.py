@@ -26,14 +26,14 @@ def test_install_as_mrgcn_leaves_the_rest_of_the_reference_importable(order):
     assert f"dropin ok {order}" in r.stdout
 
 
-def test_install_as_mrgcn_without_a_reference_installation():
+def test_install_as_mrgcn_without_a_reference_installation(tmp_path):
     """No reference on sys.path: the leaves still import under the reference's names."""
     code = ("import sys; sys.path.insert(0, %r); import mrgcn_amd; mrgcn_amd.install_as_mrgcn();"
             "from mrgcn.models.mrgcn import MRGCN; from mrgcn.data.batch import FullBatch;"
             "import mrgcn.layers.graph as g; assert g.__name__ == 'mrgcn_amd.layers.graph';"
             "import importlib.util as u; assert u.find_spec('mrgcn.tasks') is None; print('ok')" % ROOT)
     r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300,
-                       cwd="/tmp")
+                       cwd=str(tmp_path))
     assert r.returncode == 0 and "ok" in r.stdout, r.stdout + r.stderr
 
 

@@ -256,7 +256,7 @@ def test_bench_runs_the_partitioned_engine_for_the_partitioned_workload():
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    common = ["--workload", "synth10m", "--scale", "0.002", "--steps", "3", "--warmup", "1", "--no-cpu-baseline",
+    common = ["--workload", "synth10m", "--scale", "0.002", "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline",
               "--no-literal-spmm", "--no-renumbered-extra", "--spmm-iters", "3"]
     env = dict(os.environ, MRGCN_DIST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     multi = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
@@ -300,7 +300,7 @@ def test_bench_link_prediction_workload_single_and_partitioned():
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    common = ["--workload", "fb15k", "--scale", "0.1", "--steps", "3", "--warmup", "1", "--no-cpu-baseline",
+    common = ["--workload", "fb15k", "--scale", "0.1", "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline",
               "--spmm-iters", "3"]
     single = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1"] + common,
                             capture_output=True, text=True, cwd=root, timeout=800)
@@ -336,7 +336,7 @@ def test_bench_replicas_also_run_the_partitioned_engine_in_child_processes():
     multi = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                             "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
                             os.path.join(root, "bench.py"), "--gpus", "2", "--scale", "0.02", "--steps", "2", "--warmup", "1",
-                            "--no-cpu-baseline", "--spmm-iters", "3"],
+                            "--full", "--no-cpu-baseline", "--spmm-iters", "3"],
                            capture_output=True, text=True, cwd=root, env=env, timeout=900)
     assert multi.returncode == 0, multi.stderr[-2000:]
     lines = [ln for ln in multi.stdout.splitlines() if ln.startswith("{")]

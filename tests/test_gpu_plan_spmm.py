@@ -436,7 +436,7 @@ def test_model_on_a_plan_with_replicas_matches_the_golden():
         np.testing.assert_allclose(float(loss), float(c[f"loss_step{step}"]), rtol=2e-4, atol=2e-5)
 
 
-def test_operand_order_keeps_reread_rows_off_the_straddling_slots():
+def test_operand_order_keeps_reread_rows_off_the_straddling_slots(tmp_path):
     """plan.hip::k_avoid_straddle on a graph with many multi-reader columns: the operand order stays a permutation,
     every aligned group of 32 positions holds the same columns as the plain hot / first-touch order (a local
     exchange), and no column with several readers sits on a slot whose 48-byte row straddles a 128-byte line while
@@ -472,10 +472,10 @@ def test_operand_order_keeps_reread_rows_off_the_straddling_slots():
             "from mrgcn_amd import synth, _lib as L\nfrom mrgcn_amd.plan import GraphPlan\n"
             "g = synth.make_graph('am', seed=2, scale=0.02)\nN, R = g.num_nodes, g.num_relations\n"
             "A = torch.sparse_coo_tensor(torch.from_numpy(np.stack([g.rows, g.cols])), torch.from_numpy(g.vals), (N, R * N)).cuda()\n"
-            "p = GraphPlan(A, N, R)\nnp.save('/tmp/_mpos_plain.npy', p.export(L.ARR_MPOS))\n")
+            "p = GraphPlan(A, N, R)\nnp.save(%r, p.export(L.ARR_MPOS))\n" % str(tmp_path / "mpos_plain.npy"))
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     subprocess.run([sys.executable, "-c", code], check=True, cwd=root, env=dict(os.environ, MRGCN_AVOID_STRADDLE="0"))
-    plain = np.load("/tmp/_mpos_plain.npy").astype(np.int64)
+    plain = np.load(tmp_path / "mpos_plain.npy").astype(np.int64)
     assert not np.array_equal(plain, mpos)
     assert np.array_equal(plain // 32, mpos // 32)   # every column stayed inside its group of 32
     M = torch.randn((nc, 12), device="cuda")

@@ -27,20 +27,20 @@ cp $o/spmm_pmc_fb15k.json profiles/spmm_pmc_fb15k.json
 # clocks / power beside the bench line (one sample per 0.5 s while it runs; needs nothing but read access)
 ( for i in $(seq 1 400); do rocm-smi --showclocks --showpower --csv 2>/dev/null | tr '\n' ' '; echo; sleep 0.5; done > $o/rocm_smi_during_bench.txt ) &
 smi_pid=$!
-python3 bench.py > $o/bench_line.json 2> $o/bench_line.err
+python3 bench.py --full > $o/bench_line.json 2> $o/bench_line.err
 kill $smi_pid 2>/dev/null; wait $smi_pid 2>/dev/null
-rocprofv3 --kernel-trace --stats --output-format csv -d $o/stats -o run -- python3 bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-renumbered-extra --no-reference-loop --no-seeds --no-side-workloads > $o/bench_under_rocprof.json 2> $o/bench_under_rocprof.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $o/stats -o run -- python3 bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-renumbered-extra --no-reference-loop --no-seeds --no-side-workloads > $o/bench_under_rocprof.json 2> $o/bench_under_rocprof.err
 python3 tools/prof_summary.py $o/stats 40 > $o/epoch_kernel_stats.md
 python3 tools/trace_summary.py $o/stats > $o/epoch_kernel_trace_medians.md 2>/dev/null
 python3 tools/epoch_sequence.py $o/stats "k_xform_mfma_fwd<1, false, 10" > $o/epoch_sequence.md 2>/dev/null
-bash tools/pmc_passes.sh $o/pmc_epoch all -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-renumbered-extra --no-reference-loop --no-literal-spmm --no-graph --no-seeds --no-side-workloads
+bash tools/pmc_passes.sh $o/pmc_epoch all -- python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-renumbered-extra --no-reference-loop --no-literal-spmm --no-graph --no-seeds --no-side-workloads
 for k in k_mix_fwd k_mix_bwd_sup k_dcomp k_adam_rows k_xform_mfma_fwd k_xform_cols_lds k_xform_mfma_dw "k_spmm<" k_spmm3; do
   echo "## $k"; python3 tools/pmc_summary.py $o "$k" | tail -n +3
 done > $o/epoch_pmc.md
 python3 tools/roofline_table.py $o/stats $o/bench_line.json $o > $o/kernel_roofline.md 2> $o/kernel_roofline.err
 rm -rf $o/stats $o/pmc_epoch_*/
-python3 bench.py --workload fb15k > $o/bench_fb15k.json 2> $o/bench_fb15k.err
-rocprofv3 --kernel-trace --stats --output-format csv -d $o/stats_lp -o run -- python3 bench.py --workload fb15k --steps 20 --warmup 3 --no-cpu-baseline > /dev/null 2> $o/bench_fb15k_prof.err
+python3 bench.py --full --workload fb15k > $o/bench_fb15k.json 2> $o/bench_fb15k.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $o/stats_lp -o run -- python3 bench.py --full --workload fb15k --steps 20 --warmup 3 --no-cpu-baseline > /dev/null 2> $o/bench_fb15k_prof.err
 python3 tools/epoch_sequence.py $o/stats_lp k_corrupt_triples > $o/lp_epoch_sequence.md 2>&1
 rm -rf $o/stats_lp
 # (6) the encoders' tiled product over the TCNN-M shapes: per-product rates, MFMA counters; (7) the next-rows probe
@@ -62,12 +62,12 @@ rocprofv3 --kernel-trace --output-format csv -d $o/stats_encb -o run -- python3 
 python3 tools/am_encoders_step.py summary $o/stats_encb > $o/am_encoders_step_bf16.md 2>> $o/am_encoders_step_bf16.err
 rm -rf $o/stats_encb
 # (10) the bf16 pipeline's epoch in launch order; (11) the yardstick and LDS labs (tools/lab)
-rocprofv3 --kernel-trace --stats --output-format csv -d $o/stats_bf16 -o run -- python3 bench.py --operand bf16 --steps 20 --warmup 3 --no-cpu-baseline --no-renumbered-extra --no-reference-loop --no-seeds --no-side-workloads --no-literal-spmm > $o/bench_bf16_under_rocprof.json 2> $o/bench_bf16_under_rocprof.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $o/stats_bf16 -o run -- python3 bench.py --full --operand bf16 --steps 20 --warmup 3 --no-cpu-baseline --no-renumbered-extra --no-reference-loop --no-seeds --no-side-workloads --no-literal-spmm > $o/bench_bf16_under_rocprof.json 2> $o/bench_bf16_under_rocprof.err
 python3 tools/epoch_sequence.py $o/stats_bf16 k_xform_bf16_fwd > $o/bf16_epoch_sequence.md 2>&1
 rm -rf $o/stats_bf16
 # (10b) the small graphs' replayed epochs in launch order (BASELINE configs 1 and 2: launch-bound)
 for w in aifb mutag; do
-  rocprofv3 --kernel-trace --stats --output-format csv -d $o/stats_$w -o run -- python3 bench.py --workload $w --steps 50 --warmup 5 --no-cpu-baseline --no-renumbered-extra --no-reference-loop --no-seeds --no-side-workloads --no-literal-spmm > $o/bench_${w}_under_rocprof.json 2> $o/bench_${w}_under_rocprof.err
+  rocprofv3 --kernel-trace --stats --output-format csv -d $o/stats_$w -o run -- python3 bench.py --full --workload $w --steps 50 --warmup 5 --no-cpu-baseline --no-renumbered-extra --no-reference-loop --no-seeds --no-side-workloads --no-literal-spmm > $o/bench_${w}_under_rocprof.json 2> $o/bench_${w}_under_rocprof.err
   python3 tools/epoch_sequence.py $o/stats_$w k_xent_rows shortest > $o/${w}_epoch_sequence.md 2>&1
   rm -rf $o/stats_$w
 done
@@ -78,5 +78,5 @@ python3 -m pytest tests -q -x -m "not gpu" > $o/cpu_suite.txt 2>&1; tail -2 $o/c
 ls -la $o
 # (12) the driver's multi-rank command with two ranks on this one GPU (gloo: the ranks share the device, so the times
 # are time-shared upper bounds): both partitioned engines priced, logits against the single-GPU model
-timeout 900 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 2 --steps 5 --warmup 2 --no-cpu-baseline --no-renumbered-extra --no-reference-loop --no-seeds --no-side-workloads --no-literal-spmm > $o/bench_two_ranks_one_gpu.json 2> $o/bench_two_ranks_one_gpu.err
+timeout 900 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 bench.py --full --gpus 2 --steps 5 --warmup 2 --no-cpu-baseline --no-renumbered-extra --no-reference-loop --no-seeds --no-side-workloads --no-literal-spmm > $o/bench_two_ranks_one_gpu.json 2> $o/bench_two_ranks_one_gpu.err
 ls -la $o

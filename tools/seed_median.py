@@ -21,7 +21,7 @@ def main():
     runs = []
     for seed in a.seeds:
         out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", str(a.steps), "--warmup",
-                              str(a.warmup), "--seed", str(seed), "--no-cpu-baseline", "--no-renumbered-extra",
+                              str(a.warmup), "--seed", str(seed), "--full", "--no-cpu-baseline", "--no-renumbered-extra",
                               "--no-literal-spmm", "--no-reference-loop"], capture_output=True, text=True, cwd=ROOT)
         line = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
         if out.returncode != 0 or not line:
