@@ -814,6 +814,54 @@ int mrgcn_frontier_emit(const int64_t *indptr, const int64_t *indices, const flo
                         int64_t n_neighbours, int32_t value_dtype, int64_t *out_row, int64_t *out_col,
                         void *out_val, int64_t *out_col_sliced, int64_t *neighbours, void *stream);
 
+/* ---- literal encodings of a mini-batch on the device (reference mrgcn/data/batch.py:272-316 mksubset, :25-68 pad_ /
+ * to_dense_, data/utils.py:109-152) -----------------------------------------------------------------------------------
+ * Every encoding set is resident in HBM; per batch the caller runs `rows` for all sets at once, reads its stats back
+ * ONCE, allocates, then gathers.  Nothing allocates inside; no atomics anywhere (bitwise deterministic outputs).
+ *   rows        : for every set (one block each; descriptors passed by value, 32 per launch) the members the batch's
+ *                 nodes carry.  out_pos[set, i] = ascending batch positions p with member_of_node[nodes[p]] >= 0;
+ *                 out_member[set, i] = the selected members in ascending member order (the reference's
+ *                 np.in1d(nodes_idx, common)); both [num_sets, n_nodes] int64, the first count entries of a row valid.
+ *                 stats [num_sets + 1, 4] int64: per set (count, max seq_length, max width, max extent) of the selected
+ *                 members, then (node ids outside [0, num_nodes): > 0 if any, 0, 0, 0).  An unordered set (node ids
+ *                 not ascending in member order) needs member_flags, one int32 per member, private to the call.
+ *   gather_rows : dst[i, :] = src[clamp(index[i]), :] for `count` rows of `row_bytes`, moved in pieces of `unit` bytes
+ *                 (1, 2, 4, 8 or 16; must divide row_bytes and both pointers); 32 gathers per launch.
+ *   tokens      : out [k, L] int64 (16-byte aligned): member members[i]'s tokens tokens[offsets[m] .. offsets[m+1])
+ *                 left-aligned in row i, pad_symbol beyond its length and where a token is -1.  tokens holds one
+ *                 readable entry past the last member.  Members longer than L are the caller's error to raise.
+ *   csr_dense   : out [k, C, L] float32 (16-byte aligned): row r of member members[i] is the CSR row
+ *                 row_ptr[m * (C + 1) + r] .. row_ptr[m * (C + 1) + r + 1] of (values, columns) with sorted, distinct
+ *                 columns; element (i, r, t) = the entry of column t or 0.  Every element is stored exactly once.
+ *                 values / columns hold one readable entry past the last entry. */
+typedef struct {
+  const int32_t *member_of_node; /* [num_nodes] member row of every node, -1: none */
+  const int64_t *seq_lengths;    /* [max(members, 1)] */
+  const int64_t *widths;         /* [max(members, 1)] length along the padded axis, or NULL (0) */
+  const int64_t *extents;        /* [max(members, 1)] 1 + the largest used position, or NULL (0) */
+  int32_t *member_flags;         /* [members] workspace of an unordered set, or NULL */
+  int64_t members;
+  int32_t ordered;               /* node ids ascend in member order: the batch order is the member order */
+  int32_t reserved;
+} mrgcn_literal_set;
+typedef struct {
+  const void *src;
+  void *dst;
+  const int64_t *index; /* [count] rows of src */
+  int64_t count;
+  int64_t row_bytes;
+  int64_t src_rows;
+  int32_t unit;
+  int32_t reserved;
+} mrgcn_literal_gather;
+int mrgcn_literal_rows(const mrgcn_literal_set *sets, int32_t num_sets, int64_t num_nodes, const int64_t *nodes,
+                       int64_t n_nodes, int64_t *out_member, int64_t *out_pos, int64_t *stats, void *stream);
+int mrgcn_literal_gather_rows(const mrgcn_literal_gather *gathers, int32_t num_gathers, void *stream);
+int mrgcn_literal_tokens(const int64_t *tokens, const int64_t *offsets, const int64_t *members, int64_t k, int64_t L,
+                         int64_t pad_symbol, int64_t *out, void *stream);
+int mrgcn_literal_csr_dense(const float *values, const int32_t *columns, const int64_t *row_ptr,
+                            const int64_t *members, int64_t k, int64_t C, int64_t L, float *out, void *stream);
+
 /* ---- timing helpers (HIP events on the caller's stream; used by bench.py) ------ */
 int mrgcn_event_create(void **event);
 int mrgcn_event_destroy(void *event);

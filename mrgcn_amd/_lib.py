@@ -51,6 +51,18 @@ SUPPORT_FORWARD = 1
 _p = C.c_void_p
 _i32, _i64, _u32 = C.c_int32, C.c_int64, C.c_uint32
 
+
+class LiteralSet(C.Structure):
+    """include/mrgcn_hip.h: mrgcn_literal_set (device pointers as integers)."""
+    _fields_ = [("member_of_node", _p), ("seq_lengths", _p), ("widths", _p), ("extents", _p), ("member_flags", _p),
+                ("members", _i64), ("ordered", _i32), ("reserved", _i32)]
+
+
+class LiteralGather(C.Structure):
+    """include/mrgcn_hip.h: mrgcn_literal_gather."""
+    _fields_ = [("src", _p), ("dst", _p), ("index", _p), ("count", _i64), ("row_bytes", _i64), ("src_rows", _i64),
+                ("unit", _i32), ("reserved", _i32)]
+
 # name -> (restype, argtypes); kept in one table so that tests can compare it with the header
 SIGNATURES = {
     "mrgcn_abi_version": (C.c_int, []),
@@ -166,6 +178,10 @@ SIGNATURES = {
     "mrgcn_frontier_workspace_bytes": (C.c_size_t, [_i64, _i64]),
     "mrgcn_frontier_count": (C.c_int, [_p, _p, _i64, _p, _i64, _p, _p, _p, C.c_size_t, _p]),
     "mrgcn_frontier_emit": (C.c_int, [_p, _p, _p, _i64, _p, _i64, _p, _p, _i64, _i32, _p, _p, _p, _p, _p, _p]),
+    "mrgcn_literal_rows": (C.c_int, [C.POINTER(LiteralSet), _i32, _i64, _p, _i64, _p, _p, _p, _p]),
+    "mrgcn_literal_gather_rows": (C.c_int, [C.POINTER(LiteralGather), _i32, _p]),
+    "mrgcn_literal_tokens": (C.c_int, [_p, _p, _p, _i64, _i64, _i64, _p, _p]),
+    "mrgcn_literal_csr_dense": (C.c_int, [_p, _p, _p, _p, _i64, _i64, _i64, _p, _p]),
     "mrgcn_plan_entry_relations": (C.c_int, [_p, _p, _p]),
     "mrgcn_wide_input_bwd_supported": (_i32, [_p, _i32, _i32]),
     "mrgcn_wide_input_bwd_f32": (C.c_int, [_p, _p, _p, _p, _p, _p, _i64, _p, _i64, _p, _p, _i32, _i32, _p, _p, _p]),

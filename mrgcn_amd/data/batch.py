@@ -17,6 +17,7 @@ import numpy as np
 import torch
 
 from .. import _lib as L_
+from ..stats import bump
 
 VALUE_MODES = ("ref_int8", "norm_f32")
 
@@ -51,7 +52,9 @@ def pad_token_sequences(seqs, pad_symbol=0, min_width=5):
 
 def pad_sparse_members(mats, time_dim=1, min_width=5):
     """`mats`: object array of scipy CSR matrices that differ in length along `time_dim`.  Each is
-    re-declared with that dimension = `L` (no entry moves; data/utils.py:109-133)."""
+    re-declared with that dimension = `L` (no entry moves; data/utils.py:109-133).  A member with an entry
+    at or beyond L is an error: the reference re-declares it all the same (scipy does not check the column
+    indices there), and densifying it later writes out of bounds."""
     import scipy.sparse as sp
     n = len(mats)
     longest = max((m.shape[time_dim] for m in mats), default=0)
@@ -59,6 +62,9 @@ def pad_sparse_members(mats, time_dim=1, min_width=5):
     out = np.empty(n, dtype=object)
     for i, m in enumerate(mats):
         if time_dim == 1:
+            if m.nnz and int(m.indices.max()) >= L:
+                raise ValueError(f"a member with an entry at position {int(m.indices.max())} does not fit the padded "
+                                 f"width {L}")
             out[i] = sp.csr_matrix((m.data, m.indices, m.indptr), shape=(m.shape[0], L), dtype=m.dtype)
         else:  # rows are the time axis: the row pointer grows by empty rows
             indptr = np.concatenate([m.indptr, np.full(max(L - m.shape[0], 0), m.indptr[-1], m.indptr.dtype)])
@@ -192,15 +198,16 @@ def sliceSparseCOO(t, idx):
 
 
 def mksubset(X, sample_idx):
-    """Rows / encodings of the nodes in `sample_idx`, same list structure (batch.py:272-316);
-    fixed-width (numeric array) encodings only."""
+    """Rows / encodings of the nodes in `sample_idx`, same list structure (batch.py:272-316), for fixed-width
+    arrays and object arrays (token sequences, CSR members) alike.  As in the reference, the encodings keep the set's
+    own member order while the node-id column is the sorted intersection, and a set without a member among the
+    sample becomes the placeholder `[np.empty(0)] * 3`.  `DeviceEncodings.subset` is the same on the GPU."""
+    bump("literals.host")
     X0, F = X[0], X[1:]
     X_sample = [X0[sample_idx]]
     for modality, F_set, gpu_acceleration in F:
         F_set_sample = []
         for encodings, nodes_idx, seq_lengths in F_set:
-            if getattr(encodings, "dtype", None) == np.dtype("O"):
-                raise NotImplementedError("variable-length encodings are outside mrgcn_amd's scope")
             common = np.intersect1d(nodes_idx, sample_idx)
             if len(common) <= 0:
                 F_set_sample.append([np.empty(0), np.empty(0), np.empty(0)])
@@ -257,14 +264,26 @@ class MiniBatch(Batch):
         that plan (A_BatchMasked: no slices, no per-batch plans); everything else — `X` subset to the outermost
         neighbours, `as_tensors_`, `to(devices)`, `MRGCN.forward(batch)` — is unchanged."""
         super().__init__(batch_node_idx)
+        self._x_nodes = None  # (X from a DeviceEncodings: the neighbour tensor it was subset for)
         if plan is not None:
             self.A = A_BatchMasked(plan, self.node_index, num_layers)
             if X is not None:
-                self.X = mksubset(X, self.A.neighbours[-1].cpu().numpy())
+                self.X = self._subset(X, self.A.neighbours[-1])
         elif A is not None:
             self.A = A_Batch(A, self.node_index, num_layers, value_mode=value_mode)
             if X is not None:  # not featureless: features of the outermost neighbours
-                self.X = mksubset(X, self.A.neighbours[-1])
+                self.X = self._subset(X, self.A.neighbours[-1])
+
+    def _subset(self, X, nodes):
+        """`X` a feature list: `mksubset` on the host (the neighbour ids read back first when they live on the device).
+        `X` a DeviceEncodings: the subset is built on its device, already padded, dense and as tensors (`pad_`,
+        `to_dense_` and `as_tensors_` leave it alone: its members are no object arrays and X[0] is a tensor)."""
+        if isinstance(X, DeviceEncodings):
+            if not isinstance(nodes, torch.Tensor):
+                nodes = torch.from_numpy(np.asarray(nodes, dtype=np.int64))
+            self._x_nodes = nodes.to(X.device, torch.long).contiguous()
+            return X.subset(self._x_nodes)
+        return mksubset(X, nodes.cpu().numpy() if isinstance(nodes, torch.Tensor) else nodes)
 
     def as_tensors_(self):
         super().as_tensors_()
@@ -279,6 +298,11 @@ class MiniBatch(Batch):
                     self.X[i][1][j][1] = node_idx.to(device)
                     self.X[i][1][j][2] = seq_lengths.to(device)
         self.A.to(devices["relational"])
+        nb = self.A.neighbours
+        if self._x_nodes is not None and nb and isinstance(nb[-1], torch.Tensor) and nb[-1].device == self._x_nodes.device:
+            # the outermost neighbours as the very tensor the device subset was made for (same ids): the encoding sets'
+            # batch positions refer to it, and MRGCN recognises it by identity
+            nb[-1] = self._x_nodes
         kinds = {str(d) for d in devices.values()}
         self.device = next(iter(devices.values())) if len(kinds) == 1 else "ambigious"
         return self
@@ -334,6 +358,196 @@ class DeviceCSR:
                                             val.data_ptr(), col_sl.data_ptr(), nb.data_ptr(), s),
                     "mrgcn_frontier_emit")
         return row, col, val, col_sl, nb
+
+
+def _gather_unit(row_bytes, *ptrs):
+    for u in (16, 8, 4, 2, 1):
+        if row_bytes % u == 0 and all(p % u == 0 for p in ptrs):
+            return u
+
+
+class DeviceEncodings:
+    """The feature list `X = [X0, [datatype, [[encodings, node_idx, seq_lengths], ...], gpu_flag], ...]` resident in HBM
+    (uploaded once), for mini-batches whose literal encodings are subset, padded and made dense on the GPU
+    (csrc/literals.hip).  Per encoding set it holds the node -> member-row map (int32, -1: no member) and
+      fixed-width sets   the encodings as one dense tensor
+      token sets         the tokens of all members concatenated (int64) and the member offsets
+      CSR-member sets    the members' CSR concatenated (values float32, columns, per-member row pointers) and the widths
+                         (WKT: members [C, width], padded along the columns: time_dim = 1, the TCNN's layout).
+    `subset(nodes)` returns what the host path gives after `mksubset` + `pad_(pad_symbols=...)` + `to_dense_()` +
+    `as_tensors_()` + `to(device)`: the same list structure, contents and dtypes — with one exception: CSR members
+    come out as float32 whatever their stored dtype (the encoders cast to float32 anyway).  Each set's node-id column
+    carries the set's batch positions (`_mrgcn_batch_rows`), so the model places the encoder outputs without matching
+    node ids again.  One call at a time per instance (the unordered sets share a member-flag workspace)."""
+
+    def __init__(self, X, device="cuda", pad_symbols=None, time_dim=1):
+        import scipy.sparse as sp
+        if time_dim != 1:
+            raise ValueError("DeviceEncodings pads CSR members along their columns (time_dim=1)")
+        self.device = torch.device(device)
+        if self.device.type == "cuda" and self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.pad_symbols = dict(pad_symbols or {})
+        X0 = np.ascontiguousarray(X[0])
+        self.num_nodes = int(X0.shape[0])
+        if self.num_nodes <= 0:
+            raise ValueError("X[0] has no rows")
+        self.X0 = torch.from_numpy(X0).to(self.device)
+        self.modalities, self._sets = [], []
+        for datatype, F_set, gpu_acceleration in X[1:]:
+            recs = [self._upload(datatype, enc, nidx, seq, sp) for enc, nidx, seq in F_set]
+            self.modalities.append((datatype, recs, gpu_acceleration))
+            self._sets.extend(recs)
+        from .. import _lib as L
+        self._desc = (L.LiteralSet * max(len(self._sets), 1))()
+        for i, r in enumerate(self._sets):
+            self._desc[i] = L.LiteralSet(r.map.data_ptr(), r.seq64.data_ptr(),
+                                         r.widths.data_ptr() if r.widths is not None else None,
+                                         r.extents.data_ptr() if r.extents is not None else None,
+                                         r.flags.data_ptr() if r.flags is not None else None,
+                                         r.members, int(r.ordered), 0)
+
+    def _upload(self, datatype, encodings, nodes_idx, seq_lengths, sp):
+        from types import SimpleNamespace
+        dev, N = self.device, self.num_nodes
+        nodes_idx = np.asarray(nodes_idx)
+        seq_lengths = np.asarray(seq_lengths)
+        M = len(nodes_idx)
+        if len(encodings) != M or len(seq_lengths) != M:
+            raise ValueError(f"{datatype}: encodings, node ids and seq_lengths differ in length")
+        if nodes_idx.dtype.kind != "i":   # (the node-id column of a subset is then int64, as np.intersect1d gives it)
+            raise TypeError(f"{datatype}: node ids must be signed integers, not {nodes_idx.dtype}")
+        if M and (nodes_idx.min() < 0 or nodes_idx.max() >= N):
+            raise ValueError(f"{datatype}: node ids outside [0, {N})")
+        if len(np.unique(nodes_idx)) != M:
+            raise ValueError(f"{datatype}: a node carries two members of one encoding set")
+        rec = SimpleNamespace(datatype=datatype, members=M, widths=None, extents=None, flags=None)
+        rec.ordered = bool(M < 2 or np.all(np.diff(nodes_idx) > 0))
+        mp = np.full(N, -1, dtype=np.int32)
+        mp[nodes_idx.astype(np.int64)] = np.arange(M, dtype=np.int32)
+        rec.map = torch.from_numpy(mp).to(dev)
+        if not rec.ordered:
+            rec.flags = torch.empty(M, dtype=torch.int32, device=dev)
+        one = lambda a, dt: np.concatenate([np.asarray(a, dtype=dt).reshape(-1), np.zeros(1, dtype=dt)])  # noqa: E731
+        rec.seq = torch.from_numpy(np.ascontiguousarray(seq_lengths)).to(dev)     # the column as it is stored
+        rec.seq64 = torch.from_numpy(one(seq_lengths, np.int64)).to(dev)          # (>= 1 entry, for the kernel)
+        if getattr(encodings, "dtype", None) != np.dtype("O"):
+            rec.kind = "dense"
+            rec.enc = torch.from_numpy(np.ascontiguousarray(encodings)).to(dev)
+            return rec
+        if M and sp.issparse(encodings[0]):
+            rec.kind = "csr"
+            mats = [sp.csr_matrix(m) for m in encodings]
+            C = mats[0].shape[0]
+            if any(m.shape[0] != C for m in mats):
+                raise ValueError(f"{datatype}: CSR members differ in their number of rows")
+            for i, m in enumerate(mats):
+                if not m.has_canonical_format:      # sorted, distinct columns per row (toarray() sums duplicates)
+                    m = m.copy()
+                    m.sum_duplicates()
+                    mats[i] = m
+            nnz = np.asarray([m.nnz for m in mats], dtype=np.int64)
+            start = np.concatenate([[0], np.cumsum(nnz)[:-1]])
+            rowptr = np.stack([m.indptr.astype(np.int64) for m in mats]) + start[:, None]
+            rec.C = int(C)
+            rec.rowptr = torch.from_numpy(np.ascontiguousarray(rowptr)).to(dev)
+            rec.values = torch.from_numpy(one(np.concatenate([m.data for m in mats]), np.float32)).to(dev)
+            rec.columns = torch.from_numpy(one(np.concatenate([m.indices for m in mats]), np.int32)).to(dev)
+            widths = np.asarray([m.shape[1] for m in mats], dtype=np.int64)
+            extents = np.asarray([int(m.indices.max()) + 1 if m.nnz else 0 for m in mats], dtype=np.int64)
+        else:
+            rec.kind = "tokens"
+            seqs = [np.asarray(a).reshape(-1) for a in encodings]
+            widths = np.asarray([len(a) for a in seqs], dtype=np.int64)
+            extents = widths
+            rec.offsets = torch.from_numpy(np.concatenate([[0], np.cumsum(widths)]).astype(np.int64)).to(dev)
+            flat = np.concatenate(seqs) if M else np.zeros(0, dtype=np.int64)
+            rec.tokens = torch.from_numpy(one(flat, np.int64)).to(dev)
+        rec.widths = torch.from_numpy(one(widths, np.int64)).to(dev)
+        rec.extents = torch.from_numpy(one(extents, np.int64)).to(dev)
+        return rec
+
+    def subset(self, nodes):
+        """The feature list of the nodes `nodes` (a mini-batch's outermost neighbours: ascending, distinct, int64 —
+        on the device, no host copy is made of them), as `mksubset` + `pad_` + `to_dense_` + `as_tensors_` + `to`
+        give it.  One host synchronisation: the per-set counts and widths, read back together."""
+        from .. import _lib as L
+        lib = L.load()
+        dev = self.device
+        if not isinstance(nodes, torch.Tensor):
+            nodes = torch.from_numpy(np.asarray(nodes, dtype=np.int64))
+        nodes = nodes.to(dev, torch.long).contiguous()          # (the same tensor when it already is one)
+        n, S = int(nodes.numel()), len(self._sets)
+        out_member = torch.empty((S, n), dtype=torch.long, device=dev)
+        out_pos = torch.empty((S, n), dtype=torch.long, device=dev)
+        st_dev = torch.empty((S + 1, 4), dtype=torch.long, device=dev)
+        s = torch.cuda.current_stream(dev).cuda_stream
+        with torch.cuda.device(dev):
+            L.check(lib.mrgcn_literal_rows(self._desc, S, self.num_nodes, nodes.data_ptr() if n else None, n,
+                                           out_member.data_ptr() if n * S else None,
+                                           out_pos.data_ptr() if n * S else None, st_dev.data_ptr(), s),
+                    "mrgcn_literal_rows")
+            st = st_dev.cpu().tolist()                                    # the one readback
+            if st[S][0] > 0:
+                raise IndexError(f"node ids outside [0, {self.num_nodes})")
+            gathers, launches = [], []
+
+            def gather(src, dst, index, count, row_bytes, src_rows):
+                if count and row_bytes:
+                    gathers.append(L.LiteralGather(src.data_ptr(), dst.data_ptr(), index.data_ptr(), count, row_bytes,
+                                                   src_rows, _gather_unit(row_bytes, src.data_ptr(), dst.data_ptr()), 0))
+
+            X0 = torch.empty((n, *self.X0.shape[1:]), dtype=self.X0.dtype, device=dev)
+            gather(self.X0, X0, nodes, n, self.X0[0].numel() * self.X0.element_size(), self.num_nodes)
+            out, slot = [X0], 0
+            for datatype, recs, gpu_acceleration in self.modalities:
+                sets = []
+                for r in recs:
+                    k, max_seq, max_w, max_e = st[slot]
+                    pos, mem = out_pos[slot, :k], out_member[slot, :k]
+                    slot += 1
+                    if k == 0:           # the reference's placeholder [np.empty(0)] * 3 (batch.py:291-300)
+                        e = [torch.empty(0, dtype=torch.float64, device=dev) for _ in range(3)]
+                        e[1]._mrgcn_batch_rows = (nodes, pos)
+                        sets.append(e)
+                        continue
+                    node_col = torch.empty(k, dtype=torch.long, device=dev)
+                    gather(nodes, node_col, pos, k, 8, n)
+                    seq_col = torch.empty(k, dtype=r.seq.dtype, device=dev)
+                    gather(r.seq, seq_col, mem, k, r.seq.element_size(), r.members)
+                    if r.kind == "dense":
+                        enc = torch.empty((k, *r.enc.shape[1:]), dtype=r.enc.dtype, device=dev)
+                        gather(r.enc, enc, mem, k, r.enc[0].numel() * r.enc.element_size(), r.members)
+                    else:
+                        # padded width (data/utils.py:109-152 with min_padded_length = max(seq_length), batch.py:36)
+                        width = max(int(max_seq), min(int(max_w), _MAX_BATCH_LENGTH))
+                        if max_e > width:
+                            raise ValueError(f"{datatype}: a member of length {int(max_e)} does not fit the padded "
+                                             f"width {width}")
+                        if r.kind == "tokens":
+                            enc = torch.empty((k, width), dtype=torch.long, device=dev)
+                            if width:
+                                launches.append(lambda r=r, mem=mem, k=k, width=width, enc=enc, dt=datatype: L.check(
+                                    lib.mrgcn_literal_tokens(r.tokens.data_ptr(), r.offsets.data_ptr(), mem.data_ptr(),
+                                                             k, width, int(self.pad_symbols.get(dt, 0)),
+                                                             enc.data_ptr(), s), "mrgcn_literal_tokens"))
+                        else:
+                            enc = torch.empty((k, r.C, width), dtype=torch.float32, device=dev)
+                            if width:
+                                launches.append(lambda r=r, mem=mem, k=k, width=width, enc=enc: L.check(
+                                    lib.mrgcn_literal_csr_dense(r.values.data_ptr(), r.columns.data_ptr(),
+                                                                r.rowptr.data_ptr(), mem.data_ptr(), k, r.C, width,
+                                                                enc.data_ptr(), s), "mrgcn_literal_csr_dense"))
+                    node_col._mrgcn_batch_rows = (nodes, pos)
+                    sets.append([enc, node_col, seq_col])
+                out.append([datatype, sets, gpu_acceleration])
+            if gathers:
+                tab = (L.LiteralGather * len(gathers))(*gathers)
+                L.check(lib.mrgcn_literal_gather_rows(tab, len(gathers), s), "mrgcn_literal_gather_rows")
+            for launch in launches:
+                launch()
+        bump("literals.device")
+        return out
 
 
 class A_BatchDevice(A_Batch):

@@ -18,6 +18,7 @@ import warnings
 import torch
 import torch.nn as nn
 
+from ..stats import bump
 from .heads import ImageCNN, Normalizer, Transformer
 from .perceptron import MLP
 from .rgcn import RGCN
@@ -251,9 +252,24 @@ class MRGCN(nn.Module):
                     continue
                 encodings, node_idx, _ = encoding_set
                 hit = cache.get((datatype, i)) if cache is not None else None
+                known = getattr(node_idx, "_mrgcn_batch_rows", None)
                 if hit is not None and hit[0] is encodings and hit[1] is node_idx and hit[2] == len(batch_idx):
                     rows, data = hit[3], hit[4]
+                elif known is not None and known[0] is batch_idx:
+                    # a subset made on the device for exactly these nodes (DeviceEncodings.subset): it carries the
+                    # batch positions of its members — the rows the two masks below would find — and every member
+                    bump("modality.rows_known")
+                    rows = known[1].to(dev)
+                    if rows.numel() == 0:
+                        rows = data = None
+                    else:
+                        data = encodings
+                        if datatype in ("xsd.string", "xsd.anyURI"):
+                            data = data.int()
+                        elif datatype != "blob.image":
+                            data = data.float()
                 else:
+                    bump("modality.isin")
                     # rows of the batch that carry this encoding (mrgcn.py:276-277, :303); in a full
                     # batch the position equals the node id
                     nidx = torch.as_tensor(node_idx)

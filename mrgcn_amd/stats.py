@@ -19,7 +19,9 @@ def stats() -> dict:
     `backward.wide_input` (which backward a fused layer ran), `weight_I.fused_rows` / `weight_I.rows` / `weight_I.dense`
     (how the node table's gradient left the layer), `loss.sparse_rows` / `loss.flagged` / `loss.plain` (how much the
     cross-entropy knew about its rows), `discovered_rows` (plain dense gradients whose rows were looked up),
-    `adam.list` / `adam.rows_fused` / `adam.rows` (row-sparse optimizer updates)."""
+    `adam.list` / `adam.rows_fused` / `adam.rows` (row-sparse optimizer updates), `literals.device` / `literals.host` (where a
+    mini-batch's literal encodings were subset: DeviceEncodings or mksubset), `modality.rows_known` / `modality.isin`
+    (per encoding set: batch positions carried by the subset, or found by matching node ids)."""
     return dict(_COUNTS)
 
 
