@@ -534,6 +534,23 @@ int mrgcn_support_mix_fwd_f32(const mrgcn_support_t *support, const float *V, co
  * scatter == 0: M[k] = table[LREL[k] * N + node(k)];  scatter != 0: table is zeroed whole, then those rows = M[k]. */
 int mrgcn_support_literal_rows_f32(const mrgcn_support_t *support, int32_t scatter, float *table, int32_t F, float *M,
                                    int64_t ldM, void *stream);
+/* The WIDE featureless input layer on a forward support (masked_wide.hip): 1 <= B <= 4 bases, 16 < F <= 256,
+ * F % 4 == 0, V node-major [N][B][F] (16-byte aligned), no compact operand M.  The reference's mini-batch
+ * link-prediction encoder (tasks/link_prediction.py:477-530 batches through rgcn.py:91-128 into graph.py:66-81:
+ * AI = A[sample] . (comp (x) weight_I), then the ReLU of rgcn.py:86-87).
+ *   _fwd_f32   Y[q] = relu?( sum over FPTR entries e of flagged row q: FVAL[e] sum_b comp[LREL[c]][b] V[node(c)][b] ),
+ *              rows by FROW rank, whole rows written (replaces mrgcn_support_mix_fwd_f32 + _spmm_fwd_f32 there).
+ *   _bwd_f32   from dY [NR] x F (rows by FROW rank, the ReLU mask already applied): dV rows of the support's nodes
+ *              (NODE_FLAGS; dense != 0 zeroes the rest of the [N][B][F] table first), dcomp [R][B] written whole and
+ *              *dV_sumsq (nullable) = ||dV||^2, all summed in a fixed order (no atomics: bitwise reproducible).
+ *              Replaces mrgcn_support_spmm_t_compact_f32 + mrgcn_support_mix_bwd_f32 for this shape family. */
+int32_t mrgcn_support_wide_supported(const mrgcn_support_t *support, int32_t B, int32_t F);
+int mrgcn_support_wide_fwd_f32(const mrgcn_support_t *support, const float *V, const float *comp, int32_t B, int32_t F,
+                               float *Y, int64_t ldY, int32_t relu, void *stream);
+int64_t mrgcn_support_wide_bwd_workspace(const mrgcn_support_t *support, int32_t B); /* floats */
+int mrgcn_support_wide_bwd_f32(const mrgcn_support_t *support, const float *dY, int64_t ldY, const float *V,
+                               const float *comp, int32_t B, int32_t F, float *dV, int32_t dense, float *dcomp,
+                               double *dV_sumsq, float *workspace, int64_t workspace_floats, void *stream);
 int32_t mrgcn_support_rel_transform_supported(const mrgcn_support_t *support, int32_t K, int32_t F, int32_t need_dX);
 int mrgcn_support_rel_transform_fwd_f32(const mrgcn_support_t *support, const float *X, int64_t ldX, int32_t x_by_node,
                                         int32_t K, const float *W, int32_t F, float *T, int64_t ldT, void *stream);

@@ -150,6 +150,11 @@ int mix_fwd_arrays(const int32_t *nptr, const int32_t *urel, const int32_t *node
 int mix_bwd_nm_arrays(const int32_t *nptr, const int32_t *urel, int64_t N, int R, int top_rel, const float *dM,
                       int64_t ldM, const float *V, const float *comp, int32_t B, int32_t F, float *dV, float *dcomp,
                       double *dV_sumsq, hipStream_t s, const uint8_t *col_live, uint8_t *node_cur);
+// dcomp[r][b] = the D [L][B] rows of relation r summed in the support's relation-major chunk order, and *sumsq (nullable)
+// = the n_parts doubles of sq_part added in a fixed order (support.hip: k_dcomp_chunks_any / k_dcomp_final); `slab`:
+// wide.n_chunks x B floats
+int support_dcomp_from_D(const ::mrgcn_support *q, const float *D, int B, float *slab, const double *sq_part,
+                         int64_t n_parts, float *dcomp, double *sumsq, hipStream_t s);
 // k_adam_rows_fused over explicit arrays (rgcn_fused.hip)
 int adam_rows_fused_arrays(const int32_t *nptr, const int32_t *urel, const uint8_t *col_live, int64_t N, int R,
                            const float *dM, int64_t ldM, const float *comp, int32_t B, int32_t F, float *param,

@@ -363,6 +363,20 @@ __global__ void k_xent_scatter_rows(const float *__restrict__ drows, const int64
 }
 
 }  // namespace
+
+int support_dcomp_from_D(const mrgcn_support *q, const float *D, int B, float *slab, const double *sq_part,
+                         int64_t n_parts, float *dcomp, double *sumsq, hipStream_t s) {
+  const mrgcn_support::Order &o = q->wide;
+  const int R = (int)q->plan->num_relations;
+  if (o.n_chunks > 0) {
+    k_dcomp_chunks_any<<<dim3((unsigned)o.n_chunks), dim3(256), 0, s>>>(o.chunk_beg, o.chunk_end, o.lperm, D, B, slab);
+    MRGCN_HIP_TRY(hipGetLastError());
+  }
+  k_dcomp_final<<<dim3((unsigned)(R + 1)), dim3(256), 0, s>>>(o.chunk_ptr, o.chunk_ids, slab, R, B, dcomp, sq_part,
+                                                             (int)n_parts, sumsq);
+  MRGCN_HIP_TRY(hipGetLastError());
+  return MRGCN_OK;
+}
 }  // namespace mrgcn
 
 extern "C" {

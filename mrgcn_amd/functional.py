@@ -756,10 +756,12 @@ def _support_of(plan, meta, F, dev):
     return plan.support_for(rf)
 
 
-def _support_weight_I_grads(owner, sup, plan, dM, ld, weight_I, comp_I, F, s):
+def _support_weight_I_grads(owner, sup, plan, dM, ld, weight_I, comp_I, F, s, wide_dY=None):
     """(d weight_I, d weight_I_comp) of the input term from dM ([L, ld] by the support's live numbers).  With a
     row-sparse consumer on the parameter (mrgcn_amd.optim / ClipAdam) d weight_I is None: the entry left on the
-    parameter (`_mrgcn_rows`) holds what the optimizer's row update reads.  (Call under torch.cuda.device.)"""
+    parameter (`_mrgcn_rows`) holds what the optimizer's row update reads.  `wide_dY`: the layer's output gradient
+    ([NR, F] by flagged-row rank, ReLU mask applied) of a wide featureless layer on a forward support — the gradients
+    then come straight from it (mrgcn_support_wide_bwd_f32) and `dM` is not used.  (Call under torch.cuda.device.)"""
     lib = L.load()
     dev = plan.device
     d_wI = None
@@ -774,7 +776,7 @@ def _support_weight_I_grads(owner, sup, plan, dM, ld, weight_I, comp_I, F, s):
         if rows is not None and rows["fresh"]:
             raise L.MrgcnError("row-sparse weight_I gradient: the layer ran twice in one train_step "
                                "(use train_step(..., row_sparse=False))")
-        fused = bool(lib.mrgcn_adam_rows_fused_supported(plan.handle, Bn, F))
+        fused = wide_dY is None and bool(lib.mrgcn_adam_rows_fused_supported(plan.handle, Bn, F))
         if rows is None or rows["shape"] != tuple(weight_I.shape) or rows["ever"].device != dev:
             rows = dict(g=None, shape=tuple(weight_I.shape), cur=None,
                         ever=torch.zeros(N_, dtype=torch.uint8, device=dev), sumsq=None, fresh=False,
@@ -793,6 +795,9 @@ def _support_weight_I_grads(owner, sup, plan, dM, ld, weight_I, comp_I, F, s):
             L.check(lib.mrgcn_support_mix_bwd_f32(
                 sup.handle, dM.data_ptr(), ld, wI.data_ptr(), comp_I.data_ptr(), Bn, F, 0, 0,
                 d_comp.data_ptr(), sq.data_ptr(), ws.data_ptr(), ws.numel(), s), "mrgcn_support_mix_bwd_f32")
+        elif wide_dY is not None:
+            sq = torch.empty((), dtype=torch.float64, device=dev)
+            _wide_bwd(sup, wide_dY, wI, comp_I, Bn, F, rows["g"], False, d_comp, sq, s)
         else:
             sq = torch.zeros((), dtype=torch.float64, device=dev)
             L.check(lib.mrgcn_support_mix_bwd_f32(
@@ -807,10 +812,24 @@ def _support_weight_I_grads(owner, sup, plan, dM, ld, weight_I, comp_I, F, s):
     else:
         bump("weight_I.dense")
         d_wI = torch.empty_like(wI)
+        if wide_dY is not None:
+            _wide_bwd(sup, wide_dY, wI, comp_I, Bn, F, d_wI, True, d_comp, None, s)
+            return d_wI, d_comp
         L.check(lib.mrgcn_support_mix_bwd_f32(
             sup.handle, dM.data_ptr(), ld, wI.data_ptr(), comp_I.data_ptr(), Bn, F, d_wI.data_ptr(), 1,
             d_comp.data_ptr(), 0, 0, 0, s), "mrgcn_support_mix_bwd_f32")
     return d_wI, d_comp
+
+
+def _wide_bwd(sup, dY, wI, comp_I, Bn, F, dV, dense, d_comp, sq, s):
+    """mrgcn_support_wide_bwd_f32: dV rows of the support's nodes (all others zeroed when `dense`), dcomp, ||dV||^2."""
+    lib = L.load()
+    ws = sup.workspace(("wide", Bn), int(lib.mrgcn_support_wide_bwd_workspace(sup.handle, Bn)))
+    L.check(lib.mrgcn_support_wide_bwd_f32(
+        sup.handle, dY.data_ptr(), dY.stride(0), wI.data_ptr(), comp_I.contiguous().data_ptr(), Bn, F, dV.data_ptr(),
+        int(dense), d_comp.data_ptr(), sq.data_ptr() if sq is not None else 0, ws.data_ptr(), ws.numel(), s),
+        "mrgcn_support_wide_bwd_f32")
+    bump("weight_I.wide_masked")
 
 
 def _support_backward_workspace(ctx, sup):
@@ -942,7 +961,18 @@ class _MaskedLayer(torch.autograd.Function):
                 L.check(lib.mrgcn_support_rel_transform_fwd_f32(sup.handle, Xc.data_ptr(), Xc.stride(0), int(x_by_node),
                                                                 Xc.shape[1], Wc.data_ptr(), F, T.data_ptr(), ld, s),
                         "mrgcn_support_rel_transform_fwd_f32")
-            if has_I:
+            wide = has_I and not has_X and comp_I is not None and _masked_wide(sup, comp_I.shape[1], F)
+            if wide:
+                # the wide featureless input layer straight from the support's forward CSR (csrc/masked_wide.hip)
+                wI, cI = weight_I.contiguous(), comp_I.contiguous()
+                L.check(lib.mrgcn_support_wide_fwd_f32(sup.handle, wI.data_ptr(), cI.data_ptr(), cI.shape[1], F,
+                                                       Y.data_ptr(), F, int(relu and bias is None), s),
+                        "mrgcn_support_wide_fwd_f32")
+                if bias is not None:
+                    Y.add_(bias)
+                    if relu:
+                        Y.relu_()
+            elif has_I:
                 wI = weight_I.contiguous()
                 M = torch.empty((Lc, ld), dtype=torch.float32, device=dev)
                 if comp_I is not None:
@@ -957,7 +987,9 @@ class _MaskedLayer(torch.autograd.Function):
             # drops the values, batch.py:258-270) — or, for a batch built with `full_batch_values`, the stored values
             # like the input term: the FULL-batch arithmetic of graph.py:93-95 restricted to the batch's receptive field
             fv = int(bool(getattr(sup, "feature_values", False)))
-            if has_I and has_X:
+            if wide:
+                pass   # (Y written above)
+            elif has_I and has_X:
                 YI = torch.empty((NR, F), dtype=torch.float32, device=dev)
                 L.check(lib.mrgcn_support_spmm_fwd_f32(sup.handle, 1, M.data_ptr(), ld, F, YI.data_ptr(), F, 0, 0, s),
                         "mrgcn_support_spmm_fwd_f32")
@@ -971,6 +1003,7 @@ class _MaskedLayer(torch.autograd.Function):
                 L.check(lib.mrgcn_support_spmm_fwd_f32(sup.handle, int(has_I or fv), (M if has_I else T).data_ptr(), ld, F,
                                                        Y.data_ptr(), F, b, int(relu), s), "mrgcn_support_spmm_fwd_f32")
         ctx.sup, ctx.plan, ctx.F, ctx.ld, ctx.relu, ctx.owner = sup, plan, F, ld, relu, owner
+        ctx.wide = wide
         ctx.x_by_node = bool(has_X and x_by_node)
         ctx.x_is_relu_out = has_X and bool(getattr(X, "_mrgcn_relu_out", False))
         ctx.has = (has_I, has_X, bias is not None)
@@ -993,7 +1026,10 @@ class _MaskedLayer(torch.autograd.Function):
         d_wI = d_comp = dX = dW = None
         Lc = max(sup.L, 1)
         with torch.cuda.device(dev):
-            if has_I:
+            if ctx.wide:
+                d_wI, d_comp = _support_weight_I_grads(ctx.owner, sup, plan, None, 0, weight_I, comp_I, F, s,
+                                                       wide_dY=dY.contiguous())
+            elif has_I:
                 dM = torch.empty((Lc, ld), dtype=torch.float32, device=dev)
                 L.check(lib.mrgcn_support_spmm_t_compact_f32(sup.handle, 1, dY.data_ptr(), dY.stride(0), F,
                                                              dM.data_ptr(), ld, s), "mrgcn_support_spmm_t_compact_f32")
@@ -1031,10 +1067,20 @@ class _MaskedLayer(torch.autograd.Function):
         return None, None, d_wI, d_comp, dX, dW, dbias, None, None
 
 
+def _masked_wide(sup, B: int, F: int) -> bool:
+    """A featureless input layer with bases this wide takes csrc/masked_wide.hip (1 <= B <= 4, 16 < F <= 256,
+    F % 4 == 0)."""
+    return F > 16 and bool(L.load().mrgcn_support_wide_supported(sup.handle, int(B), int(F)))
+
+
 def masked_layer_supported(sup, layer, K: int, need_dX: bool = False) -> bool:
-    """Can `masked_layer` run this layer?  (narrow f32 rows, the matrix-core transforms' shapes.)"""
-    if layer.outdim > 16 or getattr(layer, "operand_dtype", "f32") != "f32":
+    """Can `masked_layer` run this layer?  (narrow f32 rows and the matrix-core transforms' shapes, or a wide
+    featureless input layer with 1 to 4 bases.)"""
+    if getattr(layer, "operand_dtype", "f32") != "f32":
         return False
+    if layer.outdim > 16:
+        return bool(layer.input_layer and layer.featureless and layer.num_bases > 0
+                    and _masked_wide(sup, layer.num_bases, layer.outdim))
     if not (layer.input_layer and layer.featureless):
         return bool(L.load().mrgcn_support_rel_transform_supported(sup.handle, int(K), int(layer.outdim), int(need_dX)))
     return True

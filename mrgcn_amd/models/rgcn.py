@@ -102,8 +102,9 @@ class RGCN(nn.Module):
             need_dX = K > 0 and bool(X.requires_grad) and torch.is_grad_enabled()
             if layer.engine != "fused" or not Fn.masked_layer_supported(sup, layer, K, need_dX):
                 raise _lib.MrgcnError(
-                    f"{key}: outside the masked mini-batch pass (fused engine, out <= 16, f32 operand, matrix-core "
-                    "transform shapes: an input that wants its gradient has at most 64 columns); use "
+                    f"{key}: outside the masked mini-batch pass (fused engine, f32 operand; out <= 16 with the "
+                    "matrix-core transform shapes: an input that wants its gradient has at most 64 columns; or a "
+                    "featureless input layer with 1 to 4 bases and 16 < out <= 256, out % 4 == 0); use "
                     "data.batch.A_BatchDevice / MiniBatch for it")
             fuse_relu = isinstance(f_activation, nn.ReLU) and self.p_dropout <= 0.0
             X = Fn.masked_layer(sup, layer, None if K == 0 else X, relu=fuse_relu)

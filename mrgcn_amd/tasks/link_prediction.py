@@ -1,8 +1,9 @@
 """DistMult link-prediction decoder on the R-GCN encoder's output — the numeric core of
 `mrgcn/tasks/link_prediction.py` (scores :645-665, loss :550-554, negative sampling :247-263,
 ranks :593-643, metrics :373-420), same function names and argument meaning, computed by the
-HIP kernels of `csrc/distmult.hip` through the C ABI.  The reference's run loop, logging, TSV
-writers and mini-batch machinery are out of scope."""
+HIP kernels of `csrc/distmult.hip` through the C ABI.  The reference's mini-batch flow (mkbatches
+:477-530, train_model's batch loop :226-331, test_model :375-422) is mirrored at the end of this
+file; its run loop, logging and TSV writers are out of scope."""
 from __future__ import annotations
 
 import ctypes as C
@@ -365,3 +366,174 @@ def mrr_hits(ranks, K=(1, 3, 10)):
     """One batch's metrics as test_model computes them (link_prediction.py:403-407)."""
     r = ranks.float()
     return torch.mean(1.0 / r).item(), [float(torch.mean((ranks <= k).float())) for k in K]
+
+
+# ---- mini-batch link prediction (link_prediction.py:191-530 with gcn_batchsize > 0) -----------------------------
+def mkbatches(A, X, data, gcn_batchsize, mrr_batchsize, num_layers, plan=None):
+    """link_prediction.py:477-530: batches of the nodes that occur in `data` (`gcn_batchsize` of them each, in rising
+    id order), each batch's facts (those with a batch node as head or tail: a fact can sit in two batches) cut by
+    `np.array_split` into parts of about `mrr_batchsize` facts, every part with the sorted nodes of its facts
+    (`union1d`) and its facts remapped to positions among them.  Returns [(batch, facts)], as the reference does.
+    `plan` (the full graph's GraphPlan on the GPU): the batches are masked batches on it (`MiniBatch(plan=...)`, no row
+    slices); otherwise the reference's `MiniBatch` slices of the scipy CSR `A`.  gcn_batchsize <= 0: one FullBatch per
+    part, facts keep their global ids (:536-545)."""
+    from ..data.batch import FullBatch, MiniBatch
+    data = np.asarray(data)
+    sample_nodes = np.union1d(data[:, 0], data[:, 2])
+    num_nodes = len(sample_nodes)
+    if gcn_batchsize <= 0:
+        gcn_batchsize = num_nodes
+    if mrr_batchsize <= 0:
+        mrr_batchsize = data.shape[0]
+    batch_slices = [slice(begin, min(begin + gcn_batchsize, num_nodes)) for begin in range(0, num_nodes, gcn_batchsize)]
+    batches = []
+    if len(batch_slices) > 1:
+        for slce in batch_slices:
+            batch_node_idx = sample_nodes[slce]
+            data_mask = np.isin(data[:, 0], batch_node_idx) | np.isin(data[:, 2], batch_node_idx)
+            batch_data = data[data_mask]
+            num_samples = batch_data.shape[0]
+            for subset in np.array_split(np.arange(num_samples), max(num_samples // mrr_batchsize, 1)):
+                data_subset = np.copy(batch_data[subset])
+                subset_node_idx = np.union1d(data_subset[:, 0], data_subset[:, 2])
+                # (the reference's {node: position} map: subset_node_idx is sorted and holds every head and tail)
+                data_subset[:, 0] = np.searchsorted(subset_node_idx, data_subset[:, 0])
+                data_subset[:, 2] = np.searchsorted(subset_node_idx, data_subset[:, 2])
+                if plan is not None:
+                    batch = MiniBatch(None, X, subset_node_idx, num_layers, plan=plan)
+                else:
+                    batch = MiniBatch(A, X, subset_node_idx, num_layers)
+                batches.append((batch, data_subset))
+    else:
+        num_samples = data.shape[0]
+        for subset in np.array_split(np.arange(num_samples), max(num_samples // mrr_batchsize, 1)):
+            data_subset = np.copy(data[subset])
+            subset_node_idx = np.union1d(data_subset[:, 0], data_subset[:, 2])
+            batches.append((FullBatch(A, X, subset_node_idx), data_subset))
+    return batches
+
+
+def _embed(model, batch):
+    """The batch nodes' embeddings: `model(batch)` for an MRGCN (mrgcn.py:216-248), the R-GCN's mini-batch forward
+    on the batch structure for a bare RGCN (featureless: no X)."""
+    if hasattr(model, "rgcn"):
+        return model(batch)
+    return model(batch.X, batch.A)
+
+
+def _relations(model):
+    return model.rgcn.relations if hasattr(model, "rgcn") else model.relations
+
+
+def _batch_state(batch, facts, device):
+    """What a batch keeps on the device across epochs (built once, outside the steps): the facts, the negative
+    sampler over the batch's nodes (the remapped facts' nodes are exactly 0 .. len(node_index) - 1)."""
+    device = torch.device(device)
+    if device.type == "cuda" and device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    st = getattr(batch, "_mrgcn_lp", None)
+    if st is None or st["device"] != device:
+        if not torch.is_tensor(batch.node_index):   # (train_model :207-214: as tensors, on the device)
+            batch.as_tensors_()
+            batch.to({"relational": device})
+        f = torch.as_tensor(np.asarray(facts), dtype=torch.int64).to(device).contiguous()
+        st = dict(device=device, facts=f, sampler=DeviceNegativeSampler(f), lists=None)
+        batch._mrgcn_lp = st
+    return st
+
+
+def train_batch_step(model, batch, facts, optimizer, negatives=None, clip=1.0):
+    """One batch of train_model (link_prediction.py:226-331): 20 % of the batch's facts corrupted inside the batch
+    (half the heads, half the tails replaced by batch nodes, :239-263) — drawn on the device, or `negatives` (an
+    [n // 5, 3] array of batch-local triples, e.g. the reference's draws) —, DistMult scores of facts + negatives, BCE,
+    clip_grad_norm_(clip) and the optimizer step.  No host readback: returns the loss as a device scalar.  A
+    `mrgcn_amd.train.ClipAdam` with a max_norm clips inside its own step; any other optimizer gets
+    `mrgcn_amd.optim.clip_grad_norm_` first (torch's, unless a row-sparse weight_I gradient is among the parameters:
+    `mrgcn_amd.optim.RowSparseAdam` then steps only the node blocks of the batch and the ones that ever had
+    gradient)."""
+    from ..optim import clip_grad_norm_
+    from ..train import ClipAdam
+    E = _embed(model, batch)
+    st = _batch_state(batch, facts, E.device)
+    if negatives is None:
+        triples, labels = st["sampler"]()
+    else:
+        neg = torch.as_tensor(np.asarray(negatives), dtype=torch.int64).to(E.device)
+        triples = torch.cat([st["facts"], neg.reshape(-1, 3)])
+        labels = torch.ones(triples.shape[0], dtype=torch.float32, device=E.device)
+        labels[st["facts"].shape[0]:] = 0
+    optimizer.zero_grad()
+    loss = binary_crossentropy(score_distmult_bc(triples, E, _relations(model)), labels)
+    loss.backward()
+    if not (isinstance(optimizer, ClipAdam) and optimizer.max_norm is not None):
+        clip_grad_norm_(model.parameters(), clip)
+    optimizer.step()
+    return loss.detach()
+
+
+def prepare_batches(batches, device):
+    """Moves the batches of `mkbatches` to `device` once (train_model :207-228) and builds their device state."""
+    for batch, facts in batches:
+        _batch_state(batch, facts, device)
+    return batches
+
+
+def train_epoch(batches, model, optimizer, clip=1.0):
+    """One epoch of train_model (:226-331): every batch once, in the fixed order of `mkbatches`; the mean of the batch
+    losses (:326-331), read back once after the last step."""
+    model.train()
+    losses = [train_batch_step(model, batch, facts, optimizer, clip=clip) for batch, facts in batches]
+    return float(np.mean([float(x) for x in torch.stack(losses).cpu().numpy()])) if losses else float("nan")
+
+
+def evaluate_batches(batches, model, filtered=True):
+    """test_model (link_prediction.py:375-422): every batch's facts ranked against that batch's embeddings only
+    (mrgcn_distmult_ranks), raw and — `filtered` — filtered by the true facts of that batch (truedicts(batch facts),
+    computed once per batch and kept).  Returns (mrr, hits_at_k, rankings) as test_model does: {"raw", "flt"} means
+    over the batches of the batches' MRR and hits@{1, 3, 10} (-1 for "flt" when not `filtered`), and the ranks of all
+    batches flattened."""
+    lib = _lib.load()
+    model.eval()
+    K = [1, 3, 10]
+    hits_at_k = {"flt": [[] for _ in K], "raw": [[] for _ in K]}
+    mrr = {"flt": [], "raw": []}
+    rankings = {"flt": [], "raw": []}
+    with torch.no_grad():
+        for batch, facts in batches:
+            E = _f32_rows(_embed(model, batch).detach(), "node_embeddings")
+            Rel = _f32_rows(_relations(model).detach(), "edge_embeddings")
+            st = _batch_state(batch, facts, E.device)
+            dev = E.device
+            tr, nf, N, H = st["facts"], int(st["facts"].shape[0]), E.shape[0], E.shape[1]
+            for flt in (False, True):
+                rank_type = "flt" if flt else "raw"
+                if flt and not filtered:
+                    mrr[rank_type].append(-1)
+                    for i, _ in enumerate(K):
+                        hits_at_k[rank_type][i].append(-1)
+                    rankings[rank_type].append(-1)
+                    continue
+                lists = [None] * 4
+                if flt:
+                    if st["lists"] is None:
+                        ls = [torch.from_numpy(a).to(dev) for a in filter_lists(np.asarray(facts))]
+                        st["lists"] = [a if a.numel() else torch.zeros(1, dtype=a.dtype, device=dev) for a in ls]
+                    lists = st["lists"]
+                ranks = torch.empty(2 * nf, dtype=torch.int64, device=dev)
+                if nf:
+                    ws_bytes = lib.mrgcn_distmult_ranks_workspace(N, H, nf)
+                    ws = torch.empty((ws_bytes + 3) // 4, dtype=torch.int32, device=dev)
+                    _lib.check(lib.mrgcn_distmult_ranks(_ptr(E), E.stride(0), N, _ptr(Rel), Rel.stride(0), H, _ptr(tr),
+                                                        nf, _ptr(lists[0]), _ptr(lists[1]), _ptr(lists[2]),
+                                                        _ptr(lists[3]), _ptr(ws), ws_bytes, _ptr(ranks), _stream()),
+                               "distmult_ranks")
+                mrr[rank_type].append(torch.mean(1.0 / ranks.float()).item())
+                for i, k in enumerate(K):
+                    hits_at_k[rank_type][i].append(float(torch.mean((ranks <= k).float())))
+                rankings[rank_type].append(ranks.tolist())
+    for rank_type in ("flt", "raw"):
+        mrr[rank_type] = np.mean(mrr[rank_type])
+        hits_at_k[rank_type] = [np.mean(k) for k in hits_at_k[rank_type]]
+        rankings[rank_type] = [r for r_list in rankings[rank_type]
+                               for r in (r_list if isinstance(r_list, list) else [r_list])]
+    return mrr, hits_at_k, rankings
