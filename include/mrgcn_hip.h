@@ -551,6 +551,38 @@ int64_t mrgcn_support_wide_bwd_workspace(const mrgcn_support_t *support, int32_t
 int mrgcn_support_wide_bwd_f32(const mrgcn_support_t *support, const float *dY, int64_t ldY, const float *V,
                                const float *comp, int32_t B, int32_t F, float *dV, int32_t dense, float *dcomp,
                                double *dV_sumsq, float *workspace, int64_t workspace_floats, void *stream);
+/* The WIDE layer WITH a feature term on a forward support (masked_wide.hip, two tables; the multimodal
+ * link-prediction encoders of configs/ml100k+.toml / yago3-10+.toml in mini-batch mode), same shapes as above
+ * (mrgcn_support_wide_supported).  The feature term is reassociated through P = X . V_F (mrgcn_support_basis_xform_f32):
+ *   _fwd_f32   Y[q] = relu?( sum over FPTR entries e of q:  v_e sum_b comp[LREL[c]][b] V[node(c)][b]      (V, comp: NULL
+ *                                                                                        on a layer without input term)
+ *                                                 + w_e sum_b comp_F[LREL[c]][b] P[rank(c)][b] )
+ *              P [NL][B][F] by live-node rank (16-byte aligned), w_e = v_e when feature_values, else 1.
+ *   _bwd_f32   from dY (ReLU mask applied): dV / dcomp / *dV_sumsq exactly as mrgcn_support_wide_bwd_f32 (all NULL
+ *              without input term), dP [NL][B][F] written whole and dcomp_F [R][B] written whole; one pass over the dY
+ *              rows, fixed-order sums, no atomics. */
+int mrgcn_support_wide_feat_fwd_f32(const mrgcn_support_t *support, const float *V, const float *comp, const float *P,
+                                    const float *comp_F, int32_t feature_values, int32_t B, int32_t F, float *Y,
+                                    int64_t ldY, int32_t relu, void *stream);
+int64_t mrgcn_support_wide_feat_bwd_workspace(const mrgcn_support_t *support, int32_t B); /* floats */
+int mrgcn_support_wide_feat_bwd_f32(const mrgcn_support_t *support, const float *dY, int64_t ldY, const float *V,
+                                    const float *comp, const float *P, const float *comp_F, int32_t feature_values,
+                                    int32_t B, int32_t F, float *dV, int32_t dense, float *dcomp, double *dV_sumsq,
+                                    float *dP, float *dcomp_F, float *workspace, int64_t workspace_floats,
+                                    void *stream);
+/* The basis transform of that feature term on the matrix cores (basis_xform.hip, exact fp32):
+ *   _f32       P[l][b][f] = sum_k X[row(l)][k] V_F[b][k][f], l < NL; row(l) = LNODE[l] when x_by_node (X holds every
+ *              node), else l (X holds the live nodes by rank).  V_F [B][K][F] (the reference's weight_F), K >= 1.
+ *   _bwd_f32   dX [NL] x K (ld_dX; by rank, nullable) = sum_b dP[:, b] . V_F[b]^T and dV_F [B][K][F] (nullable) =
+ *              X^T . dP, the live nodes summed in fixed chunks and the chunks in order: no atomics. */
+int mrgcn_support_basis_xform_f32(const mrgcn_support_t *support, const float *X, int64_t ldX, int32_t x_by_node,
+                                  int32_t K, const float *V_F, int32_t B, int32_t F, float *P, void *stream);
+int64_t mrgcn_support_basis_xform_bwd_workspace(const mrgcn_support_t *support, int32_t K, int32_t B,
+                                                int32_t F); /* floats */
+int mrgcn_support_basis_xform_bwd_f32(const mrgcn_support_t *support, const float *dP, const float *X, int64_t ldX,
+                                      int32_t x_by_node, int32_t K, const float *V_F, int32_t B, int32_t F, float *dX,
+                                      int64_t ld_dX, float *dV_F, float *workspace, int64_t workspace_floats,
+                                      void *stream);
 int32_t mrgcn_support_rel_transform_supported(const mrgcn_support_t *support, int32_t K, int32_t F, int32_t need_dX);
 int mrgcn_support_rel_transform_fwd_f32(const mrgcn_support_t *support, const float *X, int64_t ldX, int32_t x_by_node,
                                         int32_t K, const float *W, int32_t F, float *T, int64_t ldT, void *stream);

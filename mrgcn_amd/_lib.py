@@ -201,6 +201,14 @@ SIGNATURES = {
     "mrgcn_support_wide_fwd_f32": (C.c_int, [_p, _p, _p, _i32, _i32, _p, _i64, _i32, _p]),
     "mrgcn_support_wide_bwd_workspace": (C.c_int64, [_p, _i32]),
     "mrgcn_support_wide_bwd_f32": (C.c_int, [_p, _p, _i64, _p, _p, _i32, _i32, _p, _i32, _p, _p, _p, _i64, _p]),
+    "mrgcn_support_wide_feat_fwd_f32": (C.c_int, [_p, _p, _p, _p, _p, _i32, _i32, _i32, _p, _i64, _i32, _p]),
+    "mrgcn_support_wide_feat_bwd_workspace": (C.c_int64, [_p, _i32]),
+    "mrgcn_support_wide_feat_bwd_f32": (C.c_int, [_p, _p, _i64, _p, _p, _p, _p, _i32, _i32, _i32, _p, _i32, _p, _p, _p,
+                                                  _p, _p, _i64, _p]),
+    "mrgcn_support_basis_xform_f32": (C.c_int, [_p, _p, _i64, _i32, _i32, _p, _i32, _i32, _p, _p]),
+    "mrgcn_support_basis_xform_bwd_workspace": (C.c_int64, [_p, _i32, _i32, _i32]),
+    "mrgcn_support_basis_xform_bwd_f32": (C.c_int, [_p, _p, _p, _i64, _i32, _i32, _p, _i32, _i32, _p, _i64, _p, _p,
+                                                    _i64, _p]),
     "mrgcn_support_rel_transform_supported": (_i32, [_p, _i32, _i32, _i32]),
     "mrgcn_support_rel_transform_fwd_f32": (C.c_int, [_p, _p, _i64, _i32, _i32, _p, _i32, _p, _i64, _p]),
     "mrgcn_support_rel_transform_bwd_compact_f32": (C.c_int, [_p, _p, _i64, _p, _i64, _i32, _i32, _p, _i32, _p, _i64, _p,

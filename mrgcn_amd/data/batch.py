@@ -259,14 +259,16 @@ class A_Batch:
 
 
 class MiniBatch(Batch):
-    def __init__(self, A=None, X=None, batch_node_idx=None, num_layers=None, value_mode="ref_int8", plan=None):
+    def __init__(self, A=None, X=None, batch_node_idx=None, num_layers=None, value_mode="ref_int8", plan=None,
+                 wide_features=False):
         """`plan` (a GraphPlan of the FULL graph on the GPU) instead of `A`: the batch structure is a masked batch on
         that plan (A_BatchMasked: no slices, no per-batch plans); everything else — `X` subset to the outermost
-        neighbours, `as_tensors_`, `to(devices)`, `MRGCN.forward(batch)` — is unchanged."""
+        neighbours, `as_tensors_`, `to(devices)`, `MRGCN.forward(batch)` — is unchanged.  `wide_features`: see
+        A_BatchMasked."""
         super().__init__(batch_node_idx)
         self._x_nodes = None  # (X from a DeviceEncodings: the neighbour tensor it was subset for)
         if plan is not None:
-            self.A = A_BatchMasked(plan, self.node_index, num_layers)
+            self.A = A_BatchMasked(plan, self.node_index, num_layers, wide_features=wide_features)
             if X is not None:
                 self.X = self._subset(X, self.A.neighbours[-1])
         elif A is not None:
@@ -608,9 +610,13 @@ class A_BatchMasked:
     `full_batch_values=True`: the feature term multiplies the adjacency's stored values like the input term does —
     not the reference's mini-batch arithmetic (its slices drop the values: batch.py:258-270) but its FULL-batch
     arithmetic (graph.py:93-95) restricted to the batch's receptive field: a batch that holds every labelled node then
-    trains exactly like the full-batch epoch while computing only the rows the loss can see."""
+    trains exactly like the full-batch epoch while computing only the rows the loss can see.
 
-    def __init__(self, plan, batch_idx, num_layers, full_batch_values=False):
+    `wide_features=True`: wide layers WITH a feature term (1 to 4 bases, 16 < out <= 256, out % 4 == 0 — the
+    multimodal link-prediction encoders) run on this batch as a masked pass too (functional._MaskedWideFeat); a batch
+    built without it refuses them as before."""
+
+    def __init__(self, plan, batch_idx, num_layers, full_batch_values=False, wide_features=False):
         from ..plan import GraphSupport
         dev = plan.device
         if plan.num_rows != plan.num_nodes:
@@ -625,6 +631,7 @@ class A_BatchMasked:
         self.supports = GraphSupport.chain(plan, flags, num_layers, forward=True) if num_layers else []
         for sup in self.supports:
             sup.feature_values = bool(full_batch_values)
+            sup.wide_features = bool(wide_features)
         self.neighbours = [sup.view(L_.SUP_LNODE).long() for sup in self.supports]
         self.row = self.supports
         # position of every batch node among the (sorted, distinct) rows the top layer computes

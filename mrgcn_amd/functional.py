@@ -756,17 +756,22 @@ def _support_of(plan, meta, F, dev):
     return plan.support_for(rf)
 
 
-def _support_weight_I_grads(owner, sup, plan, dM, ld, weight_I, comp_I, F, s, wide_dY=None):
+def _support_weight_I_grads(owner, sup, plan, dM, ld, weight_I, comp_I, F, s, wide_dY=None, wide_run=None):
     """(d weight_I, d weight_I_comp) of the input term from dM ([L, ld] by the support's live numbers).  With a
     row-sparse consumer on the parameter (mrgcn_amd.optim / ClipAdam) d weight_I is None: the entry left on the
     parameter (`_mrgcn_rows`) holds what the optimizer's row update reads.  `wide_dY`: the layer's output gradient
     ([NR, F] by flagged-row rank, ReLU mask applied) of a wide featureless layer on a forward support — the gradients
-    then come straight from it (mrgcn_support_wide_bwd_f32) and `dM` is not used.  (Call under torch.cuda.device.)"""
+    then come straight from it (mrgcn_support_wide_bwd_f32) and `dM` is not used.  `wide_run(dV, dense, d_comp, sq)`:
+    the same for a wide layer with a feature term (its backward kernel writes the input term's gradients too).
+    (Call under torch.cuda.device.)"""
     lib = L.load()
     dev = plan.device
     d_wI = None
     N_, Bn, _ = weight_I.shape
     wI = weight_I.contiguous()
+    if wide_dY is not None:
+        def wide_run(dV, dense, d_comp, sq):
+            _wide_bwd(sup, wide_dY, wI, comp_I, Bn, F, dV, dense, d_comp, sq, s)
     d_comp = torch.empty_like(comp_I)
     param = getattr(owner, "weight_I", None)
     rows = None
@@ -776,7 +781,7 @@ def _support_weight_I_grads(owner, sup, plan, dM, ld, weight_I, comp_I, F, s, wi
         if rows is not None and rows["fresh"]:
             raise L.MrgcnError("row-sparse weight_I gradient: the layer ran twice in one train_step "
                                "(use train_step(..., row_sparse=False))")
-        fused = wide_dY is None and bool(lib.mrgcn_adam_rows_fused_supported(plan.handle, Bn, F))
+        fused = wide_run is None and bool(lib.mrgcn_adam_rows_fused_supported(plan.handle, Bn, F))
         if rows is None or rows["shape"] != tuple(weight_I.shape) or rows["ever"].device != dev:
             rows = dict(g=None, shape=tuple(weight_I.shape), cur=None,
                         ever=torch.zeros(N_, dtype=torch.uint8, device=dev), sumsq=None, fresh=False,
@@ -795,9 +800,9 @@ def _support_weight_I_grads(owner, sup, plan, dM, ld, weight_I, comp_I, F, s, wi
             L.check(lib.mrgcn_support_mix_bwd_f32(
                 sup.handle, dM.data_ptr(), ld, wI.data_ptr(), comp_I.data_ptr(), Bn, F, 0, 0,
                 d_comp.data_ptr(), sq.data_ptr(), ws.data_ptr(), ws.numel(), s), "mrgcn_support_mix_bwd_f32")
-        elif wide_dY is not None:
+        elif wide_run is not None:
             sq = torch.empty((), dtype=torch.float64, device=dev)
-            _wide_bwd(sup, wide_dY, wI, comp_I, Bn, F, rows["g"], False, d_comp, sq, s)
+            wide_run(rows["g"], False, d_comp, sq)
         else:
             sq = torch.zeros((), dtype=torch.float64, device=dev)
             L.check(lib.mrgcn_support_mix_bwd_f32(
@@ -812,8 +817,8 @@ def _support_weight_I_grads(owner, sup, plan, dM, ld, weight_I, comp_I, F, s, wi
     else:
         bump("weight_I.dense")
         d_wI = torch.empty_like(wI)
-        if wide_dY is not None:
-            _wide_bwd(sup, wide_dY, wI, comp_I, Bn, F, d_wI, True, d_comp, None, s)
+        if wide_run is not None:
+            wide_run(d_wI, True, d_comp, None)
             return d_wI, d_comp
         L.check(lib.mrgcn_support_mix_bwd_f32(
             sup.handle, dM.data_ptr(), ld, wI.data_ptr(), comp_I.data_ptr(), Bn, F, d_wI.data_ptr(), 1,
@@ -1067,6 +1072,109 @@ class _MaskedLayer(torch.autograd.Function):
         return None, None, d_wI, d_comp, dX, dW, dbias, None, None
 
 
+class _MaskedWideFeat(torch.autograd.Function):
+    """A WIDE `GraphConvolution` with a feature term on a masked batch (graph.py:62-102 with A_idx): the basis form
+    P = X . V_F (csrc/basis_xform.hip, one product for all relations), then one gather over the support's forward CSR
+    with the input table V_I (input layers only) and P (csrc/masked_wide.hip, two tables).  The feature term multiplies
+    the all-ones slice (batch.py:258-270) or the stored values (`feature_values`), as _MaskedLayer does."""
+
+    @staticmethod
+    def forward(ctx, sup, F: int, weight_I, comp_I, X, V_F, comp_F, bias, relu: bool, owner=None):
+        lib = L.load()
+        plan = sup.plan
+        dev = sup.device
+        s = _stream(dev)
+        Bn, K = V_F.shape[0], V_F.shape[1]
+        Xc = X if (X.dim() == 2 and X.stride(1) == 1) else X.contiguous()
+        x_by_node = Xc.shape[0] == plan.num_nodes and sup.NL != plan.num_nodes
+        if Xc.shape[0] != sup.NL and not x_by_node:
+            raise L.MrgcnError(f"masked layer: X has {Xc.shape[0]} rows, the sample has {sup.NL} neighbours "
+                               f"(or hand over all {plan.num_nodes} rows)")
+        VFc, cF = V_F.contiguous(), comp_F.contiguous()
+        has_I = weight_I is not None
+        wI = weight_I.contiguous() if has_I else None
+        cI = comp_I.contiguous() if has_I else None
+        fv = int(bool(getattr(sup, "feature_values", False)))
+        P = torch.empty((max(sup.NL, 1), Bn, F), dtype=torch.float32, device=dev)
+        Y = torch.empty((sup.NR, F), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            L.check(lib.mrgcn_support_basis_xform_f32(sup.handle, Xc.data_ptr(), Xc.stride(0), int(x_by_node), K,
+                                                      VFc.data_ptr(), Bn, F, P.data_ptr(), s),
+                    "mrgcn_support_basis_xform_f32")
+            L.check(lib.mrgcn_support_wide_feat_fwd_f32(
+                sup.handle, wI.data_ptr() if has_I else 0, cI.data_ptr() if has_I else 0, P.data_ptr(), cF.data_ptr(),
+                fv, Bn, F, Y.data_ptr(), F, int(relu and bias is None), s), "mrgcn_support_wide_feat_fwd_f32")
+            if bias is not None:
+                Y.add_(bias)
+                if relu:
+                    Y.relu_()
+        bump("masked.wide_feat")
+        ctx.sup, ctx.F, ctx.relu, ctx.owner, ctx.fv = sup, F, relu, owner, fv
+        ctx.x_by_node, ctx.has_I, ctx.has_bias = bool(x_by_node), has_I, bias is not None
+        ctx.save_for_backward(wI, cI, Xc, VFc, cF, P, Y if relu else None)
+        return Y
+
+    @staticmethod
+    def backward(ctx, dY):
+        lib = L.load()
+        sup, F = ctx.sup, ctx.F
+        plan = sup.plan
+        wI, cI, X, V_F, comp_F, P, Y = ctx.saved_tensors
+        dev = sup.device
+        s = _stream(dev)
+        Bn, K = V_F.shape[0], V_F.shape[1]
+        dY = dY.contiguous()
+        meta = _grad_meta(dY)
+        if ctx.relu and not (meta and meta["relu_applied"]):
+            dY = relu_bwd(dY, Y)
+        dY = dY.contiguous()
+        dbias = _bias_grad(dY) if ctx.has_bias else None
+        d_wI = d_comp = dX = dVF = None
+        dP = torch.empty_like(P)
+        d_compF = torch.empty_like(comp_F)
+        ws = sup.workspace(("wide_feat", Bn), int(lib.mrgcn_support_wide_feat_bwd_workspace(sup.handle, Bn)))
+
+        def run(dV, dense, dcI, sq):
+            L.check(lib.mrgcn_support_wide_feat_bwd_f32(
+                sup.handle, dY.data_ptr(), dY.stride(0), wI.data_ptr() if dV is not None else 0,
+                cI.data_ptr() if dV is not None else 0, P.data_ptr(), comp_F.data_ptr(), ctx.fv, Bn, F,
+                dV.data_ptr() if dV is not None else 0, int(dense), dcI.data_ptr() if dV is not None else 0,
+                sq.data_ptr() if sq is not None else 0, dP.data_ptr(), d_compF.data_ptr(), ws.data_ptr(), ws.numel(),
+                s), "mrgcn_support_wide_feat_bwd_f32")
+
+        with torch.cuda.device(dev):
+            if ctx.has_I:
+                d_wI, d_comp = _support_weight_I_grads(ctx.owner, sup, plan, None, 0, wI, cI, F, s, wide_run=run)
+                bump("weight_I.wide_feat")
+            else:
+                run(None, False, None, None)
+            need_dX, need_dVF = ctx.needs_input_grad[4], ctx.needs_input_grad[5]
+            if need_dX or need_dVF:
+                if need_dX:
+                    dX = torch.empty((sup.NL, K), dtype=torch.float32, device=dev)
+                if need_dVF:
+                    dVF = torch.empty_like(V_F)
+                nws = int(lib.mrgcn_support_basis_xform_bwd_workspace(sup.handle, K, Bn, F)) if need_dVF else 0
+                xws = sup.workspace(("basis_xform", K, Bn, F), nws) if nws > 0 else None
+                L.check(lib.mrgcn_support_basis_xform_bwd_f32(
+                    sup.handle, dP.data_ptr(), X.data_ptr(), X.stride(0), int(ctx.x_by_node), K, V_F.data_ptr(), Bn, F,
+                    dX.data_ptr() if need_dX else 0, K, dVF.data_ptr() if need_dVF else 0,
+                    xws.data_ptr() if xws is not None else 0, nws, s), "mrgcn_support_basis_xform_bwd_f32")
+                if need_dX and ctx.x_by_node:  # the whole matrix wants its gradient: zeros outside the neighbours
+                    full = torch.zeros((X.shape[0], K), dtype=torch.float32, device=dev)
+                    full.index_copy_(0, sup.view(L.SUP_LNODE).long(), dX)
+                    dX = full
+        return (None, None, d_wI, d_comp, dX, dVF, d_compF if ctx.needs_input_grad[6] else None, dbias, None, None)
+
+
+def _masked_wide_feat(sup, layer) -> bool:
+    """A wide layer WITH a feature term takes _MaskedWideFeat on a batch built with `wide_features=True` (1 <= B <= 4,
+    16 < F <= 256, F % 4 == 0, f32)."""
+    return (bool(getattr(sup, "wide_features", False)) and not (layer.input_layer and layer.featureless)
+            and layer.num_bases > 0 and getattr(layer, "operand_dtype", "f32") == "f32"
+            and _masked_wide(sup, layer.num_bases, layer.outdim))
+
+
 def _masked_wide(sup, B: int, F: int) -> bool:
     """A featureless input layer with bases this wide takes csrc/masked_wide.hip (1 <= B <= 4, 16 < F <= 256,
     F % 4 == 0)."""
@@ -1079,8 +1187,9 @@ def masked_layer_supported(sup, layer, K: int, need_dX: bool = False) -> bool:
     if getattr(layer, "operand_dtype", "f32") != "f32":
         return False
     if layer.outdim > 16:
-        return bool(layer.input_layer and layer.featureless and layer.num_bases > 0
-                    and _masked_wide(sup, layer.num_bases, layer.outdim))
+        if not (layer.input_layer and layer.featureless):
+            return K >= 1 and _masked_wide_feat(sup, layer)
+        return bool(layer.num_bases > 0 and _masked_wide(sup, layer.num_bases, layer.outdim))
     if not (layer.input_layer and layer.featureless):
         return bool(L.load().mrgcn_support_rel_transform_supported(sup.handle, int(K), int(layer.outdim), int(need_dX)))
     return True
@@ -1097,9 +1206,14 @@ def masked_layer(sup, layer, X, relu: bool = False) -> torch.Tensor:
         if X is None:
             raise L.MrgcnError("masked_layer: the feature term needs X")
         Xin, W_F = X, layer.weight_F
-        if B > 0:
+        if B > 0 and not (F > 16 and _masked_wide_feat(sup, layer)):
             W_F = _BasisContract.apply(layer.weight_F_comp, W_F)
     bias = layer.b if layer.bias else None
+    if F > 16 and Xin is not None and _masked_wide_feat(sup, layer):
+        Y = _MaskedWideFeat.apply(sup, F, weight_I, comp_I, Xin, layer.weight_F, layer.weight_F_comp, bias, relu, layer)
+        if relu:
+            Y._mrgcn_relu_out = True
+        return Y
     Y = _MaskedLayer.apply(sup, F, weight_I, comp_I, Xin, W_F, bias, relu, layer)
     if relu:
         Y._mrgcn_relu_out = True

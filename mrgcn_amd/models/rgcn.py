@@ -104,8 +104,10 @@ class RGCN(nn.Module):
                 raise _lib.MrgcnError(
                     f"{key}: outside the masked mini-batch pass (fused engine, f32 operand; out <= 16 with the "
                     "matrix-core transform shapes: an input that wants its gradient has at most 64 columns; or a "
-                    "featureless input layer with 1 to 4 bases and 16 < out <= 256, out % 4 == 0); use "
-                    "data.batch.A_BatchDevice / MiniBatch for it")
+                    "featureless input layer with 1 to 4 bases and 16 < out <= 256, out % 4 == 0; a layer of "
+                    "that shape with a feature term on a batch built with wide_features=True, as "
+                    "tasks.link_prediction.mkbatches(plan=...) builds them); use data.batch.A_BatchDevice / "
+                    "MiniBatch for it")
             fuse_relu = isinstance(f_activation, nn.ReLU) and self.p_dropout <= 0.0
             X = Fn.masked_layer(sup, layer, None if K == 0 else X, relu=fuse_relu)
             if self.p_dropout > 0.0:

@@ -21,7 +21,8 @@ def stats() -> dict:
     cross-entropy knew about its rows), `discovered_rows` (plain dense gradients whose rows were looked up),
     `adam.list` / `adam.rows_fused` / `adam.rows` (row-sparse optimizer updates), `literals.device` / `literals.host` (where a
     mini-batch's literal encodings were subset: DeviceEncodings or mksubset), `modality.rows_known` / `modality.isin`
-    (per encoding set: batch positions carried by the subset, or found by matching node ids)."""
+    (per encoding set: batch positions carried by the subset, or found by matching node ids), `masked.wide_feat` /
+    `weight_I.wide_feat` (wide masked layers with a feature term, and those of them with an input term)."""
     return dict(_COUNTS)
 
 

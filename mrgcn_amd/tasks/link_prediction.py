@@ -374,8 +374,8 @@ def mkbatches(A, X, data, gcn_batchsize, mrr_batchsize, num_layers, plan=None):
     id order), each batch's facts (those with a batch node as head or tail: a fact can sit in two batches) cut by
     `np.array_split` into parts of about `mrr_batchsize` facts, every part with the sorted nodes of its facts
     (`union1d`) and its facts remapped to positions among them.  Returns [(batch, facts)], as the reference does.
-    `plan` (the full graph's GraphPlan on the GPU): the batches are masked batches on it (`MiniBatch(plan=...)`, no row
-    slices); otherwise the reference's `MiniBatch` slices of the scipy CSR `A`.  gcn_batchsize <= 0: one FullBatch per
+    `plan` (the full graph's GraphPlan on the GPU): the batches are masked batches on it (`MiniBatch(plan=...,
+    wide_features=True)`, no row slices: wide encoder layers with literal features run on it too); otherwise the reference's `MiniBatch` slices of the scipy CSR `A`.  gcn_batchsize <= 0: one FullBatch per
     part, facts keep their global ids (:536-545)."""
     from ..data.batch import FullBatch, MiniBatch
     data = np.asarray(data)
@@ -400,7 +400,7 @@ def mkbatches(A, X, data, gcn_batchsize, mrr_batchsize, num_layers, plan=None):
                 data_subset[:, 0] = np.searchsorted(subset_node_idx, data_subset[:, 0])
                 data_subset[:, 2] = np.searchsorted(subset_node_idx, data_subset[:, 2])
                 if plan is not None:
-                    batch = MiniBatch(None, X, subset_node_idx, num_layers, plan=plan)
+                    batch = MiniBatch(None, X, subset_node_idx, num_layers, plan=plan, wide_features=True)
                 else:
                     batch = MiniBatch(A, X, subset_node_idx, num_layers)
                 batches.append((batch, data_subset))
