@@ -655,6 +655,20 @@ int mrgcn_sumsq_clip_multi_f32(int32_t n_tensors, const float *const *grads, con
                                const double *const *extra, double *accum, uint32_t *ticket, float max_norm,
                                double *sumsq_out, float *coef, float *norm, int64_t *step_dev, float beta1,
                                float beta2, float *bc_dev, void *stream);
+/* The three sums above in a fixed order, for torch.use_deterministic_algorithms(True): per-block double partials of a
+ * fixed tree, added in block order by the block that arrives last; grids depend on the sizes only, never on the
+ * device.  Same results bit for bit on every run.  `partials`: device scratch of mrgcn_sumsq_det_workspace() bytes
+ * (fully written before it is read); `ticket`: a uint32 that is zero at the first call, left zero.  The _clip_ form
+ * takes the arguments of mrgcn_sumsq_clip_multi_f32 (its ticket is the same word) and `partials`. */
+int64_t mrgcn_sumsq_det_workspace(void);
+int mrgcn_sumsq_accum_det_f32(const float *x, int64_t n, double *accum, double *partials, uint32_t *ticket,
+                              void *stream);
+int mrgcn_sumsq_accum_multi_det_f32(int32_t n_tensors, const float *const *grads, const int64_t *numel, double *accum,
+                                    double *partials, uint32_t *ticket, void *stream);
+int mrgcn_sumsq_clip_multi_det_f32(int32_t n_tensors, const float *const *grads, const int64_t *numel, int32_t n_extra,
+                                   const double *const *extra, double *accum, uint32_t *ticket, float max_norm,
+                                   double *sumsq_out, float *coef, float *norm, int64_t *step_dev, float beta1,
+                                   float beta2, float *bc_dev, double *partials, void *stream);
 /* mrgcn_adam_step_f32 / _dev_f32 for <= 16 small tensors in one launch (per-tensor lr / weight_decay; bc_dev
  * nullable: host-side bias corrections from `step`). */
 int mrgcn_adam_step_multi_f32(int32_t n_tensors, float *const *params, const float *const *grads,
@@ -715,6 +729,22 @@ int mrgcn_distmult_score_bwd_sorted_f32(const float *E, int64_t ldE, const float
  * gradient w.r.t. x */
 int mrgcn_bce_logits_f32(const float *x, const float *y, int64_t n, float *loss, float *dx,
                          void *stream);
+/* Deterministic twins for torch.use_deterministic_algorithms(True): the same results, bit for bit on every run.
+ * _score_bwd_det: dE / dRel (nullable) ACCUMULATED into, every row by one owner per pass, no float atomics.
+ *   n <= 4096: one block sorts the columns itself (orders ignored, may be NULL).  Larger n: order_s / _p / _o must be
+ *   STABLE sorts of the columns (SortedTriples, mrgcn_distmult_orders; not the counting sort); runs that cross a
+ *   wave's span meet in a slab and are added in wave order.  workspace: mrgcn_distmult_bwd_det_workspace(n, H) bytes.
+ * _bce_logits_det: *loss WRITTEN (block partials added in block order; one block for n <= 8192); workspace:
+ *   mrgcn_bce_logits_det_workspace(n) bytes, unread for small n. */
+int64_t mrgcn_distmult_bwd_det_workspace(int64_t n, int32_t H);
+int mrgcn_distmult_score_bwd_det_f32(const float *E, int64_t ldE, const float *Rel, int64_t ldR, int32_t H,
+                                     const int64_t *triples, int64_t n, const float *dscores, const int64_t *order_s,
+                                     const int64_t *order_p, const int64_t *order_o, float *dE, int64_t lddE,
+                                     float *dRel, int64_t lddR, void *workspace, int64_t workspace_bytes,
+                                     void *stream);
+int64_t mrgcn_bce_logits_det_workspace(int64_t n);
+int mrgcn_bce_logits_det_f32(const float *x, const float *y, int64_t n, float *loss, float *dx, void *workspace,
+                             int64_t workspace_bytes, void *stream);
 /* compute_ranks_fast (link_prediction.py:593-643): ranks[0:nf] tail-corruption, ranks[nf:2nf]
  * head-corruption rank of every fact against all num_nodes candidates;
  * rank = #greater + round_half_even((#ties-1)/2) + 1.  Filtered ranks: per fact a sorted list

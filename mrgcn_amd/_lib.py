@@ -145,6 +145,16 @@ SIGNATURES = {
     "mrgcn_distmult_score_bwd_sorted_f32": (C.c_int, [_p, _i64, _p, _i64, _i32, _p, _i64, _p, _p, _p, _p, _p, _i64,
                                                       _p, _i64, _p]),
     "mrgcn_bce_logits_f32": (C.c_int, [_p, _p, _i64, _p, _p, _p]),
+    "mrgcn_distmult_bwd_det_workspace": (C.c_int64, [_i64, _i32]),
+    "mrgcn_distmult_score_bwd_det_f32": (C.c_int, [_p, _i64, _p, _i64, _i32, _p, _i64, _p, _p, _p, _p, _p, _i64, _p,
+                                                   _i64, _p, _i64, _p]),
+    "mrgcn_bce_logits_det_workspace": (C.c_int64, [_i64]),
+    "mrgcn_bce_logits_det_f32": (C.c_int, [_p, _p, _i64, _p, _p, _p, _i64, _p]),
+    "mrgcn_sumsq_det_workspace": (C.c_int64, []),
+    "mrgcn_sumsq_accum_det_f32": (C.c_int, [_p, _i64, _p, _p, _p, _p]),
+    "mrgcn_sumsq_accum_multi_det_f32": (C.c_int, [_i32, _p, _p, _p, _p, _p, _p]),
+    "mrgcn_sumsq_clip_multi_det_f32": (C.c_int, [_i32, _p, _p, _i32, _p, _p, _p, C.c_float, _p, _p, _p, _p, C.c_float,
+                                                 C.c_float, _p, _p, _p]),
     "mrgcn_random_subset_i64": (C.c_int, [_i64, _i64, _p, _p, _p]),
     "mrgcn_corrupt_triples_i64": (C.c_int, [_p, _i64, _p, _i64, _p, _i64, _i64, _p, _p]),
     "mrgcn_distmult_orders_workspace": (C.c_int64, [_i64]),

@@ -883,3 +883,344 @@ int mrgcn_distmult_ranks(const float *E, int64_t ldE, int64_t num_nodes, const f
 }
 
 }  // extern "C"
+
+// ---- deterministic backward and loss (torch.use_deterministic_algorithms(True)) -----------------------------------
+// Every dE / dRel row is written by ONE owner per launch, in a fixed order, with no float atomics; the loss is written,
+// not accumulated.  The host picks these entries under the flag; the kernels above stay as they are.
+//   n <= kDetSmallN  one block: a stable LDS sort of each column by (key, triple index), then every run of equal keys
+//                    summed in sorted order by the wave its first element falls to (a mini-batch step: ~70 triples).
+//   larger           stable orders from the caller (SortedTriples / mrgcn_distmult_orders).  Pass 1: a wave walks
+//                    kRun sorted triples; a run that starts and ends inside them is summed in registers and added to
+//                    its row, a run that crosses the wave's span leaves a partial row in a slab.  Pass 2: the wave in
+//                    which a crossing run starts adds its partial and those of the waves after it, in wave order.
+namespace mrgcn {
+namespace {
+
+constexpr int kDetSmallN = 4096;
+constexpr int kDetSmallTB = 1024;
+
+// a lane's four features: VEC — 4 lane .. 4 lane + 3 (H % 4 == 0, H <= 256, 16-byte rows); otherwise
+// h0 + lane + 64 k (h0 = 256 blockIdx.y)
+template <bool VEC>
+__device__ __forceinline__ void det_load(const float *__restrict__ row, int lane, int h0, int H, float v[4]) {
+  if constexpr (VEC) {
+    const f32x4d t = 4 * lane < H ? *reinterpret_cast<const f32x4d *>(row + 4 * lane) : f32x4d{0.f, 0.f, 0.f, 0.f};
+    v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
+  } else {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int h = h0 + lane + kWave * k;
+      v[k] = h < H ? row[h] : 0.f;
+    }
+  }
+}
+template <bool VEC, bool ADD>
+__device__ __forceinline__ void det_store(float *__restrict__ row, int lane, int h0, int H, const float v[4]) {
+  if constexpr (VEC) {
+    if (4 * lane < H) {
+      f32x4d *p = reinterpret_cast<f32x4d *>(row + 4 * lane);
+      f32x4d t = {v[0], v[1], v[2], v[3]};
+      if (ADD) t += *p;
+      *p = t;
+    }
+  } else {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int h = h0 + lane + kWave * k;
+      if (h < H) row[h] = ADD ? row[h] + v[k] : v[k];
+    }
+  }
+}
+
+// flags of a pass-1 wave: its last run goes on past its span and starts in it (the wave owns the run) / its span holds
+// one run that started before it and goes on after it (the run passes through)
+constexpr int32_t kDetOwner = 1, kDetThrough = 2;
+
+template <int WHICH, bool VEC>
+__global__ __launch_bounds__(kTB) void k_distmult_bwd_det_runs(
+    const float *__restrict__ E, int64_t ldE, const float *__restrict__ Rel, int64_t ldR, int H,
+    const int64_t *__restrict__ tr, const int64_t *__restrict__ order, int64_t n, const float *__restrict__ g,
+    float *__restrict__ out, int64_t ldo, float *__restrict__ slab, int32_t *__restrict__ flags,
+    int32_t *__restrict__ keys) {
+  const int lane = threadIdx.x & 63;
+  const int64_t w = (int64_t)blockIdx.x * (kTB / kWave) + (threadIdx.x >> 6);
+  const int64_t t0 = w * kRun;
+  if (t0 >= n) return;
+  const int h0 = VEC ? 0 : (int)blockIdx.y * kRunF;
+  const int cnt = (int)((n - t0 < kRun) ? n - t0 : kRun);
+  // lane l < cnt: sorted triple t0 + l; lane kRun: the one before the span, lane kRun + 1: the one after it
+  int64_t pos = lane < cnt ? t0 + lane : lane == kRun ? t0 - 1 : lane == kRun + 1 ? t0 + cnt : -1;
+  if (pos >= n) pos = -1;
+  int32_t si = 0, pi = 0, oi = 0, kk = -1;
+  float gi = 0.f;
+  if (pos >= 0) {
+    const int64_t i = order[pos];
+    si = (int32_t)tr[3 * i]; pi = (int32_t)tr[3 * i + 1]; oi = (int32_t)tr[3 * i + 2];
+    kk = WHICH == 0 ? si : WHICH == 1 ? pi : oi;
+    gi = g[i];
+  }
+  const int32_t key_prev = __builtin_amdgcn_readlane(kk, kRun), key_next = __builtin_amdgcn_readlane(kk, kRun + 1);
+  const int32_t key_first = __builtin_amdgcn_readlane(kk, 0);
+  float acc[4] = {0.f, 0.f, 0.f, 0.f};
+  int32_t cur = key_first;
+  bool first = true;
+  auto flush = [&](bool last) {
+    if (first && cur == key_prev) det_store<VEC, false>(slab + (2 * w) * (int64_t)H, lane, h0, H, acc);
+    else if (last && cur == key_next) det_store<VEC, false>(slab + (2 * w + 1) * (int64_t)H, lane, h0, H, acc);
+    else det_store<VEC, true>(out + (int64_t)cur * ldo, lane, h0, H, acc);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) acc[k] = 0.f;
+  };
+  for (int tb = 0; tb < cnt; tb += 4) {
+    float a[4][4], b[4][4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {  // four triples' rows in flight
+      const int tt = (tb + u < cnt) ? tb + u : cnt - 1;
+      const int64_t s_ = __builtin_amdgcn_readlane(si, tt), p_ = __builtin_amdgcn_readlane(pi, tt),
+                    o_ = __builtin_amdgcn_readlane(oi, tt);
+      det_load<VEC>(WHICH == 0 ? Rel + p_ * ldR : E + s_ * ldE, lane, h0, H, a[u]);
+      det_load<VEC>(WHICH == 2 ? Rel + p_ * ldR : E + o_ * ldE, lane, h0, H, b[u]);
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      if (tb + u < cnt) {  // wave uniform
+        const int32_t key = __builtin_amdgcn_readlane(kk, tb + u);
+        const float gt = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, gi), tb + u));
+        if (key != cur) {
+          flush(false);
+          first = false;
+          cur = key;
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) acc[k] += (a[u][k] * gt) * b[u][k];
+      }
+    }
+  }
+  flush(true);
+  if (lane == 0 && blockIdx.y == 0) {
+    const bool single = key_first == cur, from_prev = key_first == key_prev, to_next = cur == key_next;
+    flags[w] = (to_next && !(single && from_prev) ? kDetOwner : 0) | (single && from_prev && to_next ? kDetThrough : 0);
+    keys[w] = cur;
+  }
+}
+
+// the owner of a crossing run: its partial, then the first-run partials of the waves after it in wave order (those the
+// run passes through, and the one it ends in)
+template <bool VEC>
+__global__ __launch_bounds__(kTB) void k_distmult_bwd_det_join(int H, int64_t nw, const int32_t *__restrict__ flags,
+                                                               const int32_t *__restrict__ keys,
+                                                               const float *__restrict__ slab, float *__restrict__ out,
+                                                               int64_t ldo) {
+  const int lane = threadIdx.x & 63;
+  const int64_t w = (int64_t)blockIdx.x * (kTB / kWave) + (threadIdx.x >> 6);
+  if (w >= nw || !(flags[w] & kDetOwner)) return;
+  const int h0 = VEC ? 0 : (int)blockIdx.y * kRunF;
+  float acc[4];
+  det_load<VEC>(slab + (2 * w + 1) * (int64_t)H, lane, h0, H, acc);
+  for (int64_t v = w + 1; v < nw;) {
+    const int64_t q = v + lane;
+    const uint64_t stop = __ballot(!(q < nw && (flags[q] & kDetThrough)));
+    int m = stop ? __builtin_ctzll(stop) + 1 : kWave;  // partials to add from v on (the last one ends the run)
+    if (m > nw - v) m = (int)(nw - v);
+    for (int j = 0; j < m; j += 4) {
+      float p[4][4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) det_load<VEC>(slab + (2 * (v + (j + u < m ? j + u : m - 1))) * (int64_t)H, lane, h0, H, p[u]);
+#pragma unroll
+      for (int u = 0; u < 4; ++u)
+        if (j + u < m)
+#pragma unroll
+          for (int k = 0; k < 4; ++k) acc[k] += p[u][k];
+    }
+    if (stop) break;
+    v += kWave;
+  }
+  det_store<VEC, true>(out + (int64_t)keys[w] * ldo, lane, h0, H, acc);
+}
+
+// n <= kDetSmallN: the whole backward in one block.  Per column (s, o into dE, then p into dRel): keys (key << 32 |
+// triple) bitonic-sorted in LDS — a stable order by key —, then every run of equal keys summed in sorted order by the
+// wave whose slice holds its first element, and added to its row.
+__global__ __launch_bounds__(kDetSmallTB) void k_distmult_bwd_det_small(
+    const float *__restrict__ E, int64_t ldE, const float *__restrict__ Rel, int64_t ldR, int H,
+    const int64_t *__restrict__ tr, int n, const float *__restrict__ g, float *__restrict__ dE, int64_t lddE,
+    float *__restrict__ dRel, int64_t lddR) {
+  __shared__ uint64_t s_key[kDetSmallN];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  constexpr int kWaves = kDetSmallTB / kWave;
+  int P = 1;
+  while (P < n) P <<= 1;
+  const int per = (n + kWaves - 1) / kWaves;
+  for (int cc = 0; cc < 3; ++cc) {
+    const int c = cc == 0 ? 0 : cc == 1 ? 2 : 1;
+    float *out = c == 1 ? dRel : dE;
+    const int64_t ldo = c == 1 ? lddR : lddE;
+    if (!out) continue;
+    for (int i = threadIdx.x; i < P; i += kDetSmallTB)
+      s_key[i] = i < n ? ((uint64_t)(uint32_t)tr[3 * (int64_t)i + c] << 32) | (uint32_t)i : ~0ull;
+    __syncthreads();
+    for (int k = 2; k <= P; k <<= 1)
+      for (int j = k >> 1; j > 0; j >>= 1) {
+        for (int i = threadIdx.x; i < P; i += kDetSmallTB) {
+          const int ixj = i ^ j;
+          if (ixj > i) {
+            const uint64_t x = s_key[i], y = s_key[ixj];
+            if (((i & k) == 0) == (x > y)) {
+              s_key[i] = y;
+              s_key[ixj] = x;
+            }
+          }
+        }
+        __syncthreads();
+      }
+    const int b0 = wv * per, b1 = min(n, b0 + per);
+    for (int t = b0; t < b1; ++t) {
+      const uint32_t key = (uint32_t)(s_key[t] >> 32);
+      if (t > 0 && (uint32_t)(s_key[t - 1] >> 32) == key) continue;  // (wave uniform) not the run's first element
+      for (int h0 = 0; h0 < H; h0 += kRunF) {
+        float acc[4] = {0.f, 0.f, 0.f, 0.f};
+        for (int u = t; u < n && (uint32_t)(s_key[u] >> 32) == key; ++u) {
+          const int64_t i = (int64_t)(uint32_t)s_key[u];
+          const int64_t s_ = tr[3 * i], p_ = tr[3 * i + 1], o_ = tr[3 * i + 2];
+          const float gt = g[i];
+          float a[4], b[4];
+          det_load<false>(c == 0 ? Rel + p_ * ldR : E + s_ * ldE, lane, h0, H, a);
+          det_load<false>(c == 2 ? Rel + p_ * ldR : E + o_ * ldE, lane, h0, H, b);
+#pragma unroll
+          for (int k = 0; k < 4; ++k) acc[k] += (a[k] * gt) * b[k];
+        }
+        det_store<false, true>(out + (int64_t)key * ldo, lane, h0, H, acc);
+      }
+    }
+    __syncthreads();  // (the next column rewrites s_key, and its runs add onto the rows written here)
+  }
+}
+
+// BCE with the loss summed in a fixed order: block partials (one block for small n writes the loss itself), then one
+// wave adds them in block order
+constexpr int64_t kBceOneBlock = 8192;
+constexpr int kBceBlocks = 256;
+__global__ __launch_bounds__(kTB) void k_bce_logits_det(const float *__restrict__ x, const float *__restrict__ y,
+                                                        int64_t n, float *__restrict__ partial,
+                                                        float *__restrict__ loss, float *__restrict__ dx) {
+  __shared__ float s_part[kTB / kWave];
+  float acc = 0.f;
+  const float inv = 1.f / (float)n;
+  for (int64_t i = (int64_t)blockIdx.x * kTB + threadIdx.x; i < n; i += (int64_t)gridDim.x * kTB) {
+    const float xi = x[i], yi = y[i];
+    acc += fmaxf(xi, 0.f) - xi * yi + log1pf(expf(-fabsf(xi)));
+    if (dx) dx[i] = (1.f / (1.f + expf(-xi)) - yi) * inv;
+  }
+  acc = wave_sum(acc);
+  if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float t = 0.f;
+    for (int i = 0; i < kTB / kWave; ++i) t += s_part[i];
+    if (loss) *loss = t * inv;
+    else partial[blockIdx.x] = t;
+  }
+}
+__global__ __launch_bounds__(kWave) void k_bce_final(const float *__restrict__ partial, int nb, int64_t n,
+                                                     float *__restrict__ loss) {
+  float acc = 0.f;
+  for (int b = threadIdx.x; b < nb; b += kWave) acc += partial[b];
+  acc = wave_sum(acc);
+  if (threadIdx.x == 0) *loss = acc * (1.f / (float)n);
+}
+
+inline bool det_vec4_ok(const float *E, int64_t ldE, const float *Rel, int64_t ldR, int H, const float *dE,
+                        int64_t lddE, const float *dRel, int64_t lddR) {
+  return rows_vec4_ok(E, ldE, Rel, ldR, H) && (!dE || (lddE % 4 == 0 && ((uintptr_t)dE & 15) == 0)) &&
+         (!dRel || (lddR % 4 == 0 && ((uintptr_t)dRel & 15) == 0));
+}
+
+template <int WHICH, bool VEC>
+void det_column(dim3 grid, hipStream_t st, const float *E, int64_t ldE, const float *Rel, int64_t ldR, int H,
+                const int64_t *tr, const int64_t *order, int64_t n, const float *g, float *out, int64_t ldo,
+                float *slab, int32_t *flags, int32_t *keys, int64_t nw) {
+  k_distmult_bwd_det_runs<WHICH, VEC><<<grid, kTB, 0, st>>>(E, ldE, Rel, ldR, H, tr, order, n, g, out, ldo, slab,
+                                                             flags, keys);
+  k_distmult_bwd_det_join<VEC><<<grid, kTB, 0, st>>>(H, nw, flags, keys, slab, out, ldo);
+}
+
+template <bool VEC>
+void det_columns(dim3 grid, hipStream_t st, const float *E, int64_t ldE, const float *Rel, int64_t ldR, int H,
+                 const int64_t *tr, int64_t n, const float *g, const int64_t *os, const int64_t *op, const int64_t *oo,
+                 float *dE, int64_t lddE, float *dRel, int64_t lddR, float *slab, int32_t *flags, int32_t *keys,
+                 int64_t nw) {
+  if (dE) {
+    det_column<0, VEC>(grid, st, E, ldE, Rel, ldR, H, tr, os, n, g, dE, lddE, slab, flags, keys, nw);
+    det_column<2, VEC>(grid, st, E, ldE, Rel, ldR, H, tr, oo, n, g, dE, lddE, slab, flags, keys, nw);
+  }
+  if (dRel) det_column<1, VEC>(grid, st, E, ldE, Rel, ldR, H, tr, op, n, g, dRel, lddR, slab, flags, keys, nw);
+}
+
+}  // namespace
+}  // namespace mrgcn
+
+extern "C" {
+
+int64_t mrgcn_distmult_bwd_det_workspace(int64_t n, int32_t H) {
+  if (n < 0 || H <= 0) return -1;
+  if (n <= mrgcn::kDetSmallN) return 256;
+  const int64_t nw = (n + mrgcn::kRun - 1) / mrgcn::kRun;
+  return (2 * nw * H * 4 + 255) / 256 * 256 + 2 * ((nw * 4 + 255) / 256 * 256);
+}
+
+int mrgcn_distmult_score_bwd_det_f32(const float *E, int64_t ldE, const float *Rel, int64_t ldR, int32_t H,
+                                     const int64_t *triples, int64_t n, const float *dscores, const int64_t *order_s,
+                                     const int64_t *order_p, const int64_t *order_o, float *dE, int64_t lddE,
+                                     float *dRel, int64_t lddR, void *workspace, int64_t workspace_bytes,
+                                     void *stream) {
+  using namespace mrgcn;
+  MRGCN_REQUIRE(E && Rel && triples && dscores && H > 0 && n >= 0, "distmult_score_bwd_det: bad argument");
+  if (n == 0 || (!dE && !dRel)) return MRGCN_OK;
+  hipStream_t st = (hipStream_t)stream;
+  if (n <= kDetSmallN) {
+    k_distmult_bwd_det_small<<<1, kDetSmallTB, 0, st>>>(E, ldE, Rel, ldR, H, triples, (int)n, dscores, dE, lddE, dRel,
+                                                        lddR);
+    MRGCN_HIP_TRY(hipGetLastError());
+    return MRGCN_OK;
+  }
+  MRGCN_REQUIRE((!dE || (order_s && order_o)) && (!dRel || order_p), "distmult_score_bwd_det: missing order");
+  MRGCN_REQUIRE(workspace && workspace_bytes >= mrgcn_distmult_bwd_det_workspace(n, H),
+                "distmult_score_bwd_det: workspace too small");
+  const int64_t nw = (n + kRun - 1) / kRun;
+  char *w = (char *)workspace;
+  float *slab = (float *)w;
+  int32_t *flags = (int32_t *)(w + (2 * nw * H * 4 + 255) / 256 * 256);
+  int32_t *keys = (int32_t *)((char *)flags + (nw * 4 + 255) / 256 * 256);
+  const unsigned blocks = (unsigned)((nw + kTB / kWave - 1) / (kTB / kWave));
+  if (det_vec4_ok(E, ldE, Rel, ldR, H, dE, lddE, dRel, lddR))
+    det_columns<true>(dim3(blocks), st, E, ldE, Rel, ldR, H, triples, n, dscores, order_s, order_p, order_o, dE, lddE,
+                      dRel, lddR, slab, flags, keys, nw);
+  else
+    det_columns<false>(dim3(blocks, (unsigned)((H + kRunF - 1) / kRunF)), st, E, ldE, Rel, ldR, H, triples, n, dscores,
+                       order_s, order_p, order_o, dE, lddE, dRel, lddR, slab, flags, keys, nw);
+  MRGCN_HIP_TRY(hipGetLastError());
+  return MRGCN_OK;
+}
+
+int64_t mrgcn_bce_logits_det_workspace(int64_t n) { return n < 0 ? -1 : (int64_t)mrgcn::kBceBlocks * 4; }
+
+int mrgcn_bce_logits_det_f32(const float *x, const float *y, int64_t n, float *loss, float *dx, void *workspace,
+                             int64_t workspace_bytes, void *stream) {
+  using namespace mrgcn;
+  MRGCN_REQUIRE(x && y && loss && n > 0, "bce_logits_det: bad argument");
+  hipStream_t st = (hipStream_t)stream;
+  if (n <= kBceOneBlock) {
+    k_bce_logits_det<<<1, kTB, 0, st>>>(x, y, n, nullptr, loss, dx);
+  } else {
+    MRGCN_REQUIRE(workspace && workspace_bytes >= mrgcn_bce_logits_det_workspace(n), "bce_logits_det: workspace");
+    int64_t b = (n + kTB - 1) / kTB;
+    if (b > kBceBlocks) b = kBceBlocks;
+    float *partial = (float *)workspace;
+    k_bce_logits_det<<<(unsigned)b, kTB, 0, st>>>(x, y, n, partial, nullptr, dx);
+    k_bce_final<<<1, kWave, 0, st>>>(partial, (int)b, n, loss);
+  }
+  MRGCN_HIP_TRY(hipGetLastError());
+  return MRGCN_OK;
+}
+
+}  // extern "C"

@@ -532,6 +532,100 @@ __global__ __launch_bounds__(kTB) void k_sumsq_multi(MultiSumsq a, double *__res
   }
 }
 
+// ---- the same squared norms in a fixed order (torch.use_deterministic_algorithms(True)) -------------------------------
+// A block's float sum (block_sum: a fixed tree) becomes a double partial; the last block to take a ticket adds the
+// partials in block order.  Grids are functions of the sizes only.  `partials`: >= mrgcn_sumsq_det_workspace() bytes;
+// `ticket` is zero at the first call and left zero.
+constexpr int kDetMaxBlocks = kMultiMax * 64;
+__device__ __forceinline__ float sumsq_part(const float *__restrict__ x, int64_t n, int b, int nb) {
+  const int64_t nv = n >> 2;
+  const float4 *x4 = reinterpret_cast<const float4 *>(x);
+  float s = 0.f;
+  const int64_t stride = (int64_t)nb * kTB;
+  for (int64_t i = (int64_t)b * kTB + threadIdx.x; i < nv; i += 4 * stride) {
+    float4 v[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) v[u] = x4[i + u * stride < nv ? i + u * stride : i];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      if (i + u * stride < nv) {
+        s = fmaf(v[u].x, v[u].x, s);
+        s = fmaf(v[u].y, v[u].y, s);
+        s = fmaf(v[u].z, v[u].z, s);
+        s = fmaf(v[u].w, v[u].w, s);
+      }
+    }
+  }
+  if (b == 0)
+    for (int64_t i = (nv << 2) + threadIdx.x; i < n; i += kTB) s = fmaf(x[i], x[i], s);
+  return block_sum(s);
+}
+// thread 0: publish this block's partial; true in the block that arrives last (which then sees every partial)
+__device__ __forceinline__ bool det_last_block(double part, double *__restrict__ partials,
+                                               unsigned int *__restrict__ ticket) {
+  partials[blockIdx.x] = part;
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  const unsigned int seen = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (seen != gridDim.x - 1) return false;
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  return true;
+}
+__device__ __forceinline__ double det_ordered_sum(const double *__restrict__ partials, unsigned int *__restrict__ ticket) {
+  double t = 0.0;
+  for (unsigned int b = 0; b < gridDim.x; ++b) t += partials[b];
+  __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  return t;
+}
+__device__ __forceinline__ int multi_tensor_of(const MultiSumsq &a) {
+  int t = 0;
+  while (t + 1 < a.n_tensors && (int)blockIdx.x >= a.blk0[t + 1]) ++t;
+  return t;
+}
+
+__global__ __launch_bounds__(kTB) void k_sumsq_det(const float *__restrict__ x, int64_t n, double *__restrict__ accum,
+                                                   double *__restrict__ partials, unsigned int *__restrict__ ticket) {
+  const float t = sumsq_part(x, n, blockIdx.x, gridDim.x);
+  if (threadIdx.x == 0 && det_last_block((double)t, partials, ticket)) *accum += det_ordered_sum(partials, ticket);
+}
+
+__global__ __launch_bounds__(kTB) void k_sumsq_multi_accum_det(MultiSumsq a, double *__restrict__ accum,
+                                                               double *__restrict__ partials,
+                                                               unsigned int *__restrict__ ticket) {
+  const int t = multi_tensor_of(a);
+  const float s = sumsq_part(a.g[t], a.n[t], blockIdx.x - a.blk0[t], a.blk0[t + 1] - a.blk0[t]);
+  if (threadIdx.x == 0 && det_last_block((double)s, partials, ticket)) *accum += det_ordered_sum(partials, ticket);
+}
+
+__global__ __launch_bounds__(kTB) void k_sumsq_multi_det(MultiSumsq a, double *__restrict__ accum,
+                                                         unsigned int *__restrict__ ticket, float max_norm,
+                                                         double *__restrict__ sumsq_out, float *__restrict__ coef,
+                                                         float *__restrict__ norm, int64_t *__restrict__ step, float b1,
+                                                         float b2, float *__restrict__ bc,
+                                                         double *__restrict__ partials) {
+  const int t = multi_tensor_of(a);
+  const float s = sumsq_part(a.g[t], a.n[t], blockIdx.x - a.blk0[t], a.blk0[t + 1] - a.blk0[t]);
+  if (threadIdx.x == 0 && det_last_block((double)s, partials, ticket)) {
+    double total = *accum + det_ordered_sum(partials, ticket);
+    for (int e = 0; e < a.n_extra; ++e) total += *a.extra[e];
+    if (sumsq_out) *sumsq_out = total;
+    const float nrm = (float)sqrt(total);
+    if (coef) {
+      const float c = max_norm / (nrm + 1e-6f);
+      *coef = (max_norm > 0.f && c < 1.f) ? c : 1.f;
+    }
+    if (norm) *norm = nrm;
+    if (step) {
+      const int64_t tt = *step + 1;
+      *step = tt;
+      bc[0] = (float)(1.0 - pow((double)b1, (double)tt));
+      bc[1] = (float)sqrt(1.0 - pow((double)b2, (double)tt));
+    }
+    *accum = 0.0;
+  }
+}
+
 struct MultiAdam {
   float *p[kMultiMax];
   const float *g[kMultiMax];
@@ -1097,6 +1191,70 @@ int mrgcn_adam_step_multi_f32(int32_t n_tensors, float *const *params, const flo
   const double bc2 = bc_dev ? 1.0 : 1.0 - pow((double)beta2, (double)step);
   mrgcn::k_adam_multi<<<dim3(blk), dim3(kTB), 0, (hipStream_t)stream>>>(a, beta1, beta2, eps, (float)bc1,
                                                                        (float)sqrt(bc2), grad_scale, bc_dev);
+  MRGCN_HIP_TRY(hipGetLastError());
+  return MRGCN_OK;
+}
+
+// ---- deterministic squared norms ----------------------------------------------------------------------------------
+int64_t mrgcn_sumsq_det_workspace(void) { return (int64_t)mrgcn::kDetMaxBlocks * (int64_t)sizeof(double); }
+
+int mrgcn_sumsq_accum_det_f32(const float *x, int64_t n, double *accum, double *partials, uint32_t *ticket,
+                              void *stream) {
+  MRGCN_REQUIRE(x && accum && partials && ticket, "NULL");
+  MRGCN_REQUIRE(((uintptr_t)x & 15) == 0, "16-byte alignment");
+  if (n == 0) return MRGCN_OK;
+  mrgcn::k_sumsq_det<<<dim3(std::min(stream_grid(((n >> 2) + 3) / 4), 512)), dim3(kTB), 0, (hipStream_t)stream>>>(
+      x, n, accum, partials, ticket);
+  MRGCN_HIP_TRY(hipGetLastError());
+  return MRGCN_OK;
+}
+
+static int multi_sumsq_args(int32_t n_tensors, const float *const *grads, const int64_t *numel, mrgcn::MultiSumsq &a,
+                            int &blk) {
+  MRGCN_REQUIRE(n_tensors >= 1 && n_tensors <= mrgcn::kMultiMax && grads && numel, "1..16 tensors per call");
+  a.n_tensors = n_tensors;
+  blk = 0;
+  for (int t = 0; t < n_tensors; ++t) {
+    MRGCN_REQUIRE(grads[t] && numel[t] >= 0 && ((uintptr_t)grads[t] & 15) == 0, "gradient: NULL / 16-byte alignment");
+    a.g[t] = grads[t];
+    a.n[t] = numel[t];
+    a.blk0[t] = blk;
+    int64_t nb = ((numel[t] >> 2) + kTB - 1) / kTB;
+    blk += (int)(nb < 1 ? 1 : (nb > 64 ? 64 : nb));
+  }
+  a.blk0[n_tensors] = blk;
+  return MRGCN_OK;
+}
+
+int mrgcn_sumsq_accum_multi_det_f32(int32_t n_tensors, const float *const *grads, const int64_t *numel, double *accum,
+                                    double *partials, uint32_t *ticket, void *stream) {
+  MRGCN_REQUIRE(accum && partials && ticket, "NULL");
+  mrgcn::MultiSumsq a{};
+  int blk = 0;
+  if (int rc = multi_sumsq_args(n_tensors, grads, numel, a, blk)) return rc;
+  mrgcn::k_sumsq_multi_accum_det<<<dim3(blk), dim3(kTB), 0, (hipStream_t)stream>>>(a, accum, partials, ticket);
+  MRGCN_HIP_TRY(hipGetLastError());
+  return MRGCN_OK;
+}
+
+int mrgcn_sumsq_clip_multi_det_f32(int32_t n_tensors, const float *const *grads, const int64_t *numel, int32_t n_extra,
+                                   const double *const *extra, double *accum, uint32_t *ticket, float max_norm,
+                                   double *sumsq_out, float *coef, float *norm, int64_t *step_dev, float beta1,
+                                   float beta2, float *bc_dev, double *partials, void *stream) {
+  MRGCN_REQUIRE(n_extra >= 0 && n_extra <= mrgcn::kMultiMax, "at most 16 extra sums per call");
+  MRGCN_REQUIRE(accum && ticket && partials && (n_extra == 0 || extra), "NULL");
+  MRGCN_REQUIRE(!step_dev || bc_dev, "bc_dev is NULL");
+  mrgcn::MultiSumsq a{};
+  int blk = 0;
+  if (int rc = multi_sumsq_args(n_tensors, grads, numel, a, blk)) return rc;
+  a.n_extra = n_extra;
+  for (int e = 0; e < n_extra; ++e) {
+    MRGCN_REQUIRE(extra[e], "extra sum is NULL");
+    a.extra[e] = extra[e];
+  }
+  mrgcn::k_sumsq_multi_det<<<dim3(blk), dim3(kTB), 0, (hipStream_t)stream>>>(a, accum, ticket, max_norm, sumsq_out, coef,
+                                                                            norm, step_dev, beta1, beta2, bc_dev,
+                                                                            partials);
   MRGCN_HIP_TRY(hipGetLastError());
   return MRGCN_OK;
 }

@@ -532,7 +532,8 @@ class _RgcnLayer(torch.autograd.Function):
         # (the units of the wide-layer backward are built on first use, with host round trips: not inside a capture)
         if (has_I and has_comp and not has_X and not sparse_rows and weight_I.dim() == 3 and not plan.lean
                 and dY.stride(0) % 4 == 0
-                and (("_wide_units_det" if _WIDE_DET else "_wide_units") in plan.__dict__
+                and (("_wide_units_det" if (_WIDE_DET or torch.are_deterministic_algorithms_enabled())
+                      else "_wide_units") in plan.__dict__
                      or not torch.cuda.is_current_stream_capturing())):
             Bn = weight_I.shape[1]
             param = getattr(ctx.owner, "weight_I", None)
@@ -542,7 +543,10 @@ class _RgcnLayer(torch.autograd.Function):
                 # dY over the plan's entries — the 4 F-byte rows of dM are never written (csrc/wide_input.hip)
                 wI = weight_I.contiguous()
                 d_wI, d_comp = torch.empty_like(wI), torch.empty_like(comp_I)
-                if _WIDE_DET:
+                flag = torch.are_deterministic_algorithms_enabled()
+                if flag:
+                    bump("deterministic.wide_input")
+                if _WIDE_DET or flag:
                     # units of 64 entries, no float atomics: bitwise reproducible (plan.wide_units_det)
                     u = plan.wide_units_det(_WIDE_UNIT)
                     nws = int(lib.mrgcn_wide_input_bwd_det_workspace(plan.handle, u["n_slots"], Bn, F))

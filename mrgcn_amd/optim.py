@@ -31,6 +31,7 @@ import torch
 
 from . import _lib as L
 from .functional import clear_row_grads
+from .stats import bump
 from .train import ClipAdam, _stream, _to_reference_layout, merge_row_grad
 
 
@@ -77,6 +78,18 @@ class RowSparseAdam(Adam):
         super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=amsgrad, **kw)
 
 
+_DET_SCRATCH: dict = {}  # device -> (block partials, ticket) of the deterministic squared norms
+
+
+def _det_scratch(dev):
+    ent = _DET_SCRATCH.get(str(dev))
+    if ent is None:  # (the ticket starts at zero and every launch leaves it zero; the partials are written before read)
+        ent = _DET_SCRATCH[str(dev)] = (
+            torch.empty(int(L.load().mrgcn_sumsq_det_workspace()) // 8, dtype=torch.float64, device=dev),
+            torch.zeros((), dtype=torch.int32, device=dev))
+    return ent
+
+
 def clip_grad_norm_(parameters, max_norm, norm_type=2.0, error_if_nonfinite=False, foreach=None):
     """`torch.nn.utils.clip_grad_norm_` that also sees gradients in row-sparse form.  The total norm, the
     coefficient `max_norm / (norm + 1e-6)` (clamped to 1) and the scaling stay on the device; the returned norm
@@ -115,14 +128,23 @@ def clip_grad_norm_(parameters, max_norm, norm_type=2.0, error_if_nonfinite=Fals
     coef = torch.ones((), dtype=torch.float32, device=dev)
     norm = torch.zeros((), dtype=torch.float32, device=dev)
     s = _stream(dev)
+    det = torch.are_deterministic_algorithms_enabled()
+    if det:  # torch.use_deterministic_algorithms(True): the squared norms summed in block order
+        bump("deterministic.sumsq")
+        dp, dt = _det_scratch(dev)
+
+    def accum(t):
+        if det:
+            L.check(lib.mrgcn_sumsq_accum_det_f32(t.data_ptr(), t.numel(), sumsq.data_ptr(), dp.data_ptr(),
+                                                  dt.data_ptr(), s), "mrgcn_sumsq_accum_det_f32")
+        else:
+            L.check(lib.mrgcn_sumsq_accum_f32(t.data_ptr(), t.numel(), sumsq.data_ptr(), s), "mrgcn_sumsq_accum_f32")
     with torch.cuda.device(dev):
         for g in dense:
-            gc = g if g.is_contiguous() else g.contiguous()
-            L.check(lib.mrgcn_sumsq_accum_f32(gc.data_ptr(), gc.numel(), sumsq.data_ptr(), s), "mrgcn_sumsq_accum_f32")
+            accum(g if g.is_contiguous() else g.contiguous())
         for _, e in rows:
             if e.get("kind") == "index":   # compact rows of a literal operand: the norm of the compact gradient
-                L.check(lib.mrgcn_sumsq_accum_f32(e["g"].data_ptr(), e["g"].numel(), sumsq.data_ptr(), s),
-                        "mrgcn_sumsq_accum_f32")
+                accum(e["g"])
             else:
                 sumsq.add_(e["sumsq"])
         L.check(lib.mrgcn_clip_coef_f32(sumsq.data_ptr(), float(max_norm), coef.data_ptr(), norm.data_ptr(), s),

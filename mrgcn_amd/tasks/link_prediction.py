@@ -13,9 +13,20 @@ import numpy as np
 import torch
 
 from .. import _lib
+from ..stats import bump
 
 
 _SORTED_BWD_MIN = 4096  # below this the scatter kernel's atomics do not collide enough to matter
+_DET_SMALL_N = 4096     # mrgcn_distmult_score_bwd_det_f32 sorts up to this many triples itself (one block)
+_DET_WS: dict = {}      # (device, what) -> scratch of the deterministic entries, kept (fully written before it is read)
+
+
+def _det_scratch(device, what: str, nbytes: int) -> torch.Tensor:
+    key = (str(device), what)
+    t = _DET_WS.get(key)
+    if t is None or t.numel() < nbytes:
+        t = _DET_WS[key] = torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=device)
+    return t
 
 
 def _stream():
@@ -69,6 +80,15 @@ class SortedTriples:
         self.order = [torch.argsort(s_ * nn_ + o_, stable=True), torch.argsort(p_ * nn_ + s_, stable=True),
                       torch.argsort(o_ * nn_ + s_, stable=True)]
         self._tail = None
+        self._tail_det = None
+
+    def tail_orders_stable(self, nt: int, num_nodes: int, num_relations: int):
+        """The same buffers for the stable radix sort (mrgcn_distmult_orders: what the deterministic backward needs)."""
+        if self._tail_det is None or self._tail_det[0] != nt:
+            dev = self.triples.device
+            ws = torch.empty(int(_lib.load().mrgcn_distmult_orders_workspace(nt)), dtype=torch.uint8, device=dev)
+            self._tail_det = (nt, [torch.empty(nt, dtype=torch.int64, device=dev) for _ in range(3)] + [ws])
+        return self._tail_det[1]
 
     def tail_orders(self, nt: int, num_nodes: int, num_relations: int):
         """Buffers for the orders of the `nt` triples behind the fixed facts (+ the counting sort's workspace), kept."""
@@ -122,6 +142,10 @@ class _DistMultScore(torch.autograd.Function):
             dR = torch.zeros_like(Rel, memory_format=torch.contiguous_format) if ctx.needs_input_grad[1] else None
         n = triples.shape[0]
         st = ctx.static
+        if torch.are_deterministic_algorithms_enabled():
+            bump("deterministic.distmult_bwd")
+            _distmult_bwd_det(lib, E, Rel, triples, g, dE, dR, st)
+            return dE, dR, None, None
         if st is not None and st.covers(triples) and os.environ.get("MRGCN_LP_SORTED_BWD", "1") != "0":
             # the fixed facts through their stored orders (runs of equal targets summed in registers), the few
             # freshly drawn ones behind them through the scatter kernel: no sort in the epoch
@@ -170,6 +194,46 @@ class _DistMultScore(torch.autograd.Function):
         return dE, dR, None, None
 
 
+def _distmult_bwd_det(lib, E, Rel, triples, g, dE, dR, st):
+    """The backward under torch.use_deterministic_algorithms(True): every dE / dRel row summed in a fixed order by one
+    owner (mrgcn_distmult_score_bwd_det_f32).  The stored facts of `st` go through their stored (stable) orders, the
+    triples behind them — or all of them without `st` — through a stable radix sort, or none up to _DET_SMALL_N (the
+    kernel then sorts them itself in one block)."""
+    n, H, dev = triples.shape[0], E.shape[1], E.device
+    lddE, lddR = (dE.stride(0) if dE is not None else 0), (dR.stride(0) if dR is not None else 0)
+
+    def run(tr, m, gm, orders):
+        ws = _det_scratch(dev, "distmult_bwd", int(lib.mrgcn_distmult_bwd_det_workspace(m, H)))
+        _lib.check(lib.mrgcn_distmult_score_bwd_det_f32(
+            _ptr(E), E.stride(0), _ptr(Rel), Rel.stride(0), H, tr, m, gm, _ptr(orders[0]), _ptr(orders[1]),
+            _ptr(orders[2]), _ptr(dE), lddE, _ptr(dR), lddR, _ptr(ws), ws.numel(), _stream()),
+            "distmult_score_bwd_det")
+
+    def stable_orders(tr, m, bufs):
+        _lib.check(lib.mrgcn_distmult_orders(tr, m, E.shape[0], Rel.shape[0], _ptr(bufs[0]), _ptr(bufs[1]),
+                                             _ptr(bufs[2]), _ptr(bufs[3]), bufs[3].numel(), _stream()),
+                   "distmult_orders")
+        return bufs[:3]
+
+    ns = 0
+    if st is not None and st.covers(triples) and os.environ.get("MRGCN_LP_SORTED_BWD", "1") != "0":
+        ns = len(st)
+        run(_ptr(triples), ns, _ptr(g), st.order)
+    m = n - ns
+    if m == 0:
+        return
+    tr, gm = C.c_void_p(triples.data_ptr() + 24 * ns), C.c_void_p(g.data_ptr() + 4 * ns)
+    if m <= _DET_SMALL_N:
+        run(tr, m, gm, [None] * 3)
+        return
+    if ns:
+        bufs = st.tail_orders_stable(m, E.shape[0], Rel.shape[0])
+    else:
+        bufs = [torch.empty(m, dtype=torch.int64, device=dev) for _ in range(3)]
+        bufs.append(torch.empty(int(lib.mrgcn_distmult_orders_workspace(m)), dtype=torch.uint8, device=dev))
+    run(tr, m, gm, stable_orders(tr, m, bufs))
+
+
 def score_distmult_bc(data, node_embeddings, edge_embeddings, static: "SortedTriples | None" = None):
     """link_prediction.py:645-665 for the 1-D (s, p, o) index tensors train_model passes (or an int64 [n, 3] tensor).
     `static`: the stored orders of the facts the triples START with (SortedTriples): the backward then sorts nothing."""
@@ -185,8 +249,15 @@ class _BceLogits(torch.autograd.Function):
         x = x.contiguous()
         loss = torch.empty((), dtype=torch.float32, device=x.device)
         dx = torch.empty_like(x)
-        _lib.check(lib.mrgcn_bce_logits_f32(_ptr(x), _ptr(y), x.numel(), _ptr(loss), _ptr(dx), _stream()),
-                   "bce_logits")
+        if torch.are_deterministic_algorithms_enabled():
+            # the loss summed in block order and written (no float atomic on it)
+            bump("deterministic.bce")
+            ws = _det_scratch(x.device, "bce", int(lib.mrgcn_bce_logits_det_workspace(x.numel())))
+            _lib.check(lib.mrgcn_bce_logits_det_f32(_ptr(x), _ptr(y), x.numel(), _ptr(loss), _ptr(dx), _ptr(ws),
+                                                    ws.numel(), _stream()), "bce_logits_det")
+        else:
+            _lib.check(lib.mrgcn_bce_logits_f32(_ptr(x), _ptr(y), x.numel(), _ptr(loss), _ptr(dx), _stream()),
+                       "bce_logits")
         ctx.save_for_backward(dx)
         return loss
 

@@ -221,7 +221,10 @@ class ClipAdam(torch.optim.Optimizer):
                      sumsq=torch.zeros((), dtype=torch.float64, device=device),
                      sumsq_sharded=torch.zeros((), dtype=torch.float64, device=device),
                      coef=torch.ones((), dtype=torch.float32, device=device),
-                     norm=torch.zeros((), dtype=torch.float32, device=device))
+                     norm=torch.zeros((), dtype=torch.float32, device=device),
+                     # (block partials of the deterministic sums: written before they are read)
+                     partials=torch.empty(int(L.load().mrgcn_sumsq_det_workspace()) // 8, dtype=torch.float64,
+                                          device=device))
             self._scratch[device] = s
         return s
 
@@ -293,6 +296,17 @@ class ClipAdam(torch.optim.Optimizer):
         small = [i for i, g in enumerate(grads) if g.numel() <= _MULTI_MAX_NUMEL]
         # (16 tensors per launch: a model with more — an MRGCN with encoders has ~40 — takes a few launches, not 2 x 40)
         multi = (_MULTI and self._dist is None and len(hyper) == 1 and len(small) >= 1 and len(rowsparse) <= 16)
+        # torch.use_deterministic_algorithms(True): every squared norm summed in block order (the _det twins)
+        det = torch.are_deterministic_algorithms_enabled()
+        if det:
+            bump("deterministic.sumsq")
+        dp, dt = sc["partials"].data_ptr(), sc["ticket"].data_ptr()
+
+        def sumsq_accum(ptr, numel, acc):
+            if det:
+                L.check(lib.mrgcn_sumsq_accum_det_f32(ptr, numel, acc, dp, dt, s), "mrgcn_sumsq_accum_det_f32")
+            else:
+                L.check(lib.mrgcn_sumsq_accum_f32(ptr, numel, acc, s), "mrgcn_sumsq_accum_f32")
         with torch.cuda.device(device):
             bias = {}
             if self.capturable:
@@ -315,31 +329,36 @@ class ClipAdam(torch.optim.Optimizer):
                     b1m, b2m, _ = next(iter(hyper))
                     for i, g in enumerate(grads):
                         if i not in small:  # (a large dense gradient: its own streaming pass into the same accumulator)
-                            L.check(lib.mrgcn_sumsq_accum_f32(g.data_ptr(), g.numel(), sc["accum"].data_ptr(), s),
-                                    "mrgcn_sumsq_accum_f32")
+                            sumsq_accum(g.data_ptr(), g.numel(), sc["accum"].data_ptr())
                     for c0 in range(0, len(small) - 16, 16) if len(small) > 16 else ():
                         part = small[c0:c0 + 16]
-                        L.check(lib.mrgcn_sumsq_accum_multi_f32(
-                            len(part), (C.c_void_p * len(part))(*[grads[i].data_ptr() for i in part]),
-                            (C.c_int64 * len(part))(*[grads[i].numel() for i in part]), sc["accum"].data_ptr(), s),
-                            "mrgcn_sumsq_accum_multi_f32")
+                        gp_, gn_ = ((C.c_void_p * len(part))(*[grads[i].data_ptr() for i in part]),
+                                    (C.c_int64 * len(part))(*[grads[i].numel() for i in part]))
+                        if det:
+                            L.check(lib.mrgcn_sumsq_accum_multi_det_f32(len(part), gp_, gn_, sc["accum"].data_ptr(), dp,
+                                                                        dt, s), "mrgcn_sumsq_accum_multi_det_f32")
+                        else:
+                            L.check(lib.mrgcn_sumsq_accum_multi_f32(len(part), gp_, gn_, sc["accum"].data_ptr(), s),
+                                    "mrgcn_sumsq_accum_multi_f32")
                     last = small[(len(small) - 1) // 16 * 16:]   # the launch that also closes the norm
                     closing = [grads[i] for i in last]
                     for _, _, ent in indexed:  # (a compact gradient: in the closing launch while it has room for it)
                         if len(closing) < 16 and ent["g"].numel() <= 4 * _MULTI_MAX_NUMEL:
                             closing.append(ent["g"])
                         else:
-                            L.check(lib.mrgcn_sumsq_accum_f32(ent["g"].data_ptr(), ent["g"].numel(),
-                                                              sc["accum"].data_ptr(), s), "mrgcn_sumsq_accum_f32")
+                            sumsq_accum(ent["g"].data_ptr(), ent["g"].numel(), sc["accum"].data_ptr())
                     gp = (C.c_void_p * len(closing))(*[g.data_ptr() for g in closing])
                     gn = (C.c_int64 * len(closing))(*[g.numel() for g in closing])
                     ex = (C.c_void_p * max(len(rowsparse), 1))(*[ent["sumsq"].data_ptr() for _, _, ent in rowsparse])
                     dstep = self._dev_step.get((b1m, b2m)) if self.capturable else None
-                    L.check(lib.mrgcn_sumsq_clip_multi_f32(
-                        len(closing), gp, gn, len(rowsparse), ex, sc["accum"].data_ptr(), sc["ticket"].data_ptr(),
-                        float(self.max_norm) if use_clip else 0.0, sc["sumsq"].data_ptr(), sc["coef"].data_ptr(),
-                        sc["norm"].data_ptr(), dstep[0].data_ptr() if dstep else 0, b1m, b2m,
-                        dstep[1].data_ptr() if dstep else 0, s), "mrgcn_sumsq_clip_multi_f32")
+                    args = (len(closing), gp, gn, len(rowsparse), ex, sc["accum"].data_ptr(), sc["ticket"].data_ptr(),
+                            float(self.max_norm) if use_clip else 0.0, sc["sumsq"].data_ptr(), sc["coef"].data_ptr(),
+                            sc["norm"].data_ptr(), dstep[0].data_ptr() if dstep else 0, b1m, b2m,
+                            dstep[1].data_ptr() if dstep else 0)
+                    if det:
+                        L.check(lib.mrgcn_sumsq_clip_multi_det_f32(*args, dp, s), "mrgcn_sumsq_clip_multi_det_f32")
+                    else:
+                        L.check(lib.mrgcn_sumsq_clip_multi_f32(*args, s), "mrgcn_sumsq_clip_multi_f32")
                     for key, bc_t in bias.items():  # groups with other betas (no gradient this step): their counters too
                         if key != (b1m, b2m):
                             L.check(lib.mrgcn_adam_bias_f32(self._dev_step[key][0].data_ptr(), key[0], key[1],
@@ -356,13 +375,11 @@ class ClipAdam(torch.optim.Optimizer):
                 sharded = self._dist[1] if self._dist else ()
                 for (_, p), g in zip(live, grads):
                     acc = sc["sumsq_sharded"] if id(p) in sharded else sc["sumsq"]
-                    L.check(lib.mrgcn_sumsq_accum_f32(g.data_ptr(), g.numel(), acc.data_ptr(), s),
-                            "mrgcn_sumsq_accum_f32")
+                    sumsq_accum(g.data_ptr(), g.numel(), acc.data_ptr())
                 for _, p, ent in rowsparse:  # ||g||^2 came for free with the gradient
                     (sc["sumsq_sharded"] if id(p) in sharded else sc["sumsq"]).add_(ent["sumsq"])
                 for _, _, ent in indexed:
-                    L.check(lib.mrgcn_sumsq_accum_f32(ent["g"].data_ptr(), ent["g"].numel(), sc["sumsq"].data_ptr(), s),
-                            "mrgcn_sumsq_accum_f32")
+                    sumsq_accum(ent["g"].data_ptr(), ent["g"].numel(), sc["sumsq"].data_ptr())
                 if self._dist:
                     from .partition import all_reduce_sum_
                     all_reduce_sum_(sc["sumsq_sharded"], self._dist[0])
