@@ -941,6 +941,28 @@ int mrgcn_literal_tokens(const int64_t *tokens, const int64_t *offsets, const in
 int mrgcn_literal_csr_dense(const float *values, const int32_t *columns, const int64_t *row_ptr,
                             const int64_t *members, int64_t k, int64_t C, int64_t L, float *out, void *stream);
 
+/* ---- node dropout on the device (mrgcn/models/rgcn.py:78-84) -----------------------------------
+ * The node masks of one step: masks[l * ld + i], l < layers, i < n, is 0 when node i of layer (layer0 + l) is dropped
+ * and `keep_value` (the caller's fp32 1 / (1 - p)) otherwise.  The draw is Philox4x32-10: the four nodes 4g .. 4g+3
+ * take the four output words of counter (g, layer0 + l, position lo, position hi) under key (seed lo, seed hi), and a
+ * node is dropped when its word is below `threshold` = floor(p * 2^32) (0: nobody, 2^32: everybody) — a mask depends
+ * on (seed, position, layer, node) only, never on the launch.  `state_dev` is two int64 in DEVICE memory, {seed,
+ * position}, read by the draw; with `advance` a one-thread launch behind the draw adds one to the position, in stream
+ * order — a captured step therefore draws new masks at every replay.  `masks` on a 16-byte base, n <= 2^32, and
+ * ld % 4 == 0 when layers > 1.  (mrgcn_amd/host.py: node_dropout_mask is the bit-exact host mirror.) */
+int mrgcn_node_dropout_draw_f32(float *masks, int64_t ld, int64_t n, int32_t layers, int32_t layer0,
+                                int64_t threshold, float keep_value, int64_t *state_dev, int32_t advance,
+                                void *stream);
+/* Y[r, 0:F] *= m[r] in place, r < rows, on rows with leading dimension ld; columns F .. ld of a row are left as
+ * they are.  16-byte accesses when ld % 4 == 0 or ld == F (and a 16-byte base). */
+int mrgcn_row_scale_f32(float *Y, int64_t ld, int64_t rows, int32_t F, const float *m, void *stream);
+/* The backward twin on the row-live form: out[r, 0:F] = m[r] * dY[r, 0:F] for the rows with row_flags[r] != 0 (NULL:
+ * all rows); the other rows of dY are not read, and their rows of `out` are zeroed (`zero_dead`) or, without it, hold
+ * nothing a reader may rely on: each is left unwritten or zeroed, whichever the 16-byte store it shares with a live
+ * row makes cheaper (a gradient whose consumer goes by the same flags).  out may be dY. */
+int mrgcn_row_scale_live_f32(const float *dY, int64_t ld_dY, int64_t rows, int32_t F, const float *m,
+                             const uint8_t *row_flags, int32_t zero_dead, float *out, int64_t ld_out, void *stream);
+
 /* ---- timing helpers (HIP events on the caller's stream; used by bench.py) ------ */
 int mrgcn_event_create(void **event);
 int mrgcn_event_destroy(void *event);

@@ -234,6 +234,9 @@ SIGNATURES = {
     "mrgcn_support_rel_transform_bwd_f32": (C.c_int, [_p, _p, _i64, _p, _i64, _i32, _p, _i32, _p, _i64, _p, _p, _i64,
                                                       _i32, _p]),
     "mrgcn_softmax_xent_bwd_rows_f32": (C.c_int, [_p, _p, _i64, _i32, _p, _p, _i64, _p]),
+    "mrgcn_node_dropout_draw_f32": (C.c_int, [_p, _i64, _i64, _i32, _i32, _i64, C.c_float, _p, _i32, _p]),
+    "mrgcn_row_scale_f32": (C.c_int, [_p, _i64, _i64, _i32, _p, _p]),
+    "mrgcn_row_scale_live_f32": (C.c_int, [_p, _i64, _i64, _i32, _p, _p, _i32, _p, _i64, _p]),
     "mrgcn_event_create": (C.c_int, [C.POINTER(_p)]),
     "mrgcn_event_destroy": (C.c_int, [_p]),
     "mrgcn_event_record": (C.c_int, [_p, _p]),

@@ -280,13 +280,103 @@ def line_aligned_rows(X: torch.Tensor) -> torch.Tensor:
     return Xp
 
 
+# ---- node dropout on the device (csrc/node_dropout.hip) --------------------------------------------------------------
+# A node mask m (fp32, one value per output row: 0 or 1 / (1 - p)) is a per-row scale with m >= 0, so
+# act(m_i z_i) = m_i act(z_i) for ReLU and for no activation: the layers below take it as `row_scale`, scale their
+# output rows in place behind the product's ReLU epilogue and scale the incoming row gradient before anything else.
+# The scaled output is still "the output of a fused ReLU" for the layer above (`_mrgcn_relu_out`: its sign is the mask
+# of m . relu(z)), and the notes that ride on the gradient tensors keep travelling — no tensor is made in between.
+def node_dropout_state(seed: int, position: int, device) -> torch.Tensor:
+    """{seed, position} of the device draw as the int64 pair mrgcn_node_dropout_draw_f32 reads."""
+    to_i64 = lambda v: ((int(v) & 0xFFFFFFFFFFFFFFFF) ^ (1 << 63)) - (1 << 63)  # noqa: E731  (two's complement)
+    return torch.tensor([to_i64(seed), to_i64(position)], dtype=torch.int64).to(device)
+
+
+def node_dropout_draw(state: torch.Tensor, n: int, p: float, layers: int = 1, layer0: int = 0,
+                      advance: bool = True) -> list:
+    """Draws the node masks of `layers` consecutive layers (n nodes each) from the device state; returns them as
+    views of one buffer.  `advance`: the stream position moves on behind the draw (the last draw of a step)."""
+    from .host import node_dropout_keep_value, node_dropout_threshold
+    if state.dtype != torch.int64 or state.numel() != 2 or not state.is_cuda:
+        raise L.MrgcnError("node dropout: the state is an int64 pair {seed, position} in device memory")
+    ld = (n + 3) // 4 * 4
+    buf = torch.empty((layers, max(ld, 4)), dtype=torch.float32, device=state.device)
+    with torch.cuda.device(state.device):
+        L.check(L.load().mrgcn_node_dropout_draw_f32(
+            buf.data_ptr(), buf.stride(0), n, layers, layer0, node_dropout_threshold(p),
+            float(node_dropout_keep_value(p)), state.data_ptr(), int(advance), _stream(state.device)),
+            "mrgcn_node_dropout_draw_f32")
+    return [buf[l, :n] for l in range(layers)]
+
+
+def _check_row_scale(m, rows: int, dev):
+    if m is None:
+        return None
+    if (not isinstance(m, torch.Tensor) or m.dtype != torch.float32 or m.dim() != 1 or m.numel() != rows
+            or m.device != dev or m.stride(0) != 1 or m.requires_grad):
+        raise L.MrgcnError(f"row_scale: a contiguous fp32 vector of {rows} values on {dev} without gradient")
+    return m
+
+
+def row_scale_(Y: torch.Tensor, m: torch.Tensor) -> torch.Tensor:
+    """Y[r, :] *= m[r] in place; Y may be the first F columns of a buffer with padded rows (its pad is left alone)."""
+    assert Y.dim() == 2 and Y.stride(1) == 1 and Y.dtype == torch.float32
+    with torch.cuda.device(Y.device):
+        L.check(L.load().mrgcn_row_scale_f32(Y.data_ptr(), Y.stride(0), Y.shape[0], Y.shape[1], m.data_ptr(),
+                                             _stream(Y.device)), "mrgcn_row_scale_f32")
+    bump("node_dropout.device")
+    return Y
+
+
+def row_scale_live(dY: torch.Tensor, m: torch.Tensor, row_flags=None, zero_dead: bool = True) -> torch.Tensor:
+    """m[r] * dY[r, :] for the flagged rows (None: all); the others are zeroed, or with `zero_dead=False` left unwritten
+    (a gradient with unwritten rows stays one).  Rows without a flag are not read."""
+    assert dY.dim() == 2 and dY.stride(1) == 1 and dY.dtype == torch.float32
+    if row_flags is not None and (row_flags.numel() != dY.shape[0] or row_flags.device != dY.device
+                                  or row_flags.dtype != torch.uint8):
+        if not zero_dead:
+            raise L.MrgcnError("internal: an output gradient with unwritten rows arrived without usable row flags")
+        row_flags = None
+    out = torch.empty(dY.shape, dtype=torch.float32, device=dY.device)
+    if dY.shape[0] == 0:
+        return out
+    with torch.cuda.device(dY.device):
+        L.check(L.load().mrgcn_row_scale_live_f32(
+            dY.data_ptr(), dY.stride(0), dY.shape[0], dY.shape[1], m.data_ptr(),
+            row_flags.data_ptr() if row_flags is not None else 0, int(zero_dead), out.data_ptr(), out.stride(0),
+            _stream(dY.device)), "mrgcn_row_scale_live_f32")
+    return out
+
+
+class _RowScale(torch.autograd.Function):
+    """m[r] * X[r, :] as a node of its own: for a layer output that is not one fused function's (the slice walk sums
+    two products)."""
+
+    @staticmethod
+    def forward(ctx, X, m):
+        Xc = X if (X.dim() == 2 and X.stride(1) == 1) else X.contiguous()
+        ctx.m = _check_row_scale(m, Xc.shape[0], Xc.device)
+        Y = row_scale_live(Xc, m)
+        bump("node_dropout.device")
+        return Y
+
+    @staticmethod
+    def backward(ctx, dY):
+        dY = dY if (dY.dim() == 2 and dY.stride(1) == 1) else dY.contiguous()
+        return row_scale_live(dY, ctx.m), None
+
+
+def row_scale(X: torch.Tensor, m: torch.Tensor) -> torch.Tensor:
+    return _RowScale.apply(X, m)
+
+
 class _SpmmLiteral(torch.autograd.Function):
     """Y = A . D with D the dense (R*N) x F operand in the reference's row order
     (mrgcn/layers/graph.py:75, :95).  Backward = A^T dY scattered into a dense
     (R*N) x F gradient, as SparseAddmmBackward produces for the reference."""
 
     @staticmethod
-    def forward(ctx, plan: GraphPlan, D: torch.Tensor, bias, relu: bool, owner=None):
+    def forward(ctx, plan: GraphPlan, D: torch.Tensor, bias, relu: bool, owner=None, row_scale=None):
         # `owner`: the layer whose `weight_I` parameter IS the operand (a featureless layer without bases): its
         # gradient may then travel in compact form (below)
         ctx.param = None
@@ -294,6 +384,9 @@ class _SpmmLiteral(torch.autograd.Function):
             ctx.param = D
         D = D.contiguous()
         Y = plan.spmm(L.VIEW_LITERAL, D, bias=bias, relu=relu)
+        ctx.row_scale = _check_row_scale(row_scale, Y.shape[0], Y.device)
+        if ctx.row_scale is not None:
+            row_scale_(Y, ctx.row_scale)   # (node dropout: behind the ReLU epilogue, m >= 0)
         ctx.plan, ctx.relu, ctx.has_bias = plan, relu, bias is not None
         ctx.d_rows = D.shape[0]
         ctx.save_for_backward(Y if relu else None)
@@ -310,6 +403,8 @@ class _SpmmLiteral(torch.autograd.Function):
             raise L.MrgcnError("internal: an output gradient with unwritten rows reached the literal product")
         if ctx.relu and not (meta and meta["relu_applied"]):
             dY = relu_bwd(dY, Y)
+        if ctx.row_scale is not None:
+            dY = row_scale_live(dY, ctx.row_scale)
         dbias = _bias_grad(dY) if ctx.has_bias else None
         dD = None
         if ctx.needs_input_grad[1]:
@@ -342,15 +437,16 @@ class _SpmmLiteral(torch.autograd.Function):
                 plan.spmm(L.VIEW_TRANSPOSED, dY, out=g)
                 rows["g"], rows["fresh"] = g, True
                 bump("weight_I.index_rows")
-                return None, None, dbias, None, None
+                return None, None, dbias, None, None, None
             dD = torch.zeros((ctx.d_rows, F), dtype=torch.float32, device=dY.device)
             ulcol_ptr, _ = plan.array_ptr(L.ARR_ULCOL)
             plan.spmm(L.VIEW_TRANSPOSED, dY, out=dD, out_index=ulcol_ptr)
-        return None, dD, dbias, None, None
+        return None, dD, dbias, None, None, None
 
 
-def spmm_literal(plan: GraphPlan, D: torch.Tensor, bias=None, relu: bool = False, owner=None) -> torch.Tensor:
-    return _SpmmLiteral.apply(plan, D, bias, relu, owner)
+def spmm_literal(plan: GraphPlan, D: torch.Tensor, bias=None, relu: bool = False, owner=None,
+                 row_scale=None) -> torch.Tensor:
+    return _SpmmLiteral.apply(plan, D, bias, relu, owner, row_scale)
 
 
 def relu_bwd(dY: torch.Tensor, Y: torch.Tensor) -> torch.Tensor:
@@ -415,7 +511,7 @@ class _RgcnLayer(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, plan: GraphPlan, F: int, weight_I, comp_I, X, W_F, bias, relu: bool, bf16: bool = False,
-                owner=None):
+                owner=None, row_scale=None):
         lib = L.load()
         dev = plan.device
         # bf16: the compact operand M is stored in bf16 (one rounding at its store); a WIDE input (K > 16) is read as
@@ -484,6 +580,11 @@ class _RgcnLayer(torch.autograd.Function):
         # an output the caller sees is dense like the reference's
         Y = plan.spmm(L.VIEW_COMPACT, M, F=F, bias=bias, relu=relu,
                       padded_rows=bool(getattr(owner, "padded_output", False)))
+        # node dropout: the fp32 output rows scaled in place behind the ReLU epilogue (m >= 0; also the bf16 pipeline:
+        # Y is its fp32 accumulator's store); the pad columns of a padded row stay as the product left them
+        ctx.row_scale = _check_row_scale(row_scale, Y.shape[0], Y.device)
+        if ctx.row_scale is not None:
+            row_scale_(Y, ctx.row_scale)
         ctx.plan, ctx.F, ctx.ld, ctx.relu, ctx.owner = plan, F, ld, relu, owner
         ctx.Xb = Xb   # the input's bf16 rows (the bf16 pipeline): what the backward's dW gathers
         # the layer's input is the output of a fused ReLU (marked by the layer that made it): its own sign is that
@@ -495,6 +596,10 @@ class _RgcnLayer(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dY):
+        return _RgcnLayer._backward(ctx, dY) + (None,)   # (row_scale)
+
+    @staticmethod
+    def _backward(ctx, dY):
         lib = L.load()
         plan, F = ctx.plan, ctx.F
         weight_I, comp_I, X, W_F, Y = ctx.saved_tensors
@@ -513,9 +618,20 @@ class _RgcnLayer(torch.autograd.Function):
         sparse_rows = bool(meta and meta.get("sparse_rows"))
         if sparse_rows and row_flags is None:
             raise L.MrgcnError("internal: an output gradient with unwritten rows arrived without its row flags")
+        m = getattr(ctx, "row_scale", None)
+        looked = False
+        if m is not None:
+            # node dropout: dz_i = m_i . relu_bwd(y_i, dy_i), over the rows that hold anything.  A plain dense gradient's
+            # rows are looked up BEFORE the scale: the label set is the same every epoch, the dropped rows are not
+            if meta is None and _SUPPORT and _LIVE_COLS and _DISCOVER and F <= 16:
+                meta, looked = _discovered_rows(ctx.owner, plan, dY, F, dev), True
+                if meta:
+                    bump("discovered_rows")
+                row_flags = meta["row_live"] if meta else row_flags
+            dY = row_scale_live(dY, m, row_flags, zero_dead=not sparse_rows)
         # (rows outside the flags are zeros — or, with `sparse_rows`, unwritten: the flagged rows are all there is to add)
         dbias = _bias_grad(dY, row_flags) if has_bias else None
-        if meta is None and _SUPPORT and _LIVE_COLS and _DISCOVER and F <= 16:
+        if meta is None and not looked and _SUPPORT and _LIVE_COLS and _DISCOVER and F <= 16:
             # a plain dense gradient (the reference's own loss: CrossEntropyLoss on Y_hat[idx] leaves zeros + the
             # labelled rows): which rows hold anything is looked up, and while that set equals last epoch's the
             # backward runs on the support built for it
@@ -946,7 +1062,7 @@ class _MaskedLayer(torch.autograd.Function):
     stored values, the feature term the all-ones slice (batch.py:258-270)."""
 
     @staticmethod
-    def forward(ctx, sup, F: int, weight_I, comp_I, X, W_F, bias, relu: bool, owner=None):
+    def forward(ctx, sup, F: int, weight_I, comp_I, X, W_F, bias, relu: bool, owner=None, row_scale=None):
         lib = L.load()
         plan = sup.plan
         dev = sup.device
@@ -1011,6 +1127,9 @@ class _MaskedLayer(torch.autograd.Function):
             else:
                 L.check(lib.mrgcn_support_spmm_fwd_f32(sup.handle, int(has_I or fv), (M if has_I else T).data_ptr(), ld, F,
                                                        Y.data_ptr(), F, b, int(relu), s), "mrgcn_support_spmm_fwd_f32")
+        ctx.row_scale = _check_row_scale(row_scale, NR, dev)
+        if ctx.row_scale is not None:
+            row_scale_(Y, ctx.row_scale)   # (node dropout: one value per row of the sample, behind the ReLU)
         ctx.sup, ctx.plan, ctx.F, ctx.ld, ctx.relu, ctx.owner = sup, plan, F, ld, relu, owner
         ctx.wide = wide
         ctx.x_by_node = bool(has_X and x_by_node)
@@ -1031,6 +1150,8 @@ class _MaskedLayer(torch.autograd.Function):
         meta = _grad_meta(dY)
         if ctx.relu and not (meta and meta["relu_applied"]):
             dY = relu_bwd(dY, Y)
+        if ctx.row_scale is not None:
+            dY = row_scale_live(dY, ctx.row_scale)
         dbias = _bias_grad(dY) if has_bias else None
         d_wI = d_comp = dX = dW = None
         Lc = max(sup.L, 1)
@@ -1073,7 +1194,7 @@ class _MaskedLayer(torch.autograd.Function):
                     full = torch.zeros((X.shape[0], K), dtype=torch.float32, device=dev)
                     full.index_copy_(0, sup.view(L.SUP_LNODE).long(), dX)
                     dX = full
-        return None, None, d_wI, d_comp, dX, dW, dbias, None, None
+        return None, None, d_wI, d_comp, dX, dW, dbias, None, None, None
 
 
 class _MaskedWideFeat(torch.autograd.Function):
@@ -1083,7 +1204,7 @@ class _MaskedWideFeat(torch.autograd.Function):
     the all-ones slice (batch.py:258-270) or the stored values (`feature_values`), as _MaskedLayer does."""
 
     @staticmethod
-    def forward(ctx, sup, F: int, weight_I, comp_I, X, V_F, comp_F, bias, relu: bool, owner=None):
+    def forward(ctx, sup, F: int, weight_I, comp_I, X, V_F, comp_F, bias, relu: bool, owner=None, row_scale=None):
         lib = L.load()
         plan = sup.plan
         dev = sup.device
@@ -1112,6 +1233,9 @@ class _MaskedWideFeat(torch.autograd.Function):
                 Y.add_(bias)
                 if relu:
                     Y.relu_()
+        ctx.row_scale = _check_row_scale(row_scale, sup.NR, dev)
+        if ctx.row_scale is not None:
+            row_scale_(Y, ctx.row_scale)
         bump("masked.wide_feat")
         ctx.sup, ctx.F, ctx.relu, ctx.owner, ctx.fv = sup, F, relu, owner, fv
         ctx.x_by_node, ctx.has_I, ctx.has_bias = bool(x_by_node), has_I, bias is not None
@@ -1132,6 +1256,8 @@ class _MaskedWideFeat(torch.autograd.Function):
         if ctx.relu and not (meta and meta["relu_applied"]):
             dY = relu_bwd(dY, Y)
         dY = dY.contiguous()
+        if ctx.row_scale is not None:
+            dY = row_scale_live(dY, ctx.row_scale)
         dbias = _bias_grad(dY) if ctx.has_bias else None
         d_wI = d_comp = dX = dVF = None
         dP = torch.empty_like(P)
@@ -1168,7 +1294,8 @@ class _MaskedWideFeat(torch.autograd.Function):
                     full = torch.zeros((X.shape[0], K), dtype=torch.float32, device=dev)
                     full.index_copy_(0, sup.view(L.SUP_LNODE).long(), dX)
                     dX = full
-        return (None, None, d_wI, d_comp, dX, dVF, d_compF if ctx.needs_input_grad[6] else None, dbias, None, None)
+        return (None, None, d_wI, d_comp, dX, dVF, d_compF if ctx.needs_input_grad[6] else None, dbias, None, None,
+                None)
 
 
 def _masked_wide_feat(sup, layer) -> bool:
@@ -1199,9 +1326,10 @@ def masked_layer_supported(sup, layer, K: int, need_dX: bool = False) -> bool:
     return True
 
 
-def masked_layer(sup, layer, X, relu: bool = False) -> torch.Tensor:
+def masked_layer(sup, layer, X, relu: bool = False, row_scale=None) -> torch.Tensor:
     """One `GraphConvolution` on a mini-batch sample given as a forward support of the full graph's plan
-    (data.batch.A_BatchMasked): graph.py:62-102 with A_idx, both terms."""
+    (data.batch.A_BatchMasked): graph.py:62-102 with A_idx, both terms.  `row_scale`: a node-dropout mask, one fp32
+    value per row of the sample, applied to the output inside the layer's function."""
     F, B = layer.outdim, layer.num_bases
     weight_I = comp_I = Xin = W_F = None
     if layer.input_layer:
@@ -1214,11 +1342,12 @@ def masked_layer(sup, layer, X, relu: bool = False) -> torch.Tensor:
             W_F = _BasisContract.apply(layer.weight_F_comp, W_F)
     bias = layer.b if layer.bias else None
     if F > 16 and Xin is not None and _masked_wide_feat(sup, layer):
-        Y = _MaskedWideFeat.apply(sup, F, weight_I, comp_I, Xin, layer.weight_F, layer.weight_F_comp, bias, relu, layer)
+        Y = _MaskedWideFeat.apply(sup, F, weight_I, comp_I, Xin, layer.weight_F, layer.weight_F_comp, bias, relu, layer,
+                                  row_scale)
         if relu:
             Y._mrgcn_relu_out = True
         return Y
-    Y = _MaskedLayer.apply(sup, F, weight_I, comp_I, Xin, W_F, bias, relu, layer)
+    Y = _MaskedLayer.apply(sup, F, weight_I, comp_I, Xin, W_F, bias, relu, layer, row_scale)
     if relu:
         Y._mrgcn_relu_out = True
     return Y
@@ -1256,9 +1385,10 @@ class _BasisContract(torch.autograd.Function):
 
 
 def rgcn_layer(plan: GraphPlan, layer, X, relu: bool = False, input_term: bool = True,
-               feature_term: bool = True, use_bias: bool = True) -> torch.Tensor:
+               feature_term: bool = True, use_bias: bool = True, row_scale=None) -> torch.Tensor:
     """Fused forward of one `GraphConvolution` (graph.py:62-102).  `input_term` / `feature_term`
-    select the two summands (mini-batch mode runs them on different column spaces)."""
+    select the two summands (mini-batch mode runs them on different column spaces).  `row_scale`: a node-dropout mask
+    (fp32, one value >= 0 per output row), applied to the output rows inside the layer's autograd function."""
     F = layer.outdim
     B = layer.num_bases
     weight_I = comp_I = W_F = None
@@ -1280,11 +1410,11 @@ def rgcn_layer(plan: GraphPlan, layer, X, relu: bool = False, input_term: bool =
     bias = layer.b if (layer.bias and use_bias) else None
     if weight_I is not None and comp_I is None and Xin is None and not bf16:
         # featureless layer without bases: weight_I already *is* the literal operand
-        Y = spmm_literal(plan, weight_I, bias=bias, relu=relu, owner=layer)
+        Y = spmm_literal(plan, weight_I, bias=bias, relu=relu, owner=layer, row_scale=row_scale)
         if relu:
             Y._mrgcn_relu_out = True   # (the layer above masks its input gradient with this output's sign)
         return Y
-    Y = _RgcnLayer.apply(plan, F, weight_I, comp_I, Xin, W_F, bias, relu, bf16, layer)
+    Y = _RgcnLayer.apply(plan, F, weight_I, comp_I, Xin, W_F, bias, relu, bf16, layer, row_scale)
     if relu:
         Y._mrgcn_relu_out = True  # (a Python attribute of this tensor object: a copy or a view does not carry it)
     if F <= 16 and _SUPPORT and _LIVE_COLS and not plan.lean:

@@ -214,8 +214,8 @@ class GraphConvolution(nn.Module):
         return Fn.operand_row_bytes(self.outdim, getattr(self, "operand_dtype", "f32") == "bf16")
 
     # -- fused engine ----------------------------------------------------------------------
-    def _forward_fused(self, X, plan, relu=False):
-        return Fn.rgcn_layer(plan, self, X, relu=relu)
+    def _forward_fused(self, X, plan, relu=False, row_scale=None):
+        return Fn.rgcn_layer(plan, self, X, relu=relu, row_scale=row_scale)
 
 
 def _weight_I_to_reference(module, state_dict, prefix, local_metadata):

@@ -154,6 +154,12 @@ class MRGCN(nn.Module):
             self.gate_weights = self.gate_weights.to(device)
 
     # ------------------------------------------------------------------------------
+    def set_node_dropout(self, mode: str, seed=None):
+        """Where the R-GCN's node masks come from when `p_dropout > 0`: "host" (the reference's CPU draw, the default)
+        or "device" (drawn and applied on the GPU; graph-capturable) — `RGCN.set_node_dropout`."""
+        self.rgcn.set_node_dropout(mode, seed)
+        return self
+
     def set_compute_dtype(self, dtype: str):
         """"f32" (the reference's arithmetic: the parity default) or "bf16" — BASELINE config 3's pipeline: the R-GCN
         layers store their activations in bf16 (`RGCN.set_operand_dtype`), the encoders' products (MLP / TCNN / heads)

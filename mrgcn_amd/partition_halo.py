@@ -656,6 +656,14 @@ class HaloPartitionedRGCN(nn.Module):
         self.plans = None
 
     # (the same sharding helpers as the column-partition model)
+
+    def set_node_dropout(self, mode: str, seed=None):
+        """The partitioned engines have no node dropout on the device (models/rgcn.py: RGCN.set_node_dropout)."""
+        if mode != "host":
+            raise Fn.L.MrgcnError(f"{type(self).__name__}: node dropout mode {mode!r} is outside the partitioned engines "
+                                  "(the single-GPU RGCN on the fused engine draws on the device)")
+        return self
+
     def sharded_parameters(self):
         return [l.weight_I for l in self.layers.values() if l.weight_I is not None]
 

@@ -22,7 +22,8 @@ def stats() -> dict:
     `adam.list` / `adam.rows_fused` / `adam.rows` (row-sparse optimizer updates), `literals.device` / `literals.host` (where a
     mini-batch's literal encodings were subset: DeviceEncodings or mksubset), `modality.rows_known` / `modality.isin`
     (per encoding set: batch positions carried by the subset, or found by matching node ids), `masked.wide_feat` /
-    `weight_I.wide_feat` (wide masked layers with a feature term, and those of them with an input term).
+    `weight_I.wide_feat` (wide masked layers with a feature term, and those of them with an input term),
+    `node_dropout.device` (layers that applied a node-dropout mask on the device: `RGCN.set_node_dropout("device")`).
     Under `torch.use_deterministic_algorithms(True)`: `deterministic.distmult_bwd` (DistMult backwards on the owner
     form), `deterministic.bce` (BCE losses summed in block order), `deterministic.sumsq` (clips whose squared norms were
     summed in block order: ClipAdam steps and `optim.clip_grad_norm_` calls), `deterministic.wide_input` (wide

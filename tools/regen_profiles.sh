@@ -71,6 +71,11 @@ for w in aifb mutag; do
   python3 tools/epoch_sequence.py $o/stats_$w k_xent_rows shortest > $o/${w}_epoch_sequence.md 2>&1
   rm -rf $o/stats_$w
 done
+# (10c) node dropout: the replayed epoch with p = 0 and with the device draw, the eager epoch with the host draw.
+# Row (a) of DESIGN section 12 is the PARENT commit's p = 0 epoch on the same box: check the parent out beside this tree,
+# build it, copy tools/node_dropout_probe.py into it and run `python3 tools/node_dropout_probe.py --rows p0 --out <file>`
+# there first; NODE_DROPOUT_PARENT_JSON=<file> then puts that row into the result.  Without it the file holds no row (a).
+python3 tools/node_dropout_probe.py ${NODE_DROPOUT_PARENT_JSON:+--parent $NODE_DROPOUT_PARENT_JSON} --out $o/node_dropout_probe.json > $o/node_dropout_probe.txt 2> $o/node_dropout_probe.err
 hipcc -O3 --offload-arch=gfx950 -std=c++17 tools/lab/copy_lab.hip -o /tmp/copy_lab 2>/dev/null && /tmp/copy_lab > $o/copy_lab.txt 2>&1
 python3 tools/lab/spmm_hot_lab.py > $o/spmm_hot_lab.txt 2>&1
 # the CPU suite last: the tree these artefacts describe is green
