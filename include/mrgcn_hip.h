@@ -757,6 +757,21 @@ int mrgcn_distmult_ranks(const float *E, int64_t ldE, int64_t num_nodes, const f
                          const int64_t *tail_ptr, const int32_t *tail_idx, const int64_t *head_ptr,
                          const int32_t *head_idx, void *workspace, int64_t workspace_bytes,
                          int64_t *ranks, void *stream);
+/* Top-k completion of (s, p, ?) / (?, p, o) queries: what a user of the reference reads off the [facts, nodes] score
+ * matrix of compute_ranks_fast (link_prediction.py:593-643; scores :645-665) with a sort.  queries: device int64
+ * [nq, 2] rows (anchor node, relation); head == 0: candidates fill the tail slot, score = sum_h (E[s,h] Rel[p,h])
+ * E[c,h]; head == 1: the head slot, sum_h (E[c,h] Rel[p,h]) E[o,h] - float32, sequential over h, uncontracted: the rank
+ * kernel's scores bit for bit (one shared body).  Row q of out_idx / out_score [nq, k]: the k best candidates, score
+ * descending, equal scores (-0 == +0) by ascending node id; candidates in excl_idx[excl_ptr[q] : excl_ptr[q+1]]
+ * (sorted per query; both arrays or neither) never appear; a row with fewer than k candidates ends in (-1, -inf).
+ * A pure function of its inputs (no atomics); embeddings must be finite (NaN: undefined).  1 <= k <= 256.  The score
+ * matrix is never stored: workspace = H N floats + nq * k * ceil(N / 256) 64-bit keys,
+ * mrgcn_distmult_topk_workspace() bytes (-1 for bad arguments).  No host synchronisation; capturable. */
+int64_t mrgcn_distmult_topk_workspace(int64_t num_nodes, int32_t H, int64_t num_queries, int32_t k);
+int mrgcn_distmult_topk(const float *E, int64_t ldE, int64_t num_nodes, const float *Rel, int64_t ldR, int32_t H,
+                        const int64_t *queries, int64_t num_queries, int32_t head, const int64_t *excl_ptr,
+                        const int32_t *excl_idx, int32_t k, void *workspace, int64_t workspace_bytes,
+                        int64_t *out_idx, float *out_score, void *stream);
 
 /* Graph-capturable Adam (torch.optim.Adam(capturable=True) semantics): the step counter and the
  * bias corrections live in device memory, so a captured epoch replays with the right step.

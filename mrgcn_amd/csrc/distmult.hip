@@ -17,13 +17,14 @@
 
 #include "common.hpp"
 #include "config.hpp"
+#include "lp_score.hpp"
 
 namespace mrgcn {
 namespace {
 
-constexpr int kTB = 256;
-constexpr int kFB = 8;     // facts per block in the rank kernel
-constexpr int kHT = 64;    // h tile of the per-fact query vectors in LDS
+constexpr int kTB = kLpTB;
+constexpr int kFB = kLpFB;   // facts per block in the rank kernel
+constexpr int kHT = kLpHT;   // h tile of the per-fact query vectors in LDS
 
 __device__ __forceinline__ float wave_sum(float x) {
 #pragma unroll
@@ -289,16 +290,6 @@ __global__ void k_true_scores(const float *__restrict__ E, int64_t ldE, const fl
   truth[f] = acc;
 }
 
-__device__ __forceinline__ bool in_sorted(const int32_t *__restrict__ a, int64_t lo, int64_t hi, int32_t key) {
-  while (lo < hi) {
-    const int64_t mid = (lo + hi) >> 1;
-    const int32_t v = a[mid];
-    if (v == key) return true;
-    if (v < key) lo = mid + 1; else hi = mid;
-  }
-  return false;
-}
-
 // grid (candidate tiles, fact tiles, 2 directions).  HEAD=false: candidate replaces o,
 // score = (E[s] Rel[p]) * E[c];  HEAD=true: candidate replaces s, score = (E[c] Rel[p]) * E[o].
 __global__ __launch_bounds__(kTB) void k_rank_counts(
@@ -317,50 +308,14 @@ __global__ __launch_bounds__(kTB) void k_rank_counts(
   const int nfb = (int)((nf - f0) < kFB ? (nf - f0) : kFB);
   const bool live = c < N;
   float acc[kFB];
-#pragma unroll
-  for (int i = 0; i < kFB; ++i) acc[i] = 0.f;
   if (threadIdx.x < kFB * 2) s_cnt[threadIdx.x >> 1][threadIdx.x & 1] = 0;
-
-  for (int h0 = 0; h0 < H; h0 += kHT) {
-    const int hn = (H - h0) < kHT ? (H - h0) : kHT;
-    __syncthreads();
-    for (int i = threadIdx.x; i < kFB * kHT; i += kTB) {
-      const int fi = i / kHT, h = i % kHT;
-      float a = 0.f, b = 0.f;
-      if (fi < nfb && h < hn) {
-        const int64_t f = f0 + fi;
-        const float pv = Rel[tr[3 * f + 1] * ldR + h0 + h];
-        if (head) {
-          a = pv;
-          b = E[tr[3 * f + 2] * ldE + h0 + h];
-        } else {
-          a = E[tr[3 * f] * ldE + h0 + h] * pv;
-        }
-      }
-      s_a[fi][h] = a;
-      s_b[fi][h] = b;
-    }
-    __syncthreads();
-    if (live) {
-      for (int h = 0; h < hn; ++h) {
-        const float e = Et[(int64_t)(h0 + h) * N + c];
-        if (head) {
-#pragma unroll
-          for (int i = 0; i < kFB; ++i) {
-            const float ep = e * s_a[i][h];
-            const float epo = ep * s_b[i][h];
-            acc[i] = acc[i] + epo;
-          }
-        } else {
-#pragma unroll
-          for (int i = 0; i < kFB; ++i) {
-            const float spe = s_a[i][h] * e;
-            acc[i] = acc[i] + spe;
-          }
-        }
-      }
-    }
-  }
+  lp_score_tile(Et, N, H, E, ldE, Rel, ldR, head, c, live, nfb,
+                [&](int fi, int64_t &anchor, int64_t &rel) {
+                  const int64_t f = f0 + fi;
+                  anchor = tr[3 * f + (head ? 2 : 0)];
+                  rel = tr[3 * f + 1];
+                },
+                s_a, s_b, acc);
   const int64_t *fptr = head ? head_ptr : tail_ptr;
   const int32_t *fidx = head ? head_idx : tail_idx;
   const int lane = threadIdx.x & 63;
@@ -404,6 +359,12 @@ __global__ void k_rank_final(const int32_t *__restrict__ counts, int64_t nf, int
 }
 
 }  // namespace
+
+hipError_t lp_transpose(const float *E, int64_t ldE, int64_t N, int H, float *Et, hipStream_t s) {
+  dim3 tg((unsigned)((N + 31) / 32), (unsigned)((H + 31) / 32));
+  k_transpose<<<tg, 256, 0, s>>>(E, ldE, N, H, Et);
+  return hipGetLastError();
+}
 }  // namespace mrgcn
 
 using namespace mrgcn;
@@ -868,8 +829,7 @@ int mrgcn_distmult_ranks(const float *E, int64_t ldE, int64_t num_nodes, const f
   float *Et = (float *)workspace;
   float *truth = Et + (int64_t)H * num_nodes;
   int32_t *counts = (int32_t *)(truth + num_facts);
-  dim3 tg((unsigned)((num_nodes + 31) / 32), (unsigned)((H + 31) / 32));
-  k_transpose<<<tg, 256, 0, st>>>(E, ldE, num_nodes, H, Et);
+  MRGCN_HIP_TRY(lp_transpose(E, ldE, num_nodes, H, Et, st));
   k_true_scores<<<(unsigned)((num_facts + 127) / 128), 128, 0, st>>>(E, ldE, Rel, ldR, H, triples, num_facts,
                                                                       num_nodes, truth, counts);
   const int64_t ftiles = (num_facts + kFB - 1) / kFB;

@@ -1,0 +1,85 @@
+// The DistMult candidate scores shared by the rank kernel (distmult.hip: k_rank_counts) and the top-k kernel
+// (distmult_topk.hip: k_topk_tiles): ONE body, so that a fact that "ranks 3" sits at position 3 of the list
+// predict_topk returns — the same float32 products in the same order, bit for bit.
+#pragma once
+
+#include "common.hpp"
+
+namespace mrgcn {
+
+constexpr int kLpTB = 256;  // candidates per block (one per thread)
+constexpr int kLpFB = 8;    // facts / queries per block
+constexpr int kLpHT = 64;   // h tile of the per-fact vectors in LDS
+
+// Et[h, c] = E[c, h] on `s` (distmult.hip)
+hipError_t lp_transpose(const float *E, int64_t ldE, int64_t N, int H, float *Et, hipStream_t s);
+
+__device__ __forceinline__ bool in_sorted(const int32_t *__restrict__ a, int64_t lo, int64_t hi, int32_t key) {
+  while (lo < hi) {
+    const int64_t mid = (lo + hi) >> 1;
+    const int32_t v = a[mid];
+    if (v == key) return true;
+    if (v < key) lo = mid + 1; else hi = mid;
+  }
+  return false;
+}
+
+// acc[i] = the score of candidate c (this thread's; `live` = c < N) for pair i < nfb of the block, candidates read
+// coalesced from the transposed table.  head == false: the candidate fills the tail slot,
+// acc += (E[anchor,h] Rel[rel,h]) * E[c,h]; head == true: the head slot, acc += (E[c,h] Rel[rel,h]) * E[anchor,h];
+// sequential over h = 0 .. H-1, nothing contracted.  ids(i, anchor, rel) names pair i's rows.  Every thread of the
+// block must call it (barriers); s_a / s_b are the block's [kLpFB][kLpHT] staging arrays.
+template <class Ids>
+__device__ __forceinline__ void lp_score_tile(const float *__restrict__ Et, int64_t N, int H,
+                                              const float *__restrict__ E, int64_t ldE,
+                                              const float *__restrict__ Rel, int64_t ldR, bool head, int64_t c,
+                                              bool live, int nfb, Ids ids, float (*s_a)[kLpHT], float (*s_b)[kLpHT],
+                                              float (&acc)[kLpFB]) {
+#pragma clang fp contract(off)
+#pragma unroll
+  for (int i = 0; i < kLpFB; ++i) acc[i] = 0.f;
+  for (int h0 = 0; h0 < H; h0 += kLpHT) {
+    const int hn = (H - h0) < kLpHT ? (H - h0) : kLpHT;
+    __syncthreads();
+    for (int i = threadIdx.x; i < kLpFB * kLpHT; i += kLpTB) {
+      const int fi = i / kLpHT, h = i % kLpHT;
+      float a = 0.f, b = 0.f;
+      if (fi < nfb && h < hn) {
+        int64_t anchor, rel;
+        ids(fi, anchor, rel);
+        const float pv = Rel[rel * ldR + h0 + h];
+        const float ev = E[anchor * ldE + h0 + h];
+        if (head) {
+          a = pv;
+          b = ev;
+        } else {
+          a = ev * pv;
+        }
+      }
+      s_a[fi][h] = a;
+      s_b[fi][h] = b;
+    }
+    __syncthreads();
+    if (live) {
+      for (int h = 0; h < hn; ++h) {
+        const float e = Et[(int64_t)(h0 + h) * N + c];
+        if (head) {
+#pragma unroll
+          for (int i = 0; i < kLpFB; ++i) {
+            const float ep = e * s_a[i][h];
+            const float epo = ep * s_b[i][h];
+            acc[i] = acc[i] + epo;
+          }
+        } else {
+#pragma unroll
+          for (int i = 0; i < kLpFB; ++i) {
+            const float spe = s_a[i][h] * e;
+            acc[i] = acc[i] + spe;
+          }
+        }
+      }
+    }
+  }
+}
+
+}  // namespace mrgcn

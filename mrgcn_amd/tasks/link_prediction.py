@@ -608,3 +608,149 @@ def evaluate_batches(batches, model, filtered=True):
         rankings[rank_type] = [r for r_list in rankings[rank_type]
                                for r in (r_list if isinstance(r_list, list) else [r_list])]
     return mrr, hits_at_k, rankings
+
+
+# ---- top-k candidate completion (the question a trained model answers: which nodes complete (s, p, ?) / (?, p, o)) ---
+TOPK_MAX = 256  # include/mrgcn_hip.h: mrgcn_distmult_topk takes 1 <= k <= 256
+_SIDES = {"tail": 0, "head": 1}
+
+
+def _side(side) -> int:
+    if side not in _SIDES:
+        raise ValueError(f"side must be 'tail' or 'head', not {side!r}")
+    return _SIDES[side]
+
+
+def known_lists(queries, known, side="tail"):
+    """Per query (anchor, relation) the sorted, duplicate-free int32 nodes c for which the completed triple is a row of
+    `known` ([m, 3] facts): (anchor, relation, c) for side="tail", (c, relation, anchor) for side="head".  Returns the
+    CSR pair (ptr int64 [nq + 1], idx int32) `predict_topk` excludes.  Unlike `filter_lists` nothing is taken out as
+    "the fact's own answer": a query has no answer, what is known is excluded."""
+    head = _side(side)
+    q = np.asarray(queries, dtype=np.int64).reshape(-1, 2)
+    kn = np.asarray(known, dtype=np.int64).reshape(-1, 3)
+    nq = len(q)
+    ptr = np.zeros(nq + 1, np.int64)
+    if nq == 0 or len(kn) == 0:
+        return ptr, np.zeros(0, np.int32)
+    ka, kr, kc = (kn[:, 2], kn[:, 1], kn[:, 0]) if head else (kn[:, 0], kn[:, 1], kn[:, 2])
+    # the distinct (anchor, relation, completion) rows, sorted; groups of equal (anchor, relation)
+    order = np.lexsort((kc, kr, ka))
+    ka, kr, kc = ka[order], kr[order], kc[order]
+    uniq = np.ones(len(ka), bool)
+    uniq[1:] = (ka[1:] != ka[:-1]) | (kr[1:] != kr[:-1]) | (kc[1:] != kc[:-1])
+    ka, kr, kc = ka[uniq], kr[uniq], kc[uniq]
+    first = np.ones(len(ka), bool)
+    first[1:] = (ka[1:] != ka[:-1]) | (kr[1:] != kr[:-1])
+    gstart = np.flatnonzero(first)                       # group -> first member
+    gend = np.append(gstart[1:], len(ka))
+    # every query's group: the (anchor, relation) pairs of groups and queries ranked together
+    ga, gr = ka[gstart], kr[gstart]
+    both_a, both_r = np.concatenate([ga, q[:, 0]]), np.concatenate([gr, q[:, 1]])
+    _, inv = np.unique(np.stack([both_a, both_r], 1), axis=0, return_inverse=True)
+    inv = inv.reshape(-1)
+    ng = len(ga)
+    group_of_rank = np.full(int(inv.max()) + 1, -1, np.int64)
+    group_of_rank[inv[:ng]] = np.arange(ng)
+    gq = group_of_rank[inv[ng:]]                         # -1: nothing known for the query
+    has = gq >= 0
+    cnt = np.where(has, gend[np.maximum(gq, 0)] - gstart[np.maximum(gq, 0)], 0)
+    np.cumsum(cnt, out=ptr[1:])
+    off = np.arange(int(ptr[-1])) - np.repeat(ptr[:-1], cnt)
+    idx = kc[np.repeat(gstart[np.maximum(gq, 0)], cnt) + off].astype(np.int32)
+    return ptr, idx
+
+
+def _check_ids(queries, num_nodes: int, num_relations: int):
+    """Raises for a query whose node is outside [0, num_nodes) or whose relation is outside [0, num_relations)."""
+    if len(queries) == 0:
+        return
+    if torch.is_tensor(queries):   # (on the device: one readback for the four bounds)
+        lo_n, lo_r, hi_n, hi_r = torch.cat([queries.min(0).values, queries.max(0).values]).tolist()
+    else:
+        (lo_n, lo_r), (hi_n, hi_r) = (int(v) for v in queries.min(0)), (int(v) for v in queries.max(0))
+    if lo_n < 0 or hi_n >= num_nodes:
+        raise ValueError(f"predict_topk: query node ids must lie in [0, {num_nodes}): found {lo_n} .. {hi_n}")
+    if lo_r < 0 or hi_r >= num_relations:
+        raise ValueError(f"predict_topk: relation ids must lie in [0, {num_relations}) (the rows of edge_embeddings): "
+                         f"found {lo_r} .. {hi_r}")
+
+
+def predict_topk(queries, node_embeddings, edge_embeddings, k, side="tail", known=None):
+    """The k best completions of every query: `queries` [nq, 2] rows (anchor node, relation) — numpy or a tensor —,
+    side="tail" ranks the nodes c of (anchor, relation, c), side="head" those of (c, relation, anchor).  Returns
+    (idx int64 [nq, k], scores float32 [nq, k]) on the embeddings' device: score descending, equal scores (-0 == +0) by
+    ascending node id, rows with fewer than k candidates end in (-1, -inf).  The scores are those of
+    `compute_ranks_fast`, bit for bit (sequential float32 sums), so a fact of rank r sits at position r of its row
+    when no score ties; the [nq, nodes] score matrix is never stored (mrgcn_distmult_topk).  `known`: None, an [m, 3]
+    array of facts whose completions are excluded (`known_lists` builds the lists), or a ready (ptr, idx) pair of
+    device tensors (int64 [nq + 1], int32) — with it and `queries` as a device tensor a call builds nothing on the host
+    and can be captured in a graph (ids are then checked outside captures only).  1 <= k <= 256.  Embeddings must be
+    finite; results with NaN are undefined."""
+    head = _side(side)
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= TOPK_MAX:
+        raise ValueError(f"predict_topk: k must be an integer in [1, {TOPK_MAX}], not {k!r}")
+    k = int(k)
+    E = _f32_rows(node_embeddings.detach(), "node_embeddings")
+    Rel = _f32_rows(edge_embeddings.detach(), "edge_embeddings")
+    dev = E.device
+    N, H = int(E.shape[0]), int(E.shape[1])
+    if Rel.shape[1] != H:
+        raise ValueError("predict_topk: node and edge embeddings differ in width")
+    if N == 0:
+        raise ValueError("predict_topk: no nodes")
+    on_device = torch.is_tensor(queries) and queries.is_cuda
+    q_host = None
+    if on_device:
+        q = queries.to(dev, torch.int64).reshape(-1, 2).contiguous()
+        if not torch.cuda.is_current_stream_capturing():
+            _check_ids(q, N, int(Rel.shape[0]))
+    else:
+        q_host = (queries.numpy() if torch.is_tensor(queries) else np.asarray(queries)).astype(np.int64).reshape(-1, 2)
+        _check_ids(q_host, N, int(Rel.shape[0]))
+        q = torch.from_numpy(np.ascontiguousarray(q_host)).to(dev)
+    nq = int(q.shape[0])
+    ptr = idx = None
+    if known is not None:
+        if isinstance(known, (tuple, list)) and len(known) == 2 and all(torch.is_tensor(a) for a in known):
+            ptr, idx = known
+            if not (ptr.is_cuda and idx.is_cuda and ptr.dtype == torch.int64 and idx.dtype == torch.int32
+                    and ptr.numel() == nq + 1):
+                raise ValueError("predict_topk: known=(ptr, idx) must be device tensors, int64 [nq + 1] and int32")
+            ptr, idx = ptr.contiguous(), idx.contiguous()
+        elif isinstance(known, (tuple, list)) and len(known) == 2 and any(a is None or torch.is_tensor(a) for a in known):
+            raise _lib.MrgcnError("predict_topk: exclusion lists need both tensors of the (ptr, idx) pair")
+        else:
+            if q_host is None:
+                q_host = q.cpu().numpy()
+            kn = known.cpu().numpy() if torch.is_tensor(known) else np.asarray(known)
+            ptr, idx = (torch.from_numpy(a).to(dev) for a in known_lists(q_host, kn, side))
+        if idx.numel() == 0:   # (an empty tensor has no address; the lists are empty either way)
+            idx = torch.zeros(1, dtype=torch.int32, device=dev)
+    out_idx = torch.empty((nq, k), dtype=torch.int64, device=dev)
+    out_score = torch.empty((nq, k), dtype=torch.float32, device=dev)
+    if nq == 0:
+        return out_idx, out_score
+    lib = _lib.load()
+    ws_bytes = int(lib.mrgcn_distmult_topk_workspace(N, H, nq, k))
+    if ws_bytes < 0:
+        raise _lib.MrgcnError("predict_topk: sizes outside mrgcn_distmult_topk's limits")
+    ws = torch.empty((ws_bytes + 7) // 8, dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(lib.mrgcn_distmult_topk(_ptr(E), E.stride(0), N, _ptr(Rel), Rel.stride(0), H, _ptr(q), nq, head,
+                                           _ptr(ptr), _ptr(idx), k, _ptr(ws), ws_bytes, _ptr(out_idx),
+                                           _ptr(out_score), _stream()), "distmult_topk")
+    return out_idx, out_score
+
+
+def predict_links(model, batch, queries, k, side="tail", known=None):
+    """`predict_topk` on a model's own embeddings: `model.eval()`, then — without gradients — the batch's node
+    embeddings (`_embed`: an MRGCN's forward, or a bare RGCN on the batch structure) against the model's relation
+    embeddings.  `batch`: a FullBatch or a masked / sliced MiniBatch.  With a mini-batch the node ids of `queries`,
+    `known` and the result are the BATCH-LOCAL ones (positions in `batch.node_index`, as in the facts `mkbatches`
+    returns); map results back with `batch.node_index[idx]`.  The model is left in eval mode."""
+    _side(side)
+    model.eval()
+    with torch.no_grad():
+        E = _embed(model, batch)
+        return predict_topk(queries, E, _relations(model), k, side=side, known=known)

@@ -76,6 +76,8 @@ done
 # build it, copy tools/node_dropout_probe.py into it and run `python3 tools/node_dropout_probe.py --rows p0 --out <file>`
 # there first; NODE_DROPOUT_PARENT_JSON=<file> then puts that row into the result.  Without it the file holds no row (a).
 python3 tools/node_dropout_probe.py ${NODE_DROPOUT_PARENT_JSON:+--parent $NODE_DROPOUT_PARENT_JSON} --out $o/node_dropout_probe.json > $o/node_dropout_probe.txt 2> $o/node_dropout_probe.err
+# (10d) top-k completion at the FB15k-237 decoder shape: predict_topk, torch.topk over the score matrix, compute_ranks_fast
+python3 tools/lp_topk_probe.py --out $o/lp_topk_probe.json > $o/lp_topk_probe.txt 2> $o/lp_topk_probe.err
 hipcc -O3 --offload-arch=gfx950 -std=c++17 tools/lab/copy_lab.hip -o /tmp/copy_lab 2>/dev/null && /tmp/copy_lab > $o/copy_lab.txt 2>&1
 python3 tools/lab/spmm_hot_lab.py > $o/spmm_hot_lab.txt 2>&1
 # the CPU suite last: the tree these artefacts describe is green
