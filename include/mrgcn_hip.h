@@ -247,7 +247,10 @@ int mrgcn_basis_contract_bwd_f32(const float *comp, const float *V, const float 
 /* relation transform — replaces einsum('ij,bjk->bik', X, W_F) + reshape of graph.py:93-94,
  * restricted to touched columns (f32 MFMA 16x16x4 when K <= 256 and F <= 64):
  *     Out[o(c), 0:F] = X[j_c, 0:K] . W[r_c, 0:K, 0:F]          X: [N, ldX], W: [R, K, F]
- * o(c) = c (plain compact order, e.g. to serve as `addend`) or MPOS[c] (`operand_order` != 0) */
+ * o(c) = c (plain compact order, e.g. to serve as `addend`) or MPOS[c] (`operand_order` != 0).  Every kernel form
+ * writes the whole padded row, zeros in [F, ldOut), for any F <= ldOut <= INT32_MAX, and nothing else.  F <= 64: a
+ * wider transform is an error (MRGCN_ERR_INVALID) — tile the feature dimension: one call per slice of W's columns,
+ * each with an output of its own. */
 int mrgcn_rel_transform_fwd_f32(const mrgcn_plan_t *plan, const float *X, int64_t ldX, int32_t K,
                                 const float *W, int32_t F, float *Out, int64_t ldOut,
                                 int32_t operand_order, void *stream);

@@ -101,7 +101,7 @@ int mrgcn_support_rel_transform_fwd_f32(const mrgcn_support_t *q, const float *X
                                         int32_t K, const float *W, int32_t F, float *T, int64_t ldT, void *stream) {
   REQUIRE_FORWARD(q);
   MRGCN_REQUIRE(X && W && T, "NULL");
-  MRGCN_REQUIRE(K > 0 && F > 0 && ldX >= K && ldT >= F, "K / F / leading dimensions");
+  MRGCN_REQUIRE(K > 0 && F > 0 && ldX >= K && ldT >= F && ldT <= INT32_MAX, "K / F / leading dimensions");
   if (!xform_mfma_fwd_supported(K, F)) {
     set_error("mrgcn_support_rel_transform_fwd_f32: shape outside the matrix-core transforms' limits");
     return MRGCN_ERR_UNSUPPORTED;

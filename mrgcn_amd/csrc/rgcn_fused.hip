@@ -1925,7 +1925,7 @@ template <typename OT>
 int rel_transform_fwd_impl(const mrgcn_plan_t *p, const float *X, int64_t ldX, int32_t K, const float *W,
                            int32_t F, OT *Out, int64_t ldOut, int32_t operand_order, void *stream) {
   MRGCN_REQUIRE(p && X && W && Out, "NULL");
-  MRGCN_REQUIRE(K > 0 && F > 0 && ldX >= K && ldOut >= F, "K / F / leading dimensions");
+  MRGCN_REQUIRE(K > 0 && F > 0 && ldX >= K && ldOut >= F && ldOut <= INT32_MAX, "K / F / leading dimensions");
   MRGCN_REQUIRE(F <= 64, "rel_transform supports F <= 64 (tile the feature dimension)");
   const RelOrder o = p->order_for(K);  // narrow inputs: the order with narrow node bands
   if (o.n_relchunks == 0) return MRGCN_OK;

@@ -237,6 +237,15 @@ __global__ __launch_bounds__(256) void k_xform_mfma_fwd(
         if (n < n_store) store_operand<OT>(Out + orow * ldOut + n, acc[nt][reg]);  // zeros past F: whole padded row
       }
     }
+    if (n_store > NT * 16) {  // (block uniform) a padded row that ends past the launch's tiles: zeros to its end
+#pragma unroll
+      for (int reg = 0; reg < 4; ++reg) {
+        const int32_t ok = __shfl(cid, 4 * kq + reg, 64);
+        const int64_t orow = __shfl(my_rout, 4 * kq + reg, 64);
+        if (ok < 0) continue;
+        for (int n = NT * 16 + m; n < n_store; n += 16) store_operand<OT>(Out + orow * ldOut + n, 0.f);
+      }
+    }
   }
 }
 
@@ -977,6 +986,7 @@ static int xform_mfma_fwd_one(const mrgcn_plan *p, const RelOrder &o, const int3
   if (o.n_relchunks == 0) return MRGCN_OK;
   int NT = (n_store + 15) / 16;  // tiles that cover the columns to write
   if (NT < (F + 15) / 16) NT = (F + 15) / 16;
+  if (NT > kMaxNT) NT = kMaxNT;  // (columns past the last tile: the kernel's zero tail)
   const int ksteps = (K + 15) / 16;
   // (the staged weight tile is sized by the INSTANTIATED k-step count: its row stride is a compile-time constant)
   auto lds_for = [&](int ks_inst) { return (size_t)NT * 16 * (ks_inst * 16 + 4) * sizeof(float); };
@@ -1044,11 +1054,13 @@ int xform_mfma_fwd(const mrgcn_plan *p, const RelOrder &o, const int32_t *rin_id
                    const float *In, int64_t ldIn, int K, const float *W, bool trans_w, int F, void *Out,
                    int64_t ldOut, hipStream_t s, bool out_bf16, const uint8_t *col_live) {
   const int64_t rstride = (int64_t)K * F;
-  // columns a row may receive: zeros past F up to the end of the padded row (at most the launch's 64 / the last tile)
-  const int width = (int)std::min<int64_t>(ldOut, F <= kMaxNT * 16 ? kMaxNT * 16 : (F + 15) / 16 * 16);
+  // columns a row may receive: zeros past F up to the end of the padded row — the WHOLE row in the one-launch form
+  // (a row longer than the launch's 64 tile columns ends in the kernel's zero tail), up to the last tile in the sliced
+  // form (its rows are the dX pass's workspace, padded to four floats)
   if (F <= kMaxNT * 16)
     return xform_mfma_fwd_one(p, o, rin_idx, rout_idx, In, ldIn, K, W, trans_w, F, Out, ldOut, s, out_bf16, col_live,
-                              rstride, std::min(width, kMaxNT * 16));
+                              rstride, (int)ldOut);  // (the entry points refuse ldOut > INT32_MAX)
+  const int width = (int)std::min<int64_t>(ldOut, (F + 15) / 16 * 16);
   // wide outputs (the dX pass of a wide layer: Z[c, 0:K_x] = dM[c] . W[r_c]^T with K_x up to 256): slices of 64
   // columns, one launch each — the input rows are 40 bytes, every slice reads them again
   if (!trans_w || out_bf16) {
