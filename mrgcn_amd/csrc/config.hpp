@@ -20,17 +20,11 @@ enum CfgKey : int {
   CFG_NODE_BAND_NARROW,
   CFG_HOT_MIN,
   CFG_AVOID_STRADDLE,
-  CFG_DEBUG_CAPTURED_MEMSET,
   CFG_SUP_TIMING,
   CFG_XFORM_MFMA,
-  CFG_MIX_PAD,
-  CFG_MIX_COLS,
   CFG_MIX_WIDE,
   CFG_MIX_MFMA,
-  CFG_MIX_FWD_TB,
   CFG_MIX_NODE,
-  CFG_MIX_BWD_TB,
-  CFG_MIX_BWD_PER_CU,
   CFG_FUSED_ADAM,
   CFG_ADAM_LIST,
   CFG_DCOMP_WIDE,
@@ -39,9 +33,6 @@ enum CfgKey : int {
   CFG_SPMM_XCD,
   CFG_SPMM_TAIL,
   CFG_SPMM_FOLD,
-  CFG_SPMM_TINY,
-  CFG_SUP_MIX_TB,
-  CFG_SUP_MIX_NB,
   CFG_WIDE_BWD,
   CFG_XFORM_COLS_LDS,
   CFG_SPMM_LITERAL_V3,
@@ -51,7 +42,6 @@ enum CfgKey : int {
   CFG_MIX_TICKETS,
   CFG_MIX_TICKET_TILE,
   CFG_SPMM_T_SEG,
-  CFG_SUP_MIX_ONCE,
   CFG_COUNT
 };
 int64_t cfg(CfgKey k);

@@ -38,9 +38,9 @@ constexpr int kMixFwdTB = 1024;
 constexpr int kPre = 8;
 
 // =====================================================================================
-// basis mix, forward.  thread = (node j, padded feature o < FW); V[j, ., o] in registers.
+// basis mix, forward.  thread = (node j, feature o < F); V[j, ., o] in registers.
 //   M[mpos[c], o] = (addend ? addend[c, o] : 0) (+ old value if accumulate)
-//                   + sum_b comp[r_c, b] * V[j, b, o]          for o < F;  0 for F <= o < FW
+//                   + sum_b comp[r_c, b] * V[j, b, o]
 // =====================================================================================
 // LDS row stride of the staged comp slice: multiple of 4 floats (16-byte ds_read_b128) and
 // = 12 mod 32 banks when BT = 40, so that the 4-6 relations a wave touches at once land on
@@ -67,7 +67,7 @@ __global__ __launch_bounds__(kMixFwdTB) void k_mix_fwd(const int32_t *__restrict
                                                     const int32_t *__restrict__ mpos,
                                                     const float *__restrict__ V,
                                                     const float *__restrict__ comp, int64_t N, int R,
-                                                    int B, int b0, int F, int FW,
+                                                    int B, int b0, int F,
                                                     const float *__restrict__ addend, int64_t ldA,
                                                     OT *__restrict__ M, int64_t ldM, int accumulate,
                                                     int comp_in_lds,
@@ -82,19 +82,20 @@ __global__ __launch_bounds__(kMixFwdTB) void k_mix_fwd(const int32_t *__restrict
     }
     __syncthreads();
   }
-  const int64_t total = N * FW;
+  const int64_t total = N * F;
   for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total;
        t += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t j = t / FW;
-    const int o = (int)(t - j * FW);
-    const bool live = o < F;
+    const int64_t j = t / F;
+    const int o = (int)(t - j * F);
     const int32_t c0 = nptr[j], c1 = nptr[j + 1];
     if (c0 == c1) continue;
     float v[BT];
     const int64_t jv = node_ids ? (int64_t)node_ids[j] : j;  // (a node list: entry j of it owns columns nptr[j] ..)
+    // (the redundant `o < F` keeps these loads lane-predicated: without it the allocator takes one more register in
+    // most instantiations and the BT = 64 form, which already spills at its 128, one more dword of scratch)
 #pragma unroll
     for (int b = 0; b < BT; ++b)
-      v[b] = (live && b < nb) ? V[(jv * B + (b0 + b)) * F + o] : 0.f;
+      v[b] = (o < F && b < nb) ? V[(jv * B + (b0 + b)) * F + o] : 0.f;
 
     // the node's columns in chunks of kPre: everything a chunk needs (relation id, operand row,
     // addend) is requested up front, so a chunk costs one round trip however long the node is
@@ -107,7 +108,7 @@ __global__ __launch_bounds__(kMixFwdTB) void k_mix_fwd(const int32_t *__restrict
         const int32_t c = (cb + i < c1) ? cb + i : cb;
         rr[i] = urel[c];
         pp[i] = mpos ? mpos[c] : c;
-        aa[i] = (addend && live) ? addend[(int64_t)c * ldA + o] : 0.f;
+        aa[i] = addend ? addend[(int64_t)c * ldA + o] : 0.f;
       }
 #pragma unroll
       for (int i = 0; i < kPre; ++i) {
@@ -129,16 +130,15 @@ __global__ __launch_bounds__(kMixFwdTB) void k_mix_fwd(const int32_t *__restrict
           if constexpr (sizeof(OT) == 2) {
             // bf16 rows: two features per 4-byte store (2-byte scattered stores were measured
             // 30 % slower than the fp32 rows they replace).  Lanes o and o + 1 belong to the same
-            // node (FW is even), so they take this branch together.
-            const float mine = live ? s : 0.f;
-            const float next = __shfl_down(mine, 1, kWave);
-            if ((o & 1) == 0 && (FW & 1) == 0) {
-              *reinterpret_cast<uint32_t *>(m) = (uint32_t)f32_to_bf16(mine) | ((uint32_t)f32_to_bf16(next) << 16);
-            } else if (FW & 1) {
-              store_operand<OT>(m, mine);
+            // node (F is even), so they take this branch together.
+            const float next = __shfl_down(s, 1, kWave);
+            if ((o & 1) == 0 && (F & 1) == 0) {
+              *reinterpret_cast<uint32_t *>(m) = (uint32_t)f32_to_bf16(s) | ((uint32_t)f32_to_bf16(next) << 16);
+            } else if (F & 1) {
+              store_operand<OT>(m, s);
             }
           } else {
-            store_operand<OT>(m, live ? s : 0.f);
+            store_operand<OT>(m, s);
           }
         }
       }
@@ -456,80 +456,6 @@ __global__ __launch_bounds__(kFwdTB) void k_mix_fwd_mfma(
 }
 
 // =====================================================================================
-// basis mix, forward, column-parallel form (B <= 64): thread = compact column c, lanes =
-// consecutive columns.  Index loads (urel / unode / mpos) are coalesced and independent, there
-// is no per-node loop (no divergence under degree skew, no dependent load chain); the V rows of
-// a node are re-read by its ~5 columns out of L1/L2, so HBM still streams V once.
-//   M[mpos[c], 0:FW] = [ addend[c, 0:F] + sum_b comp[r_c, b] * V[b, j_c, 0:F] | 0 ]
-// comp lives in LDS with an odd row stride (lanes hold different relations: conflict free).
-// =====================================================================================
-template <int FT, bool VEC2>
-__global__ __launch_bounds__(kMixTB) void k_mix_fwd_cols(const int32_t *__restrict__ urel,
-                                                         const int32_t *__restrict__ unode,
-                                                         const int32_t *__restrict__ mpos,
-                                                         const float *__restrict__ V,
-                                                         const float *__restrict__ comp, int64_t N, int R,
-                                                         int B, int F, int FW,
-                                                         const float *__restrict__ addend, int64_t ldA,
-                                                         float *__restrict__ M, int64_t ldM, int64_t ncols,
-                                                         int comp_in_lds) {
-  extern __shared__ float s_comp[];  // [R][BS], BS = B | 1
-  const int BS = B | 1;
-  if (comp_in_lds) {
-    for (int t = threadIdx.x; t < R * B; t += blockDim.x) {
-      const int r = t / B, b = t - r * B;
-      s_comp[r * BS + b] = comp[t];
-    }
-    __syncthreads();
-  }
-  for (int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; c < ncols;
-       c += (int64_t)gridDim.x * blockDim.x) {
-    const int r = urel[c];
-    const int64_t j = unode[c];
-    const int64_t pos = mpos ? mpos[c] : c;
-    float acc[FT];
-#pragma unroll
-    for (int o = 0; o < FT; ++o) acc[o] = (addend && o < F) ? addend[c * ldA + o] : 0.f;
-    const float *cr = comp_in_lds ? (s_comp + r * BS) : (comp + (int64_t)r * B);
-#pragma unroll 4
-    for (int b = 0; b < B; ++b) {
-      const float w = cr[b];
-      const float *vp = V + ((int64_t)j * B + b) * F;
-      if (VEC2) {
-#pragma unroll
-        for (int o = 0; o < FT; o += 2)
-          if (o < F) {
-            const float2 vv = *reinterpret_cast<const float2 *>(vp + o);
-            acc[o] = fmaf(w, vv.x, acc[o]);
-            acc[o + 1] = fmaf(w, vv.y, acc[o + 1]);
-          }
-      } else {
-#pragma unroll
-        for (int o = 0; o < FT; ++o)
-          if (o < F) acc[o] = fmaf(w, vp[o], acc[o]);
-      }
-    }
-    float *m = M + pos * ldM;
-    if ((ldM & 3) == 0 && (FW & 3) == 0) {
-#pragma unroll
-      for (int o = 0; o < FT; o += 4)
-        if (o < FW) {
-          float4 q;
-          q.x = (o + 0 < F) ? acc[o + 0] : 0.f;
-          q.y = (o + 1 < F) ? acc[o + 1] : 0.f;
-          q.z = (o + 2 < F) ? acc[o + 2] : 0.f;
-          q.w = (o + 3 < F) ? acc[o + 3] : 0.f;
-          *reinterpret_cast<float4 *>(m + o) = q;
-        }
-    } else {
-#pragma unroll
-      for (int o = 0; o < FT; ++o)
-        if (o < FW) m[o] = (o < F) ? acc[o] : 0.f;
-    }
-  }
-}
-
-// =====================================================================================
 // basis mix, backward.
 //
 //   k_mix_bwd_nm    (F <= 16, B <= 64) WAVE STEPS OVER NODES, LANE = BASIS: dV and dcomp in one pass.
@@ -618,7 +544,9 @@ __global__ __launch_bounds__(kMixTB) void k_mix_bwd_dv(const int32_t *__restrict
 }
 
 // ---- wave over nodes, lane = basis ---------------------------------------------------------------
-constexpr int kNodeTB = 1024;  // launch bound; the block size is picked at launch (MRGCN_MIX_BWD_TB): its waves share one LDS copy of the dcomp accumulators
+constexpr int kNodeTB = 1024;  // launch bound; the blocks are launched with kNodeLaunchTB threads: their waves share one LDS copy of the dcomp accumulators
+constexpr int kNodeLaunchTB = 512;
+static_assert(kNodeLaunchTB % 64 == 0 && kNodeLaunchTB <= kNodeTB && 4 * kNodeLaunchTB <= 2048, "whole waves; four blocks per CU");
 constexpr int kGroup = 4;     // consecutive nodes whose pointers / flags / relation ids a wave fetches at once
 
 // F floats of one basis row, rows only 4 * F bytes apart: 8-byte aligned when F is even.  The vector memory
@@ -1566,7 +1494,7 @@ namespace {
 
 // the columns a basis mix walks: a plan's (every node) or a gradient support's (a node list, rows by live number)
 struct MixCols {
-  const int32_t *nptr, *urel, *mpos, *unode, *node_ids;
+  const int32_t *nptr, *urel, *mpos, *node_ids;
   int64_t N, ncols;
   int R;
   unsigned long long *tickets = nullptr;  // the plan's work-ticket counters (k_mix_fwd_mfma's TK form), or NULL
@@ -1585,39 +1513,9 @@ int mix_fwd_cols(const MixCols *p, const float *V, const float *comp, int32_t B,
   const int32_t *node_ids = p->node_ids;
   // Columns F..ldM of M are padding that only the SpMM's 16-byte gathers touch, and their
   // products land in accumulator lanes that are never stored (test: padding set to 1e30 does
-  // not leak): by default only the F real features are computed and written (a sixth fewer
-  // lanes and stores at F = 10, ld = 12); MRGCN_MIX_PAD=1 writes zeros there.
-  const bool write_pad = cfg(CFG_MIX_PAD) != 0;
-  const int FW = write_pad ? (int)ldM : F;
-  // node-major is the default: measured 2.7 ms vs 4.95 ms for the column-parallel form (AM shape)
-  const bool by_cols = cfg(CFG_MIX_COLS) != 0;
+  // not leak): only the F real features are computed and written (a sixth fewer lanes and
+  // stores at F = 10, ld = 12).
   const int32_t *mpos_arg = p->mpos;
-  if constexpr (sizeof(OT) == 4 && sizeof(AT) == 4) if (by_cols && !node_ids && B <= 64 && F <= 64 && FW <= 64) {
-    size_t lds = (size_t)R * (B | 1) * sizeof(float);
-    int in_lds = lds <= kLdsBudget;
-    if (!in_lds) lds = 0;
-    int grid = mix_grid(lds, p->ncols);
-    const bool v2 = (F % 2 == 0) && (((uintptr_t)V) % 8 == 0);
-    const int need = FW > F ? FW : F;
-#define MIXC_GO(T)                                                                                      \
-  do {                                                                                                  \
-    if (v2)                                                                                             \
-      k_mix_fwd_cols<T, true><<<dim3(grid), dim3(kMixTB), lds, s>>>(                                    \
-          p->urel, p->unode, mpos_arg, V, comp, N, R, B, F, FW, addend, ldA, M, ldM, p->ncols, in_lds);  \
-    else                                                                                                \
-      k_mix_fwd_cols<T, false><<<dim3(grid), dim3(kMixTB), lds, s>>>(                                   \
-          p->urel, p->unode, mpos_arg, V, comp, N, R, B, F, FW, addend, ldA, M, ldM, p->ncols, in_lds);  \
-  } while (0)
-    if (need <= 4) MIXC_GO(4);
-    else if (need <= 8) MIXC_GO(8);
-    else if (need <= 12) MIXC_GO(12);
-    else if (need <= 16) MIXC_GO(16);
-    else if (need <= 32) MIXC_GO(32);
-    else MIXC_GO(64);
-#undef MIXC_GO
-    MRGCN_HIP_TRY(hipGetLastError());
-    return MRGCN_OK;
-  }
   if constexpr (sizeof(OT) == 4) {
     const bool wide_on = cfg(CFG_MIX_WIDE) != 0;
     if (wide_on && !addend && F > 16 && F <= 256 && F % 4 == 0 && B <= 4 && ldM % 4 == 0 &&
@@ -1708,12 +1606,11 @@ int mix_fwd_cols(const MixCols *p, const float *V, const float *comp, int32_t B,
     size_t lds = (size_t)R * comp_stride(BT) * sizeof(float);
     int in_lds = lds <= kLdsBudget;
     if (!in_lds) lds = 0;
-    const int fwd_tb = (int)cfg(CFG_MIX_FWD_TB);
-    int grid = mix_grid(lds, N * FW);
+    int grid = mix_grid(lds, N * F);
     const float *add = acc ? nullptr : addend;
 #define MIX_GO(T)                                                                                    \
-  k_mix_fwd<T, OT><<<dim3(grid), dim3(fwd_tb), lds, s>>>(p->nptr, p->urel, mpos_arg, V, comp, N, R, B, b0, \
-                                                     F, FW, add, ldA, M, ldM, acc, in_lds, node_ids)
+  k_mix_fwd<T, OT><<<dim3(grid), dim3(kMixFwdTB), lds, s>>>(p->nptr, p->urel, mpos_arg, V, comp, N, R, B, b0, \
+                                                        F, add, ldA, M, ldM, acc, in_lds, node_ids)
     switch (BT) {
       case 2: MIX_GO(2); break;
       case 4: MIX_GO(4); break;
@@ -1735,7 +1632,7 @@ template <typename OT>
 int mix_fwd_impl(const mrgcn_plan_t *p, const float *V, const float *comp, int32_t B, int32_t F,
                  const float *addend, int64_t ldA, OT *M, int64_t ldM, void *stream) {
   MRGCN_REQUIRE(p, "NULL");
-  const MixCols c{p->nptr, p->urel, p->mpos, p->unode, nullptr, p->num_nodes, p->ncols, (int)p->num_relations,
+  const MixCols c{p->nptr, p->urel, p->mpos, nullptr, p->num_nodes, p->ncols, (int)p->num_relations,
                   p->work_tickets};
   return mix_fwd_cols<OT>(&c, V, comp, B, F, addend, ldA, M, ldM, stream);
 }
@@ -1745,7 +1642,7 @@ namespace mrgcn {
 int mix_fwd_arrays(const int32_t *nptr, const int32_t *urel, const int32_t *node_ids, int64_t n_nodes, int64_t ncols,
                    int R, const float *V, const float *comp, int32_t B, int32_t F, float *M, int64_t ldM,
                    hipStream_t s) {
-  const MixCols c{nptr, urel, nullptr, nullptr, node_ids, n_nodes, ncols, R};
+  const MixCols c{nptr, urel, nullptr, node_ids, n_nodes, ncols, R};
   return mix_fwd_cols<float, float>(&c, V, comp, B, F, (const float *)nullptr, 0, M, ldM, (void *)s);
 }
 }  // namespace mrgcn
@@ -2005,7 +1902,7 @@ int mrgcn_basis_mix_fwd_abf16(const mrgcn_plan_t *p, const float *V, const float
                               void *stream) {
   MRGCN_REQUIRE(p && addend, "NULL");
   MRGCN_REQUIRE(B <= 64 && F <= 16 && (B * F) % 4 == 0, "basis_mix_fwd_abf16: B <= 64, F <= 16, B*F % 4 == 0");
-  const MixCols c{p->nptr, p->urel, p->mpos, p->unode, nullptr, p->num_nodes, p->ncols, (int)p->num_relations,
+  const MixCols c{p->nptr, p->urel, p->mpos, nullptr, p->num_nodes, p->ncols, (int)p->num_relations,
                   p->work_tickets};
   if (out_bf16) return mix_fwd_cols<uint16_t, uint16_t>(&c, V, comp, B, F, addend, ldA, (uint16_t *)M, ldM, stream);
   return mix_fwd_cols<float, uint16_t>(&c, V, comp, B, F, addend, ldA, (float *)M, ldM, stream);
@@ -2049,14 +1946,10 @@ int mix_bwd_nm_launch_arrays(const int32_t *nptr, const int32_t *urel, int64_t N
   if (!dc_in_lds) lds = 0;
   // register arrays of exactly F features for the hidden sizes of the BASELINE configs (10, 11)
   const int FT = (F == 10 || F == 11) ? F : (F + 3) / 4 * 4;
-  const int tb_cfg = (int)cfg(CFG_MIX_BWD_TB);
-  const int tb = (tb_cfg >= 64 && tb_cfg <= kNodeTB) ? tb_cfg / 64 * 64 : 512;
+  constexpr int tb = kNodeLaunchTB;
   int per_cu = lds > 0 ? (int)((160 * 1024) / (lds + 1024)) : 4;
   if (per_cu < 1) per_cu = 1;
-  if (per_cu > 4) per_cu = 4;
-  if (per_cu * tb > 2048) per_cu = 2048 / tb;  // 32 waves per CU at most
-  const int per_cu_cap = (int)cfg(CFG_MIX_BWD_PER_CU);  // experiments
-  if (per_cu_cap > 0 && per_cu > per_cu_cap) per_cu = per_cu_cap;
+  if (per_cu > 4) per_cu = 4;  // 32 waves per CU at most
   const int64_t want = ((N + kGroup - 1) / kGroup + (tb / 64) - 1) / (tb / 64);
   int64_t grid = (int64_t)256 * per_cu;
   if (grid > want) grid = want;

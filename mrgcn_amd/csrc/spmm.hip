@@ -189,7 +189,7 @@ __global__ __launch_bounds__(256) void k_spmm(SparseView v, const DT *__restrict
                                               const int32_t *__restrict__ out_index,
                                               int store_vec_ok, float *__restrict__ partials,
                                               int ldP, int chunk_blocks, int64_t short_blocks,
-                                              int64_t xcd_per, int min_len,
+                                              int64_t xcd_per,
                                               const uint8_t *__restrict__ op_live = nullptr,
                                               const uint8_t *__restrict__ out_live = nullptr) {
   constexpr int SLOTS = kWave / G;
@@ -333,9 +333,8 @@ __global__ __launch_bounds__(256) void k_spmm(SparseView v, const DT *__restrict
     b = v.ptr[row];
     n = v.ptr[row + 1] - b;
   }
-  // rows longer than kLongThreshold belong to the chunk path; with the tiny-row pre-pass
-  // (min_len > 0) rows of <= min_len entries (empty rows included) were already written
-  const bool mine = row < v.rows && n <= kLongThreshold && !(min_len > 0 && n <= min_len);
+  // rows longer than kLongThreshold belong to the chunk path
+  const bool mine = row < v.rows && n <= kLongThreshold;
   if (!mine) n = 0;
   if (!__any(mine)) return;  // wave uniform
   if (G <= 8) {
@@ -765,15 +764,6 @@ __global__ __launch_bounds__(256) void k_spmm3_finalize(View3 w, const float *__
   }
 }
 
-// ---- tiny rows (<= kTiny entries) ------------------------------------------------------------
-// The transposed view has millions of rows of 1-2 entries (AM: 8.2 M rows, 87 % single entry):
-// a wave that owns only 64/G such rows is pure latency (pointer -> index -> gather, three
-// dependent round trips for 16 entries).  Here every G-lane group owns kRpg rows at once and
-// walks their dependency chains side by side: 4x the rows, the same three round trips.
-// Rows are 4-byte aligned only (ld = F): 16-byte loads from dword-aligned addresses, scalar tail.
-constexpr int kTiny = 4;
-constexpr int kRpg = 4;
-
 __device__ __forceinline__ void load4_tail_safe(const float *row, int f0, int F, float (&x)[4]) {
   if (f0 + 4 <= F) {
     const float4 t = *reinterpret_cast<const float4 *>(row + f0);
@@ -781,75 +771,6 @@ __device__ __forceinline__ void load4_tail_safe(const float *row, int f0, int F,
   } else {
 #pragma unroll
     for (int i = 0; i < 4; ++i) x[i] = (f0 + i < F) ? row[f0 + i] : 0.f;
-  }
-}
-
-template <int G>
-__global__ __launch_bounds__(256) void k_spmm_tiny(SparseView v, const float *__restrict__ D, int64_t ldD,
-                                                   int F, float *__restrict__ Y, int64_t ldY,
-                                                   const float *__restrict__ bias, int relu,
-                                                   const int32_t *__restrict__ out_index) {
-  constexpr int SLOTS = kWave / G;
-  const int lane = threadIdx.x & (kWave - 1);
-  const int slot = lane / G, q = lane % G;
-  const int f0 = q * 4;
-  const bool active = f0 < F;
-  const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / kWave;
-  const int64_t row0 = wave * (SLOTS * kRpg) + slot;  // rows row0 + k*SLOTS, k < kRpg
-  int32_t b[kRpg], n[kRpg];
-#pragma unroll
-  for (int k = 0; k < kRpg; ++k) {
-    const int64_t row = row0 + (int64_t)k * SLOTS;
-    b[k] = 0; n[k] = -1;  // -1: not this kernel's row
-    if (row < v.rows) {
-      b[k] = v.ptr[row];
-      n[k] = v.ptr[row + 1] - b[k];
-      if (n[k] > kTiny) n[k] = -1;  // the general kernel owns this row
-    }
-  }
-  int32_t ci[kRpg][kTiny];
-  float ca[kRpg][kTiny];
-#pragma unroll
-  for (int k = 0; k < kRpg; ++k)
-#pragma unroll
-    for (int e = 0; e < kTiny; ++e) {
-      const bool on = e < n[k];
-      ci[k][e] = on ? v.idx[b[k] + e] : 0;
-      ca[k][e] = on ? v.val[b[k] + e] : 0.f;
-    }
-  float x[kRpg][kTiny][4];
-#pragma unroll
-  for (int k = 0; k < kRpg; ++k)
-#pragma unroll
-    for (int e = 0; e < kTiny; ++e) {
-      if (active && e < n[k]) load4_tail_safe(D + (int64_t)ci[k][e] * ldD, f0, F, x[k][e]);
-      else { x[k][e][0] = x[k][e][1] = x[k][e][2] = x[k][e][3] = 0.f; }
-    }
-#pragma unroll
-  for (int k = 0; k < kRpg; ++k) {
-    if (n[k] < 0 || !active) continue;  // empty rows (n = 0) are written (bias / zeros)
-    float acc[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int e = 0; e < kTiny; ++e)
-#pragma unroll
-      for (int i = 0; i < 4; ++i) acc[i] = fmaf(ca[k][e], x[k][e][i], acc[i]);
-    const int64_t row = row0 + (int64_t)k * SLOTS;
-    const int64_t orow = out_index ? (int64_t)out_index[row] : row;
-    float *y = Y + orow * ldY;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      float o = acc[i];
-      if (bias && f0 + i < F) o += bias[f0 + i];
-      if (relu) o = fmaxf(o, 0.f);
-      acc[i] = o;
-    }
-    if ((ldY & 3) == 0 && f0 + 4 <= F && (((uintptr_t)Y) & 15) == 0) {
-      *reinterpret_cast<float4 *>(y + f0) = make_float4(acc[0], acc[1], acc[2], acc[3]);
-    } else {
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-        if (f0 + i < F) y[f0 + i] = acc[i];
-    }
   }
 }
 
@@ -1032,7 +953,7 @@ __global__ __launch_bounds__(256) void k_spmm_finalize(SparseView v, const float
 
 template <int G, int VEC, bool TAIL = false, typename DT = float>
 int launch(const SparseView &v, const DT *D, int64_t ldD, int F, float *Y, int64_t ldY,
-           const float *bias, int relu, const int32_t *out_index, float *partials, bool use_tiny,
+           const float *bias, int relu, const int32_t *out_index, float *partials,
            hipStream_t s, const View3 *w3 = nullptr) {
   constexpr int SLOTS = kWave / G;
   constexpr int SV = VEC > 4 ? 4 : VEC;  // widest single store
@@ -1092,22 +1013,10 @@ int launch(const SparseView &v, const DT *D, int64_t ldD, int F, float *Y, int64
   const bool xcd_map = cfg(CFG_SPMM_XCD) != 0;
   const int64_t xcd_per = xcd_map ? (short_blocks + 7) / 8 : 0;
   const int64_t launch_short = xcd_map ? xcd_per * 8 : short_blocks;
-  int min_len = 0;
-  if constexpr (sizeof(DT) == 4) {
-  if (use_tiny && v.rows > 0) {  // G*4 >= F guaranteed by the caller
-    constexpr int TG = (G * VEC + 3) / 4 < 1 ? 1 : (G * VEC + 3) / 4;  // lanes per row at 4 floats each
-    constexpr int TSLOTS = kWave / TG;
-    const int64_t waves = (v.rows + (int64_t)TSLOTS * kRpg - 1) / ((int64_t)TSLOTS * kRpg);
-    k_spmm_tiny<TG><<<dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, s>>>(v, D, ldD, F, Y, ldY, bias, relu,
-                                                                            out_index);
-    MRGCN_HIP_TRY(hipGetLastError());
-    min_len = kTiny;
-  }
-  }
   if (launch_short + chunk_blocks > 0) {
     k_spmm<G, VEC, TAIL, DT><<<dim3((unsigned)(launch_short + chunk_blocks)), dim3(256), 0, s>>>(
         v, D, ldD, F, Y, ldY, bias, relu, out_index, store_vec_ok ? 1 : 0, partials, kWsFeatures,
-        (int)chunk_blocks, short_blocks, xcd_per, min_len);
+        (int)chunk_blocks, short_blocks, xcd_per);
     MRGCN_HIP_TRY(hipGetLastError());
   }
   if (v.n_multi > 0 && !v.ticket) {  // (with arrival counters the product finished its split rows itself)
@@ -1122,7 +1031,7 @@ int launch(const SparseView &v, const DT *D, int64_t ldD, int F, float *Y, int64
 // picks lanes-per-row G and vector width VEC for one feature tile of width F <= 256
 int dispatch(const SparseView &v, const float *D, int64_t ldD, int64_t avail, int F, float *Y,
              int64_t ldY, const float *bias, int relu, const int32_t *out_index, float *partials,
-             bool use_tiny, bool operand_cached, hipStream_t s, const View3 *w3 = nullptr) {
+             bool operand_cached, hipStream_t s, const View3 *w3 = nullptr) {
   // widest vector the operand layout allows; loads past F must stay inside the row
   // (`avail` = floats left in a row of D from this tile's first column)
   int vec = 1;
@@ -1130,8 +1039,6 @@ int dispatch(const SparseView &v, const float *D, int64_t ldD, int64_t avail, in
     int64_t padded = ((int64_t)F + w - 1) / w * w;
     return ldD % w == 0 && ((uintptr_t)D) % (w * 4) == 0 && avail >= padded;
   };
-  // MRGCN_SPMM_UNALIGNED=1: 16-byte loads on rows that are only 4/8-byte aligned (gfx950 global
-  // loads need dword alignment only); the caller guarantees 12 readable bytes past the operand
   if (ok(4)) vec = 4; else if (ok(2)) vec = 2;
   // unpadded rows that are only 4/8-byte aligned (e.g. the dY of a 10- or 11-class layer, ld = F):
   // 16-byte loads from dword-aligned addresses with a scalar tail instead of 4- or 8-byte lanes
@@ -1141,13 +1048,13 @@ int dispatch(const SparseView &v, const float *D, int64_t ldD, int64_t avail, in
   // on the 17.8 GB literal operand, 453 vs 496 / 472 vs 725 us on the 67-73 MB dY)
   if (vec < 4 && F <= 32 && !no_tail && operand_cached) {
     const int l4 = (F + 3) / 4;
-    if (l4 <= 1) return launch<1, 4, true>(v, D, ldD, F, Y, ldY, bias, relu, out_index, partials, use_tiny, s, w3);
-    if (l4 <= 2) return launch<2, 4, true>(v, D, ldD, F, Y, ldY, bias, relu, out_index, partials, use_tiny, s, w3);
-    if (l4 <= 4) return launch<4, 4, true>(v, D, ldD, F, Y, ldY, bias, relu, out_index, partials, use_tiny, s, w3);
-    return launch<8, 4, true>(v, D, ldD, F, Y, ldY, bias, relu, out_index, partials, use_tiny, s);
+    if (l4 <= 1) return launch<1, 4, true>(v, D, ldD, F, Y, ldY, bias, relu, out_index, partials, s, w3);
+    if (l4 <= 2) return launch<2, 4, true>(v, D, ldD, F, Y, ldY, bias, relu, out_index, partials, s, w3);
+    if (l4 <= 4) return launch<4, 4, true>(v, D, ldD, F, Y, ldY, bias, relu, out_index, partials, s, w3);
+    return launch<8, 4, true>(v, D, ldD, F, Y, ldY, bias, relu, out_index, partials, s);
   }
   const int lanes = (F + vec - 1) / vec;  // lanes needed per row
-#define MRGCN_GO(G, V) return launch<G, V>(v, D, ldD, F, Y, ldY, bias, relu, out_index, partials, use_tiny, s, w3)
+#define MRGCN_GO(G, V) return launch<G, V>(v, D, ldD, F, Y, ldY, bias, relu, out_index, partials, s, w3)
   if (vec == 4) {
     if (lanes <= 1) MRGCN_GO(1, 4);
     if (lanes <= 2) MRGCN_GO(2, 4);
@@ -1191,13 +1098,13 @@ int dispatch_bf16(const SparseView &v, const uint16_t *D, int64_t ldD, int64_t a
   // load needs.  COMPACT view only (w3): the general kernel keeps its 4-byte lanes for such rows.
   if (w3 && ldD == F && F >= 4 && F <= 16 && (F & 3) && (F & 1) == 0 && ((uintptr_t)D) % 4 == 0 && avail >= F) {
     const int l4 = (F + 3) / 4;
-    if (l4 <= 2) return launch<2, 4, true, uint16_t>(v, D, ldD, F, Y, ldY, bias, relu, out_index, partials, false, s, w3);
-    return launch<4, 4, true, uint16_t>(v, D, ldD, F, Y, ldY, bias, relu, out_index, partials, false, s, w3);
+    if (l4 <= 2) return launch<2, 4, true, uint16_t>(v, D, ldD, F, Y, ldY, bias, relu, out_index, partials, s, w3);
+    return launch<4, 4, true, uint16_t>(v, D, ldD, F, Y, ldY, bias, relu, out_index, partials, s, w3);
   }
   const int vec = ok(8) ? 8 : ok(4) ? 4 : ok(2) ? 2 : 1;
   const int lanes = (F + vec - 1) / vec;
 #define MRGCN_GO(G, V) \
-  return launch<G, V, false, uint16_t>(v, D, ldD, F, Y, ldY, bias, relu, out_index, partials, false, s, w3)
+  return launch<G, V, false, uint16_t>(v, D, ldD, F, Y, ldY, bias, relu, out_index, partials, s, w3)
 #define MRGCN_LANES(V)            \
   if (lanes <= 1) MRGCN_GO(1, V); \
   if (lanes <= 2) MRGCN_GO(2, V); \
@@ -1266,7 +1173,7 @@ int spmm_on_view(const SparseView &v, const float *D, int64_t ldD, int F, float 
   else if (ldD % 2 == 0 && ((uintptr_t)D) % 8 == 0) tile = 128;
   for (int f = 0; f < F; f += tile) {
     const int w = (F - f < tile) ? (F - f) : tile;
-    int rc = dispatch(v, D + f, ldD, ldD - f, w, Y + f, ldY, bias ? bias + f : nullptr, relu, nullptr, partials, false,
+    int rc = dispatch(v, D + f, ldD, ldD - f, w, Y + f, ldY, bias ? bias + f : nullptr, relu, nullptr, partials,
                       true, s, nullptr);
     if (rc != MRGCN_OK) return rc;
   }
@@ -1389,7 +1296,7 @@ extern "C" int mrgcn_spmm_transposed_live_flagged_f32(const mrgcn_plan_t *plan, 
 #define LIVE_LONG(G_)                                                                               \
   k_spmm<G_, 4, true, float, true><<<dim3((unsigned)chunk_blocks), dim3(256), 0, s>>>(              \
       v, D, ldD, F, Y, ldY, nullptr, 0, nullptr, store_vec_ok ? 1 : 0, partials, kWsFeatures,       \
-      (int)chunk_blocks, 0, 0, 0, row_live, col_live)
+      (int)chunk_blocks, 0, 0, row_live, col_live)
     if (F <= 4) LIVE_LONG(1);
     else if (F <= 8) LIVE_LONG(2);
     else LIVE_LONG(4);
@@ -1757,10 +1664,6 @@ extern "C" int mrgcn_spmm_f32(const mrgcn_plan_t *plan, int32_t view, const floa
   else if (ldD % 2 == 0 && ((uintptr_t)D) % 8 == 0) tile = 128;
   for (int f = 0; f < F; f += tile) {
     int w = (F - f < tile) ? (F - f) : tile;
-    // optional tiny-row pre-pass for views whose rows are mostly 1-2 entries (the transposed view);
-    // measured no faster than the general kernel on the AM shape, so opt-in (MRGCN_SPMM_TINY=1)
-    const bool tiny_on = cfg(CFG_SPMM_TINY) != 0;
-    const bool use_tiny = tiny_on && w <= 64 && v.rows > 0 && (plan->nnz < 3 * v.rows);
     const int64_t operand_rows = view == MRGCN_VIEW_LITERAL ? plan->num_relations * plan->num_nodes
                                  : view == MRGCN_VIEW_COMPACT ? plan->n_op : plan->num_rows;
     // (the compact operand is read front to back by the rows that own its single-use columns: a 16-byte load
@@ -1772,7 +1675,7 @@ extern "C" int mrgcn_spmm_f32(const mrgcn_plan_t *plan, int32_t view, const floa
     w3.fold = fold;
     w3.ticket = ticket;
     int rc = dispatch(v, D + f, ldD, ldD - f, w, Y + f, ldY, bias ? bias + f : nullptr, relu,
-                      out_index, partials, use_tiny, operand_cached, s,
+                      out_index, partials, operand_cached, s,
                       ((view == MRGCN_VIEW_COMPACT || lit) && F <= 16 && !plan->lean) ? &w3 : nullptr);
     if (rc != MRGCN_OK) return rc;
   }

@@ -19,7 +19,6 @@
 #include <cstdlib>
 
 #include "common.hpp"
-#include "config.hpp"
 
 namespace mrgcn {
 namespace {
@@ -87,23 +86,18 @@ __device__ __forceinline__ void load_basis_row(const float *__restrict__ p, int 
 // trip on every node).  v_readlane hands a dM row and its relation round; lane b stores D[k][b] (a live column's B
 // products: one 4 B-byte row per column, coalesced) and keeps the column's share of its dV row for the squared norm.
 // Nodes with more than four live columns (9 % at the AM shape) walk the rest of their columns with direct loads.
-// GC (round 6): `comp` is read from the (L2-resident) global table — lane b loads comp[r][b] of the node's first four
-// live columns right behind their relation ids — instead of from an LDS image: the kernel then has no workgroup state
-// and runs as a ONE-SHOT grid (a wave per 64 list entries) without re-staging 43 KB per block (`sup_mix_once = 2`).
-template <int FT, int NB, int TB, bool EXACT, bool GC = false>
-__global__ __launch_bounds__(TB) void k_mix_bwd_sup(const int32_t *__restrict__ lnode,
-                                                        const int32_t *__restrict__ lnptr,
-                                                        const int32_t *__restrict__ lrel,
-                                                        const float *__restrict__ dM, int64_t ldM,
-                                                        const float *__restrict__ V, const float *__restrict__ comp,
-                                                        int64_t NL, int R, int B, int F_, float *__restrict__ D,
-                                                        double *__restrict__ sq_part, int epw) {
+template <int FT, int NB, bool EXACT>
+__global__ __launch_bounds__(kSupTB) void k_mix_bwd_sup(const int32_t *__restrict__ lnode,
+                                                           const int32_t *__restrict__ lnptr,
+                                                           const int32_t *__restrict__ lrel,
+                                                           const float *__restrict__ dM, int64_t ldM,
+                                                           const float *__restrict__ V, const float *__restrict__ comp,
+                                                           int64_t NL, int R, int B, int F_, float *__restrict__ D,
+                                                           double *__restrict__ sq_part, int epw) {
   const int F = EXACT ? FT : F_;  // (a compile-time constant in the shapes that matter)
-  extern __shared__ __align__(16) float s_comp[];  // [R][B]  (not with GC)
-  if constexpr (!GC) {
-    for (int t = threadIdx.x; t < R * B; t += blockDim.x) s_comp[t] = comp[t];
-    __syncthreads();
-  }
+  extern __shared__ __align__(16) float s_comp[];  // [R][B]
+  for (int t = threadIdx.x; t < R * B; t += blockDim.x) s_comp[t] = comp[t];
+  __syncthreads();
   const int lane = threadIdx.x & 63;
   const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   const int nw = blockDim.x >> 6;
@@ -133,14 +127,6 @@ __global__ __launch_bounds__(TB) void k_mix_bwd_sup(const int32_t *__restrict__ 
         dmine[u] = dM[(int64_t)kk * ldM + oqc];
         rmine[u] = lrel[kk];
       }
-      float w4[NB][4];
-      if constexpr (GC) {  // the comp rows of the first four live columns of every node of the step: unconditional loads
-#pragma unroll
-        for (int u = 0; u < NB; ++u)
-#pragma unroll
-          for (int t = 0; t < 4; ++t)
-            w4[u][t] = comp[(int64_t)__builtin_amdgcn_readlane(rmine[u], 16 * t) * B + b];
-      }
 #pragma unroll
       for (int u = 0; u < NB; ++u) {
         if (i0 + u < cnt) {  // wave uniform
@@ -152,7 +138,7 @@ __global__ __launch_bounds__(TB) void k_mix_bwd_sup(const int32_t *__restrict__ 
           for (int t = 0; t < 4; ++t) {
             if (t < nc) {  // wave uniform
               const int r = __builtin_amdgcn_readlane(rmine[u], 16 * t);
-              const float w = GC ? w4[u][t] : s_comp[r * B + b];
+              const float w = s_comp[r * B + b];
               float d[FT];
 #pragma unroll
               for (int o = 0; o < FT; ++o)
@@ -176,7 +162,7 @@ __global__ __launch_bounds__(TB) void k_mix_bwd_sup(const int32_t *__restrict__ 
             for (int t = 0; t < 4; ++t) {
               if (t < nc2) {
                 const int r = __builtin_amdgcn_readlane(rm, 16 * t);
-                const float w = GC ? comp[(int64_t)r * B + b] : s_comp[r * B + b];
+                const float w = s_comp[r * B + b];
                 float d[FT];
 #pragma unroll
                 for (int o = 0; o < FT; ++o)
@@ -200,7 +186,7 @@ __global__ __launch_bounds__(TB) void k_mix_bwd_sup(const int32_t *__restrict__ 
       }
     }
   }
-  __shared__ float s_sq[TB / 64];
+  __shared__ float s_sq[kSupTB / 64];
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) sq += __shfl_xor(sq, off, 64);
   if (lane == 0) s_sq[wv] = sq;
@@ -426,56 +412,37 @@ int mrgcn_support_mix_bwd_f32(const mrgcn_support_t *q, const float *dM, int64_t
   const size_t lds = (size_t)R * B * sizeof(float);
   MRGCN_REQUIRE(lds <= 64 * 1024, "R * B * 4 must fit 64 KB of LDS");
   // nodes in flight per wave (NB) x waves per CU.  512-thread blocks with two nodes per step (62 VGPRs at F = 10: three
-  // blocks of eight waves per CU, bounded by the 42 KB of comp in LDS); MRGCN_SUP_MIX = "<threads>x<nodes>" picks
-  // another shape (experiments)
+  // blocks of eight waves per CU, bounded by the 42 KB of comp in LDS)
   // AM shape, kernel alone on one box: 512x1 598 us, 512x2 512, 512x4 557, 1024x2 501
-  int tb = (int)cfg(CFG_SUP_MIX_TB), nb = (int)cfg(CFG_SUP_MIX_NB);
-  if (nb < 1 || nb > 4) nb = 2;
   // (a small support: a wave's 64 list entries are one serial chain of 64 / NB steps — 122 us at MUTAG's 23 k nodes with
   // two per step; four per step halve the chain where occupancy does not matter)
-  if (q->NL < 262144 && nb < 4) nb = 4;
-  if (tb != 1024) tb = 512;
-  if (tb == 1024 && nb > 2) nb = 2;
-  const int nw = tb / 64;
+  const int nb = q->NL < 262144 ? 4 : 2;
+  constexpr int nw = kSupTB / 64;
   int epw = 64;
   if (q->NL < 262144) {  // ~4096 waves' worth of entries each, a multiple of the step
     epw = (int)((q->NL / 4096 + nb - 1) / nb * nb);
     epw = std::min(64, std::max(epw, nb));
   }
   int64_t grid = (q->NL + (int64_t)epw * nw - 1) / ((int64_t)epw * nw);
-  int per_cu = (int)std::min<size_t>(tb == 1024 ? 2 : 4, (160 * 1024) / (lds + 1024));
+  int per_cu = (int)std::min<size_t>(4, (160 * 1024) / (lds + 1024));
   if (per_cu < 1) per_cu = 1;
-  // (`sup_mix_once`: a ONE-SHOT grid — a wave takes one group of 64 list entries and ends; the block dispatcher hands the
-  // groups out in address order: tools/lab/copy_lab.hip.  0: a resident grid striding through the list)
-  const int once = (int)cfg(CFG_SUP_MIX_ONCE);  // 0: resident grid; 1: one-shot, LDS comp; 2: one-shot, comp from global
-  if (once == 0 && grid > 256 * per_cu) grid = 256 * per_cu;
+  // a resident grid striding through the list
+  if (grid > 256 * per_cu) grid = 256 * per_cu;
   if (grid > kSqParts) grid = kSqParts;
   if (grid < 1) grid = 1;
   const int FT = (F == 10 || F == 11) ? F : (F + 3) / 4 * 4;
-#define SUP_GO3(T, NB_, TB_)                                                                                        \
-  do {                                                                                                              \
-    if (F == T) SUP_GO4(T, NB_, TB_, true);                                                                         \
-    else SUP_GO4(T, 1, 512, false);                                                                                 \
+#define SUP_GO2(T, NB_, EX_)                                                                                      \
+  do {                                                                                                            \
+    auto kfn = k_mix_bwd_sup<T, NB_, EX_>;                                                                        \
+    MRGCN_HIP_TRY(mrgcn::raise_lds_limit((const void *)kfn, lds));                                                \
+    kfn<<<dim3((unsigned)grid), dim3(kSupTB), lds, s>>>(q->lnode, q->lnptr, q->lrel, dM, ldM, V, comp, q->NL,  \
+                                                           R, B, F, D, sq_part, epw);                             \
   } while (0)
-#define SUP_GO4(T, NB_, TB_, EX_)                                                                                   \
-  do {                                                                                                              \
-    if (once == 2 && EX_) {                                                                                         \
-      k_mix_bwd_sup<T, NB_, TB_, EX_, true><<<dim3((unsigned)grid), dim3(TB_), 0, s>>>(                             \
-          q->lnode, q->lnptr, q->lrel, dM, ldM, V, comp, q->NL, R, B, F, D, sq_part, epw);                          \
-    } else {                                                                                                        \
-      auto kfn = k_mix_bwd_sup<T, NB_, TB_, EX_>;                                                                   \
-      MRGCN_HIP_TRY(mrgcn::raise_lds_limit((const void *)kfn, lds));                                               \
-      kfn<<<dim3((unsigned)grid), dim3(TB_), lds, s>>>(q->lnode, q->lnptr, q->lrel, dM, ldM, V, comp, q->NL, R, B,  \
-                                                       F, D, sq_part, epw);                                         \
-    }                                                                                                               \
-  } while (0)
-#define SUP_GO(T)                                  \
-  do {                                             \
-    if (tb == 1024 && nb >= 2) SUP_GO3(T, 2, 1024); \
-    else if (tb == 1024) SUP_GO3(T, 1, 1024);      \
-    else if (nb >= 4) SUP_GO3(T, 4, 512);          \
-    else if (nb >= 2) SUP_GO3(T, 2, 512);          \
-    else SUP_GO3(T, 1, 512);                       \
+#define SUP_GO(T)                        \
+  do {                                   \
+    if (F != T) SUP_GO2(T, 1, false);    \
+    else if (nb == 4) SUP_GO2(T, 4, true); \
+    else SUP_GO2(T, 2, true);            \
   } while (0)
   if (q->NL > 0) {
     switch (FT) {
@@ -488,8 +455,7 @@ int mrgcn_support_mix_bwd_f32(const mrgcn_support_t *q, const float *dM, int64_t
     }
   }
 #undef SUP_GO
-#undef SUP_GO3
-#undef SUP_GO4
+#undef SUP_GO2
   MRGCN_HIP_TRY(hipGetLastError());
   if (o.n_chunks > 0) {
     const dim3 cg((unsigned)o.n_chunks);

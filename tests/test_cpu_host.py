@@ -277,6 +277,25 @@ def test_library_configuration_table_through_the_abi():
             assert "getenv" not in open(os.path.join(ROOT, "mrgcn_amd", "csrc", f)).read(), f
 
 
+def test_retired_configuration_keys_are_gone():
+    """The ten switches retired with the kernel forms only they reached: neither spelling names an entry
+    any more, and every remaining row still carries its description."""
+    from mrgcn_amd import _lib
+    retired = ["mix_cols", "mix_pad", "mix_fwd_tb", "mix_bwd_tb", "mix_bwd_per_cu", "spmm_tiny", "sup_mix_once",
+               "sup_mix_tb", "sup_mix_nb", "debug_captured_memset"]
+    lib = _lib.load()
+    cfg = _lib.config()
+    for name in retired:
+        assert name not in cfg, name
+        for spelling in (name, "MRGCN_" + name.upper()):
+            assert lib.mrgcn_config_set(spelling.encode(), 1) != 0, spelling
+    assert _lib.config() == cfg
+    n = lib.mrgcn_config_count()
+    assert n == len(cfg)
+    for i in range(n):
+        assert lib.mrgcn_config_doc(i), i
+
+
 def test_cpu_pool_follows_the_container_quota(monkeypatch, tmp_path):
     """mrgcn_amd.host: cgroup v2 `cpu.max` -> CPUs per period (None for "max" / no file); the torch intra-op pool is
     sized to it, never enlarged."""
