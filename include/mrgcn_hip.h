@@ -438,7 +438,14 @@ enum mrgcn_support_array_id {
   MRGCN_SUP_FCOL = 12,      /* int32 [E]         live number of each entry's column (the plan's row order) */
   MRGCN_SUP_FVAL = 13,      /* float [E]         its stored value                            */
   MRGCN_SUP_LNODE_ORD = 14, /* int32 [L]         rank of the live column's node in LNODE     */
-  MRGCN_SUP_ROWRANK = 15    /* int32 [num_rows]  rank in FROW, -1 for rows outside the set   */
+  MRGCN_SUP_ROWRANK = 15,   /* int32 [num_rows]  rank in FROW, -1 for rows outside the set   */
+  /* the (row, relation) pairs, once mrgcn_support_pair_sums_info has built them (count 0 before): */
+  MRGCN_SUP_PAIR_PTR = 16,     /* int32 [P+1]    entry range of each pair in the pair order        */
+  MRGCN_SUP_PAIR_ROW = 17,     /* int32 [P]      output row of each pair                           */
+  MRGCN_SUP_REL_PAIR_PTR = 18, /* int32 [R+1]    pair range of each relation                       */
+  MRGCN_SUP_PAIR_NODE = 19,    /* int32 [E]      source node of each entry in the pair order       */
+  MRGCN_SUP_PAIR_VAL = 20,     /* float [E]      its stored value                                  */
+  MRGCN_SUP_PAIR_CHUNK_PTR = 21 /* int32 [R+1]   chunk range of each relation (mrgcn_support_dw_pairs_f32) */
 };
 int mrgcn_support_create(mrgcn_support_t **support, const mrgcn_plan_t *plan, const uint8_t *row_flags,
                          void *stream);
@@ -494,6 +501,37 @@ int mrgcn_support_rel_transform_bwd_f32(const mrgcn_support_t *support, const fl
                                         int64_t ldX, int32_t K, const float *W, int32_t F, float *dX, int64_t lddX,
                                         float *dW, float *workspace, int64_t workspace_floats,
                                         int32_t relu_mask_from_x, void *stream);
+/* dW of the relation transform from a TABLE of per-(row, relation) sums of a constant layer input X.  The support's
+ * kept entries, sorted by (relation, output row, the transposed view's entry order), fall into P pairs; with
+ *   S[p, 0:K]  = sum over the entries e of pair p of val_e . X[node_e, 0:K]          (mrgcn_support_pair_sums_build_f32)
+ *   dW[r]      = sum over the pairs p of relation r of S[p]^T . dY[row_p, 0:F]       (mrgcn_support_dw_pairs_f32)
+ * which is the dW of mrgcn_support_rel_transform_bwd_f32 with the sums reassociated: S depends on the graph, the row
+ * set and X only, so a caller whose X is data builds it once and every epoch reads P rows of K floats in order
+ * instead of gathering the X row of every live column.  No float atomics, fixed summation orders (a pair's entries in
+ * the sorted order, pairs longer than `piece_entries` in pieces added in piece order; dW in chunks of `chunk_pairs`
+ * pairs added in chunk order): both calls are bitwise reproducible.
+ *   _info       builds the pair structure on first use (device work and host waits on `stream`; inside a stream
+ *               capture nothing is built and an unbuilt structure reports pairs = -1)
+ *   _build_f32  S [P, K] dense rows (K >= 4); X rows 4-byte aligned
+ *   _dw_pairs   dY as the layer received it (only rows of the support's row set are read); dW [R, K, F] written whole
+ *               (zeros for a relation without pairs); F <= 16; workspace: mrgcn_support_dw_pairs_workspace floats */
+typedef struct mrgcn_pair_sums_info {
+  int64_t pairs;            /* P (-1: not built, see above) */
+  int64_t table_bytes;      /* P * K * 4 */
+  int64_t chunks;           /* blocks of the dW pass */
+  int64_t chunk_pairs;      /* pairs per chunk at most */
+  int64_t piece_entries;    /* entries per piece of a pair's sum */
+  int64_t max_pair_entries; /* entries of the longest pair */
+  int64_t device_bytes;     /* of the pair structure */
+} mrgcn_pair_sums_info_t;
+int mrgcn_support_pair_sums_info(const mrgcn_support_t *support, int32_t K, mrgcn_pair_sums_info_t *h_info,
+                                 void *stream);
+int mrgcn_support_pair_sums_build_f32(const mrgcn_support_t *support, const float *X, int64_t ldX, int32_t K, float *S,
+                                      void *stream);
+int64_t mrgcn_support_dw_pairs_workspace(const mrgcn_support_t *support, int32_t K, int32_t F); /* floats */
+int mrgcn_support_dw_pairs_f32(const mrgcn_support_t *support, const float *S, int32_t K, const float *dY,
+                               int64_t ldY, int32_t F, float *dW, float *workspace, int64_t workspace_floats,
+                               void *stream);
 /* the same with the layer input X in bf16 rows (the bf16 pipeline; ldX in elements): dW's products and sums are fp32
  * on the widened elements; dX (= dM . W^T summed per node) never reads X */
 int mrgcn_support_rel_transform_bwd_xbf16(const mrgcn_support_t *support, const float *dM, int64_t ldM,

@@ -44,8 +44,14 @@ class SupportInfo(C.Structure):
         "live_cols", "live_entries", "live_nodes", "device_bytes", "chunks_wide", "chunks_narrow", "flagged_rows")]
 
 
+class PairSumsInfo(C.Structure):
+    _fields_ = [(n, C.c_int64) for n in (
+        "pairs", "table_bytes", "chunks", "chunk_pairs", "piece_entries", "max_pair_entries", "device_bytes")]
+
+
 (SUP_COL_FLAGS, SUP_NODE_FLAGS, SUP_LCOL, SUP_LREL, SUP_NLPTR, SUP_LPTR, SUP_LROW, SUP_LVAL, SUP_LNODE,
- SUP_LPERM, SUP_FROW, SUP_FPTR, SUP_FCOL, SUP_FVAL, SUP_LNODE_ORD, SUP_ROWRANK) = range(16)
+ SUP_LPERM, SUP_FROW, SUP_FPTR, SUP_FCOL, SUP_FVAL, SUP_LNODE_ORD, SUP_ROWRANK, SUP_PAIR_PTR, SUP_PAIR_ROW,
+ SUP_REL_PAIR_PTR, SUP_PAIR_NODE, SUP_PAIR_VAL, SUP_PAIR_CHUNK_PTR) = range(22)
 SUPPORT_FORWARD = 1
 
 _p = C.c_void_p
@@ -236,6 +242,10 @@ SIGNATURES = {
     "mrgcn_support_rel_transform_bwd_workspace": (C.c_int64, [_p, _i32, _i32, _i32, _i32]),
     "mrgcn_support_rel_transform_bwd_f32": (C.c_int, [_p, _p, _i64, _p, _i64, _i32, _p, _i32, _p, _i64, _p, _p, _i64,
                                                       _i32, _p]),
+    "mrgcn_support_pair_sums_info": (C.c_int, [_p, _i32, _p, _p]),
+    "mrgcn_support_pair_sums_build_f32": (C.c_int, [_p, _p, _i64, _i32, _p, _p]),
+    "mrgcn_support_dw_pairs_workspace": (C.c_int64, [_p, _i32, _i32]),
+    "mrgcn_support_dw_pairs_f32": (C.c_int, [_p, _p, _i32, _p, _i64, _i32, _p, _p, _i64, _p]),
     "mrgcn_softmax_xent_bwd_rows_f32": (C.c_int, [_p, _p, _i64, _i32, _p, _p, _i64, _p]),
     "mrgcn_node_dropout_draw_f32": (C.c_int, [_p, _i64, _i64, _i32, _i32, _i64, C.c_float, _p, _i32, _p]),
     "mrgcn_row_scale_f32": (C.c_int, [_p, _i64, _i64, _i32, _p, _p]),

@@ -49,6 +49,8 @@ constexpr int kChunk3Cap = 64;  // chunks per row at most: longer rows get chunk
 constexpr int kHotMinRefs = 16;    // columns read by >= this many rows go to the dense hot region of M
 constexpr int kNodeBand = 131072;  // source nodes per band of the transform order (see plan.hip)
 constexpr int kRelChunk = 1024;    // compact columns of one relation per transform block
+constexpr int kPairPiece = 64;     // entries per piece of a (row, relation) pair's sum (support.hip: k_pair_sums)
+constexpr int kPairChunk = 128;    // pairs of one relation per block of the pair-sum dW (support.hip: k_dw_pairs)
 
 // One CSR-shaped view of the adjacency: `rows` output rows, entry e of row i
 // multiplies dense row idx[e] by val[e].  Rows longer than kLongThreshold are cut into
@@ -163,6 +165,9 @@ int adam_rows_fused_arrays(const int32_t *nptr, const int32_t *urel, const uint8
                            const float *grad_scale, hipStream_t s, const int32_t *lnode = nullptr,
                            const int32_t *lnptr = nullptr, int64_t NL = 0, int ever_outside = 1);
 bool xform_use_mfma();
+// the pair structure of a support (mrgcn_support::Pairs), built by the first call outside a capture (plan.hip);
+// MRGCN_OK with q->pairs.built == false: a capture is under way and the structure does not exist yet
+int support_pairs(const ::mrgcn_support *q, hipStream_t s);
 // narrow transform with every relation's weights in LDS, columns in output order (xform_mfma.hip)
 bool xform_cols_lds_supported(const mrgcn_plan *p, int K, int F, int64_t ldOut, bool operand_order);
 int xform_cols_lds(const mrgcn_plan *p, bool operand_order, const float *In, int64_t ldIn, int K, const float *W, int F,
@@ -365,6 +370,27 @@ struct mrgcn_support {
     int32_t n_chunks = 0, max_chunks = 0;
   } wide, narrow;
   bool has_narrow = false;
+  // The (row, relation) PAIRS of the kept entries (plan.hip: support_pairs, built by the first caller outside a
+  // capture): the entries sorted by (relation, row, the transposed view's entry order).  With a constant layer input X
+  // the sums S[p] = sum of val_e . X[node_e] over a pair's entries are a table made once, and the layer's
+  // dW[r] = sum over r's pairs of S[p]^T . dY[row_p] reads that table instead of gathering X rows every epoch
+  // (support.hip: k_pair_sums / k_dw_pairs).
+  struct Pairs {
+    bool built = false;
+    int64_t P = 0;                    // pairs
+    int32_t *pair_ptr = nullptr;      // [P+1]  entry range of each pair in the sorted order
+    int32_t *pair_row = nullptr;      // [P]    output row of each pair
+    int32_t *rel_pair_ptr = nullptr;  // [R+1]  pair range of each relation
+    int32_t *node = nullptr;          // [E]    source node of each sorted entry
+    float *val = nullptr;             // [E]    its stored value
+    int32_t *chunk_beg = nullptr, *chunk_end = nullptr;  // [n_chunks] pair range of each chunk (<= kPairChunk pairs
+                                                         // of one relation), relation-major
+    int32_t *chunk_ptr = nullptr;     // [R+1]  chunk range of each relation
+    int32_t n_chunks = 0, max_pair_entries = 0;
+    int64_t device_bytes = 0;
+  };
+  mutable Pairs pairs;
+  mutable std::mutex pairs_mu;
   std::vector<void *> owned;
   mrgcn::SparseView tview() const {
     mrgcn::SparseView v;

@@ -1954,7 +1954,142 @@ void release_support(mrgcn_support *q) {
   parked.swap(keep);
 }
 
+// ---- the (row, relation) pairs of a support's kept entries (common.hpp: mrgcn_support::Pairs) ------------------------
+// key of kept entry e (the transposed view's order: live column, then rising row): relation * rows + row; its live
+// column is found by bisection of lptr (E log L steps, once per support)
+__global__ void k_pair_keys(const int32_t *__restrict__ lptr, const int32_t *__restrict__ lrel,
+                            const int32_t *__restrict__ lrow, int64_t L, int64_t E, int64_t rows,
+                            int64_t *__restrict__ keys, int32_t *__restrict__ ecol, int32_t *__restrict__ ids) {
+  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= E) return;
+  int64_t lo = 0, hi = L;  // the last column c with lptr[c] <= e
+  while (hi - lo > 1) {
+    const int64_t mid = (lo + hi) >> 1;
+    if (lptr[mid] <= e) lo = mid; else hi = mid;
+  }
+  keys[e] = (int64_t)lrel[lo] * rows + lrow[e];
+  ecol[e] = (int32_t)lo;
+  ids[e] = (int32_t)e;
+}
+
+// sorted position k -> source node and value of its entry; the first entry of a pair writes the pair's arrays
+__global__ void k_pair_fill(const int64_t *__restrict__ keys_s, const int32_t *__restrict__ ids_s,
+                            const int32_t *__restrict__ head, const int32_t *__restrict__ cid1,
+                            const int32_t *__restrict__ ecol, const int32_t *__restrict__ lcol,
+                            const int32_t *__restrict__ unode, const float *__restrict__ lval, int64_t E, int64_t rows,
+                            int32_t *__restrict__ node, float *__restrict__ val, int32_t *__restrict__ pair_ptr,
+                            int32_t *__restrict__ pair_row, int64_t *__restrict__ pair_key) {
+  const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= E) return;
+  const int32_t e = ids_s[k];
+  node[k] = unode[lcol[ecol[e]]];
+  val[k] = lval[e];
+  if (head[k]) {
+    const int32_t pid = cid1[k] - 1;
+    pair_ptr[pid] = (int32_t)k;
+    pair_row[pid] = (int32_t)(keys_s[k] % rows);
+    pair_key[pid] = keys_s[k];
+  }
+  if (k == E - 1) pair_ptr[cid1[k]] = (int32_t)E;
+}
+
 }  // namespace
+
+int support_pairs(const mrgcn_support *cq, hipStream_t s) {
+  mrgcn_support *q = const_cast<mrgcn_support *>(cq);
+  std::lock_guard<std::mutex> lock(q->pairs_mu);
+  mrgcn_support::Pairs &pr = q->pairs;
+  if (pr.built) return MRGCN_OK;
+  hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
+  if (hipStreamIsCapturing(s, &st) != hipSuccess || st != hipStreamCaptureStatusNone) return MRGCN_OK;  // (not built)
+  const mrgcn_plan *p = q->plan;
+  const int64_t E = q->E, L = q->L, R = p->num_relations, rows = p->num_rows;
+  MRGCN_REQUIRE(E < ((int64_t)1 << 31), "kept entries");
+  const int64_t before = q->device_bytes;
+  int64_t P = 0;
+  {
+    Scratch sc;
+    sc.s = s;
+    int64_t *keys, *keys_s, *pair_key;
+    int32_t *ecol, *ids, *ids_s, *head, *cid1;
+    MRGCN_HIP_TRY(sc.alloc(&keys, E));
+    MRGCN_HIP_TRY(sc.alloc(&keys_s, E));
+    MRGCN_HIP_TRY(sc.alloc(&pair_key, E));
+    MRGCN_HIP_TRY(sc.alloc(&ecol, E));
+    MRGCN_HIP_TRY(sc.alloc(&ids, E));
+    MRGCN_HIP_TRY(sc.alloc(&ids_s, E));
+    MRGCN_HIP_TRY(sc.alloc(&head, E));
+    MRGCN_HIP_TRY(sc.alloc(&cid1, E));
+    MRGCN_HIP_TRY(sup_alloc(q, &pr.node, E));
+    MRGCN_HIP_TRY(sup_alloc(q, &pr.val, E));
+    MRGCN_HIP_TRY(sup_alloc(q, &pr.rel_pair_ptr, R + 1));
+    MRGCN_HIP_TRY(sup_alloc(q, &pr.chunk_ptr, R + 1));
+    if (E > 0) {
+      k_pair_keys<<<nblocks(E), kTB, 0, s>>>(q->lptr, q->lrel, q->lrow, L, E, rows, keys, ecol, ids);
+      MRGCN_HIP_TRY(hipGetLastError());
+      size_t tb = 0;
+      const int end_bit = bits_for(R * rows + rows);
+      // (a stable sort: the entries of a pair keep the transposed view's order)
+      MRGCN_HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, keys, keys_s, ids, ids_s, (int)E, 0, end_bit, s));
+      char *tmp;
+      MRGCN_HIP_TRY(sc.alloc(&tmp, (int64_t)tb));
+      MRGCN_HIP_TRY(hipcub::DeviceRadixSort::SortPairs(tmp, tb, keys, keys_s, ids, ids_s, (int)E, 0, end_bit, s));
+      k_heads<<<nblocks(E), kTB, 0, s>>>(keys_s, E, head);
+      MRGCN_HIP_TRY(hipGetLastError());
+      size_t tb2 = 0;
+      MRGCN_HIP_TRY(hipcub::DeviceScan::InclusiveSum(nullptr, tb2, head, cid1, (int)E, s));
+      char *tmp2;
+      MRGCN_HIP_TRY(sc.alloc(&tmp2, (int64_t)tb2));
+      MRGCN_HIP_TRY(hipcub::DeviceScan::InclusiveSum(tmp2, tb2, head, cid1, (int)E, s));
+      int32_t h_P = 0;
+      MRGCN_HIP_TRY(hipMemcpyAsync(&h_P, cid1 + (E - 1), sizeof(int32_t), hipMemcpyDeviceToHost, s));
+      MRGCN_HIP_TRY(hipStreamSynchronize(s));
+      P = h_P;
+    }
+    MRGCN_HIP_TRY(sup_alloc(q, &pr.pair_ptr, P + 1));
+    MRGCN_HIP_TRY(sup_alloc(q, &pr.pair_row, P));
+    if (E > 0) {
+      k_pair_fill<<<nblocks(E), kTB, 0, s>>>(keys_s, ids_s, head, cid1, ecol, q->lcol, p->unode, q->lval, E, rows,
+                                             pr.node, pr.val, pr.pair_ptr, pr.pair_row, pair_key);
+      MRGCN_HIP_TRY(hipGetLastError());
+    } else {
+      MRGCN_HIP_TRY(hipMemsetAsync(pr.pair_ptr, 0, sizeof(int32_t), s));
+    }
+    k_lower_bound_ptr<<<nblocks(R + 1), kTB, 0, s>>>(pair_key, P, R, rows, pr.rel_pair_ptr);
+    MRGCN_HIP_TRY(hipGetLastError());
+    // chunks of <= kPairChunk pairs of one relation, relation-major, cut on the host
+    std::vector<int32_t> h_rp(R + 1), h_pp(P + 1);
+    MRGCN_HIP_TRY(hipMemcpyAsync(h_rp.data(), pr.rel_pair_ptr, (R + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    MRGCN_HIP_TRY(hipMemcpyAsync(h_pp.data(), pr.pair_ptr, (P + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    MRGCN_HIP_TRY(hipStreamSynchronize(s));
+    int32_t longest = 0;
+    for (int64_t i = 0; i < P; ++i) longest = std::max(longest, h_pp[i + 1] - h_pp[i]);
+    std::vector<int32_t> beg, end, cptr(R + 1, 0);
+    for (int64_t r = 0; r < R; ++r) {
+      for (int32_t a = h_rp[r]; a < h_rp[r + 1]; a += kPairChunk) {
+        beg.push_back(a);
+        end.push_back(std::min(a + kPairChunk, h_rp[r + 1]));
+      }
+      cptr[r + 1] = (int32_t)beg.size();
+    }
+    const int64_t nc = (int64_t)beg.size();
+    MRGCN_HIP_TRY(sup_alloc(q, &pr.chunk_beg, nc));
+    MRGCN_HIP_TRY(sup_alloc(q, &pr.chunk_end, nc));
+    if (nc > 0) {
+      MRGCN_HIP_TRY(hipMemcpyAsync(pr.chunk_beg, beg.data(), nc * sizeof(int32_t), hipMemcpyHostToDevice, s));
+      MRGCN_HIP_TRY(hipMemcpyAsync(pr.chunk_end, end.data(), nc * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    }
+    MRGCN_HIP_TRY(hipMemcpyAsync(pr.chunk_ptr, cptr.data(), (R + 1) * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    // (the vectors leave scope next, and calls on other streams may read the arrays: one wait, once per support)
+    MRGCN_HIP_TRY(hipStreamSynchronize(s));
+    pr.n_chunks = (int32_t)nc;
+    pr.max_pair_entries = longest;
+  }
+  pr.P = P;
+  pr.device_bytes = q->device_bytes - before;
+  pr.built = true;
+  return MRGCN_OK;
+}
 }  // namespace mrgcn
 
 extern "C" {
@@ -2046,6 +2181,14 @@ int mrgcn_support_array(const mrgcn_support_t *q, int32_t which, const void **d_
     case MRGCN_SUP_FVAL: *d_ptr = q->fval; *h_count = q->has_forward ? q->E : 0; break;
     case MRGCN_SUP_LNODE_ORD: *d_ptr = q->lnode_ord; *h_count = q->has_forward ? q->L : 0; break;
     case MRGCN_SUP_ROWRANK: *d_ptr = q->rowrank; *h_count = q->has_forward ? p->num_rows : 0; break;
+    case MRGCN_SUP_PAIR_PTR: *d_ptr = q->pairs.pair_ptr; *h_count = q->pairs.built ? q->pairs.P + 1 : 0; break;
+    case MRGCN_SUP_PAIR_ROW: *d_ptr = q->pairs.pair_row; *h_count = q->pairs.built ? q->pairs.P : 0; break;
+    case MRGCN_SUP_REL_PAIR_PTR:
+      *d_ptr = q->pairs.rel_pair_ptr; *h_count = q->pairs.built ? p->num_relations + 1 : 0; break;
+    case MRGCN_SUP_PAIR_NODE: *d_ptr = q->pairs.node; *h_count = q->pairs.built ? q->E : 0; break;
+    case MRGCN_SUP_PAIR_VAL: *d_ptr = q->pairs.val; *h_count = q->pairs.built ? q->E : 0; break;
+    case MRGCN_SUP_PAIR_CHUNK_PTR:
+      *d_ptr = q->pairs.chunk_ptr; *h_count = q->pairs.built ? p->num_relations + 1 : 0; break;
     default: MRGCN_REQUIRE(false, "unknown support array");
   }
   return MRGCN_OK;

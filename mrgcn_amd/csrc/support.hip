@@ -338,6 +338,143 @@ __global__ __launch_bounds__(256) void k_dcomp_final(const int32_t *__restrict__
         (s_part[0][threadIdx.x] + s_part[1][threadIdx.x]) + (s_part[2][threadIdx.x] + s_part[3][threadIdx.x]);
 }
 
+// ---- dW from per-(row, relation) sums of a constant X (common.hpp: mrgcn_support::Pairs) ----------------------------
+// 16 bytes of a 4-byte aligned row (a wide X row is K floats, any K)
+typedef float f32x4_a4 __attribute__((ext_vector_type(4), aligned(4)));
+
+// sum of val_e . X[node_e, kc .. kc + 4) over the entries [b, e) of one piece, in entry order.  Eight rows per step:
+// their loads are issued back to back at clamped entry numbers (the node and value of an entry are wave uniform), the
+// adds follow in order
+__device__ __forceinline__ f32x4s pair_piece_sum(const int32_t *__restrict__ node, const float *__restrict__ val,
+                                                 const float *__restrict__ X, int64_t ldX, int kc, int32_t b, int32_t e) {
+  f32x4s acc = {0.f, 0.f, 0.f, 0.f};
+  for (int32_t i = b; i < e; i += 8) {
+    f32x4s x[8];
+    float a[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      const int32_t ii = (i + u < e) ? i + u : e - 1;
+      a[u] = val[ii];
+      x[u] = *reinterpret_cast<const f32x4_a4 *>(X + (int64_t)node[ii] * ldX + kc);
+    }
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      f32x4s t;
+      t.x = fmaf(a[u], x[u].x, acc.x); t.y = fmaf(a[u], x[u].y, acc.y);
+      t.z = fmaf(a[u], x[u].z, acc.z); t.w = fmaf(a[u], x[u].w, acc.w);
+      acc = (i + u < e) ? t : acc;  // (wave uniform)
+    }
+  }
+  return acc;
+}
+
+// S[p, :] of four consecutive pairs per block.  Lane l owns the columns 4 l .. 4 l + 3 of a 256-column slice; the last
+// lane of a row loads at K - 4 and keeps the columns that are its own.  A pair of up to kPairPiece entries is one
+// wave's; a longer one is cut into pieces of kPairPiece entries that the block's four waves sum four at a time, the
+// partial sums meeting in LDS where wave 0 adds them in piece order.  Runs once per X: kept simple.
+__global__ __launch_bounds__(256) void k_pair_sums(const int32_t *__restrict__ pair_ptr, const int32_t *__restrict__ node,
+                                                   const float *__restrict__ val, int64_t P,
+                                                   const float *__restrict__ X, int64_t ldX, int K,
+                                                   float *__restrict__ S) {
+  __shared__ f32x4s s_part[4][64];
+  const int lane = threadIdx.x & 63;
+  const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int64_t p0 = (int64_t)blockIdx.x * 4;
+  for (int kb = 0; kb < K; kb += 256) {
+    const int kcol = kb + 4 * lane;
+    const int kc = kcol < K - 4 ? kcol : K - 4;
+    auto store = [&](int64_t p, const f32x4s &v) {
+      float *dst = S + p * K;
+      if (kcol < K) {
+        if (kc + 0 >= kcol) dst[kc + 0] = v.x;
+        if (kc + 1 >= kcol) dst[kc + 1] = v.y;
+        if (kc + 2 >= kcol) dst[kc + 2] = v.z;
+        dst[kc + 3] = v.w;
+      }
+    };
+    if (p0 + wv < P) {
+      const int32_t b = pair_ptr[p0 + wv], e = pair_ptr[p0 + wv + 1];
+      if (e - b <= kPairPiece) store(p0 + wv, pair_piece_sum(node, val, X, ldX, kc, b, e));
+    }
+    for (int u = 0; u < 4 && p0 + u < P; ++u) {  // (block uniform)
+      const int32_t b = pair_ptr[p0 + u], e = pair_ptr[p0 + u + 1];
+      if (e - b <= kPairPiece) continue;
+      f32x4s acc = {0.f, 0.f, 0.f, 0.f};
+      for (int32_t r0 = b; r0 < e; r0 += 4 * kPairPiece) {
+        const int32_t pb = r0 + wv * kPairPiece;
+        const int32_t pe = pb + kPairPiece < e ? pb + kPairPiece : e;
+        f32x4s part = {0.f, 0.f, 0.f, 0.f};
+        if (pb < e) part = pair_piece_sum(node, val, X, ldX, kc, pb, pe);
+        s_part[wv][lane] = part;
+        __syncthreads();
+        if (wv == 0) {
+#pragma unroll
+          for (int w = 0; w < 4; ++w)
+            if (r0 + w * kPairPiece < e) acc += s_part[w][lane];
+        }
+        __syncthreads();
+      }
+      if (wv == 0) store(p0 + u, acc);
+    }
+  }
+}
+
+// slab[chunk][k][f] = sum over the chunk's pairs p (rising) of S[p][k] . dY[row_p][f].  Thread k streams column k of
+// the chunk's S rows (a row is one coalesced read of the block), eight rows in flight; a pair's dY row is block
+// uniform.  FT: F rounded up to whole fours.
+template <int FT>
+__global__ __launch_bounds__(256) void k_dw_pairs(const int32_t *__restrict__ chunk_beg,
+                                                  const int32_t *__restrict__ chunk_end,
+                                                  const int32_t *__restrict__ pair_row, const float *__restrict__ S,
+                                                  int K, const float *__restrict__ dY, int64_t ldY, int F,
+                                                  float *__restrict__ slab) {
+  const int32_t p0 = chunk_beg[blockIdx.x], p1 = chunk_end[blockIdx.x];
+  for (int k = threadIdx.x; k < K; k += blockDim.x) {
+    float acc[FT];
+#pragma unroll
+    for (int f = 0; f < FT; ++f) acc[f] = 0.f;
+    for (int32_t p = p0; p < p1; p += 8) {
+      float sv[8];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) sv[u] = S[(int64_t)((p + u < p1) ? p + u : p1 - 1) * K + k];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) {
+        if (p + u < p1) {  // (block uniform)
+          const float *__restrict__ g = dY + (int64_t)pair_row[p + u] * ldY;
+#pragma unroll
+          for (int f = 0; f < FT; ++f)
+            if (f < F) acc[f] = fmaf(sv[u], g[f], acc[f]);
+        }
+      }
+    }
+    float *dst = slab + ((int64_t)blockIdx.x * K + k) * F;
+#pragma unroll
+    for (int f = 0; f < FT; ++f)
+      if (f < F) dst[f] = acc[f];
+  }
+}
+
+// dW[r][t] = relation r's chunk slabs added in chunk order (in the manner of k_dw_reduce, one writer per element at
+// any chunk count: no atomics); zeros for a relation without pairs
+__global__ __launch_bounds__(256) void k_dw_pairs_reduce(const int32_t *__restrict__ chunk_ptr,
+                                                         const float *__restrict__ slab, int KF,
+                                                         float *__restrict__ dW) {
+  const int r = blockIdx.x;
+  const int t = blockIdx.y * blockDim.x + threadIdx.x;
+  if (t >= KF) return;
+  const int c0 = chunk_ptr[r], c1 = chunk_ptr[r + 1];
+  float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
+  int c = c0;
+  for (; c + 4 <= c1; c += 4) {
+    s0 += slab[(int64_t)c * KF + t];
+    s1 += slab[(int64_t)(c + 1) * KF + t];
+    s2 += slab[(int64_t)(c + 2) * KF + t];
+    s3 += slab[(int64_t)(c + 3) * KF + t];
+  }
+  for (; c < c1; ++c) s0 += slab[(int64_t)c * KF + t];
+  dW[(int64_t)r * KF + t] = (s0 + s1) + (s2 + s3);
+}
+
 __global__ void k_xent_scatter_rows(const float *__restrict__ drows, const int64_t *__restrict__ idx, int64_t n, int C,
                                     const float *__restrict__ g, float *__restrict__ dlogits, int64_t ldd) {
   const float gg = g ? *g : 1.f;
@@ -554,6 +691,73 @@ int mrgcn_support_rel_transform_bwd_xbf16(const mrgcn_support_t *q, const float 
                                           float *dW, float *workspace, int64_t workspace_floats, void *stream) {
   return support_rel_transform_bwd(q, dM, ldM, X, true, ldX, K, W, F, dX, lddX, dW, workspace, workspace_floats, 0,
                                    stream);
+}
+
+int mrgcn_support_pair_sums_info(const mrgcn_support_t *q, int32_t K, mrgcn_pair_sums_info_t *h, void *stream) {
+  MRGCN_REQUIRE(q && h, "NULL");
+  MRGCN_REQUIRE(K >= 0, "K");
+  int rc = support_pairs(q, (hipStream_t)stream);
+  if (rc != MRGCN_OK) return rc;
+  const mrgcn_support::Pairs &pr = q->pairs;
+  h->pairs = pr.built ? pr.P : -1;
+  h->table_bytes = pr.built ? pr.P * (int64_t)K * (int64_t)sizeof(float) : 0;
+  h->chunks = pr.n_chunks;
+  h->chunk_pairs = kPairChunk;
+  h->piece_entries = kPairPiece;
+  h->max_pair_entries = pr.max_pair_entries;
+  h->device_bytes = pr.device_bytes;
+  return MRGCN_OK;
+}
+
+int mrgcn_support_pair_sums_build_f32(const mrgcn_support_t *q, const float *X, int64_t ldX, int32_t K, float *S,
+                                      void *stream) {
+  MRGCN_REQUIRE(q && X && S, "NULL");
+  MRGCN_REQUIRE(K >= 4 && ldX >= K, "K >= 4 / ldX");
+  MRGCN_REQUIRE((((uintptr_t)X) & 3) == 0, "X must be 4-byte aligned");
+  hipStream_t s = (hipStream_t)stream;
+  int rc = support_pairs(q, s);
+  if (rc != MRGCN_OK) return rc;
+  const mrgcn_support::Pairs &pr = q->pairs;
+  MRGCN_REQUIRE(pr.built, "the pair structure is built outside a stream capture (mrgcn_support_pair_sums_info)");
+  if (pr.P == 0) return MRGCN_OK;
+  k_pair_sums<<<dim3((unsigned)((pr.P + 3) / 4)), dim3(256), 0, s>>>(pr.pair_ptr, pr.node, pr.val, pr.P, X, ldX, K, S);
+  MRGCN_HIP_TRY(hipGetLastError());
+  return MRGCN_OK;
+}
+
+int64_t mrgcn_support_dw_pairs_workspace(const mrgcn_support_t *q, int32_t K, int32_t F) {
+  if (!q || !q->pairs.built || K <= 0 || F <= 0 || F > 16) return -1;
+  const int64_t n = (int64_t)q->pairs.n_chunks * K * F;
+  return n > 0 ? n : 1;
+}
+
+int mrgcn_support_dw_pairs_f32(const mrgcn_support_t *q, const float *S, int32_t K, const float *dY, int64_t ldY,
+                               int32_t F, float *dW, float *workspace, int64_t workspace_floats, void *stream) {
+  MRGCN_REQUIRE(q && dY && dW, "NULL");
+  MRGCN_REQUIRE(K > 0 && F > 0 && F <= 16 && ldY >= F, "K / F <= 16 / ldY");
+  const mrgcn_support::Pairs &pr = q->pairs;
+  MRGCN_REQUIRE(pr.built, "the pair structure is built outside a stream capture (mrgcn_support_pair_sums_info)");
+  MRGCN_REQUIRE(pr.P == 0 || S, "NULL");
+  MRGCN_REQUIRE(workspace && workspace_floats >= mrgcn_support_dw_pairs_workspace(q, K, F),
+                "workspace (mrgcn_support_dw_pairs_workspace floats)");
+  hipStream_t s = (hipStream_t)stream;
+  const int R = (int)q->plan->num_relations;
+  if (pr.n_chunks > 0) {
+    const dim3 grid((unsigned)pr.n_chunks), block((unsigned)(((K < 256 ? K : 256) + 63) / 64 * 64));
+    switch ((F + 3) / 4) {
+      case 1: k_dw_pairs<4><<<grid, block, 0, s>>>(pr.chunk_beg, pr.chunk_end, pr.pair_row, S, K, dY, ldY, F, workspace); break;
+      case 2: k_dw_pairs<8><<<grid, block, 0, s>>>(pr.chunk_beg, pr.chunk_end, pr.pair_row, S, K, dY, ldY, F, workspace); break;
+      case 3: k_dw_pairs<12><<<grid, block, 0, s>>>(pr.chunk_beg, pr.chunk_end, pr.pair_row, S, K, dY, ldY, F, workspace); break;
+      default: k_dw_pairs<16><<<grid, block, 0, s>>>(pr.chunk_beg, pr.chunk_end, pr.pair_row, S, K, dY, ldY, F, workspace); break;
+    }
+    MRGCN_HIP_TRY(hipGetLastError());
+  }
+  if (R > 0) {
+    k_dw_pairs_reduce<<<dim3((unsigned)R, (unsigned)((K * F + 255) / 256)), dim3(256), 0, s>>>(pr.chunk_ptr, workspace,
+                                                                                              K * F, dW);
+    MRGCN_HIP_TRY(hipGetLastError());
+  }
+  return MRGCN_OK;
 }
 
 int mrgcn_softmax_xent_bwd_rows_f32(const float *drows, const int64_t *idx, int64_t n, int32_t C, const float *g,

@@ -33,6 +33,27 @@ _WIDE_UNIT = int(os.environ.get("MRGCN_WIDE_UNIT", "64"))   # entries per unit o
 # bf16 layers read a wide input as bf16 rows (0: only the compact operand M is bf16, the round-5 form — the A/B switch)
 _BF16_PIPELINE = os.environ.get("MRGCN_BF16_PIPELINE", "1") != "0"
 
+# The layer-0 dW from a table of per-(row, relation) sums of X (plan.GraphSupport.pair_sums, csrc/support.hip:
+# k_pair_sums / k_dw_pairs): taken when only dW is wanted of a wide fp32 input that is DATA — the table is then the same
+# every epoch and the dW reads it in order instead of gathering an X row per live column.  0: the gather kernel always.
+# The table may take up to MRGCN_DW_PAIR_SUMS_CAP bytes (0, the default: as many as X itself).
+_DW_PAIR_SUMS = os.environ.get("MRGCN_DW_PAIR_SUMS", "1") != "0"
+_DW_PAIR_SUMS_CAP = int(os.environ.get("MRGCN_DW_PAIR_SUMS_CAP", "0"))
+# supports whose table a stream capture under way has baked into its graph (GraphedTrainStep / GraphedStep take the
+# list and re-check the tables' keys in front of every replay)
+_PAIR_SUMS_CAPTURED = []
+
+
+def take_captured_pair_sums() -> list:
+    """The supports whose pair-sum tables were read by captures since the last call (and forgets them)."""
+    out = []
+    for sup in _PAIR_SUMS_CAPTURED:
+        if not any(sup is o for o in out):
+            out.append(sup)
+    _PAIR_SUMS_CAPTURED.clear()
+    return out
+
+
 # tests: start dM as NaNs, so that any read of a row the producer left unwritten shows
 _POISON_DEAD = False
 
@@ -587,6 +608,8 @@ class _RgcnLayer(torch.autograd.Function):
             row_scale_(Y, ctx.row_scale)
         ctx.plan, ctx.F, ctx.ld, ctx.relu, ctx.owner = plan, F, ld, relu, owner
         ctx.Xb = Xb   # the input's bf16 rows (the bf16 pipeline): what the backward's dW gathers
+        # the caller's tensor behind Xc when it is data: the key of what is cached per constant input (pair sums)
+        ctx.x_src = X if (X is not None and not X.requires_grad) else None
         # the layer's input is the output of a fused ReLU (marked by the layer that made it): its own sign is that
         # ReLU's mask, so this layer's backward can hand its input gradient on already masked
         ctx.x_is_relu_out = X is not None and bool(getattr(X, "_mrgcn_relu_out", False))
@@ -994,14 +1017,31 @@ def _backward_on_support(ctx, sup, dY, dbias):
     with torch.cuda.device(dev):
         L.check(lib.mrgcn_support_spmm_t_f32(sup.handle, dY.data_ptr(), dY.stride(0), F, dM.data_ptr(), ld, s),
                 "mrgcn_support_spmm_t_f32")
-    return _support_backward_from_dM(ctx, sup, dM, ld, dbias, nws)
+    return _support_backward_from_dM(ctx, sup, dM, ld, dbias, nws, dY=dY)
 
 
-def _support_backward_from_dM(ctx, sup, dM, ld, dbias, nws):
+def _dw_pair_sums_table(ctx, sup, X, K, F, need_dX, need_dW, dY):
+    """The pair-sum table the layer's dW may run on (None: the gather kernel): only dW wanted, X wide fp32 data with no
+    bf16 copy in use, the layer's own output gradient at hand, and a valid table or the chance to build one."""
+    if not (_DW_PAIR_SUMS and dY is not None and need_dW and not need_dX and K > 16 and F <= 16):
+        return None
+    src = getattr(ctx, "x_src", None)
+    if src is None:
+        src = X
+    if (getattr(ctx, "Xb", None) is not None or X.dtype != torch.float32 or X.requires_grad or src.requires_grad
+            or src.dtype != torch.float32 or src.dim() != 2 or dY.dtype != torch.float32 or dY.stride(1) != 1):
+        return None
+    cap = _DW_PAIR_SUMS_CAP if _DW_PAIR_SUMS_CAP > 0 else src.shape[0] * K * 4
+    return sup.pair_sums(src, X, K, cap)
+
+
+def _support_backward_from_dM(ctx, sup, dM, ld, dbias, nws, dY=None):
     """The layer's parameter / input gradients from dM [L, ld] (the gradient of the live columns' operand rows, by the
     support's live numbers): mix backward, the transform's dW / dX.  `ctx`: anything with _RgcnLayer's context fields
     (plan, F, saved_tensors, has, needs_input_grad, owner, x_is_relu_out, Xb) — the node-partitioned halo engine sums
-    the ranks' contributions into dM first and calls this on its own columns' support (partition_halo.py)."""
+    the ranks' contributions into dM first and calls this on its own columns' support (partition_halo.py).  `dY`: the
+    layer's own output gradient (ReLU mask applied) when dM is this support's product with it and nothing else — the dW
+    of a constant wide input may then come from the pair-sum table (`_dw_pair_sums_table`)."""
     lib = L.load()
     plan, F = ctx.plan, ctx.F
     weight_I, comp_I, X, W_F, Y = ctx.saved_tensors
@@ -1026,10 +1066,20 @@ def _support_backward_from_dM(ctx, sup, dM, ld, dbias, nws):
                     dX = torch.empty((X.shape[0], K), dtype=torch.float32, device=dev)
                 if need_dW:
                     dW = torch.empty_like(W_F)
-                ws = sup.workspace(("xform", K, F), nws)
+                S = _dw_pair_sums_table(ctx, sup, X, K, F, need_dX, need_dW, dY)
+                ws = sup.workspace(("xform", K, F), nws) if S is None else None
                 mask = bool(need_dX and ctx.x_is_relu_out and K <= 16)
                 Xb = getattr(ctx, "Xb", None)
-                if Xb is not None and not mask:
+                if S is not None:
+                    # dW[r] = sum over r's (row, relation) pairs of S[p]^T . dY[row_p]: the table in order, dM not read
+                    bump("backward.dw_pair_sums")
+                    if torch.cuda.is_current_stream_capturing():
+                        _PAIR_SUMS_CAPTURED.append(sup)
+                    wsp = sup.workspace(("dw_pairs", K, F), int(lib.mrgcn_support_dw_pairs_workspace(sup.handle, K, F)))
+                    L.check(lib.mrgcn_support_dw_pairs_f32(
+                        sup.handle, S.data_ptr(), K, dY.data_ptr(), dY.stride(0), F, dW.data_ptr(), wsp.data_ptr(),
+                        wsp.numel(), side.cuda_stream), "mrgcn_support_dw_pairs_f32")
+                elif Xb is not None and not mask:
                     bump("bf16.dw_xbf16")
                     L.check(lib.mrgcn_support_rel_transform_bwd_xbf16(
                         sup.handle, dM.data_ptr(), ld, Xb.data_ptr(), Xb.stride(0), K, W_F.data_ptr(), F,

@@ -401,6 +401,8 @@ class GraphSupport:
         self.ordered_release = bool(forward)
         self._node_flags = None
         self._ws = {}
+        self._pair_sums = None      # the table of per-(row, relation) sums of a constant layer input (pair_sums)
+        self.pair_sums_builds = 0   # how often that table was (re)built
 
     @classmethod
     def chain(cls, plan: GraphPlan, row_flags: torch.Tensor, n: int, forward: bool = True):
@@ -449,7 +451,7 @@ class GraphSupport:
     def export(self, which: int) -> np.ndarray:
         ptr, n = self.array_ptr(which)
         dt = {L.SUP_COL_FLAGS: torch.uint8, L.SUP_NODE_FLAGS: torch.uint8, L.SUP_LVAL: torch.float32,
-              L.SUP_FVAL: torch.float32}.get(which, torch.int32)
+              L.SUP_FVAL: torch.float32, L.SUP_PAIR_VAL: torch.float32}.get(which, torch.int32)
         out = torch.empty((n,), dtype=dt, device=self.device)
         if n:
             out = _device_array(ptr, n, dt, self.device).clone()
@@ -468,6 +470,86 @@ class GraphSupport:
         """One of the support's int32 arrays as a tensor over the library's memory (valid while the support lives)."""
         ptr, n = self.array_ptr(which)
         return _device_array(ptr, n, torch.int32, self.device)
+
+    # -- dW from per-(row, relation) sums of a constant X (include/mrgcn_hip.h: mrgcn_support_pair_sums_*) ----------
+    def pair_structure(self, K: int = 0):
+        """mrgcn_pair_sums_info_t of this support for rows of K floats (builds the pair structure on first use; inside
+        a stream capture an unbuilt structure reports pairs = -1)."""
+        info = L.PairSumsInfo()
+        with torch.cuda.device(self.device):
+            L.check(L.load().mrgcn_support_pair_sums_info(self.handle, int(K), C.byref(info), _stream_ptr(self.device)),
+                    "mrgcn_support_pair_sums_info")
+        return info
+
+    @staticmethod
+    def _pair_key(src: torch.Tensor, K: int):
+        return (src._version, src.data_ptr(), src.stride(0), src.shape[0], int(K))
+
+    def _pair_sums_build(self, ent, Xc):
+        with torch.cuda.device(self.device):
+            L.check(L.load().mrgcn_support_pair_sums_build_f32(
+                self.handle, Xc.data_ptr(), Xc.stride(0), ent["K"], ent["S"].data_ptr(), _stream_ptr(self.device)),
+                "mrgcn_support_pair_sums_build_f32")
+        self.pair_sums_builds += 1
+        from .stats import bump
+        bump("dw_pair_sums.build")
+
+    def pair_sums(self, src: torch.Tensor, Xc: torch.Tensor, K: int, cap_bytes: int):
+        """S [P, K]: per (row, relation) pair of this support the sum of val_e . X[node_e] over the pair's entries, for
+        a layer input X that is DATA.  `src` is the caller's tensor — the table is valid while that object lives with
+        the same version, address, stride and shape, like the bf16 and the line-aligned copies of X — and `Xc` the rows
+        the kernels read (`src` itself or its line-aligned copy).  Built on the current stream by the first call outside
+        a capture and again, into the same buffer, when the key moves.  None: inside a capture without a valid table,
+        or a table larger than `cap_bytes` — the caller then runs the gather kernel."""
+        import weakref
+        ent = self._pair_sums
+        key = self._pair_key(src, K)
+        if ent is not None and ent["ref"]() is src and ent["key"] == key:
+            return ent["S"]
+        if torch.cuda.is_current_stream_capturing():
+            return None
+        info = self.pair_structure(K)
+        if info.pairs < 0 or info.table_bytes > cap_bytes:
+            return None
+        n = max(int(info.pairs) * int(K), 1)
+        if ent is None or ent["S"].numel() != n:   # (the address moves only with the table's shape)
+            ent = {"S": torch.empty((n,), dtype=torch.float32, device=self.device)}
+        ent.update(ref=weakref.ref(src), key=key, K=int(K), xc=(Xc if Xc is not src else None))
+        self._pair_sums = ent
+        self._pair_sums_build(ent, Xc)
+        return ent["S"]
+
+    def pair_sums_refresh(self) -> bool:
+        """The host-side check in front of a graph replay that reads the table: a captured epoch cannot see that X was
+        changed in place, so the key is compared again (integers, no device wait) and on a mismatch the line-aligned
+        copy of X, if the epoch reads one, and the table are rebuilt IN PLACE on the current stream — the addresses
+        the graph captured stay valid.  True: rebuilt."""
+        ent = self._pair_sums
+        src = ent["ref"]() if ent is not None else None
+        if src is None:
+            return False
+        key = self._pair_key(src, ent["K"])
+        if key == ent["key"] or key[2:] != ent["key"][2:]:   # (another shape or stride: not the tensor of the capture)
+            return False
+        Xc = src
+        if ent["xc"] is not None:
+            with torch.no_grad():
+                ent["xc"].copy_(src)
+            Xc = ent["xc"]
+        ent["key"] = key
+        self._pair_sums_build(ent, Xc)
+        return True
+
+    def pair_sums_info(self) -> dict:
+        """Whether the layer's dW runs on the table, and what it holds: {"active", "pairs", "table_bytes", "K",
+        "builds", "chunks", "max_pair_entries"}."""
+        ent = self._pair_sums
+        if ent is None:
+            return {"active": False, "builds": self.pair_sums_builds}
+        info = self.pair_structure(ent["K"])
+        return {"active": ent["ref"]() is not None, "pairs": int(info.pairs), "table_bytes": int(info.table_bytes),
+                "K": ent["K"], "builds": self.pair_sums_builds, "chunks": int(info.chunks),
+                "max_pair_entries": int(info.max_pair_entries)}
 
     def workspace(self, key, numel: int) -> torch.Tensor:
         """A float32 scratch tensor kept on the support (one per use: the same buffer every epoch)."""

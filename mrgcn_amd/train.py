@@ -15,6 +15,7 @@ import os
 import torch
 
 from . import _lib as L
+from . import functional as Fn
 from .functional import clear_row_grads, dense_from_rows, pop_row_grad, row_sparse_weight_grad
 from .stats import bump
 
@@ -593,11 +594,15 @@ class GraphedStep:
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize()
         self.graph = torch.cuda.CUDAGraph()
+        Fn.take_captured_pair_sums()
         with torch.cuda.graph(self.graph, stream=side, capture_error_mode="thread_local"):
             self.out = fn()
+        self._pair_sums = Fn.take_captured_pair_sums()
         self.warmup_steps = max(warmup, 1)
 
     def __call__(self):
+        for sup in self._pair_sums:   # (tables of a constant input the graph reads: rebuilt in place if X was changed)
+            sup.pair_sums_refresh()
         self.graph.replay()
         return self.out
 
@@ -630,8 +635,12 @@ class GraphedTrainStep:
         # thread_local: calls other threads make while this one captures (e.g. the process group's
         # watchdog in a multi-rank job) do not invalidate the capture.  Captured on the stream the warm-up steps ran
         # on: whatever keeps scratch per stream (a plan's product scratch) has met this stream already.
+        Fn.take_captured_pair_sums()
         with torch.cuda.graph(self.graph, stream=side, capture_error_mode="thread_local"):
             self.loss = train_step(*args)
+        # the pair-sum tables of a constant layer input that the graph reads (built by the warm-up steps): a replay
+        # cannot see an in-place change of X, so their keys are compared again on the host in front of every replay
+        self._pair_sums = Fn.take_captured_pair_sums()
         # capturing executes nothing on the device: `warmup` optimizer steps have been taken so far (the
         # optimizer's device counter says the same; ClipAdam.state_dict() reads it back)
         self.warmup_steps = max(warmup, 1)
@@ -642,5 +651,7 @@ class GraphedTrainStep:
             # load_state_dict replaced the moment tensors and the device step counter the graph was captured on
             raise L.MrgcnError("GraphedTrainStep: the optimizer's state was loaded after the capture; build a new "
                                "GraphedTrainStep (the captured graph still updates the old moment buffers)")
+        for sup in self._pair_sums:
+            sup.pair_sums_refresh()   # (integer compares; on a mismatch the table is rebuilt in place on this stream)
         self.graph.replay()
         return self.loss

@@ -16,6 +16,7 @@ from prof_summary import short  # noqa: E402
 # AM-shaped graph (mrgcn_amd/synth.py, seed 0) and model
 N, R, B, NNZ, NCOLS = 1666764, 267, 40, 13643406, 8165256
 K0, F0, F1 = 155, 10, 11
+PAIRS0 = 179122  # (flagged row, relation) pairs of the layer-0 support, seed-0 AM graph with 1 000 labels
 LD = 12
 GB = 1e9
 PEAK = 8000.0
@@ -57,6 +58,9 @@ def main():
         ("mrgcn::k_dcomp_chunks<10>", ("dcomp: D rows in, by relation", L0 * (B * 4 + 4))),
         ("mrgcn::k_xform_mfma_dw<3, 2, false, float>",
          ("layer-0 dW over the live columns: X rows of the live NODES once + dM rows + lists", NL0 * K0 * 4 + L0 * (LD * 4 + 8))),
+        ("mrgcn::k_dw_pairs<12>",
+         ("layer-0 dW from the pair-sum table: S rows in order + the flagged dY rows + chunk partials out (P = 179 122 pairs of the seed-0 AM graph, chunks of 128)",
+          PAIRS0 * K0 * 4 + NL1 * F0 * 4 + PAIRS0 * 4 + (PAIRS0 // 128 + R) * K0 * F0 * 4)),
         ("mrgcn::k_adam_rows_fused",
          ("Adam, gradient formed on the fly: p, m, v of the live blocks in and out + their dM rows", 6 * 4 * B * NL0 * F0 + L0 * LD * 4 + N * 6)),
         ("mrgcn::k_adam_rows_once<2, 1>",
