@@ -1019,6 +1019,55 @@ int mrgcn_row_scale_f32(float *Y, int64_t ld, int64_t rows, int32_t F, const flo
 int mrgcn_row_scale_live_f32(const float *dY, int64_t ld_dY, int64_t rows, int32_t F, const float *m,
                              const uint8_t *row_flags, int32_t zero_dead, float *out, int64_t ld_out, void *stream);
 
+/* ---- validation and early stopping inside a replayed epoch (csrc/early_stop.hip) ---------------------------------
+ * Evaluation of a label set: loss_out = mean cross-entropy of the rows logits[idx[i], :C] (max-subtracted
+ * log-sum-exp, as mrgcn_softmax_xent_rows_f32), correct_out = how many of those rows have their arg-max at target[i]
+ * (of equal values the lowest class wins, as Tensor.max(dim=1)), labels_out (nullable, [n]) = the arg-max of each.
+ * No gradient is written.  All sums run in a fixed order without float atomics: equal inputs give equal bits.
+ * n <= mrgcn_xent_eval_single_block_rows() takes one block and no workspace (NULL); more rows leave block partials
+ * in `workspace` (mrgcn_xent_eval_workspace() bytes, 16-byte aligned) and a second launch adds them in block order.
+ * idx may repeat rows; ld >= C. */
+int64_t mrgcn_xent_eval_workspace(void);
+int64_t mrgcn_xent_eval_single_block_rows(void);
+int mrgcn_xent_eval_rows_f32(const float *logits, int64_t ld, int32_t C, const int64_t *idx, const int64_t *target,
+                             int64_t n, float *loss_out, int64_t *correct_out, int64_t *labels_out, void *workspace,
+                             void *stream);
+/* The state of tasks/utils.py::EarlyStop on the device.  Start: best_score = -1, records = best_record = 0,
+ * delay / patience as constructed, stop = improved = 0. */
+typedef struct {
+  double best_score;   /* < 0: none yet */
+  int64_t records;     /* records taken, the swallowed ones of `delay` included */
+  int64_t best_record; /* which record (1 = the first) set best_score; 0 = none */
+  int32_t delay;       /* records still to swallow */
+  int32_t patience;
+  int32_t stop;        /* latched: once set, later records change nothing */
+  int32_t improved;    /* 1 iff THIS record set best_score (the flag mrgcn_snapshot_if reads) */
+} mrgcn_early_stop_state;
+/* One row of a float [rows, 4] ring on the device: values[k] (device floats, NULL = -1) go to row (records % rows)
+ * of `ring` before the record is counted, unless `stop` is set already.  A host struct, read at the call. */
+typedef struct {
+  const float *values[4];
+  float *ring;
+  int64_t rows;
+} mrgcn_metrics_row;
+/* EarlyStop.record (tasks/utils.py:64-81) by one thread: the first `delay` records are swallowed; the next one sets
+ * best_score and spends no patience; every later one spends one, and (double)*score + tolerance < best_score sets
+ * best_score and gives patience_default back; stop = 1 when patience <= 0 after that. */
+int mrgcn_early_stop_record(mrgcn_early_stop_state *state, const float *score, double tolerance,
+                            int32_t patience_default, const mrgcn_metrics_row *metrics_row, void *stream);
+/* Copies every entry of a device table when *flag != 0 (flag NULL: always); restore != 0 copies dst -> src instead.
+ * Any size and alignment.  first_block: the entries' running block count, an entry taking
+ * ceil(bytes / mrgcn_snapshot_block_bytes()) blocks; n_blocks: the total. */
+typedef struct {
+  const void *src;
+  void *dst;
+  int64_t bytes;
+  int64_t first_block;
+} mrgcn_copy_entry;
+int64_t mrgcn_snapshot_block_bytes(void);
+int mrgcn_snapshot_if(const int32_t *flag, const mrgcn_copy_entry *table, int32_t n_entries, int64_t n_blocks,
+                      int32_t restore, void *stream);
+
 /* ---- timing helpers (HIP events on the caller's stream; used by bench.py) ------ */
 int mrgcn_event_create(void **event);
 int mrgcn_event_destroy(void *event);

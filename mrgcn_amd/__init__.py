@@ -20,6 +20,8 @@ _ALIASES = {
     "mrgcn.models.temporal_cnn": "mrgcn_amd.models.temporal_cnn",
     "mrgcn.data.batch": "mrgcn_amd.data.batch",
     "mrgcn.data.io.tarball": "mrgcn_amd.data.io.tarball",
+    # (EarlyStop and optimizer_params; found only where a `mrgcn.tasks` package exists — the reference's)
+    "mrgcn.tasks.utils": "mrgcn_amd.tasks.utils",
 }
 _PARENTS = ("mrgcn", "mrgcn.layers", "mrgcn.models", "mrgcn.data", "mrgcn.data.io")
 
@@ -71,10 +73,11 @@ def patch_task_optimizer(module, row_sparse: bool = True) -> None:
 
 def install_as_mrgcn(patch_optimizer: bool = False):
     """Makes `import mrgcn.layers.graph`, `mrgcn.models.{rgcn,mrgcn,perceptron,temporal_cnn}`,
-    `mrgcn.data.batch` and `mrgcn.data.io.tarball` resolve to this package's modules, so that scripts
-    written against the reference (`run.py:12-19`) get the MI355X implementations unchanged.
+    `mrgcn.data.batch`, `mrgcn.data.io.tarball` and `mrgcn.tasks.utils` (`EarlyStop`, `optimizer_params`) resolve to
+    this package's modules, so that scripts written against the reference (`run.py:12-19`) get the MI355X
+    implementations unchanged.
 
-    Only those seven leaf modules are replaced.  Every other `mrgcn.*` module (`mrgcn.tasks.*`,
+    Only those eight leaf modules are replaced.  Every other `mrgcn.*` module (the other `mrgcn.tasks.*`,
     `mrgcn.data.utils`, `mrgcn.encodings.*`, `mrgcn.data.io.tsv`, ...) keeps resolving to the
     reference installation through the normal import machinery, in any import order: a finder at the
     head of `sys.meta_path` answers for the leaves, and a second one at the tail provides empty

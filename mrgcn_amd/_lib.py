@@ -69,6 +69,22 @@ class LiteralGather(C.Structure):
     _fields_ = [("src", _p), ("dst", _p), ("index", _p), ("count", _i64), ("row_bytes", _i64), ("src_rows", _i64),
                 ("unit", _i32), ("reserved", _i32)]
 
+
+class EarlyStopState(C.Structure):
+    """include/mrgcn_hip.h: mrgcn_early_stop_state (40 bytes on the device)."""
+    _fields_ = [("best_score", C.c_double), ("records", _i64), ("best_record", _i64), ("delay", _i32),
+                ("patience", _i32), ("stop", _i32), ("improved", _i32)]
+
+
+class MetricsRow(C.Structure):
+    """include/mrgcn_hip.h: mrgcn_metrics_row (device pointers as integers)."""
+    _fields_ = [("values", _p * 4), ("ring", _p), ("rows", _i64)]
+
+
+class CopyEntry(C.Structure):
+    """include/mrgcn_hip.h: mrgcn_copy_entry."""
+    _fields_ = [("src", _p), ("dst", _p), ("bytes", _i64), ("first_block", _i64)]
+
 # name -> (restype, argtypes); kept in one table so that tests can compare it with the header
 SIGNATURES = {
     "mrgcn_abi_version": (C.c_int, []),
@@ -250,6 +266,12 @@ SIGNATURES = {
     "mrgcn_node_dropout_draw_f32": (C.c_int, [_p, _i64, _i64, _i32, _i32, _i64, C.c_float, _p, _i32, _p]),
     "mrgcn_row_scale_f32": (C.c_int, [_p, _i64, _i64, _i32, _p, _p]),
     "mrgcn_row_scale_live_f32": (C.c_int, [_p, _i64, _i64, _i32, _p, _p, _i32, _p, _i64, _p]),
+    "mrgcn_xent_eval_workspace": (C.c_int64, []),
+    "mrgcn_xent_eval_single_block_rows": (C.c_int64, []),
+    "mrgcn_xent_eval_rows_f32": (C.c_int, [_p, _i64, _i32, _p, _p, _i64, _p, _p, _p, _p, _p]),
+    "mrgcn_early_stop_record": (C.c_int, [_p, _p, C.c_double, _i32, C.POINTER(MetricsRow), _p]),
+    "mrgcn_snapshot_block_bytes": (C.c_int64, []),
+    "mrgcn_snapshot_if": (C.c_int, [_p, _p, _i32, _i64, _i32, _p]),
     "mrgcn_event_create": (C.c_int, [C.POINTER(_p)]),
     "mrgcn_event_destroy": (C.c_int, [_p]),
     "mrgcn_event_record": (C.c_int, [_p, _p]),

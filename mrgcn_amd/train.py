@@ -255,6 +255,32 @@ class ClipAdam(torch.optim.Optimizer):
             st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
         return st
 
+    def _dev_step_entry(self, key, device):
+        """The device step counter and bias corrections of one (beta1, beta2) (capturable)."""
+        ent = self._dev_step.get(key)
+        if ent is None:
+            # seeded with the steps already taken (a loaded checkpoint, eager steps before)
+            t0 = max([int(self.state[p].get("step", 0)) for g2 in self.param_groups
+                      if tuple(float(b) for b in g2["betas"]) == key for p in g2["params"]
+                      if self.state.get(p)] or [0])
+            ent = (torch.full((), t0, dtype=torch.int64, device=device),
+                   torch.ones(2, dtype=torch.float32, device=device))
+            self._dev_step[key] = ent
+        return ent
+
+    def init_state(self):
+        """What the first `step()` would allocate, without taking it: zero moments for every parameter that requires
+        a gradient and, with `capturable`, the device step counters — so that a DeviceEarlyStop built in front of the
+        first epoch has every buffer it snapshots.  A parameter that then never receives a gradient keeps its zero
+        moments (and an entry in `state_dict()`) where `step()` alone would have left it without state; its value is
+        the same either way."""
+        for group in self.param_groups:
+            for p in group["params"]:
+                if p.requires_grad:
+                    self._new_state(p)
+            if self.capturable and group["params"]:
+                self._dev_step_entry(tuple(float(b) for b in group["betas"]), group["params"][0].device)
+
     @torch.no_grad()
     def step(self, closure=None):
         lib = L.load()
@@ -315,16 +341,7 @@ class ClipAdam(torch.optim.Optimizer):
                     key = tuple(float(b) for b in group["betas"])
                     if key in bias:
                         continue
-                    ent = self._dev_step.get(key)
-                    if ent is None:
-                        # seeded with the steps already taken (a loaded checkpoint, eager steps before)
-                        t0 = max([int(self.state[p].get("step", 0)) for g2 in self.param_groups
-                                  if tuple(float(b) for b in g2["betas"]) == key for p in g2["params"]
-                                  if self.state.get(p)] or [0])
-                        ent = (torch.full((), t0, dtype=torch.int64, device=device),
-                               torch.ones(2, dtype=torch.float32, device=device))
-                        self._dev_step[key] = ent
-                    bias[key] = ent[1]
+                    bias[key] = self._dev_step_entry(key, device)[1]
             if multi:
                 try:
                     b1m, b2m, _ = next(iter(hyper))
@@ -655,3 +672,429 @@ class GraphedTrainStep:
             sup.pair_sums_refresh()   # (integer compares; on a mismatch the table is rebuilt in place on this stream)
         self.graph.replay()
         return self.loss
+
+
+# ---- validation and early stopping inside the epoch (csrc/early_stop.hip) -------------------------------------------
+class EarlyStop:
+    """The reference's `tasks/utils.py::EarlyStop` on the host: same constructor, attributes and `record(score,
+    weights, optim)` — the first `delay` records are swallowed, the next sets `best_score` (kept at -1 until then)
+    and spends no patience, every later one spends one and, when `score + tolerance < best_score`, sets the best
+    score, deep-copies both `state_dict()`s and gives the patience back; `stop` is set when no patience is left
+    after that.  Scores are losses (>= 0): `best_score < 0` is the "none yet" sentinel, as in the reference.
+
+    `fit` and `GraphedTrainEvalStep` also take an instance as the configuration of a `DeviceEarlyStop`."""
+
+    def __init__(self, patience=7, tolerance=0.01, delay=10):
+        self.full_patience = self.patience = patience
+        self.tolerance, self.delay = tolerance, delay
+        self.stop = False
+        self.best_score = -1
+        self.best_weights = self.best_optim = None
+
+    def record(self, score, weights, optim):
+        import copy
+        if self.delay > 0:   # still inside the grace period
+            self.delay -= 1
+            return
+        first = self.best_score < 0
+        if not first:
+            self.patience -= 1
+        if first or score + self.tolerance < self.best_score:
+            self.best_score = score
+            self.best_weights = copy.deepcopy(weights.state_dict())
+            self.best_optim = copy.deepcopy(optim.state_dict())
+            if not first:
+                self.patience, self.stop = self.full_patience, False
+        if not first and self.patience <= 0:
+            self.stop = True
+
+
+_COUNT_ONLY = (1 << 31) - 1   # a delay that swallows every record: the state then only counts them
+
+
+class _StopState:
+    """The device struct of include/mrgcn_hip.h: mrgcn_early_stop_state, the launch that records into it and the one
+    small copy that reads it back."""
+
+    def __init__(self, device, patience, tolerance, delay):
+        self.patience_default, self.tolerance, self.delay0 = int(patience), float(tolerance), int(delay)
+        self.buf = torch.zeros(C.sizeof(L.EarlyStopState), dtype=torch.uint8, device=device)
+        self.reset()
+
+    def write(self, st):
+        self.buf.copy_(torch.frombuffer(bytearray(bytes(st)), dtype=torch.uint8))
+
+    def reset(self):
+        self.write(L.EarlyStopState(-1.0, 0, 0, self.delay0, self.patience_default, 0, 0))
+
+    def read(self):
+        """One device-to-host copy of the 40 bytes (synchronises with the stream's work so far)."""
+        return L.EarlyStopState.from_buffer_copy(self.buf.cpu().numpy().tobytes())
+
+    @property
+    def improved_ptr(self) -> int:
+        return self.buf.data_ptr() + L.EarlyStopState.improved.offset
+
+    def record(self, score, metrics=None, values=None):
+        if not (score.is_cuda and score.dtype == torch.float32 and score.numel() == 1):
+            raise L.MrgcnError("early stop: the score is one float32 on the device")
+        row = None
+        if metrics is not None:
+            if not (metrics.is_cuda and metrics.dtype == torch.float32 and metrics.dim() == 2
+                    and metrics.shape[1] == 4 and metrics.is_contiguous() and metrics.shape[0] > 0):
+                raise L.MrgcnError("metrics: a contiguous float32 [rows, 4] tensor on the device")
+            values = tuple(values or ()) + (None,) * (4 - len(values or ()))
+            for v in values:
+                if v is not None and not (v.is_cuda and v.dtype == torch.float32 and v.numel() == 1):
+                    raise L.MrgcnError("metrics: every value is one float32 on the device")
+            row = L.MetricsRow((C.c_void_p * 4)(*[v.data_ptr() if v is not None else None for v in values]),
+                               metrics.data_ptr(), int(metrics.shape[0]))
+        dev = self.buf.device
+        with torch.cuda.device(dev):
+            L.check(L.load().mrgcn_early_stop_record(self.buf.data_ptr(), score.data_ptr(), self.tolerance,
+                                                     self.patience_default, C.byref(row) if row is not None else None,
+                                                     _stream(dev)), "mrgcn_early_stop_record")
+
+
+class DeviceEarlyStop:
+    """`EarlyStop` with its state, its decision and its copy of the best weights on the device, so that a replayed epoch
+    graph records into it without the host:
+
+        stopper = DeviceEarlyStop(model, optimizer, patience=7, tolerance=0.01)   # after the first optimizer step
+        stopper.record(val_loss)       # device float32 scalar; capturable: the record launch, then the snapshot
+        if stopper.poll(): stopper.restore_()
+
+    `record` runs `mrgcn_early_stop_record` and then `mrgcn_snapshot_if` on the `improved` flag the record just wrote:
+    when this record set the best score, every parameter, every persistent module buffer (BatchNorm's running
+    statistics), every tensor of the optimizer's state (both Adam moments) and ClipAdam's device step counter and
+    bias corrections are copied into buffers allocated here, once.  (Buffers are named by address: a module that
+    replaces a buffer tensor instead of updating it in place needs a new DeviceEarlyStop.)  Once `stop`
+    is set the record launch changes nothing, `improved` stays 0, and records taken before the host polls cannot touch
+    the snapshot.  `restore_()` copies the snapshot back IN PLACE (no `load_state_dict`, no `_state_gen` bump: a
+    captured graph over these tensors stays valid).  The score is any device scalar — a link-prediction loop may pass
+    its own.  Scores are >= 0 (`best_score < 0` means "none yet", as in the reference).
+
+    The optimizer's state must exist (it is what gets snapshotted): before the first step the constructor raises.
+    A ClipAdam must be `capturable` (its step count then lives on the device and is part of the snapshot)."""
+
+    def __init__(self, model, optimizer, patience=7, tolerance=0.01, delay=10):
+        params, seen = [], set()
+        for p in list(model.parameters()) + [p for g in optimizer.param_groups for p in g["params"]]:
+            if id(p) not in seen:
+                seen.add(id(p))
+                params.append(p)
+        if not params or not all(p.is_cuda for p in params):
+            raise L.MrgcnError("DeviceEarlyStop: the parameters live on the GPU")
+        live = []
+        has_state = False
+        for p in params:
+            live.append(p.data)
+            for k, v in (optimizer.state.get(p) or {}).items():
+                if torch.is_tensor(v):
+                    live.append(v)
+                    has_state = True
+                elif k == "step" and not getattr(optimizer, "capturable", False):
+                    raise L.MrgcnError("DeviceEarlyStop: the optimizer counts its steps on the host; use "
+                                       "ClipAdam(..., capturable=True)")
+        if not has_state:
+            raise L.MrgcnError("DeviceEarlyStop: the optimizer has no state yet (its moments are what gets "
+                               "snapshotted): take the first optimizer step before building it")
+        for ent in getattr(optimizer, "_dev_step", {}).values():
+            live += [ent[0], ent[1]]
+        # the buffers a state_dict() carries (BatchNorm's running statistics and batch count in the encoders): an
+        # eval() forward after the restore then sees the best record's statistics, as with the reference's best_weights
+        self._buffers = [b for m in model.modules() for k, b in m._buffers.items()
+                         if b is not None and k not in m._non_persistent_buffers_set]
+        seen_buf = set()
+        for b in self._buffers:
+            if id(b) not in seen_buf:
+                seen_buf.add(id(b))
+                live.append(b)
+        for t in live:
+            if not t.is_contiguous() or not t.is_cuda:
+                raise L.MrgcnError("DeviceEarlyStop: parameters and optimizer state are contiguous device tensors")
+        device = params[0].device
+        self.state = _StopState(device, patience, tolerance, delay)
+        self._params, self._live = params, live
+        self._snap = [torch.empty_like(t) for t in live]
+        block = int(L.load().mrgcn_snapshot_block_bytes())
+        table = (L.CopyEntry * len(live))()
+        blocks = 0
+        for i, (s, d) in enumerate(zip(live, self._snap)):
+            nbytes = s.numel() * s.element_size()
+            table[i] = L.CopyEntry(s.data_ptr(), d.data_ptr(), nbytes, blocks)
+            blocks += (nbytes + block - 1) // block
+        self._table = torch.frombuffer(bytearray(bytes(table)), dtype=torch.uint8).to(device)
+        self._n, self._blocks = len(live), int(blocks)
+        self.snapshot_bytes = sum(s.numel() * s.element_size() for s in live)
+        self._optimizer, self._state_gen = optimizer, getattr(optimizer, "_state_gen", None)
+
+    def _check_gen(self):
+        if getattr(self._optimizer, "_state_gen", None) != self._state_gen:
+            raise L.MrgcnError("DeviceEarlyStop: the optimizer's state was loaded after this object was built (its "
+                               "table still names the old moment buffers); build a new one")
+
+    def _copy(self, flag_ptr, restore):
+        dev = self._table.device
+        with torch.cuda.device(dev):
+            L.check(L.load().mrgcn_snapshot_if(flag_ptr, self._table.data_ptr(), self._n, self._blocks,
+                                               1 if restore else 0, _stream(dev)), "mrgcn_snapshot_if")
+
+    def record(self, score_dev, metrics=None, values=None):
+        """The record, then the snapshot behind its `improved` flag.  `metrics`, `values`: a float32 [rows, 4] ring and
+        up to four device scalars written to row `records % rows` by the same launch (see train_eval_step)."""
+        self._check_gen()
+        self.state.record(score_dev, metrics, values)
+        self._copy(self.state.improved_ptr, False)
+
+    def reset(self):
+        self.state.reset()
+
+    def poll(self) -> bool:
+        """One 40-byte device-to-host copy; True once the run should stop."""
+        self._last = self.state.read()
+        return bool(self._last.stop)
+
+    def restore_(self) -> bool:
+        """The snapshot back into the live parameters, moments and step counter, in place.  False (and nothing
+        copied) while no record has set a best score."""
+        self._check_gen()
+        if self.state.read().best_record == 0:
+            return False
+        self._copy(None, True)
+        torch.autograd.graph.increment_version(self._params)
+        return True
+
+    stop = property(lambda self: self.poll())
+    best_score = property(lambda self: float(self.state.read().best_score))
+    best_record = property(lambda self: int(self.state.read().best_record))
+    records = property(lambda self: int(self.state.read().records))
+    patience = property(lambda self: int(self.state.read().patience))
+
+    def state_dict(self, snapshot: bool = True):
+        st = self.state.read()
+        sd = {f: getattr(st, f) for f, _ in L.EarlyStopState._fields_}
+        sd.update(patience_default=self.state.patience_default, tolerance=self.state.tolerance)
+        if snapshot:
+            sd["snapshot"] = [t.clone() for t in self._snap]
+        return sd
+
+    def load_state_dict(self, sd):
+        if "snapshot" in sd:
+            if len(sd["snapshot"]) != len(self._snap):
+                raise L.MrgcnError("DeviceEarlyStop: the snapshot belongs to another model / optimizer")
+            for d, s in zip(self._snap, sd["snapshot"]):
+                d.copy_(s)
+        self.state.patience_default, self.state.tolerance = int(sd["patience_default"]), float(sd["tolerance"])
+        self.state.write(L.EarlyStopState(*[sd[f] for f, _ in L.EarlyStopState._fields_]))
+
+
+_EVAL_WS: dict = {}
+_EVAL_N: dict = {}
+
+
+def evaluate(logits, idx, targets, want_labels: bool = False):
+    """`(loss, acc)` of the rows `logits[idx]` against `targets` as device scalars — the reference's
+    `categorical_crossentropy` and `categorical_accuracy` of an evaluation pass (node_classification.py:432-444) in one
+    launch that writes no gradient — and with `want_labels` the arg-max of every row as a third value (`test_model`'s
+    `labels`).  `acc = correct / n` in float32; of equal logits the lowest class wins; the sums run in a fixed
+    order, so equal inputs give equal bits.  No host synchronisation; capturable."""
+    if not (logits.is_cuda and logits.dtype == torch.float32 and logits.dim() == 2):
+        raise L.MrgcnError("evaluate: float32 [N, C] logits on the device")
+    if not (idx.dtype == torch.int64 and targets.dtype == torch.int64 and idx.numel() == targets.numel()
+            and idx.numel() > 0 and idx.device == logits.device and targets.device == logits.device):
+        raise L.MrgcnError("evaluate: idx and targets are int64 tensors of one (non-zero) length on the device of "
+                           "the logits")
+    if logits.stride(1) != 1:
+        logits = logits.contiguous()
+    idx, targets = idx.contiguous(), targets.contiguous()
+    dev, n = logits.device, int(idx.numel())
+    lib = L.load()
+    loss = torch.empty((), dtype=torch.float32, device=dev)
+    correct = torch.empty((), dtype=torch.int64, device=dev)
+    labels = torch.empty((n,), dtype=torch.int64, device=dev) if want_labels else None
+    ws = 0
+    if n > int(lib.mrgcn_xent_eval_single_block_rows()):
+        key = (dev, _stream(dev))   # (block partials: one set per stream that evaluates)
+        t = _EVAL_WS.get(key)
+        if t is None:
+            t = _EVAL_WS[key] = torch.empty(int(lib.mrgcn_xent_eval_workspace()), dtype=torch.uint8, device=dev)
+        ws = t.data_ptr()
+    with torch.cuda.device(dev):
+        L.check(lib.mrgcn_xent_eval_rows_f32(logits.data_ptr(), logits.stride(0), logits.shape[1], idx.data_ptr(),
+                                             targets.data_ptr(), n, loss.data_ptr(), correct.data_ptr(),
+                                             labels.data_ptr() if want_labels else 0, ws, _stream(dev)),
+                "mrgcn_xent_eval_rows_f32")
+    # (a tensor divisor: torch divides by a Python scalar as a multiplication by its reciprocal, an ulp off correct / n)
+    div = _EVAL_N.get((dev, n))   # (kept for good: a captured graph may read it)
+    if div is None:
+        div = _EVAL_N[(dev, n)] = torch.full((), float(n), dtype=torch.float32, device=dev)
+    acc = correct.to(torch.float32).div_(div)
+    return (loss, acc, labels) if want_labels else (loss, acc)
+
+
+def train_eval_step(model, forward_fn, idx, targets, optimizer, l1_lambda: float = 0.0, l2_lambda: float = 0.0,
+                    row_sparse=None, valid=None, early_stop=None, metrics=None, counter=None):
+    """One epoch of the reference's `train_model` (node_classification.py:146-225) without the host: `train_step`;
+    loss and accuracy of the training pass's own logits (the forward in front of the update, as the reference reports
+    them); with `valid=(idx, targets)` one more `forward_fn()` under `model.eval()` and `no_grad` and its loss and
+    accuracy on the validation rows; `(train_loss, train_acc, val_loss, val_acc)` into row `records % rows` of the
+    float32 `[rows, 4]` device ring `metrics` (-1 where there is no validation), the row counter living in the
+    early-stop state on the device; `early_stop.record(val_loss)`.  Returns the four device scalars (None for the
+    missing ones).  The model's train / eval mode is put back on exit.
+
+    `counter`: the record counter of a run without `early_stop` (fit and GraphedTrainEvalStep bring one)."""
+    if early_stop is not None and valid is None:
+        raise L.MrgcnError("train_eval_step: early stopping scores the validation loss: pass valid=(idx, targets)")
+    box = []
+
+    def fwd():
+        out = forward_fn()
+        # (at once: the logits may sit in a buffer the backward is free to reuse)
+        box[:] = evaluate(out.detach(), idx, targets)
+        return out
+    train_loss = train_step(model, fwd, idx, targets, optimizer, l1_lambda, l2_lambda, row_sparse)
+    train_acc = box[1]
+    val_loss = val_acc = None
+    if valid is not None:
+        was_training = model.training
+        model.eval()
+        try:
+            with torch.no_grad():
+                val_loss, val_acc = evaluate(forward_fn(), valid[0], valid[1])
+        finally:
+            model.train(was_training)
+    values = (train_loss, train_acc, val_loss, val_acc)
+    if early_stop is not None:
+        early_stop.record(val_loss, metrics, values)
+    elif metrics is not None:
+        if counter is None:
+            raise L.MrgcnError("train_eval_step: `metrics` without `early_stop` needs the record counter that fit / "
+                               "GraphedTrainEvalStep provide")
+        counter.record(train_loss, metrics, values)
+    return values
+
+
+def _as_device_stopper(early_stop, model, optimizer):
+    """A host `EarlyStop` stands for its configuration: the DeviceEarlyStop of that patience, tolerance and delay."""
+    if early_stop is None or isinstance(early_stop, DeviceEarlyStop):
+        return early_stop
+    if not isinstance(optimizer, ClipAdam):
+        raise L.MrgcnError("only ClipAdam's state can be allocated ahead of its first step: take one step, then "
+                           "build the DeviceEarlyStop yourself")
+    optimizer.init_state()
+    return DeviceEarlyStop(model, optimizer, early_stop.full_patience, early_stop.tolerance, early_stop.delay)
+
+
+class GraphedTrainEvalStep:
+    """`train_eval_step` captured into one hipGraph and replayed: the training step, the evaluation of both label
+    sets, the metrics row, the early-stop record and the conditional snapshot of the best state, on the one capture
+    stream (a single chain, no parallel branches), with no host synchronisation.
+
+        ring = torch.zeros((8, 4), device="cuda")
+        step = GraphedTrainEvalStep(model, lambda: model(X, A), idx, y, optimizer, valid=(vidx, vy),
+                                    early_stop=EarlyStop(7, 0.01), metrics=ring)
+        step(); ...; step.early_stop.poll()
+
+    The capture discipline is GraphedTrainStep's: `warmup` real epochs on the capture stream, `thread_local` capture,
+    pair-sum tables re-checked in front of every replay, the optimizer's `_state_gen` compared.  `warmup` optimizer
+    steps have been taken when the constructor returns (capturing executes nothing), but they leave no trace in the
+    bookkeeping: the early-stop state and the ring are reset after the warm-up, just before the capture, so the first
+    replay is record 1.  `early_stop`: a DeviceEarlyStop, or a host EarlyStop as its configuration."""
+
+    def __init__(self, model, forward_fn, idx, targets, optimizer, valid=None, early_stop=None, metrics=None,
+                 warmup: int = 3, l1_lambda: float = 0.0, l2_lambda: float = 0.0, row_sparse=None):
+        if not getattr(optimizer, "capturable", False):
+            raise L.MrgcnError("GraphedTrainEvalStep needs ClipAdam(..., capturable=True)")
+        self.early_stop = early_stop = _as_device_stopper(early_stop, model, optimizer)
+        self.metrics = metrics if metrics is not None else torch.zeros((8, 4), dtype=torch.float32, device=idx.device)
+        self.counter = early_stop.state if early_stop is not None else _StopState(idx.device, 1, 0.0, _COUNT_ONLY)
+        kw = dict(l1_lambda=l1_lambda, l2_lambda=l2_lambda, row_sparse=row_sparse, valid=valid, early_stop=early_stop,
+                  metrics=self.metrics, counter=self.counter)
+        args = (model, forward_fn, idx, targets, optimizer)
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            for _ in range(max(warmup, 1)):
+                train_eval_step(*args, **kw)
+            self.counter.reset()
+            self.metrics.zero_()
+        torch.cuda.current_stream().wait_stream(side)
+        torch.cuda.synchronize()
+        self.graph = torch.cuda.CUDAGraph()
+        Fn.take_captured_pair_sums()
+        with torch.cuda.graph(self.graph, stream=side, capture_error_mode="thread_local"):
+            self.values = train_eval_step(*args, **kw)
+        self._pair_sums = Fn.take_captured_pair_sums()
+        self.loss = self.values[0]
+        self.warmup_steps = max(warmup, 1)
+        self._optimizer, self._state_gen = optimizer, optimizer._state_gen
+
+    def __call__(self):
+        if self._optimizer._state_gen != self._state_gen:
+            raise L.MrgcnError("GraphedTrainEvalStep: the optimizer's state was loaded after the capture; build a new "
+                               "GraphedTrainEvalStep (the captured graph still updates the old moment buffers)")
+        for sup in self._pair_sums:
+            sup.pair_sums_refresh()
+        self.graph.replay()
+        return self.values
+
+    step = __call__
+
+
+def fit(model, forward_fn, train, valid, optimizer, nepoch, early_stop=None, poll=8, graphed=True,
+        l1_lambda: float = 0.0, l2_lambda: float = 0.0, row_sparse=None, warmup: int = 3):
+    """The reference's full-batch `train_model` loop (node_classification.py:112-230) as a generator over
+    `(epoch, train_loss, train_acc, val_loss, val_acc)` — floats, epochs from 1 — with the host looking in every
+    `poll` epochs only: the epochs in between run back to back (one graph replay each with `graphed=True`), their
+    rows wait in a device ring of `poll` rows and are yielded at the poll.  `train`, `valid`: `(idx, targets)` pairs;
+    `valid=None` trains without validation (the reference's `test_split == "test"`) and yields -1 for both validation
+    values.  `early_stop`: None, a DeviceEarlyStop, or a host EarlyStop as its configuration.  A run starts at record 0:
+    whatever a DeviceEarlyStop recorded before is discarded (its state is reset, graphed or not), and the first yielded
+    epoch is 1.
+
+    When a poll finds `stop` set, the rows up to and including the record that set it are yielded, the best state is
+    restored in place (`restore_()`) and the generator ends.  Up to `poll - 1` epochs have then run past the stop:
+    their optimizer steps happened, but the latched state ignored their records, their metrics rows were not written,
+    no snapshot was taken, and the restore overwrites every tensor they changed — so they are invisible afterwards
+    (other than in the dropout position and the time they took).
+
+    A run that reaches `nepoch` without a stop is left with the LAST epoch's parameters and optimizer state, as the
+    reference's loop leaves them: nothing is restored.  The best state stays in the stopper (`best_record`; pass a
+    DeviceEarlyStop of your own and call its `restore_()` to get it).
+
+    With `graphed=True` the `warmup` epochs of the capture are real optimizer steps taken before epoch 1 (see
+    GraphedTrainEvalStep)."""
+    idx, targets = train
+    poll = max(int(poll), 1)
+    ring = torch.zeros((poll, 4), dtype=torch.float32, device=idx.device)
+    stopper = _as_device_stopper(early_stop, model, optimizer)
+    if stopper is not None and valid is None:
+        raise L.MrgcnError("fit: early stopping scores the validation loss: pass valid=(idx, targets)")
+    if graphed:
+        run = GraphedTrainEvalStep(model, forward_fn, idx, targets, optimizer, valid=valid, early_stop=stopper,
+                                   metrics=ring, warmup=warmup, l1_lambda=l1_lambda, l2_lambda=l2_lambda,
+                                   row_sparse=row_sparse)
+        counter = run.counter
+    else:
+        counter = stopper.state if stopper is not None else _StopState(idx.device, 1, 0.0, _COUNT_ONLY)
+        counter.reset()
+
+        def run():
+            return train_eval_step(model, forward_fn, idx, targets, optimizer, l1_lambda, l2_lambda, row_sparse,
+                                   valid=valid, early_stop=stopper, metrics=ring, counter=counter)
+    done = 0
+    epoch = 0
+    while epoch < nepoch:
+        for _ in range(min(poll, nepoch - epoch)):
+            run()
+            epoch += 1
+        st = counter.read()
+        rows = ring.cpu()
+        for r in range(done, int(st.records)):
+            row = rows[r % poll]
+            yield (r + 1, float(row[0]), float(row[1]), float(row[2]), float(row[3]))
+        done = int(st.records)
+        if st.stop:
+            stopper.restore_()
+            return

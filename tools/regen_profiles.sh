@@ -78,6 +78,8 @@ done
 python3 tools/node_dropout_probe.py ${NODE_DROPOUT_PARENT_JSON:+--parent $NODE_DROPOUT_PARENT_JSON} --out $o/node_dropout_probe.json > $o/node_dropout_probe.txt 2> $o/node_dropout_probe.err
 # (10d) top-k completion at the FB15k-237 decoder shape: predict_topk, torch.topk over the score matrix, compute_ranks_fast
 python3 tools/lp_topk_probe.py --out $o/lp_topk_probe.json > $o/lp_topk_probe.txt 2> $o/lp_topk_probe.err
+# (10e) validation and early stopping inside the replayed epoch against the host loop around a replayed train step
+python3 tools/early_stop_probe.py --out $o/early_stop_probe.json > $o/early_stop_probe.txt 2> $o/early_stop_probe.err
 hipcc -O3 --offload-arch=gfx950 -std=c++17 tools/lab/copy_lab.hip -o /tmp/copy_lab 2>/dev/null && /tmp/copy_lab > $o/copy_lab.txt 2>&1
 python3 tools/lab/spmm_hot_lab.py > $o/spmm_hot_lab.txt 2>&1
 # the CPU suite last: the tree these artefacts describe is green
