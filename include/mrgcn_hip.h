@@ -474,7 +474,16 @@ int mrgcn_support_spmm_t_f32(const mrgcn_support_t *support, const float *dY, in
  *   dV == NULL : the norm-only pass in front of mrgcn_support_adam_rows_fused_f32: dcomp and *dV_sumsq (both
  *                WRITTEN, not accumulated: no zeroing by the caller, fixed summation order) — one pass over the
  *                live nodes' V blocks that stores each live column's B products, then a relation-major sum of
- *                those rows: no atomics anywhere.  `workspace`: mrgcn_support_mix_bwd_workspace(support, B) floats.
+ *                those rows: no atomics anywhere.  `workspace`: mrgcn_support_mix_bwd_workspace(support, B) floats,
+ *                8-byte aligned, laid out as
+ *                  D [L][B] | slab [chunks][B] (padded to whole fours) | 2048 doubles: parts of ||dV||^2 |
+ *                  ceil(NL / 8) doubles: the per-block parts of the one-shot form.
+ *                Two forms (configuration row `sup_mix_stream`): 1 — a one-shot grid, a wave per two live nodes, V blocks
+ *                as 16-byte pieces, taken when B F % 4 == 0, B F <= 1024, B <= 64, F <= 16 and even, V 16-byte
+ *                aligned; its per-block parts of ||dV||^2 are folded by blocks appended to the relation-major sum's
+ *                launch; 0, and every other shape — the resident kernel with `comp` in LDS.  D and dcomp have the
+ *                same bits under both; ||dV||^2 differs in the last bits (its parts are grouped differently) and is
+ *                bitwise reproducible under either.
  *   dV != NULL : the gradient itself; `dense` != 0 writes every block (zeros for nodes outside the support),
  *                dense == 0 only the blocks of the support's nodes (row-sparse: mrgcn_adam_step_rows_f32 with
  *                NODE_FLAGS as row_cur).  dcomp written; *dV_sumsq (nullable) ACCUMULATED into. */

@@ -111,6 +111,11 @@ template <typename OT> __device__ __forceinline__ void store_operand(OT *p, floa
 template <typename OT> __device__ __forceinline__ float load_operand(const OT *p) {
   if constexpr (sizeof(OT) == 4) return *p; else return bf16_to_f32(*p);
 }
+// orders a wave's own LDS writes before its own LDS reads (a wave-private tile: no workgroup barrier needed)
+__device__ __forceinline__ void wave_lds_fence() {
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+}
 
 // MFMA relation transforms (xform_mfma.hip)
 bool xform_mfma_fwd_supported(int K, int F);

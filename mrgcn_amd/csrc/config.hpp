@@ -42,6 +42,7 @@ enum CfgKey : int {
   CFG_MIX_TICKETS,
   CFG_MIX_TICKET_TILE,
   CFG_SPMM_T_SEG,
+  CFG_SUP_MIX_STREAM,
   CFG_COUNT
 };
 int64_t cfg(CfgKey k);

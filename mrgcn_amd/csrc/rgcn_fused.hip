@@ -158,11 +158,6 @@ __global__ __launch_bounds__(kMixFwdTB) void k_mix_fwd(const int32_t *__restrict
 // 16-byte LDS read per K step) and B = V_j[16 ks + 4 kq + s][n] (the same for every column tile of the node).
 // The result lane (n, q) holds columns 4 q + reg: addend added, row stored at its operand position.
 // =====================================================================================
-__device__ __forceinline__ void wave_lds_fence() {
-  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-}
-
 using f32x4m = __attribute__((ext_vector_type(4))) float;
 constexpr int kFwdTB = 1024;  // 16 waves share one LDS copy of comp (R x 52 floats is most of a CU's LDS at R ~ 270)
 

@@ -7,8 +7,10 @@
 // (node, relation) order and keeps, per live column, only the entries that sit in live rows.  Per epoch:
 //
 //   dM[k]      = sum over kept entries (k_spmm on the filtered view: a plain CSR product over L short rows)
-//   D[k][b]    = <dM[k], V[j_k][b]>,  ||dV||^2            one pass over the live nodes' V blocks (k_mix_bwd_sup):
-//                                                         lane = basis, a node's live columns are consecutive rows
+//   D[k][b]    = <dM[k], V[j_k][b]>,  ||dV||^2            one pass over the live nodes' V blocks: k_mix_bwd_stream (a
+//                                                         one-shot grid, blocks as 16-byte pieces) or k_mix_bwd_sup
+//                                                         (resident, comp in LDS); lane = basis in the arithmetic, a
+//                                                         node's live columns are consecutive rows
 //   dcomp[r]   = sum of the D rows of relation r          relation-major walk of D (k_dcomp_chunks / _final)
 //   dW, dX     = the matrix-core transforms on the support's relation-major lists (xform_mfma.hip, unchanged kernels)
 //   Adam       = k_adam_rows_fused with (node -> live range, relation per live column) in place of the plan's arrays
@@ -19,12 +21,16 @@
 #include <cstdlib>
 
 #include "common.hpp"
+#include "config.hpp"
 
 namespace mrgcn {
 namespace {
 
 constexpr int kSupTB = 512;
 constexpr int kSqParts = 2048;  // per-block partial sums of ||dV||^2 (doubles), added in block order by k_dcomp_final
+// list entries per wave of the one-shot form.  AM epoch, kernel medians under the tracer on one box: the resident
+// kernel 568 us, one entry per wave 519, two 452, four 447 (68 VGPRs, seven waves per SIMD): two kept
+constexpr int kStreamNPW = 2;
 
 // F floats of one basis row (rows 4 F bytes apart: 8-byte aligned when F is even).  EXACT: F == FT, known at compile
 // time — the loads are then straight-line code (a run-time F puts every piece behind a branch, and the waitcnt pass
@@ -198,19 +204,192 @@ __global__ __launch_bounds__(kSupTB) void k_mix_bwd_sup(const int32_t *__restric
   }
 }
 
+// k_mix_bwd_stream: the same pass as a ONE-SHOT grid, modelled on k_adam_rows_once (rgcn_fused.hip), which walks the
+// same list at the fabric's one-shot rate.  A wave owns NPW consecutive list entries and ends: no persistent loop, no
+// block-wide table, nothing shared between waves but the four squared-norm parts that meet behind the block's only
+// barrier, at its very end.  Rounds of straight-line loads at clamped addresses: (1) the list entries (wave uniform),
+// (2) the node's V block as B F / 4 contiguous 16-byte pieces, lane q piece q (+ 64 h), nontemporal, and with them the
+// relation and dM row of the node's first four live columns (16-lane group kq: column klo + kq), (3) the comp rows of
+// those columns from the (L2-resident) table, lane b: comp[r][b].  The pieces then cross a wave-private LDS tile
+// (B F floats per node in flight) into k_mix_bwd_sup's register layout — lane b holds V[j][b][0..F) — and from there
+// the arithmetic is k_mix_bwd_sup's, fmaf for fmaf: D has the same bits.  Nodes with more than four live columns go
+// on four at a time, reloading rows and comp values as the Adam kernel does.
+// Reach (the launcher): B F % 4 == 0, B F <= 1024 (NH <= 4), B <= 64, F <= 16 and EVEN (an odd F would put every
+// other row of the tile off the 8-byte grid of the paired LDS reads: it keeps the resident kernel), V 16-byte aligned.
+// EXACT: F == FT; otherwise FT = 16 and the rows are padded with zeros as k_mix_bwd_sup<FT, NB, false> pads them.
+// ||dV||^2: a wave's lanes by xor shuffle, the block's four waves in wave order in double -> blk_part[block]; the fold
+// blocks of k_dcomp_chunks bring those down to <= kSqParts doubles, k_dcomp_final adds them: a fixed order throughout.
+using f32x4s = __attribute__((ext_vector_type(4))) float;
+using f32x2s = __attribute__((ext_vector_type(2))) float;
+template <int FT, int NH, int NPW, bool EXACT>
+__global__ __launch_bounds__(256) void k_mix_bwd_stream(const int32_t *__restrict__ lnode,
+                                                        const int32_t *__restrict__ lnptr,
+                                                        const int32_t *__restrict__ lrel,
+                                                        const float *__restrict__ dM, int64_t ldM,
+                                                        const float *__restrict__ V, const float *__restrict__ comp,
+                                                        int64_t NL, int B, int F_, float *__restrict__ D,
+                                                        double *__restrict__ blk_part) {
+  const int F = EXACT ? FT : F_;
+  extern __shared__ __align__(16) float s_tile[];  // [4 waves][NPW][B F]
+  const int lane = threadIdx.x & 63;
+  const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int nv = (B * F) >> 2;  // 16-byte pieces of a block
+  const bool on = lane < B;
+  const int b = on ? lane : 0;
+  const int kq = lane >> 4, oq = lane & 15;
+  const int oqc = oq < F ? oq : F - 1;
+  const int64_t i0 = ((int64_t)blockIdx.x * 4 + wv) * NPW;
+  // round 1: the list entries (a wave past the end repeats the last entry and stores nothing for it)
+  int64_t j[NPW];
+  int32_t klo[NPW], khi[NPW];
+#pragma unroll
+  for (int u = 0; u < NPW; ++u) {
+    const int64_t i = (i0 + u < NL) ? i0 + u : NL - 1;
+    j[u] = lnode[i];
+    klo[u] = lnptr[i];
+    khi[u] = lnptr[i + 1];
+  }
+  // round 2: the blocks, and relation / gradient row of the first four live columns
+  f32x4s pc[NPW][NH];
+  int32_t rmine[NPW];
+  float dmine[NPW];
+#pragma unroll
+  for (int u = 0; u < NPW; ++u) {
+    const f32x4s *v4 = reinterpret_cast<const f32x4s *>(V) + j[u] * (int64_t)nv;
+#pragma unroll
+    for (int h = 0; h < NH; ++h) {
+      const int q = (lane + 64 * h < nv) ? lane + 64 * h : nv - 1;
+      pc[u][h] = __builtin_nontemporal_load(v4 + q);  // (read once per epoch)
+    }
+    const int32_t kk = (klo[u] + kq < khi[u]) ? klo[u] + kq : klo[u];
+    dmine[u] = dM[(int64_t)kk * ldM + oqc];
+    rmine[u] = lrel[kk];
+  }
+  // round 3: the comp rows of those columns (the first column's row where the node has fewer than four)
+  float cv[NPW][4];
+#pragma unroll
+  for (int u = 0; u < NPW; ++u)
+#pragma unroll
+    for (int t = 0; t < 4; ++t)
+      cv[u][t] = comp[(int64_t)__builtin_amdgcn_readlane(rmine[u], 16 * t) * B + b];
+  // the pieces cross the wave's tile: written in piece order, read as the 8-byte pairs of row b.  The writes are
+  // unconditional at the clamped piece numbers of the loads (lanes past the block's end write the last piece again,
+  // the same bytes): behind a guard the compiler sinks the piece's LOAD into the guarded block and waits for it there
+  float *tile = s_tile + (size_t)wv * NPW * (4 * nv);
+#pragma unroll
+  for (int u = 0; u < NPW; ++u)
+#pragma unroll
+    for (int h = 0; h < NH; ++h) {
+      const int q = (lane + 64 * h < nv) ? lane + 64 * h : nv - 1;
+      reinterpret_cast<f32x4s *>(tile + (size_t)u * 4 * nv)[q] = pc[u][h];
+    }
+  wave_lds_fence();
+  float sq = 0.f;
+#pragma unroll
+  for (int u = 0; u < NPW; ++u) {
+    float v[FT];
+    const float *row = tile + (size_t)u * 4 * nv + b * F;
+#pragma unroll
+    for (int o = 0; o < FT; o += 2) {
+      if (EXACT || o < F) {
+        const f32x2s t = *reinterpret_cast<const f32x2s *>(row + o);
+        v[o] = t.x; v[o + 1] = t.y;
+      } else {
+        v[o] = 0.f; v[o + 1] = 0.f;
+      }
+    }
+    // (a wave past the end of the list works on the repeated last entry and keeps nothing: an early exit here would
+    // let the compiler sink the loads above into the guarded block, behind the wait for the tile)
+    const bool keep = on && i0 + u < NL;
+    float acc[FT];
+#pragma unroll
+    for (int o = 0; o < FT; ++o) acc[o] = 0.f;
+    int32_t rm = rmine[u];
+    float dm = dmine[u];
+    float c4[4] = {cv[u][0], cv[u][1], cv[u][2], cv[u][3]};
+    for (int32_t kb = klo[u];;) {
+      const int nc = (khi[u] - kb < 4) ? khi[u] - kb : 4;
+#pragma unroll
+      for (int t = 0; t < 4; ++t) {
+        if (t < nc) {  // wave uniform
+          const float w = c4[t];
+          float d[FT];
+#pragma unroll
+          for (int o = 0; o < FT; ++o)
+            d[o] = (o < F) ? __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, dm), 16 * t + o))
+                           : 0.f;
+          float dot = 0.f;
+#pragma unroll
+          for (int o = 0; o < FT; ++o) dot = fmaf(d[o], v[o], dot);
+          if (keep) D[(int64_t)(kb + t) * B + b] = dot;
+#pragma unroll
+          for (int o = 0; o < FT; ++o) acc[o] = fmaf(w, d[o], acc[o]);
+        }
+      }
+      kb += 4;
+      if (kb >= khi[u]) break;  // (few nodes have more than four live columns)
+      const int32_t kk = (kb + kq < khi[u]) ? kb + kq : kb;
+      dm = dM[(int64_t)kk * ldM + oqc];
+      rm = lrel[kk];
+#pragma unroll
+      for (int t = 0; t < 4; ++t) c4[t] = comp[(int64_t)__builtin_amdgcn_readlane(rm, 16 * t) * B + b];
+    }
+    if (keep) {
+#pragma unroll
+      for (int o = 0; o < FT; ++o)
+        if (o < F) sq = fmaf(acc[o], acc[o], sq);
+    }
+  }
+  __shared__ float s_sq[4];
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) sq += __shfl_xor(sq, off, 64);
+  if (lane == 0) s_sq[wv] = sq;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double t = 0.0;
+    for (int i = 0; i < 4; ++i) t += (double)s_sq[i];
+    blk_part[blockIdx.x] = t;
+  }
+}
+
+// One fold block of the one-shot form's squared norm: sq_part[f] = the contiguous slice [f per, (f + 1) per) of the
+// per-block parts, thread t adding the slice's elements t, t + 256, ... in rising order, the 256 sums then in thread
+// order pairwise by wave 0.  Appended to the k_dcomp_chunks launch as the blocks behind the last chunk.
+__device__ __forceinline__ void fold_sq_parts(const double *__restrict__ blk_part, int64_t n_blk, int64_t per, int f,
+                                              double *__restrict__ sq_part) {
+  __shared__ double s_fold[256];
+  const int64_t beg = (int64_t)f * per, end = (beg + per < n_blk) ? beg + per : n_blk;
+  double t = 0.0;
+  for (int64_t i = beg + threadIdx.x; i < end; i += 256) t += blk_part[i];
+  s_fold[threadIdx.x] = t;
+  __syncthreads();
+  if (threadIdx.x < 64) {
+    double a = (s_fold[threadIdx.x] + s_fold[threadIdx.x + 64]) + (s_fold[threadIdx.x + 128] + s_fold[threadIdx.x + 192]);
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) a += __shfl_xor(a, off, 64);
+    if (threadIdx.x == 0) sq_part[f] = a;
+  }
+}
+
 // slab[chunk][b] = sum of D[k][b] over the live columns k of one relation-major chunk (<= kRelChunk columns of one
 // (node band, relation) group).  A row of D is B floats = P = B / 4 16-byte pieces: lane l takes piece l % P of row
 // slot l / P, so one load instruction brings 64 / P rows (six at B = 40) and eight of them are in flight per wave; the
 // four waves take a quarter of the chunk each.  The row slots meet in LDS, added in a fixed order.
-using f32x4s = __attribute__((ext_vector_type(4))) float;
+// Blocks behind the last chunk (the one-shot mix backward appends them) fold its squared-norm parts: fold_sq_parts.
 template <int P>
 __global__ __launch_bounds__(256) void k_dcomp_chunks(const int32_t *__restrict__ chunk_beg,
                                                       const int32_t *__restrict__ chunk_end,
                                                       const int32_t *__restrict__ lperm, const float *__restrict__ D,
-                                                      float *__restrict__ slab) {
+                                                      float *__restrict__ slab, int n_chunks,
+                                                      const double *__restrict__ blk_part, int64_t n_blk, int64_t fold_per,
+                                                      double *__restrict__ sq_part) {
   constexpr int RPI = 64 / P;  // rows per load instruction
   constexpr int B = 4 * P;
   __shared__ f32x4s s_acc[4][RPI][P];
+  if ((int)blockIdx.x >= n_chunks) {  // block uniform
+    fold_sq_parts(blk_part, n_blk, fold_per, (int)blockIdx.x - n_chunks, sq_part);
+    return;
+  }
   const int chunk = blockIdx.x;
   const int lane = threadIdx.x & 63;
   const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -255,8 +434,14 @@ __global__ __launch_bounds__(256) void k_dcomp_chunks_any(const int32_t *__restr
                                                           const int32_t *__restrict__ chunk_end,
                                                           const int32_t *__restrict__ lperm,
                                                           const float *__restrict__ D, int B,
-                                                          float *__restrict__ slab) {
+                                                          float *__restrict__ slab, int n_chunks,
+                                                          const double *__restrict__ blk_part, int64_t n_blk,
+                                                          int64_t fold_per, double *__restrict__ sq_part) {
   __shared__ float s_part[4][64];
+  if ((int)blockIdx.x >= n_chunks) {  // block uniform
+    fold_sq_parts(blk_part, n_blk, fold_per, (int)blockIdx.x - n_chunks, sq_part);
+    return;
+  }
   const int chunk = blockIdx.x;
   const int lane = threadIdx.x & 63;
   const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -492,7 +677,8 @@ int support_dcomp_from_D(const mrgcn_support *q, const float *D, int B, float *s
   const mrgcn_support::Order &o = q->wide;
   const int R = (int)q->plan->num_relations;
   if (o.n_chunks > 0) {
-    k_dcomp_chunks_any<<<dim3((unsigned)o.n_chunks), dim3(256), 0, s>>>(o.chunk_beg, o.chunk_end, o.lperm, D, B, slab);
+    k_dcomp_chunks_any<<<dim3((unsigned)o.n_chunks), dim3(256), 0, s>>>(o.chunk_beg, o.chunk_end, o.lperm, D, B, slab,
+                                                                         o.n_chunks, nullptr, 0, 0, nullptr);
     MRGCN_HIP_TRY(hipGetLastError());
   }
   k_dcomp_final<<<dim3((unsigned)(R + 1)), dim3(256), 0, s>>>(o.chunk_ptr, o.chunk_ids, slab, R, B, dcomp, sq_part,
@@ -513,10 +699,14 @@ int mrgcn_support_spmm_t_f32(const mrgcn_support_t *q, const float *dY, int64_t 
   return spmm_on_view(q->tview(), dY, ldY, F, dM, ldM, q->partials, (hipStream_t)stream);
 }
 
+// blocks of the one-shot mix backward: four waves of kStreamNPW list entries each
+static inline int64_t stream_blocks(int64_t NL) { return ((NL + kStreamNPW - 1) / kStreamNPW + 3) / 4; }
+
 int64_t mrgcn_support_mix_bwd_workspace(const mrgcn_support_t *q, int32_t B) {
   if (!q || B <= 0) return 0;
-  // D [L][B] (16-byte aligned rows when B % 4 == 0) | slab [chunks][B] | parts of ||dV||^2 (doubles, 8-byte aligned)
-  return ((q->L + q->wide.n_chunks) * (int64_t)B + 3) / 4 * 4 + 2 * (int64_t)kSqParts;
+  // D [L][B] (16-byte aligned rows when B % 4 == 0) | slab [chunks][B] | parts of ||dV||^2 (kSqParts doubles, 8-byte
+  // aligned) | the one-shot form's per-block parts (one double per eight live nodes)
+  return ((q->L + q->wide.n_chunks) * (int64_t)B + 3) / 4 * 4 + 2 * (int64_t)kSqParts + 2 * stream_blocks(q->NL);
 }
 
 int mrgcn_support_mix_bwd_f32(const mrgcn_support_t *q, const float *dM, int64_t ldM, const float *V,
@@ -546,13 +736,71 @@ int mrgcn_support_mix_bwd_f32(const mrgcn_support_t *q, const float *dM, int64_t
   float *D = workspace;
   float *slab = D + q->L * (int64_t)B;
   double *sq_part = reinterpret_cast<double *>(workspace + ((q->L + o.n_chunks) * (int64_t)B + 3) / 4 * 4);
-  const size_t lds = (size_t)R * B * sizeof(float);
-  MRGCN_REQUIRE(lds <= 64 * 1024, "R * B * 4 must fit 64 KB of LDS");
+  double *blk_part = sq_part + kSqParts;
+  const bool dvec = (B % 4 == 0) && (((uintptr_t)D) % 16 == 0);
+  // the D rows by relation, with `n_fold` blocks appended that fold the one-shot form's per-block parts
+  auto dcomp_chunks = [&](int64_t n_fold, int64_t n_blk, int64_t fold_per) {
+    const dim3 cg((unsigned)(o.n_chunks + n_fold));
+    if (dvec && B == 40)
+      k_dcomp_chunks<10><<<cg, dim3(256), 0, s>>>(o.chunk_beg, o.chunk_end, o.lperm, D, slab, o.n_chunks, blk_part, n_blk, fold_per, sq_part);
+    else if (dvec && B == 32)
+      k_dcomp_chunks<8><<<cg, dim3(256), 0, s>>>(o.chunk_beg, o.chunk_end, o.lperm, D, slab, o.n_chunks, blk_part, n_blk, fold_per, sq_part);
+    else if (dvec && B == 16)
+      k_dcomp_chunks<4><<<cg, dim3(256), 0, s>>>(o.chunk_beg, o.chunk_end, o.lperm, D, slab, o.n_chunks, blk_part, n_blk, fold_per, sq_part);
+    else if (dvec && B == 8)
+      k_dcomp_chunks<2><<<cg, dim3(256), 0, s>>>(o.chunk_beg, o.chunk_end, o.lperm, D, slab, o.n_chunks, blk_part, n_blk, fold_per, sq_part);
+    else
+      k_dcomp_chunks_any<<<cg, dim3(256), 0, s>>>(o.chunk_beg, o.chunk_end, o.lperm, D, B, slab, o.n_chunks, blk_part, n_blk, fold_per, sq_part);
+  };
+  // the one-shot form (k_mix_bwd_stream) wherever it applies, at every NL
+  const int one_shot = (int)cfg(CFG_SUP_MIX_STREAM);
+  if (one_shot > 0 && (B * F) % 4 == 0 && B * F <= 1024 && (F & 1) == 0 && (((uintptr_t)V) & 15) == 0) {
+    const int nv = (B * F) / 4;
+    const int nh = nv <= 64 ? 1 : nv <= 128 ? 2 : 4;
+    const int64_t n_blk = q->NL > 0 ? stream_blocks(q->NL) : 0;
+    // at least 256 parts per fold block, at most kSqParts fold blocks
+    const int64_t fold_per = std::max<int64_t>(256, (n_blk + kSqParts - 1) / kSqParts);
+    const int64_t n_fold = (n_blk + fold_per - 1) / fold_per;
+    const size_t tile = (size_t)4 * kStreamNPW * B * F * sizeof(float);
+#define STREAM_GO2(T, NH_, EX_)                                                                                     \
+  k_mix_bwd_stream<T, NH_, kStreamNPW, EX_><<<dim3((unsigned)n_blk), dim3(256), tile, s>>>(                       \
+      q->lnode, q->lnptr, q->lrel, dM, ldM, V, comp, q->NL, B, F, D, blk_part)
+#define STREAM_GO(T, EX_)                     \
+  do {                                        \
+    if (nh == 1) STREAM_GO2(T, 1, EX_);       \
+    else if (nh == 2) STREAM_GO2(T, 2, EX_);  \
+    else STREAM_GO2(T, 4, EX_);               \
+  } while (0)
+    if (n_blk > 0) {
+      switch (F) {
+        case 4: STREAM_GO(4, true); break;
+        case 8: STREAM_GO(8, true); break;
+        case 10: STREAM_GO(10, true); break;
+        case 12: STREAM_GO(12, true); break;
+        case 16: STREAM_GO(16, true); break;
+        default: STREAM_GO(16, false); break;
+      }
+      MRGCN_HIP_TRY(hipGetLastError());
+    }
+#undef STREAM_GO
+#undef STREAM_GO2
+    if (o.n_chunks + n_fold > 0) {
+      dcomp_chunks(n_fold, n_blk, fold_per);
+      MRGCN_HIP_TRY(hipGetLastError());
+    }
+    k_dcomp_final<<<dim3((unsigned)(R + 1)), dim3(256), 0, s>>>(o.chunk_ptr, o.chunk_ids, slab, R, B, dcomp, sq_part,
+                                                               (int)n_fold, dV_sumsq);
+    MRGCN_HIP_TRY(hipGetLastError());
+    return MRGCN_OK;
+  }
+  // The resident form (k_mix_bwd_sup).  The timings below describe IT, not the one-shot form above:
   // nodes in flight per wave (NB) x waves per CU.  512-thread blocks with two nodes per step (62 VGPRs at F = 10: three
   // blocks of eight waves per CU, bounded by the 42 KB of comp in LDS)
   // AM shape, kernel alone on one box: 512x1 598 us, 512x2 512, 512x4 557, 1024x2 501
   // (a small support: a wave's 64 list entries are one serial chain of 64 / NB steps — 122 us at MUTAG's 23 k nodes with
   // two per step; four per step halve the chain where occupancy does not matter)
+  const size_t lds = (size_t)R * B * sizeof(float);
+  MRGCN_REQUIRE(lds <= 64 * 1024, "R * B * 4 must fit 64 KB of LDS");
   const int nb = q->NL < 262144 ? 4 : 2;
   constexpr int nw = kSupTB / 64;
   int epw = 64;
@@ -595,13 +843,7 @@ int mrgcn_support_mix_bwd_f32(const mrgcn_support_t *q, const float *dM, int64_t
 #undef SUP_GO2
   MRGCN_HIP_TRY(hipGetLastError());
   if (o.n_chunks > 0) {
-    const dim3 cg((unsigned)o.n_chunks);
-    const bool vec = (B % 4 == 0) && (((uintptr_t)D) % 16 == 0);
-    if (vec && B == 40) k_dcomp_chunks<10><<<cg, dim3(256), 0, s>>>(o.chunk_beg, o.chunk_end, o.lperm, D, slab);
-    else if (vec && B == 32) k_dcomp_chunks<8><<<cg, dim3(256), 0, s>>>(o.chunk_beg, o.chunk_end, o.lperm, D, slab);
-    else if (vec && B == 16) k_dcomp_chunks<4><<<cg, dim3(256), 0, s>>>(o.chunk_beg, o.chunk_end, o.lperm, D, slab);
-    else if (vec && B == 8) k_dcomp_chunks<2><<<cg, dim3(256), 0, s>>>(o.chunk_beg, o.chunk_end, o.lperm, D, slab);
-    else k_dcomp_chunks_any<<<cg, dim3(256), 0, s>>>(o.chunk_beg, o.chunk_end, o.lperm, D, B, slab);
+    dcomp_chunks(0, 0, 0);
     MRGCN_HIP_TRY(hipGetLastError());
   }
   k_dcomp_final<<<dim3((unsigned)(R + 1)), dim3(256), 0, s>>>(o.chunk_ptr, o.chunk_ids, slab, R, B, dcomp, sq_part,

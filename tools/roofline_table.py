@@ -53,8 +53,11 @@ def main():
          ("layer-1 transform: H read once + W + M written + indices", N * F0 * 4 + R * F0 * F1 * 4 + NCOLS * F1 * 4 + NCOLS * 12)),
         ("mrgcn::k_xform_cols_lds<12, float>",
          ("layer-1 transform, output order, all weights in LDS: H read once + W + M written + (node, relation) ids", N * F0 * 4 + R * F0 * F1 * 4 + NCOLS * F1 * 4 + NCOLS * 8)),
-        ("mrgcn::k_mix_bwd_sup<10, 2, 512, true>",
-         ("norm-only mix backward: V of the live nodes + their dM rows in, D rows out", NL0 * B * F0 * 4 + L0 * (LD * 4 + B * 4 + 4) + NL0 * 8)),
+        ("mrgcn::k_mix_bwd_stream<10, 2, 2, true>",
+         ("norm-only mix backward as a one-shot grid (a wave per two live nodes): V of the live nodes + their dM rows and relations in, D rows out, the list, a squared-norm part per block of eight nodes",
+          NL0 * B * F0 * 4 + L0 * (LD * 4 + B * 4 + 4) + NL0 * 8 + (NL0 // 8) * 8)),
+        ("mrgcn::k_mix_bwd_sup<10, 2, true>",
+         ("norm-only mix backward, resident form (sup_mix_stream=0): V of the live nodes + their dM rows in, D rows out", NL0 * B * F0 * 4 + L0 * (LD * 4 + B * 4 + 4) + NL0 * 8)),
         ("mrgcn::k_dcomp_chunks<10>", ("dcomp: D rows in, by relation", L0 * (B * 4 + 4))),
         ("mrgcn::k_xform_mfma_dw<3, 2, false, float>",
          ("layer-0 dW over the live columns: X rows of the live NODES once + dM rows + lists", NL0 * K0 * 4 + L0 * (LD * 4 + 8))),
