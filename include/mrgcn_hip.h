@@ -501,6 +501,34 @@ int mrgcn_support_adam_rows_fused_f32(const mrgcn_support_t *support, const floa
                                       uint8_t *row_ever, float lr, float beta1, float beta2, float eps, int64_t step,
                                       const float *bc_dev, const float *grad_scale, int32_t ever_outside,
                                       void *stream);
+/* The node-table step under the reference's regularisation settings (node_classification.py:35-37,172-193:
+ * `weight_decay` handed to optim.Adam, l1_lambda . sum|p| + l2_lambda . sum p^2 added to the loss, then backward,
+ * clip_grad_norm_, optimizer.step()).  With any of the three non-zero every node block moves every step; the loss's
+ * gradient still lives on the support only, so both passes walk nodes 0 .. N-1 as one-shot grids and rebuild each
+ * node's gradient block g from its live columns of dM and comp in registers (a node without live columns: g = 0).
+ * r(p) = l1 sign(p) + 2 l2 p in fp32, sign(0) = 0.
+ * Shapes: those of mrgcn_adam_rows_fused_supported with B F / 4 <= 128 and F even; any other shape: a negative
+ * workspace size / MRGCN_ERR_UNSUPPORTED, nothing written.
+ *
+ * mrgcn_support_reg_norm_f32 (node_classification.py:172-193: what clip_grad_norm_ sees of the node table, and the
+ * penalty's value): out3 = { sum (g + r(p))^2, sum |p|, sum p^2 } over the whole table, in double from the element on,
+ * WRITTEN (not accumulated); per-block partials in `workspace` (mrgcn_support_reg_norm_workspace BYTES, 8-byte
+ * aligned) summed in block order by a second small launch: no atomics, bitwise reproducible.  Not needed for weight
+ * decay alone: torch adds wd . p inside Adam.step, after the clip. */
+int64_t mrgcn_support_reg_norm_workspace(const mrgcn_support_t *support, int32_t B, int32_t F);
+int mrgcn_support_reg_norm_f32(const mrgcn_support_t *support, const float *dM, int64_t ldM, const float *comp,
+                               int32_t B, int32_t F, const float *param, float l1, float l2, double *out3,
+                               void *workspace, int64_t workspace_bytes, void *stream);
+/* mrgcn_support_adam_rows_fused_f32's update over ALL N nodes (node_classification.py:35-37,172-193) with
+ *   gg = (g + r(p)) . grad_scale + weight_decay . p
+ * — torch's order: the penalty is part of .grad and is clipped, Adam adds the decay afterwards.  Sets row_ever[j] = 1
+ * for every node.  `step` / `bc_dev` / `grad_scale` as there.  With weight_decay = l1 = l2 = 0 the per-element chain is
+ * that kernel's. */
+int mrgcn_support_adam_rows_reg_f32(const mrgcn_support_t *support, const float *dM, int64_t ldM, const float *comp,
+                                    int32_t B, int32_t F, float *param, float *exp_avg, float *exp_avg_sq,
+                                    uint8_t *row_ever, float lr, float beta1, float beta2, float eps,
+                                    float weight_decay, float l1, float l2, int64_t step, const float *bc_dev,
+                                    const float *grad_scale, void *stream);
 /* mrgcn_rel_transform_bwd_masked_f32 on the support: dW (nullable; written whole) and dX (nullable; every row
  * written, zeros outside NODE_FLAGS; `relu_mask_from_x` as there).  workspace:
  * mrgcn_support_rel_transform_bwd_workspace floats. */

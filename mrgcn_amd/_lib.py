@@ -255,6 +255,11 @@ SIGNATURES = {
     "mrgcn_support_mix_bwd_f32": (C.c_int, [_p, _p, _i64, _p, _p, _i32, _i32, _p, _i32, _p, _p, _p, _i64, _p]),
     "mrgcn_support_adam_rows_fused_f32": (C.c_int, [_p, _p, _i64, _p, _i32, _i32, _p, _p, _p, _p, C.c_float, C.c_float,
                                                     C.c_float, C.c_float, _i64, _p, _p, _i32, _p]),
+    "mrgcn_support_reg_norm_workspace": (C.c_int64, [_p, _i32, _i32]),
+    "mrgcn_support_reg_norm_f32": (C.c_int, [_p, _p, _i64, _p, _i32, _i32, _p, C.c_float, C.c_float, _p, _p, _i64, _p]),
+    "mrgcn_support_adam_rows_reg_f32": (C.c_int, [_p, _p, _i64, _p, _i32, _i32, _p, _p, _p, _p, C.c_float, C.c_float,
+                                                  C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, _i64, _p, _p,
+                                                  _p]),
     "mrgcn_support_rel_transform_bwd_workspace": (C.c_int64, [_p, _i32, _i32, _i32, _i32]),
     "mrgcn_support_rel_transform_bwd_f32": (C.c_int, [_p, _p, _i64, _p, _i64, _i32, _p, _i32, _p, _i64, _p, _p, _i64,
                                                       _i32, _p]),

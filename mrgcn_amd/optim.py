@@ -43,7 +43,9 @@ class Adam(ClipAdam):
     `row_sparse` (default False: every gradient dense, `.grad` of every parameter as torch leaves it — any clip,
     scaler or inspection code sees all of it).  True: the optimizer announces itself on the node-major `weight_I`
     parameters it owns and a plain `loss.backward()` then leaves their gradient in ROW-SPARSE form (`weight_I.grad`
-    stays None; flags, `dM` and the squared norm travel on the parameter).  Only this module's `clip_grad_norm_`
+    stays None; flags, `dM` and the squared norm travel on the parameter) — with `weight_decay` as well: torch adds
+    wd . p inside `Adam.step`, after the clip, so the norm below is unchanged and the decay happens in the row update
+    (an L1 / L2 term the caller's loop writes into the loss still arrives as a dense `.grad`).  Only this module's `clip_grad_norm_`
     knows that form — torch's would skip the node table, i.e. leave its norm out of the total and step it unclipped —
     so the two go together: `RowSparseAdam` + `clip_grad_norm_`, which is what `install_as_mrgcn(patch_optimizer=True)`
     binds inside the reference's task modules."""
@@ -58,8 +60,9 @@ class Adam(ClipAdam):
         if row_sparse:
             me = weakref.ref(self)
             for g in self.param_groups:
-                if float(g["weight_decay"]) != 0.0:
-                    continue  # a decayed parameter moves without gradient: its rows cannot be skipped
+                # (a decayed group too: every node block then moves, which the regularised row update does from the
+                # same row-sparse form when the backward ran on a gradient support — ClipAdam.step; otherwise the
+                # entry is densified there, as before)
                 for p in g["params"]:
                     if getattr(p, "_mrgcn_node_major", False):
                         p._mrgcn_row_consumer = me

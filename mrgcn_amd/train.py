@@ -153,6 +153,7 @@ class ClipAdam(torch.optim.Optimizer):
         self._scratch = {}
         self._dist = None  # (group, ids of parameters sharded across ranks)
         self._state_gen = 0  # bumped by load_state_dict: row flags built for the old moments are re-derived
+        self.reg_loss = None  # the weight penalty the last step() owned (step(l1_lambda=, l2_lambda=)), a device scalar
 
     # -- checkpoints --------------------------------------------------------------------------------
     def _sync_host_steps(self):
@@ -281,26 +282,72 @@ class ClipAdam(torch.optim.Optimizer):
             if self.capturable and group["params"]:
                 self._dev_step_entry(tuple(float(b) for b in group["betas"]), group["params"][0].device)
 
+    def _reg_rows_ok(self, ent) -> bool:
+        """Can this row-sparse entry take the regularised row update (mrgcn_support_adam_rows_reg_f32)?  It needs the
+        backward to have run on a gradient support and a shape the kernels take."""
+        fz = ent.get("fused")
+        return (fz is not None and fz.get("sup") is not None and self._dist is None
+                and int(L.load().mrgcn_support_reg_norm_workspace(fz["sup"].handle, fz["B"], fz["F"])) >= 0)
+
     @torch.no_grad()
-    def step(self, closure=None):
+    def step(self, closure=None, *, l1_lambda=0.0, l2_lambda=0.0, reg_params=None):
+        """`l1_lambda` / `l2_lambda`: the reference's weight penalty (node_classification.py:172-188) on the parameters
+        the CALLER LEFT OUT of the penalty it put into the loss — `reg_params`, by default the node-major tables that
+        carry a row-sparse gradient.  The optimizer owns their penalty whichever route they end up on: r(p) =
+        l1 sign(p) + 2 l2 p joins the gradient in front of this step's clip (`max_norm`), the value
+        l1 sum|p| + l2 sum p^2 is left in `self.reg_loss` (a float32 device scalar; None when nothing was owned)."""
         lib = L.load()
+        l1, l2 = float(l1_lambda), float(l2_lambda)
+        pen = l1 > 0 or l2 > 0
+        owned = {id(p) for p in reg_params} if (pen and reg_params is not None) else None
+        self.reg_loss = None
         rowsparse = []  # gradient left on the parameter in row-sparse form (functional._ROW_SPARSE)
         indexed = []    # ... as compact rows of a literal operand (functional._SpmmLiteral: kind "index")
+        regular = set()  # ids of the row-sparse entries that take the regularised update (decay and / or penalty)
+        torch_pen = []   # owned parameters on the dense route: their penalty is added with torch ops
         for g in self.param_groups:
+            wd = float(g["weight_decay"])
             for p in g["params"]:
                 ent = pop_row_grad(p)
+                if owned is not None:
+                    mine = id(p) in owned
+                else:
+                    mine = (pen and ent is not None and ent.get("kind") != "index"
+                            and getattr(p, "_mrgcn_node_major", False))
                 if ent is None:
+                    if mine:
+                        torch_pen.append(p)
                     continue
                 if ent.get("kind") == "index":
-                    if (p.grad is None and float(g["weight_decay"]) == 0.0 and self._dist is None
+                    if (p.grad is None and wd == 0.0 and not mine and self._dist is None
                             and self._index_rows_ok(p, ent)):
                         indexed.append((g, p, ent))
-                    else:
-                        merge_row_grad(p, ent)
-                elif p.grad is None and float(g["weight_decay"]) == 0.0:
+                        continue
+                    merge_row_grad(p, ent)
+                elif p.grad is None and wd == 0.0 and not mine:
                     rowsparse.append((g, p, ent))
+                    continue
+                elif p.grad is None and self._reg_rows_ok(ent):
+                    # every node block moves (decay, penalty): the row update over all N nodes, the loss's gradient
+                    # still rebuilt from the support's dM
+                    rowsparse.append((g, p, ent))
+                    regular.add(id(ent))
+                    if mine:
+                        ent["pen"] = True
+                    continue
                 else:  # another term left a dense gradient on the same parameter (a regulariser): one dense step
                     merge_row_grad(p, ent)
+                if mine:
+                    torch_pen.append(p)
+        for p in torch_pen:  # (no support, a shape outside the kernels, a dense gradient: today's route plus the penalty)
+            r = None
+            if l1 > 0:
+                r = l1 * torch.sign(p)
+                self.reg_loss = l1 * p.abs().sum() + (0 if self.reg_loss is None else self.reg_loss)
+            if l2 > 0:
+                r = (2.0 * l2) * p if r is None else r.add_(p, alpha=2.0 * l2)
+                self.reg_loss = l2 * (p * p).sum() + (0 if self.reg_loss is None else self.reg_loss)
+            p.grad = r if p.grad is None else p.grad.add_(r)
         live = [(g, p) for g in self.param_groups for p in g["params"] if p.grad is not None]
         if not live and not rowsparse and not indexed:
             return None
@@ -328,6 +375,31 @@ class ClipAdam(torch.optim.Optimizer):
         if det:
             bump("deterministic.sumsq")
         dp, dt = sc["partials"].data_ptr(), sc["ticket"].data_ptr()
+        # the penalty's share of the norm: one read of the table in front of the clip (weight decay needs none: torch
+        # adds wd . p inside Adam.step, after the clip) — sum (g + r)^2 then stands where the entry's ||g||^2 would
+        norm_of = {}
+        with torch.cuda.device(device):
+            for _, p, ent in rowsparse:
+                if not ent.pop("pen", False):
+                    continue
+                fz = ent["fused"]
+                nbytes = int(lib.mrgcn_support_reg_norm_workspace(fz["sup"].handle, fz["B"], fz["F"]))
+                ws = fz["sup"].workspace(("reg_norm", fz["B"], fz["F"]), (nbytes + 3) // 4)
+                out3 = ent.get("reg_sums")
+                if out3 is None or out3.device != device:
+                    out3 = ent["reg_sums"] = torch.empty(3, dtype=torch.float64, device=device)
+                L.check(lib.mrgcn_support_reg_norm_f32(
+                    fz["sup"].handle, fz["dM"].data_ptr(), fz["ld"], fz["comp"].data_ptr(), fz["B"], fz["F"],
+                    p.data_ptr(), l1, l2, out3.data_ptr(), ws.data_ptr(), nbytes, s), "mrgcn_support_reg_norm_f32")
+                norm_of[id(ent)] = out3
+                term = (l1 * out3[1] + l2 * out3[2]).float()
+                self.reg_loss = term if self.reg_loss is None else self.reg_loss + term
+        if self.reg_loss is not None and self.reg_loss.dtype != torch.float32:
+            self.reg_loss = self.reg_loss.float()
+
+        def row_sumsq(ent):  # the squared norm this entry brings to the clip (a 0-dim / 1-element double view)
+            o = norm_of.get(id(ent))
+            return ent["sumsq"] if o is None else o[:1]
 
         def sumsq_accum(ptr, numel, acc):
             if det:
@@ -367,7 +439,7 @@ class ClipAdam(torch.optim.Optimizer):
                             sumsq_accum(ent["g"].data_ptr(), ent["g"].numel(), sc["accum"].data_ptr())
                     gp = (C.c_void_p * len(closing))(*[g.data_ptr() for g in closing])
                     gn = (C.c_int64 * len(closing))(*[g.numel() for g in closing])
-                    ex = (C.c_void_p * max(len(rowsparse), 1))(*[ent["sumsq"].data_ptr() for _, _, ent in rowsparse])
+                    ex = (C.c_void_p * max(len(rowsparse), 1))(*[row_sumsq(ent).data_ptr() for _, _, ent in rowsparse])
                     dstep = self._dev_step.get((b1m, b2m)) if self.capturable else None
                     args = (len(closing), gp, gn, len(rowsparse), ex, sc["accum"].data_ptr(), sc["ticket"].data_ptr(),
                             float(self.max_norm) if use_clip else 0.0, sc["sumsq"].data_ptr(), sc["coef"].data_ptr(),
@@ -395,7 +467,7 @@ class ClipAdam(torch.optim.Optimizer):
                     acc = sc["sumsq_sharded"] if id(p) in sharded else sc["sumsq"]
                     sumsq_accum(g.data_ptr(), g.numel(), acc.data_ptr())
                 for _, p, ent in rowsparse:  # ||g||^2 came for free with the gradient
-                    (sc["sumsq_sharded"] if id(p) in sharded else sc["sumsq"]).add_(ent["sumsq"])
+                    (sc["sumsq_sharded"] if id(p) in sharded else sc["sumsq"]).add_(row_sumsq(ent).reshape(()))
                 for _, _, ent in indexed:
                     sumsq_accum(ent["g"].data_ptr(), ent["g"].numel(), sc["sumsq"].data_ptr())
                 if self._dist:
@@ -411,9 +483,6 @@ class ClipAdam(torch.optim.Optimizer):
                             "mrgcn_adam_bias_f32")
             coef_ptr = step_coef_ptr = sc["coef"].data_ptr() if use_clip else 0
             for group, p, ent in rowsparse:
-                if float(group["weight_decay"]) != 0.0:
-                    raise L.MrgcnError("row-sparse gradients need weight_decay = 0 (a decayed parameter "
-                                       "moves without gradient)")
                 st = self._new_state(p)
                 owner = (id(self), self._state_gen)
                 if ent.get("seeded_for") != owner:
@@ -437,6 +506,19 @@ class ClipAdam(torch.optim.Optimizer):
                 if fz is not None and fz.get("comp_version") is not None and fz["comp"]._version != fz["comp_version"]:
                     raise L.MrgcnError("row-sparse weight_I gradient: weight_I_comp was modified between backward and "
                                        "the node table's update (the fused update re-reads it)")
+                if id(ent) in regular:
+                    # all N nodes, gg = (g + r(p)) . coef + wd . p; r only where this optimizer owns the penalty.
+                    # Every node holds moments afterwards: a later plain step must look outside its support.
+                    mine = id(ent) in norm_of
+                    ent["ever_in"] = "any"
+                    bump("adam.reg")
+                    L.check(lib.mrgcn_support_adam_rows_reg_f32(
+                        fz["sup"].handle, fz["dM"].data_ptr(), fz["ld"], fz["comp"].data_ptr(), fz["B"], fz["F"],
+                        p.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(), ent["ever"].data_ptr(),
+                        float(group["lr"]), float(b1), float(b2), float(group["eps"]), float(group["weight_decay"]),
+                        l1 if mine else 0.0, l2 if mine else 0.0, int(st["step"]), bc, coef_ptr, s),
+                        "mrgcn_support_adam_rows_reg_f32")
+                    continue
                 if fz is not None and fz.get("sup") is not None:  # the same on the gradient support of the label set
                     # every step since the flags were zeroed ran on THIS support: no node outside it holds moments and
                     # the pass that looks for such nodes is not launched
@@ -537,12 +619,14 @@ def merge_row_grad(p, ent):
     p.grad = g if p.grad is None else p.grad.add_(g)
 
 
-def weight_regularisation(model, l1_lambda: float = 0.0, l2_lambda: float = 0.0):
+def weight_regularisation(model, l1_lambda: float = 0.0, l2_lambda: float = 0.0, skip=()):
     """l1 * sum|p| + l2 * sum p^2 over the parameters whose NAME contains 'weight'
-    (node_classification.py:172-188).  Zero in every shipped config; plain tensor ops."""
+    (node_classification.py:172-188).  Zero in every shipped config; plain tensor ops.  `skip`: parameters left out
+    (their penalty is somebody else's: `ClipAdam.step(l1_lambda=, l2_lambda=, reg_params=)`)."""
     reg = None
+    skipped = {id(p) for p in skip}
     for name, p in model.named_parameters():
-        if "weight" not in name:
+        if "weight" not in name or id(p) in skipped:
             continue
         term = None
         if l1_lambda > 0:
@@ -571,28 +655,60 @@ def train_step(model, forward_fn, idx, targets, optimizer, l1_lambda: float = 0.
                row_sparse=None):
     """One full-batch epoch.  `forward_fn()` returns the logits (e.g. `lambda: model(batch)`).
     Returns the loss as a device scalar (no host sync).  `row_sparse`: None = skip the rows of a node-major
-    weight_I's gradient / Adam update that carry no gradient whenever that is exact (ClipAdam, no weight
-    decay, no regulariser — `weight_I.grad` stays None for such a step, the gradient travels on the
-    parameter); False = always the dense gradient in `.grad` and the dense Adam kernel."""
+    weight_I's gradient / Adam update that carry no gradient whenever that is exact (ClipAdam — `weight_I.grad`
+    stays None for such a step, the gradient travels on the parameter; under weight decay or an L1 / L2 penalty the
+    update visits every node but still rebuilds the loss's gradient from the support, and the returned loss includes
+    the penalty the optimizer computed: DESIGN section 14); False = always the dense gradient in `.grad` and the dense
+    Adam kernel."""
     params = [p for g in optimizer.param_groups for p in g["params"]]
     clear_row_grads(params)
     logits = forward_fn()
     loss = categorical_crossentropy(logits, idx, targets, sole_consumer=True)
     reg = l1_lambda > 0 or l2_lambda > 0
-    if reg:
-        loss = loss + weight_regularisation(model, l1_lambda, l2_lambda)
-    optimizer.zero_grad(set_to_none=True)
     # weight_I's gradient may stay unwritten where no node has any when the optimizer is the one that
-    # knows how to read it and nothing but the loss feeds that gradient (a regulariser adds its own term)
-    sparse_ok = (row_sparse is not False and _ROW_SPARSE_DEFAULT and not reg and isinstance(optimizer, ClipAdam)
-                 and all(float(g["weight_decay"]) == 0.0 for g in optimizer.param_groups))
+    # knows how to read it.  Under weight decay or a penalty every node block moves, which the regularised row update
+    # does from the same row-sparse form (csrc/adam_reg.hip) — when every input-term weight of the model is a
+    # node-major table of a shape it takes; otherwise the backward writes dense gradients as it always did.
+    sparse_ok = row_sparse is not False and _ROW_SPARSE_DEFAULT and isinstance(optimizer, ClipAdam)
+    tables = ()
+    if sparse_ok and (reg or any(float(g["weight_decay"]) != 0.0 for g in optimizer.param_groups)):
+        tables = _reg_tables(model, params)
+        sparse_ok = tables is not None and optimizer._dist is None
+        tables = tables if (sparse_ok and reg) else ()
+    if reg:
+        term = weight_regularisation(model, l1_lambda, l2_lambda, skip=tables)
+        if term is not None:
+            loss = loss + term
+    optimizer.zero_grad(set_to_none=True)
     prev = row_sparse_weight_grad(sparse_ok)
     try:
         loss.backward(gradient=_ones_like_loss(loss))
     finally:
         row_sparse_weight_grad(prev)
+    if tables:
+        optimizer.step(l1_lambda=l1_lambda, l2_lambda=l2_lambda, reg_params=tables)
+        return loss.detach() if optimizer.reg_loss is None else loss.detach() + optimizer.reg_loss
     optimizer.step()
     return loss.detach()
+
+
+def _reg_tables(model, params):
+    """The node tables of `model` that the regularised row update can step (node-major `weight_I` of a basis layer,
+    shapes of include/mrgcn_hip.h: mrgcn_support_reg_norm_workspace), or None when some input-term weight is known
+    not to be one of them (no bases, a wide layer) or is not among `params` — known before the backward runs, which
+    then writes dense gradients."""
+    stepped = {id(p) for p in params}
+    tables = []
+    for name, p in model.named_parameters():
+        if name.rsplit(".", 1)[-1] != "weight_I" or not p.requires_grad:
+            continue
+        if not getattr(p, "_mrgcn_node_major", False) or p.dim() != 3 or id(p) not in stepped:
+            return None
+        _, B, F = p.shape
+        if not (0 < B <= 64 and 0 < F <= 16 and F % 2 == 0 and (B * F) % 4 == 0 and B * F <= 512):
+            return None
+        tables.append(p)
+    return tables or None
 
 
 class GraphedStep:

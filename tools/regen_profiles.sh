@@ -80,6 +80,11 @@ python3 tools/node_dropout_probe.py ${NODE_DROPOUT_PARENT_JSON:+--parent $NODE_D
 python3 tools/lp_topk_probe.py --out $o/lp_topk_probe.json > $o/lp_topk_probe.txt 2> $o/lp_topk_probe.err
 # (10e) validation and early stopping inside the replayed epoch against the host loop around a replayed train step
 python3 tools/early_stop_probe.py --out $o/early_stop_probe.json > $o/early_stop_probe.txt 2> $o/early_stop_probe.err
+# (10f) weight decay / L1 / L2 on the row-sparse node-table step.  The baseline rows are the PARENT commit's on the same box:
+# check the parent out beside this tree, build it, copy tools/weight_reg_probe.py into it and run
+# `python3 tools/weight_reg_probe.py --rows-only --zero-repeats 3 --out <file>` there first; WEIGHT_REG_PARENT_JSON=<file>
+# then puts them into the result.  Without it the file holds this tree's rows only.
+python3 tools/weight_reg_probe.py ${WEIGHT_REG_PARENT_JSON:+--parent $WEIGHT_REG_PARENT_JSON} --out $o/weight_reg_probe.json > $o/weight_reg_probe.txt 2> $o/weight_reg_probe.err
 hipcc -O3 --offload-arch=gfx950 -std=c++17 tools/lab/copy_lab.hip -o /tmp/copy_lab 2>/dev/null && /tmp/copy_lab > $o/copy_lab.txt 2>&1
 python3 tools/lab/spmm_hot_lab.py > $o/spmm_hot_lab.txt 2>&1
 # the CPU suite last: the tree these artefacts describe is green
