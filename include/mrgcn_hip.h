@@ -835,6 +835,32 @@ int mrgcn_distmult_ranks(const float *E, int64_t ldE, int64_t num_nodes, const f
                          const int64_t *tail_ptr, const int32_t *tail_idx, const int64_t *head_ptr,
                          const int32_t *head_idx, void *workspace, int64_t workspace_bytes,
                          int64_t *ranks, void *stream);
+/* Raw AND filtered ranks from one scoring pass: what test_model (link_prediction.py:394-408) gets from two calls of
+ * compute_ranks_fast (:593-643), filtered = False and True, over the same [facts, nodes] scores.  ranks_raw / ranks_flt
+ * [2 nf] are what mrgcn_distmult_ranks writes without / with the lists, bit for bit (one shared score body); all four
+ * lists NULL: raw ranks only, ranks_flt may be NULL and stays unwritten.  One call stands for one call per PART of the
+ * facts (test_model's batches, each filtered by truedicts of its own facts): every fact owns its ptr range, and
+ * part_ptr [num_parts + 1] (device, rising, part_ptr[0] = 0; NULL: one part) names the parts, because the reference
+ * leaves the facts at positions >= num_nodes of a call unscored (:611-617) and the position meant is the one inside
+ * the fact's part.  Any num_facts: the scoring grid is launched in slices of slice_facts facts (0: the default,
+ * mrgcn_distmult_ranks_both_slice(); at most 524280, rounded up to whole tiles of 8).  workspace: device,
+ * >= mrgcn_distmult_ranks_both_workspace() bytes (Et [H, N], truth [nf], scored [nf], counts [8 nf]). */
+int64_t mrgcn_distmult_ranks_both_slice(void);
+int64_t mrgcn_distmult_ranks_both_workspace(int64_t num_nodes, int32_t H, int64_t num_facts);
+int mrgcn_distmult_ranks_both(const float *E, int64_t ldE, int64_t num_nodes, const float *Rel, int64_t ldR, int32_t H,
+                              const int64_t *triples, int64_t num_facts, const int64_t *tail_ptr,
+                              const int32_t *tail_idx, const int64_t *head_ptr, const int32_t *head_idx,
+                              const int64_t *part_ptr, int64_t num_parts, int64_t slice_facts, void *workspace,
+                              int64_t workspace_bytes, int64_t *ranks_raw, int64_t *ranks_flt, void *stream);
+/* test_model's metrics (link_prediction.py:403-419) of a rank vector [2 nf] (tail ranks, then head ranks): part p owns
+ * ranks [p0, p1) and nf + [p0, p1), p0 = part_ptr[p], p1 = part_ptr[p + 1] (NULL: one part); out4 = the mean over the
+ * parts of the parts' mean(1 / rank), mean(rank <= 1), mean(rank <= 3), mean(rank <= 10), summed in float64 in a fixed
+ * order without atomics and rounded once to float32; score_out (nullable) = (float)(1 - mrr), the score train_model
+ * records (:363).  The caller guarantees 0 = part_ptr[0] < part_ptr[1] < ... < part_ptr[num_parts] = num_facts (parts
+ * are not empty: an empty one would add nothing and still count in the mean); nothing on the device checks it, but
+ * bounds outside [0, num_facts] are clamped, so no read leaves `ranks`.  Equal inputs give equal bits. */
+int mrgcn_rank_metrics(const int64_t *ranks, int64_t num_facts, const int64_t *part_ptr, int64_t num_parts, float *out4,
+                       float *score_out, void *stream);
 /* Top-k completion of (s, p, ?) / (?, p, o) queries: what a user of the reference reads off the [facts, nodes] score
  * matrix of compute_ranks_fast (link_prediction.py:593-643; scores :645-665) with a sort.  queries: device int64
  * [nq, 2] rows (anchor node, relation); head == 0: candidates fill the tail slot, score = sum_h (E[s,h] Rel[p,h])
@@ -1092,6 +1118,12 @@ typedef struct {
  * best_score and gives patience_default back; stop = 1 when patience <= 0 after that. */
 int mrgcn_early_stop_record(mrgcn_early_stop_state *state, const float *score, double tolerance,
                             int32_t patience_default, const mrgcn_metrics_row *metrics_row, void *stream);
+/* mrgcn_early_stop_record (tasks/utils.py:64-81; link_prediction.py:362-364) with a row of any width: the `width`
+ * contiguous device floats at `row` go to row (records % rows) of the float [rows, width] device `ring` before the
+ * record is counted, unless `stop` is set already; the bookkeeping is that of mrgcn_early_stop_record. */
+int mrgcn_early_stop_record_row(mrgcn_early_stop_state *state, const float *score, double tolerance,
+                                int32_t patience_default, const float *row, int32_t width, float *ring, int64_t rows,
+                                void *stream);
 /* Copies every entry of a device table when *flag != 0 (flag NULL: always); restore != 0 copies dst -> src instead.
  * Any size and alignment.  first_block: the entries' running block count, an entry taking
  * ceil(bytes / mrgcn_snapshot_block_bytes()) blocks; n_blocks: the total. */

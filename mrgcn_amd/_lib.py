@@ -185,6 +185,11 @@ SIGNATURES = {
     "mrgcn_distmult_orders_counting": (C.c_int, [_p, _i64, _i64, _i64, _p, _p, _p, _p, _i64, _p]),
     "mrgcn_distmult_ranks_workspace": (C.c_int64, [_i64, _i32, _i64]),
     "mrgcn_distmult_ranks": (C.c_int, [_p, _i64, _i64, _p, _i64, _i32, _p, _i64, _p, _p, _p, _p, _p, _i64, _p, _p]),
+    "mrgcn_distmult_ranks_both_slice": (C.c_int64, []),
+    "mrgcn_distmult_ranks_both_workspace": (C.c_int64, [_i64, _i32, _i64]),
+    "mrgcn_distmult_ranks_both": (C.c_int, [_p, _i64, _i64, _p, _i64, _i32, _p, _i64, _p, _p, _p, _p, _p, _i64, _i64,
+                                            _p, _i64, _p, _p, _p]),
+    "mrgcn_rank_metrics": (C.c_int, [_p, _i64, _p, _i64, _p, _p, _p]),
     "mrgcn_distmult_topk_workspace": (C.c_int64, [_i64, _i32, _i64, _i32]),
     "mrgcn_distmult_topk": (C.c_int, [_p, _i64, _i64, _p, _i64, _i32, _p, _i64, _i32, _p, _p, _i32, _p, _i64, _p, _p,
                                       _p]),
@@ -275,6 +280,7 @@ SIGNATURES = {
     "mrgcn_xent_eval_single_block_rows": (C.c_int64, []),
     "mrgcn_xent_eval_rows_f32": (C.c_int, [_p, _i64, _i32, _p, _p, _i64, _p, _p, _p, _p, _p]),
     "mrgcn_early_stop_record": (C.c_int, [_p, _p, C.c_double, _i32, C.POINTER(MetricsRow), _p]),
+    "mrgcn_early_stop_record_row": (C.c_int, [_p, _p, C.c_double, _i32, _p, _i32, _p, _i64, _p]),
     "mrgcn_snapshot_block_bytes": (C.c_int64, []),
     "mrgcn_snapshot_if": (C.c_int, [_p, _p, _i32, _i64, _i32, _p]),
     "mrgcn_event_create": (C.c_int, [C.POINTER(_p)]),

@@ -5,6 +5,7 @@
 #include <cmath>
 
 #include "common.hpp"
+#include "early_stop.hpp"
 
 namespace mrgcn {
 
@@ -106,32 +107,12 @@ struct MetricsRow {
 __global__ void k_early_stop_record(mrgcn_early_stop_state *__restrict__ st, const float *__restrict__ score,
                                     double tolerance, int patience_default, MetricsRow m) {
   if (blockIdx.x != 0 || threadIdx.x != 0) return;
-  st->improved = 0;
-  if (st->stop) return;  // latched: epochs that run before the host notices leave no trace
+  if (!early_stop_open(st)) return;
   if (m.ring) {
     float *row = m.ring + (st->records % m.rows) * 4;
     for (int k = 0; k < 4; ++k) row[k] = m.src[k] ? *m.src[k] : -1.f;
   }
-  st->records += 1;
-  if (st->delay > 0) {
-    st->delay -= 1;
-    return;
-  }
-  const double s = (double)*score;
-  if (st->best_score < 0) {  // the first record that counts: no patience spent
-    st->best_score = s;
-    st->best_record = st->records;
-    st->improved = 1;
-    return;
-  }
-  st->patience -= 1;
-  if (s + tolerance < st->best_score) {
-    st->best_score = s;
-    st->best_record = st->records;
-    st->improved = 1;
-    st->patience = patience_default;
-  }
-  if (st->patience <= 0) st->stop = 1;
+  early_stop_book(st, score, tolerance, patience_default);
 }
 
 // ---- the snapshot: table-driven copy behind a device flag ------------------------------------------------------------

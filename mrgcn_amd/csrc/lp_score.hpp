@@ -24,6 +24,15 @@ __device__ __forceinline__ bool in_sorted(const int32_t *__restrict__ a, int64_t
   return false;
 }
 
+// rank = greater + round_half_even((ties - 1) / 2) + 1 (link_prediction.py:633-641): the rule of distmult.hip's
+// k_rank_final, kept here for the rank kernels of other units (lp_eval.hip)
+__device__ __forceinline__ int64_t lp_rank_of(int64_t gt, int64_t eq) {
+  const int64_t m = eq - 1;                       // >= 0: the fact's own answer always ties and is never masked
+  int64_t half = m >> 1;
+  if ((m & 1) && (half & 1)) half += 1;           // x.5 rounds to the even neighbour
+  return gt + half + 1;
+}
+
 // acc[i] = the score of candidate c (this thread's; `live` = c < N) for pair i < nfb of the block, candidates read
 // coalesced from the transposed table.  head == false: the candidate fills the tail slot,
 // acc += (E[anchor,h] Rel[rel,h]) * E[c,h]; head == true: the head slot, acc += (E[c,h] Rel[rel,h]) * E[anchor,h];

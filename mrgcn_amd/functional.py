@@ -524,6 +524,34 @@ def _grad_meta(t):
     return m if (m is not None and m["version"] == t._version) else None
 
 
+_DCOMP_CHUNK_ELEMS = 1 << 22   # elements of one [columns, B, F] piece of _dcomp_ordered (two such temporaries: 32 MB)
+
+
+def _dcomp_ordered(plan, dM, F, live, wI, comp):
+    """dcomp[r, b] = sum over the compact columns c = (r, j) of <dM[c, :F], V[j, b, :]> without float atomics: one
+    fixed-order dot per (column, basis), then the columns of a relation added by torch's index_add_, which is
+    deterministic under torch.use_deterministic_algorithms(True).  Columns whose `live` flag is 0 hold nothing (their
+    rows of dM may be unwritten).  The columns are taken in pieces of at most _DCOMP_CHUNK_ELEMS / (B F), in rising
+    order (the pieces depend on the shapes only), so the gathered V blocks and their products never hold more than
+    2 x 16 MB whatever the graph; the work is one read of dM and one gather of a V block per column."""
+    ent = plan.__dict__.get("_ulcol_rel_node")
+    if ent is None:
+        cols = plan.ulcol_long()
+        ent = plan.__dict__["_ulcol_rel_node"] = ((cols // plan.num_nodes).contiguous(),
+                                                  (cols % plan.num_nodes).contiguous())
+    rel, node = ent
+    out = torch.zeros_like(comp, dtype=torch.float32, memory_format=torch.contiguous_format)
+    ncols, B = int(rel.numel()), int(wI.shape[1])
+    step = max(_DCOMP_CHUNK_ELEMS // max(B * F, 1), 1)
+    for c0 in range(0, ncols, step):
+        c1 = min(c0 + step, ncols)
+        P = (dM[c0:c1, None, :F] * wI.index_select(0, node[c0:c1])).sum(-1)
+        if live is not None:
+            P = torch.where(live[c0:c1].bool()[:, None], P, torch.zeros((), dtype=P.dtype, device=P.device))
+        out.index_add_(0, rel[c0:c1], P)
+    return out
+
+
 class _RgcnLayer(torch.autograd.Function):
     """Y = relu?( A' . M + b ),  M[c] = comp_I[r_c] . V_I[j_c, :, :]  (or weight_I[r_c*N + j_c])
                                        + X[j_c] . W_F[r_c]
@@ -800,6 +828,11 @@ class _RgcnLayer(torch.autograd.Function):
                         plan.handle, dM.data_ptr(), ld, live.data_ptr() if live is not None else 0, wI.data_ptr(),
                         comp_I.data_ptr(), Bn, F, d_wI.data_ptr(), 0, d_comp.data_ptr(), 0, s),
                         "mrgcn_basis_mix_bwd_f32")
+                    if torch.are_deterministic_algorithms_enabled():
+                        # the kernel's dcomp is a float-atomic sum; under the flag it is summed again in a fixed order
+                        # (this branch only: the row-sparse one above keeps the kernel's)
+                        bump("deterministic.dcomp")
+                        d_comp = _dcomp_ordered(plan, dM, F, live, wI, comp_I)
             elif has_I:
                 # dense (R*N) x F gradient in one pass: the touched rows from dM, zeros everywhere else
                 d_wI = torch.empty(weight_I.shape, dtype=torch.float32, device=dev)

@@ -29,7 +29,9 @@ def stats() -> dict:
     Under `torch.use_deterministic_algorithms(True)`: `deterministic.distmult_bwd` (DistMult backwards on the owner
     form), `deterministic.bce` (BCE losses summed in block order), `deterministic.sumsq` (clips whose squared norms were
     summed in block order: ClipAdam steps and `optim.clip_grad_norm_` calls), `deterministic.wide_input` (wide
-    featureless full-batch backwards on the atomic-free units because of the flag); with the flag off they stay 0."""
+    featureless full-batch backwards on the atomic-free units because of the flag), `deterministic.dcomp` (narrow
+    full-batch backwards whose basis-coefficient gradient was summed again in a fixed order); with the flag off they
+    stay 0."""
     return dict(_COUNTS)
 
 

@@ -2,8 +2,9 @@
 `mrgcn/tasks/link_prediction.py` (scores :645-665, loss :550-554, negative sampling :247-263,
 ranks :593-643, metrics :373-420), same function names and argument meaning, computed by the
 HIP kernels of `csrc/distmult.hip` through the C ABI.  The reference's mini-batch flow (mkbatches
-:477-530, train_model's batch loop :226-331, test_model :375-422) is mirrored at the end of this
-file; its run loop, logging and TSV writers are out of scope."""
+:477-530, train_model's batch loop :226-331, test_model :375-422) is mirrored further down, its
+full-batch run loop with evaluation and early stopping on the device (`fit`, csrc/lp_eval.hip) at the
+end of this file; logging and TSV writers are out of scope."""
 from __future__ import annotations
 
 import ctypes as C
@@ -754,3 +755,387 @@ def predict_links(model, batch, queries, k, side="tail", known=None):
     with torch.no_grad():
         E = _embed(model, batch)
         return predict_topk(queries, E, _relations(model), k, side=side, known=known)
+
+
+# ---- the reference's full-batch run loop on the device (link_prediction.py:191-422; csrc/lp_eval.hip) ---------------
+EVAL_ROW = 17   # loss | train raw mrr, h@1, h@3, h@10, flt mrr, h@1, h@3, h@10 | the same eight of the validation facts
+
+
+class FactParts:
+    """The facts of an evaluation cut as `mkbatches` cuts them in full-batch mode (:536-545:
+    `np.array_split(arange(n), max(n // mrr_batchsize, 1))`), with the filter lists of EACH PART'S OWN facts
+    (test_model filters a part by `truedicts(batch_data)`, :568-591) concatenated into one CSR set with running
+    offsets, and `part_ptr` [nparts + 1] over the facts.  Built once on the host; `facts` (int64 [n, 3]), `part_ptr`
+    (int64) and `lists` (tail_ptr int64 [n + 1], tail_idx int32, head_ptr, head_idx; None when not `filtered`) are
+    tensors on `device` — default: the device of `facts` when it is a tensor, else the current GPU, else the host."""
+
+    def __init__(self, facts, mrr_batchsize, filtered=True, device=None):
+        if device is None:
+            device = facts.device if torch.is_tensor(facts) else ("cuda" if torch.cuda.is_available() else "cpu")
+        data = (facts.detach().cpu().numpy() if torch.is_tensor(facts) else np.asarray(facts)).astype(np.int64)
+        if data.ndim != 2 or data.shape[1] != 3 or len(data) == 0:
+            raise ValueError("FactParts: facts must be a non-empty [n, 3] array")
+        n = len(data)
+        if mrr_batchsize <= 0:
+            mrr_batchsize = n
+        subsets = np.array_split(np.arange(n), max(n // int(mrr_batchsize), 1))
+        self.sizes = [len(s) for s in subsets]
+        ptr = np.zeros(len(subsets) + 1, np.int64)
+        np.cumsum(self.sizes, out=ptr[1:])
+        self.n, self.nparts, self.filtered = n, len(subsets), bool(filtered)
+        self.part_ptr_host = ptr
+        self.facts = torch.from_numpy(np.ascontiguousarray(data)).to(device)
+        self.part_ptr = torch.from_numpy(ptr).to(device)
+        self.lists = None
+        if filtered:
+            tps, tis, hps, his = [np.zeros(1, np.int64)], [], [np.zeros(1, np.int64)], []
+            toff = hoff = 0
+            for p in range(self.nparts):
+                tp, ti, hp, hi = filter_lists(data[ptr[p]:ptr[p + 1]])
+                tps.append(tp[1:] + toff)
+                hps.append(hp[1:] + hoff)
+                tis.append(ti)
+                his.append(hi)
+                toff += len(ti)
+                hoff += len(hi)
+            cat = [np.concatenate(tps), np.concatenate(tis).astype(np.int32), np.concatenate(hps),
+                   np.concatenate(his).astype(np.int32)]
+            self.lists = tuple(torch.from_numpy(a).to(device) for a in cat)
+
+
+def rank_both_slice() -> int:
+    """How many facts one launch of `rank_both`'s scoring grid takes by default (any number of facts is cut into such
+    slices inside the call)."""
+    return int(_lib.load().mrgcn_distmult_ranks_both_slice())
+
+
+def rank_both(facts, node_embeddings, edge_embeddings, lists=None, part_ptr=None, slice_facts=0):
+    """Raw and filtered ranks of `facts` from ONE pass over the candidate scores (mrgcn_distmult_ranks_both): `(raw,
+    flt)`, each what `compute_ranks_fast` returns without / with the filter, bit for bit; `flt` is None without lists.
+    `facts`: an [n, 3] array, or a `FactParts` (its lists and parts are then taken).  `lists`: the four device tensors
+    of `filter_lists` (concatenated per part for several parts).  `part_ptr` (device int64 [nparts + 1]): the call
+    stands for one `compute_ranks_fast` per part — the reference leaves facts at positions >= the number of nodes of a
+    call unscored, and the position is then the one inside the part.  `slice_facts`: facts per launch of the scoring
+    grid (0: `rank_both_slice()`).  With device tensors nothing is copied from or to the host, nothing synchronises and
+    a graph captures the call."""
+    if isinstance(facts, FactParts):
+        lists = facts.lists if lists is None else lists
+        part_ptr = facts.part_ptr if part_ptr is None else part_ptr
+        facts = facts.facts
+    E = _f32_rows(node_embeddings.detach(), "node_embeddings")
+    Rel = _f32_rows(edge_embeddings.detach(), "edge_embeddings")
+    dev = E.device
+    if torch.is_tensor(facts) and facts.is_cuda and facts.dtype == torch.int64 and facts.is_contiguous():
+        tr = facts
+        if tr.dim() != 2 or tr.shape[1] != 3:
+            raise ValueError("facts must be [n, 3]")
+    else:
+        tr = _triples(facts, dev)
+    nf, N, H = int(tr.shape[0]), int(E.shape[0]), int(E.shape[1])
+    if Rel.shape[1] != H:
+        raise ValueError("rank_both: node and edge embeddings differ in width")
+    raw = torch.empty(2 * nf, dtype=torch.int64, device=dev)
+    flt = torch.empty(2 * nf, dtype=torch.int64, device=dev) if lists is not None else None
+    if nf == 0:
+        return raw, flt
+    ls = [None] * 4
+    if lists is not None:
+        ls = list(lists)
+        if len(ls) != 4 or not all(torch.is_tensor(a) and a.is_cuda for a in ls):
+            raise _lib.MrgcnError("rank_both: lists are the four device tensors of filter_lists")
+        if not (ls[0].dtype == ls[2].dtype == torch.int64 and ls[1].dtype == ls[3].dtype == torch.int32
+                and ls[0].numel() == ls[2].numel() == nf + 1):
+            raise _lib.MrgcnError("rank_both: lists are (int64 [n + 1], int32, int64 [n + 1], int32)")
+        # (an empty tensor has no address; the lists are empty either way)
+        ls = [a.contiguous() if a.numel() else torch.zeros(1, dtype=a.dtype, device=dev) for a in ls]
+    nparts = 0
+    if part_ptr is not None:
+        if not (part_ptr.is_cuda and part_ptr.dtype == torch.int64 and part_ptr.dim() == 1 and part_ptr.numel() >= 2):
+            raise _lib.MrgcnError("rank_both: part_ptr is a device int64 [nparts + 1] tensor")
+        part_ptr, nparts = part_ptr.contiguous(), int(part_ptr.numel()) - 1
+    lib = _lib.load()
+    ws_bytes = int(lib.mrgcn_distmult_ranks_both_workspace(N, H, nf))
+    ws = torch.empty((ws_bytes + 3) // 4, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(lib.mrgcn_distmult_ranks_both(_ptr(E), E.stride(0), N, _ptr(Rel), Rel.stride(0), H, _ptr(tr), nf,
+                                                 _ptr(ls[0]), _ptr(ls[1]), _ptr(ls[2]), _ptr(ls[3]), _ptr(part_ptr),
+                                                 nparts, int(slice_facts), _ptr(ws), ws_bytes, _ptr(raw), _ptr(flt),
+                                                 _stream()), "distmult_ranks_both")
+    return raw, flt
+
+
+def rank_metrics(ranks, part_ptr=None, out=None, score=None):
+    """test_model's metrics (:403-419) of an int64 `[2 * nf]` rank vector (tail ranks, then head ranks) on the device:
+    float32 `[mrr, hits@1, hits@3, hits@10]`, the mean over the parts of `part_ptr` (device int64 [nparts + 1]; None:
+    one part) of each part's means — part p owns ranks [p0, p1) and nf + [p0, p1) —, added in float64 in a fixed order
+    and rounded once (mrgcn_rank_metrics): equal ranks give equal bits.  `out`: a contiguous float32 [4] device tensor
+    to write; `score`: a float32 device scalar that receives `1 - mrr`, the score train_model records (:363).  No
+    synchronisation; capturable — so `part_ptr` is not read here: the caller guarantees `0 = part_ptr[0] < ... <
+    part_ptr[-1] = nf` (a `FactParts` does by construction, and `evaluate_facts` compares its host copy with the
+    ranks); the kernel clamps bounds outside `[0, nf]`, so a wrong one gives wrong means, never a stray read."""
+    if not (ranks.is_cuda and ranks.dtype == torch.int64 and ranks.dim() == 1 and ranks.numel() >= 2
+            and ranks.numel() % 2 == 0 and ranks.is_contiguous()):
+        raise _lib.MrgcnError("rank_metrics: a contiguous, non-empty int64 [2 * nf] rank vector on the device")
+    dev, nf = ranks.device, int(ranks.numel()) // 2
+    nparts = 1
+    if part_ptr is not None:
+        if not (part_ptr.is_cuda and part_ptr.dtype == torch.int64 and part_ptr.dim() == 1 and part_ptr.numel() >= 2
+                and part_ptr.is_contiguous()):
+            raise _lib.MrgcnError("rank_metrics: part_ptr is a contiguous device int64 [nparts + 1] tensor")
+        nparts = int(part_ptr.numel()) - 1
+    if out is None:
+        out = torch.empty(4, dtype=torch.float32, device=dev)
+    elif not (out.is_cuda and out.dtype == torch.float32 and out.numel() == 4 and out.is_contiguous()):
+        raise _lib.MrgcnError("rank_metrics: out is a contiguous float32 [4] tensor on the device")
+    if score is not None and not (score.is_cuda and score.dtype == torch.float32 and score.numel() == 1):
+        raise _lib.MrgcnError("rank_metrics: score is one float32 on the device")
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().mrgcn_rank_metrics(_ptr(ranks), nf, _ptr(part_ptr), nparts, _ptr(out), _ptr(score),
+                                                  _stream()), "rank_metrics")
+    return out
+
+
+def evaluate_facts(node_embeddings, edge_embeddings, parts: FactParts, want_ranks=False, out=None, score=None,
+                   slice_facts=0):
+    """test_model (:375-422) of the parts of a `FactParts` against ONE set of embeddings (full-batch mode: every part
+    sees the whole graph's), without the host: `rank_both` and one `rank_metrics` per rank type.  Returns the float32
+    `[8]` device vector raw mrr, hits@1, hits@3, hits@10, then the same filtered (-1 each when the parts carry no
+    lists, as test_model reports them) — `out`, when given — and with `want_ranks` also `(raw, flt)`, the ranks of all
+    parts as `rank_both` lays them out.  `score` (a float32 device scalar) receives `1 - raw mrr`.  No
+    synchronisation; capturable."""
+    ptr = parts.part_ptr_host
+    if not (ptr[0] == 0 and ptr[-1] == parts.n == parts.facts.shape[0] and bool(np.all(np.diff(ptr) > 0))
+            and parts.part_ptr.numel() == len(ptr)):
+        raise _lib.MrgcnError("evaluate_facts: part_ptr must rise from 0 to the number of facts, no part empty")
+    raw, flt = rank_both(parts, node_embeddings, edge_embeddings, slice_facts=slice_facts)
+    if out is None:
+        out = torch.empty(8, dtype=torch.float32, device=raw.device)
+    rank_metrics(raw, parts.part_ptr, out[:4], score)
+    if flt is not None:
+        rank_metrics(flt, parts.part_ptr, out[4:])
+    else:
+        out[4:].fill_(-1.0)
+    return (out, raw, flt) if want_ranks else out
+
+
+def eval_schedule(nepoch, eval_interval, has_valid):
+    """Which epochs of train_model evaluate what: `[(epoch, eval_train, eval_valid, records)]` for epochs 1 .. nepoch.
+    The training facts are evaluated when `epoch % eval_interval == 0 or epoch == nepoch` (:336); the validation
+    facts, and the early-stop record with them, only then and only with a validation set and `epoch < nepoch`
+    (:350, :362)."""
+    out = []
+    for epoch in range(1, int(nepoch) + 1):
+        eval_train = epoch % eval_interval == 0 or epoch == nepoch
+        eval_valid = bool(eval_train and has_valid and epoch < nepoch)
+        out.append((epoch, eval_train, eval_valid, eval_valid))
+    return out
+
+
+def train_step(model, forward_fn, sampler, optimizer, static=None, clip=1.0):
+    """One full-batch epoch of train_model (:231-326): `triples, labels = sampler()` (a `DeviceNegativeSampler`, or any
+    callable that returns the facts followed by their corrupted copies and the 1 / 0 labels on the device without
+    synchronising), `forward_fn()` for the node embeddings (e.g. `lambda: model(None, A)`), DistMult scores, BCE,
+    backward, the gradient clipped at `clip` — inside the step of a `ClipAdam` that has a `max_norm`, by
+    `clip_grad_norm_` otherwise — and the optimizer step.  `static`: the `SortedTriples` of the facts the triples start
+    with.  Returns the loss as a device scalar; no host read, so a graph captures it."""
+    from ..optim import clip_grad_norm_
+    from ..train import ClipAdam
+    triples, labels = sampler()
+    emb = forward_fn()
+    loss = binary_crossentropy(score_distmult_bc(triples, emb, _relations(model), static=static), labels)
+    optimizer.zero_grad(set_to_none=True)
+    loss.backward()
+    if not (isinstance(optimizer, ClipAdam) and optimizer.max_norm is not None):
+        clip_grad_norm_(model.parameters(), clip)
+    optimizer.step()
+    return loss.detach()
+
+
+def _unpack(vec):
+    """A metrics vector of evaluate_facts as the reference's pair ({"raw", "flt"} mrr, {"raw", "flt"} hits lists)."""
+    v = [float(x) for x in vec]
+    return {"raw": v[0], "flt": v[4]}, {"raw": v[1:4], "flt": v[5:8]}
+
+
+class FitEpochs:
+    """The two epochs `fit` is made of, as callables on one set of device rings (see `fit` for what they do):
+    `train_epoch()` — `train_step`, its loss into row `epochs % poll` of `loss_ring` — and `eval_epoch()` — the same,
+    then one `eval()` forward, `evaluate_facts` of the training and the validation parts, the `EVAL_ROW` values into row
+    `records % poll` of `eval_ring` by the early-stop record, the snapshot behind its flag — and `last_epoch()`:
+    a training epoch, then the training metrics into `last`, eagerly.  `graphed=True`: the first two are one captured
+    hipGraph each, a single chain on the capture stream; the `warmup` epochs of the capture are real optimizer steps
+    (the last of them an evaluating epoch), after which the counters and rings are reset."""
+
+    def __init__(self, model, forward_fn, tparts, vparts, optimizer, stopper=None, poll=8, graphed=True, sampler=None,
+                 static=None, warmup=3):
+        from .. import functional as Fn
+        from ..train import _COUNT_ONLY, _StopState
+        dev = tparts.facts.device
+        if stopper is not None and vparts is None:
+            raise _lib.MrgcnError("fit: early stopping scores the validation MRR: pass valid_facts")
+        if graphed and not getattr(optimizer, "capturable", False):
+            raise _lib.MrgcnError("fit(graphed=True) needs ClipAdam(..., capturable=True)")
+        if sampler is None:
+            sampler = DeviceNegativeSampler(tparts.facts)
+            if static is None:
+                was = model.training
+                model.eval()
+                with torch.no_grad():
+                    num_nodes = int(forward_fn().shape[0])
+                model.train(was)
+                static = SortedTriples(sampler.facts, num_nodes, int(_relations(model).shape[0]))
+        self.model, self.forward_fn, self.tparts, self.vparts = model, forward_fn, tparts, vparts
+        self.optimizer, self.stopper, self.sampler, self.static, self.poll = optimizer, stopper, sampler, static, poll
+        self.loss_ctr = _StopState(dev, 1, 0.0, _COUNT_ONLY)   # counts every epoch
+        self.eval_ctr = stopper.state if stopper is not None else _StopState(dev, 1, 0.0, _COUNT_ONLY)
+        self.loss_ring = torch.zeros((poll, 4), dtype=torch.float32, device=dev)
+        self.eval_ring = torch.zeros((poll, EVAL_ROW), dtype=torch.float32, device=dev)
+        self.row = torch.zeros(EVAL_ROW, dtype=torch.float32, device=dev)
+        self.score = torch.zeros((), dtype=torch.float32, device=dev)
+        self.last = torch.zeros(8, dtype=torch.float32, device=dev)
+        self.train_epoch, self.eval_epoch = self._train_epoch, self._eval_epoch
+        if not graphed:
+            self.reset()
+            return
+        nw = max(int(warmup), 1)
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            for _ in range(nw - 1):
+                self._train_epoch()
+            self._eval_epoch()
+            self.reset()
+        torch.cuda.current_stream().wait_stream(side)
+        torch.cuda.synchronize()
+        self.warmup_steps = nw
+        self._graphs, self._pair_sums = [], []
+        for fn in (self._train_epoch, self._eval_epoch):
+            g = torch.cuda.CUDAGraph()
+            Fn.take_captured_pair_sums()
+            with torch.cuda.graph(g, stream=side, capture_error_mode="thread_local"):
+                fn()
+            self._pair_sums.append(Fn.take_captured_pair_sums())
+            self._graphs.append(g)
+        self._state_gen = optimizer._state_gen
+        self.train_epoch, self.eval_epoch = (lambda: self._replay(0)), (lambda: self._replay(1))
+
+    def reset(self):
+        self.loss_ctr.reset()
+        self.eval_ctr.reset()
+        self.loss_ring.zero_()
+        self.eval_ring.zero_()
+
+    def _replay(self, i):
+        if self.optimizer._state_gen != self._state_gen:
+            raise _lib.MrgcnError("fit: the optimizer's state was loaded after the capture (the captured graphs still "
+                                  "update the old moment buffers)")
+        for sup in self._pair_sums[i]:
+            sup.pair_sums_refresh()
+        self._graphs[i].replay()
+
+    def _train_epoch(self):
+        self.model.train()
+        loss = train_step(self.model, self.forward_fn, self.sampler, self.optimizer, self.static)
+        self.loss_ctr.record(loss, self.loss_ring, (loss,))
+        return loss
+
+    def _evaluate_train(self, out):
+        self.model.eval()
+        with torch.no_grad():
+            E, Rel = self.forward_fn(), _relations(self.model)
+            evaluate_facts(E, Rel, self.tparts, out=out)
+        return E, Rel
+
+    def _eval_epoch(self):
+        loss = self._train_epoch()
+        self.row[0:1].copy_(loss.reshape(1))
+        try:
+            E, Rel = self._evaluate_train(self.row[1:9])
+            if self.vparts is not None:   # (against the same embeddings)
+                evaluate_facts(E, Rel, self.vparts, out=self.row[9:17], score=self.score)
+        finally:
+            self.model.train()
+        (self.stopper if self.stopper is not None else self.eval_ctr).record_row(self.score, self.row, self.eval_ring)
+        return loss
+
+    def last_epoch(self):
+        self.train_epoch()
+        try:
+            self._evaluate_train(self.last)
+        finally:
+            self.model.train()
+
+
+def fit(model, forward_fn, train_facts, valid_facts, optimizer, nepoch, eval_interval=1, mrr_batchsize=100,
+        filter_ranks=True, early_stop=None, poll=8, graphed=True, sampler=None, warmup=3, static=None):
+    """The reference's full-batch link-prediction loop (train_model, link_prediction.py:191-373, with test_model
+    :375-422) as a generator over its tuples `(epoch, loss, train_mrr, train_hits_at_k, valid_mrr, valid_hits_at_k)`
+    — epochs from 1, `loss` a float, an mrr `{"raw", "flt"}`, hits `{"raw": [h@1, h@3, h@10], "flt": [...]}`, None
+    where the reference yields None (`eval_schedule`), "flt" values -1 when `filter_ranks` is off — with the host
+    looking in every `poll` epochs only.  `forward_fn()` returns the node embeddings of the whole graph.  Training
+    facts are evaluated in parts of `mrr_batchsize` (`FactParts`), `valid_facts` (None: no validation) likewise; the
+    early stop scores `1 - valid_mrr["raw"]` (:363).  `early_stop`: None, a DeviceEarlyStop, or a host EarlyStop as
+    its configuration.  `sampler`: see `train_step`; None draws the reference's 20 % in-batch negatives on the device
+    (`DeviceNegativeSampler`, with the stored orders of the facts for the decoder's backward).
+
+    An epoch is one of two step functions, chosen on the host from the epoch number (no device read):
+    a training epoch — `train_step`, its loss into a device ring — and an evaluating epoch — the same, then ONE
+    `forward_fn()` under `model.eval()` and `no_grad`, `evaluate_facts` of the training parts and of the validation
+    parts against those same embeddings, the 17 values into row `records % poll` of a device ring by the early-stop
+    record (`record_row`), the snapshot of the best state behind the record's flag.  With `graphed=True` each is one
+    captured hipGraph, a single chain on the capture stream, and needs `ClipAdam(capturable=True)`; the `warmup`
+    epochs of the capture are REAL optimizer steps taken before epoch 1 (the last of them also evaluates; the
+    early-stop state and the rings are reset after them).  The last epoch (training metrics only, no record) evaluates
+    eagerly.
+
+    Stop semantics are `mrgcn_amd.train.fit`'s.  A run starts at record 0 (a DeviceEarlyStop's earlier state is
+    discarded).  When a poll finds `stop` set, the rows up to and including the epoch whose record set it are
+    yielded — no loss rows of later epochs —, the best state is restored in place and the generator ends; the up to
+    `poll - 1` epochs that ran past the stop took optimizer steps, but the latched state ignored their records, their
+    rows were not written, no snapshot was taken and the restore overwrites every tensor they changed.  A run that
+    reaches `nepoch` is left with the LAST epoch's parameters and optimizer state; nothing is restored.
+
+    Under `torch.use_deterministic_algorithms(True)` the step takes the deterministic decoder kernels; what is added
+    here (ranks: integer counts; metrics: a fixed-order float64 sum; records) has no float atomics."""
+    from ..train import _as_device_stopper
+    dev = next(model.parameters()).device
+    nepoch, poll = int(nepoch), max(int(poll), 1)
+    tparts = FactParts(train_facts, mrr_batchsize, filter_ranks, device=dev)
+    vparts = FactParts(valid_facts, mrr_batchsize, filter_ranks, device=dev) if valid_facts is not None else None
+    stopper = _as_device_stopper(early_stop, model, optimizer)
+    run = FitEpochs(model, forward_fn, tparts, vparts, optimizer, stopper, poll, graphed, sampler, static, warmup)
+    sched = eval_schedule(nepoch, eval_interval, vparts is not None)
+    evals_before = 0     # evaluating epochs < nepoch in front of the current window = records at its start
+    epoch = 0
+    while epoch < nepoch:
+        window = sched[epoch:epoch + poll]
+        for e, eval_train, _, _ in window:
+            if e == nepoch:
+                run.last_epoch()
+            elif eval_train:
+                run.eval_epoch()
+            else:
+                run.train_epoch()
+        epoch += len(window)
+        st = run.eval_ctr.read()
+        losses, rows, last_host = run.loss_ring.cpu(), run.eval_ring.cpu(), run.last.cpu()
+        k = evals_before
+        for e, eval_train, eval_valid, _ in window:
+            tm = th = vm = vh = None
+            if eval_train and e < nepoch:
+                if k >= int(st.records):    # the stop was latched in front of this epoch
+                    break
+                r = rows[k % poll]
+                k += 1
+                tm, th = _unpack(r[1:9])
+                if eval_valid:
+                    vm, vh = _unpack(r[9:17])
+            elif eval_train:
+                tm, th = _unpack(last_host)
+            yield (e, float(losses[(e - 1) % poll][0]), tm, th, vm, vh)
+            if st.stop and k == int(st.records) and eval_train:
+                break
+        evals_before = k
+        if st.stop:
+            stopper.restore_()
+            return

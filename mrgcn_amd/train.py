@@ -732,6 +732,9 @@ class GraphedStep:
             self.out = fn()
         self._pair_sums = Fn.take_captured_pair_sums()
         self.warmup_steps = max(warmup, 1)
+        # the captured launches name the addresses of whatever `fn` closes over (a sampler's buffers, stored orders):
+        # they live as long as the graph does, also when the caller keeps nothing but this object
+        self._fn = fn
 
     def __call__(self):
         for sup in self._pair_sums:   # (tables of a constant input the graph reads: rebuilt in place if X was changed)
@@ -872,6 +875,24 @@ class _StopState:
                                                      _stream(dev)), "mrgcn_early_stop_record")
 
 
+    def record_row(self, score, row, ring):
+        """`record` with a metrics row of any width (mrgcn_early_stop_record_row): the contiguous float32 device
+        vector `row` goes to row `records % rows` of the float32 `[rows, len(row)]` device `ring`."""
+        if not (score.is_cuda and score.dtype == torch.float32 and score.numel() == 1):
+            raise L.MrgcnError("early stop: the score is one float32 on the device")
+        if not (row.is_cuda and row.dtype == torch.float32 and row.dim() == 1 and row.is_contiguous() and row.numel() > 0
+                and ring.is_cuda and ring.dtype == torch.float32 and ring.dim() == 2 and ring.is_contiguous()
+                and ring.shape[0] > 0 and ring.shape[1] == row.numel()):
+            raise L.MrgcnError("record_row: a contiguous float32 [width] row and a contiguous float32 [rows, width] "
+                               "ring on the device")
+        dev = self.buf.device
+        with torch.cuda.device(dev):
+            L.check(L.load().mrgcn_early_stop_record_row(self.buf.data_ptr(), score.data_ptr(), self.tolerance,
+                                                         self.patience_default, row.data_ptr(), int(row.numel()),
+                                                         ring.data_ptr(), int(ring.shape[0]), _stream(dev)),
+                    "mrgcn_early_stop_record_row")
+
+
 class DeviceEarlyStop:
     """`EarlyStop` with its state, its decision and its copy of the best weights on the device, so that a replayed epoch
     graph records into it without the host:
@@ -961,6 +982,12 @@ class DeviceEarlyStop:
         up to four device scalars written to row `records % rows` by the same launch (see train_eval_step)."""
         self._check_gen()
         self.state.record(score_dev, metrics, values)
+        self._copy(self.state.improved_ptr, False)
+
+    def record_row(self, score_dev, row, ring):
+        """`record` with a metrics row of any width (`_StopState.record_row`), then the same snapshot."""
+        self._check_gen()
+        self.state.record_row(score_dev, row, ring)
         self._copy(self.state.improved_ptr, False)
 
     def reset(self):

@@ -85,6 +85,9 @@ python3 tools/early_stop_probe.py --out $o/early_stop_probe.json > $o/early_stop
 # `python3 tools/weight_reg_probe.py --rows-only --zero-repeats 3 --out <file>` there first; WEIGHT_REG_PARENT_JSON=<file>
 # then puts them into the result.  Without it the file holds this tree's rows only.
 python3 tools/weight_reg_probe.py ${WEIGHT_REG_PARENT_JSON:+--parent $WEIGHT_REG_PARENT_JSON} --out $o/weight_reg_probe.json > $o/weight_reg_probe.txt 2> $o/weight_reg_probe.err
+# (10g) link prediction's run loop on the device: rank_both against the two rank calls, the replayed evaluating epoch
+# against the host loop, the replayed training epoch against GraphedStep
+python3 tools/lp_fit_probe.py --out $o/lp_fit_probe.json > $o/lp_fit_probe.txt 2> $o/lp_fit_probe.err
 hipcc -O3 --offload-arch=gfx950 -std=c++17 tools/lab/copy_lab.hip -o /tmp/copy_lab 2>/dev/null && /tmp/copy_lab > $o/copy_lab.txt 2>&1
 python3 tools/lab/spmm_hot_lab.py > $o/spmm_hot_lab.txt 2>&1
 # the CPU suite last: the tree these artefacts describe is green
