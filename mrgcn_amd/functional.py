@@ -134,6 +134,58 @@ def clear_row_grads(params):
             ent["fresh"] = False
 
 
+# The entry `param._mrgcn_rows` is a plain dict that lives as long as the parameter; two kinds, one constructor each.
+# Written by the backward (B), the optimizer (O: mrgcn_amd.optim.ClipAdam.step) or optim.clip_grad_norm_ (C):
+#   fresh       B sets it with every gradient it leaves; pop_row_grad (O), clear_row_grads (train_step, zero_grad)
+#               and C's densifying routes clear it.  An entry that is not fresh carries no gradient.
+#   shape       B, at construction: the parameter's shape (a node entry of another shape is rebuilt).
+#   g           B: node kind — the dense-shaped buffer whose live node blocks hold the gradient, None while the
+#               update rebuilds them from dM (`fused`); index kind — the compact gradient [ncols, F].  Read by O, C
+#               and dense_from_rows until the next backward replaces it.
+#   seeded_for  O: (id of the optimizer, its state generation) whose moments the flags below were derived from;
+#               None (B at construction, O after a dense step on the parameter) = look at the moments again.
+#   coef        C: the clip coefficient of a clip between backward and step; popped by O's update of that entry (or
+#               by merge_row_grad when the entry is densified).
+# node kind only (a node-major weight_I, [N, B, F]):
+#   cur, cur_owned  B: uint8 [N], the nodes with gradient this step; `cur_owned` False = the tensor is a gradient
+#               support's own (read-only here).  Read by O's plain row updates and dense_from_rows.
+#   ever        B allocates (zeros), O's row kernels set: uint8 [N], nodes that hold non-zero moments; O zeroes and
+#               re-derives it when `seeded_for` names another optimizer state.
+#   ever_in     O: the gradient support every step since the flags were zeroed ran on, None = none yet, "any" = no
+#               single one (the update then also visits nodes outside the support).
+#   sumsq       B: 0-dim double, ||gradient||^2, read by O's and C's norm of that step.
+#   fused       B: None, or what the update rebuilds the blocks from — plan, sup (None off a support), dM, ld, live,
+#               comp (weight_I_comp as the backward read it), comp_version (checked by O), B, F.  Read by O and
+#               dense_from_rows of that step.
+#   reg_sums    O: double [3] the penalty pre-pass writes (sum (g + r)^2, sum |p|, sum p^2); scratch kept for reuse.
+# index kind only (kind="index": the literal operand of a featureless layer without bases, [R*N, F]):
+#   kind, plan  B, at construction; an entry met under another plan sets dense_only (B).
+#   index, index_ptr  B, at construction: the plan's compact columns (int64 tensor / device address of the plan's array).
+#   dense_only  O (`_index_rows_ok`: moments outside the columns) or B (another plan): dense gradients from now on.
+def _check_consumed(rows):
+    if rows is not None and rows["fresh"]:
+        raise L.MrgcnError("row-sparse weight_I gradient: the layer ran twice in one train_step "
+                           "(use train_step(..., row_sparse=False))")
+
+
+def _node_rows_entry(param, dev):
+    """The node-kind entry this backward writes: the one `param` carries while it fits, else a new one."""
+    rows = getattr(param, "_mrgcn_rows", None)
+    _check_consumed(rows)
+    if rows is None or rows["shape"] != tuple(param.shape) or rows["ever"].device != dev:
+        rows = param._mrgcn_rows = dict(g=None, shape=tuple(param.shape), cur=None, cur_owned=False,
+                                        ever=torch.zeros(param.shape[0], dtype=torch.uint8, device=dev), sumsq=None,
+                                        fresh=False, seeded_for=None, fused=None)
+    return rows
+
+
+def _index_rows_entry(param, plan):
+    rows = param._mrgcn_rows = dict(kind="index", plan=plan, shape=tuple(param.shape), g=None, index=plan.ulcol_long(),
+                                    index_ptr=plan.array_ptr(L.ARR_ULCOL)[0], fresh=False, seeded_for=None,
+                                    dense_only=False)
+    return rows
+
+
 class _LiveGauge:
     """How many rows of a layer's output gradient held anything the last time it was looked at.
     The sparse transposed product (mrgcn_spmm_transposed_live_f32) wins while few rows are live
@@ -444,16 +496,12 @@ class _SpmmLiteral(torch.autograd.Function):
                 # ones this product's autograd ever gives gradient to, whatever the labels: the gradient stays in
                 # compact order ([ncols, F], no zero fill of the table) and the consumer on the parameter
                 # (ClipAdam: mrgcn_adam_step_index_rows_f32) updates those rows only.  `.grad` stays None.
-                if rows is not None and rows["fresh"]:
-                    raise L.MrgcnError("row-sparse weight_I gradient: the layer ran twice in one train_step "
-                                       "(use train_step(..., row_sparse=False))")
+                _check_consumed(rows)
                 if rows is None or rows.get("kind") != "index":
                     if torch.cuda.is_current_stream_capturing() and getattr(plan, "_ulcol_long", None) is None:
                         raise L.MrgcnError("the literal column list of this plan is built on first use: run one "
                                            "backward of the layer before capturing it")
-                    rows = dict(kind="index", plan=plan, shape=tuple(param.shape), g=None, index=plan.ulcol_long(),
-                                index_ptr=plan.array_ptr(L.ARR_ULCOL)[0], fresh=False, seeded_for=None, dense_only=False)
-                    param._mrgcn_rows = rows
+                    rows = _index_rows_entry(param, plan)
                 g = torch.empty((plan.ncols, F), dtype=torch.float32, device=dY.device)
                 plan.spmm(L.VIEW_TRANSPOSED, dY, out=g)
                 rows["g"], rows["fresh"] = g, True
@@ -789,19 +837,11 @@ class _RgcnLayer(torch.autograd.Function):
                 rows = None
                 if (live is not None and param is not None and weight_I.is_contiguous()
                         and param.shape == weight_I.shape and _row_sparse_for(param)):
-                    rows = getattr(param, "_mrgcn_rows", None)
-                    if rows is not None and rows["fresh"]:
-                        raise L.MrgcnError("row-sparse weight_I gradient: the layer ran twice in one train_step "
-                                           "(use train_step(..., row_sparse=False))")
+                    rows = _node_rows_entry(param, dev)
                     # when the shape allows it no gradient tensor exists at all: the backward keeps flags, dcomp
                     # and ||dV||^2, and ClipAdam rebuilds each live block from dM inside the Adam pass
                     # (mrgcn_adam_step_rows_fused_f32); otherwise the blocks of the live nodes go to rows["g"]
                     fused = bool(lib.mrgcn_adam_rows_fused_supported(plan.handle, Bn, F))
-                    if rows is None or rows["shape"] != tuple(weight_I.shape) or rows["ever"].device != dev:
-                        rows = dict(g=None, shape=tuple(weight_I.shape), cur=None, cur_owned=False,
-                                    ever=torch.zeros(N_, dtype=torch.uint8, device=dev), sumsq=None, fresh=False,
-                                    seeded_for=None, fused=None)
-                        param._mrgcn_rows = rows
                     if not rows.get("cur_owned"):
                         # (`cur` may be a gradient support's own node flags — _support_weight_I_grads — which this path
                         # must not overwrite: the flags written below are this entry's own)
@@ -943,7 +983,7 @@ def _support_weight_I_grads(owner, sup, plan, dM, ld, weight_I, comp_I, F, s, wi
     lib = L.load()
     dev = plan.device
     d_wI = None
-    N_, Bn, _ = weight_I.shape
+    Bn = weight_I.shape[1]
     wI = weight_I.contiguous()
     if wide_dY is not None:
         def wide_run(dV, dense, d_comp, sq):
@@ -953,16 +993,8 @@ def _support_weight_I_grads(owner, sup, plan, dM, ld, weight_I, comp_I, F, s, wi
     rows = None
     if (param is not None and weight_I.is_contiguous() and param.shape == weight_I.shape
             and _row_sparse_for(param)):
-        rows = getattr(param, "_mrgcn_rows", None)
-        if rows is not None and rows["fresh"]:
-            raise L.MrgcnError("row-sparse weight_I gradient: the layer ran twice in one train_step "
-                               "(use train_step(..., row_sparse=False))")
+        rows = _node_rows_entry(param, dev)
         fused = wide_run is None and bool(lib.mrgcn_adam_rows_fused_supported(plan.handle, Bn, F))
-        if rows is None or rows["shape"] != tuple(weight_I.shape) or rows["ever"].device != dev:
-            rows = dict(g=None, shape=tuple(weight_I.shape), cur=None,
-                        ever=torch.zeros(N_, dtype=torch.uint8, device=dev), sumsq=None, fresh=False,
-                        seeded_for=None, fused=None)
-            param._mrgcn_rows = rows
         if not fused and rows["g"] is None:
             rows["g"] = torch.empty_like(wI)
     if rows is not None:

@@ -4,30 +4,20 @@ mrgcn/tasks/node_classification.py:154-193 —
     Y_hat = model(batch); loss = CE(Y_hat[idx], targets)
     zero_grad; backward; clip_grad_norm_(params, 1.0); Adam.step
 
-with the loss, the global gradient norm, the clip and Adam running as HIP kernels
-(csrc/optim.hip).  The clip coefficient never leaves the device, so one epoch has no
-host synchronisation."""
+with the loss here and the global gradient norm, the clip and Adam in mrgcn_amd.optim (`ClipAdam`) running as HIP
+kernels (csrc/optim.hip).  The clip coefficient never leaves the device, so one epoch has no host synchronisation."""
 from __future__ import annotations
 
 import ctypes as C
-import os
 
 import torch
 
 from . import _lib as L
 from . import functional as Fn
-from .functional import clear_row_grads, dense_from_rows, pop_row_grad, row_sparse_weight_grad
+from .functional import _ROW_SPARSE_ENV as _ROW_SPARSE_DEFAULT  # MRGCN_ROW_SPARSE=0: no row-sparse weight_I gradient
+from .functional import clear_row_grads, dense_from_rows, pop_row_grad, row_sparse_weight_grad  # noqa: F401
+from .optim import _MULTI, _MULTI_MAX_NUMEL, ClipAdam, _stream, _to_reference_layout, merge_row_grad  # noqa: F401  (once here)
 from .stats import bump
-
-# MRGCN_MULTI=0: one launch per small tensor and phase (sum of squares, Adam) instead of the two multi-tensor launches
-_MULTI = os.environ.get("MRGCN_MULTI", "1") != "0"
-_MULTI_MAX_NUMEL = 1 << 20
-# MRGCN_ROW_SPARSE=0 switches the row-sparse weight_I gradient off (A/B runs)
-_ROW_SPARSE_DEFAULT = os.environ.get("MRGCN_ROW_SPARSE", "1") != "0"
-
-
-def _stream(device) -> int:
-    return torch.cuda.current_stream(device).cuda_stream
 
 
 _LABEL_FLAGS: dict = {}
@@ -121,502 +111,6 @@ def categorical_accuracy(Y_hat, idx, targets):
     """node_classification.py:432-437"""
     labels = Y_hat[idx].argmax(dim=1)
     return (labels == targets).float().mean(), labels, targets
-
-
-def _to_reference_layout(t):
-    """(N, B, F) node-major -> the reference's (B*N, F)."""
-    N, B, F = t.shape
-    return t.permute(1, 0, 2).reshape(B * N, F)
-
-
-class ClipAdam(torch.optim.Optimizer):
-    """clip_grad_norm_(all params, max_norm) followed by torch.optim.Adam, as two passes of
-    HIP kernels: (1) sum of squares of every gradient into one device double, (2) Adam with
-    the clip coefficient read from device memory.  Same hyper-parameter names / param-group
-    layout as torch.optim.Adam so that `optimizer_params` groups (tasks/utils.py:8-45) work.
-
-    `state_dict()` / `load_state_dict()` speak the reference's layout: the moments of a node-major
-    `weight_I` (mrgcn_amd.layers.graph) are handed out and accepted as `(B*N, out)` tensors, so an
-    optimizer checkpoint (run.py:230-236) is interchangeable with torch.optim.Adam over the reference
-    model.  With `capturable=True` the step counter lives on the device (hipGraph replays advance it);
-    `state_dict()` reads it back, `load_state_dict()` seeds it."""
-
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0,
-                 max_norm=1.0, capturable=False):
-        defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
-        super().__init__(params, defaults)
-        self.max_norm = max_norm
-        # capturable: step counter and bias corrections on the device (one per distinct betas), so
-        # that a hipGraph-captured step replays correctly (see GraphedTrainStep)
-        self.capturable = capturable
-        self._dev_step = {}
-        self._scratch = {}
-        self._dist = None  # (group, ids of parameters sharded across ranks)
-        self._state_gen = 0  # bumped by load_state_dict: row flags built for the old moments are re-derived
-        self.reg_loss = None  # the weight penalty the last step() owned (step(l1_lambda=, l2_lambda=)), a device scalar
-
-    # -- checkpoints --------------------------------------------------------------------------------
-    def _sync_host_steps(self):
-        """Device step counters (capturable) -> the per-parameter `step` entries.  Synchronises."""
-        if not self._dev_step:
-            return
-        for group in self.param_groups:
-            ent = self._dev_step.get(tuple(float(b) for b in group["betas"]))
-            if ent is None:
-                continue
-            t = int(ent[0].item())
-            for p in group["params"]:
-                st = self.state.get(p)
-                if st:
-                    st["step"] = t
-
-    def state_dict(self):
-        self._sync_host_steps()
-        sd = super().state_dict()
-        params = [p for g in self.param_groups for p in g["params"]]
-        state = {}
-        for k, st in sd["state"].items():
-            p = params[k]
-            if getattr(p, "_mrgcn_node_major", False) and isinstance(st, dict) and "exp_avg" in st:
-                st = dict(st)
-                for key in ("exp_avg", "exp_avg_sq"):
-                    if st[key].dim() == 3:
-                        st[key] = _to_reference_layout(st[key])
-            state[k] = st
-        sd["state"] = state
-        return sd
-
-    def load_state_dict(self, state_dict):
-        params = [p for g in self.param_groups for p in g["params"]]
-        sd = dict(state_dict)
-        sd["state"] = dict(sd["state"])
-        for k, st in sd["state"].items():
-            p = params[k]
-            if "exp_avg" not in st:
-                continue
-            if getattr(p, "_mrgcn_node_major", False) and st["exp_avg"].dim() == 2:
-                N, B, F = p.shape
-                st = dict(st)
-                for key in ("exp_avg", "exp_avg_sq"):
-                    st[key] = st[key].view(B, N, F).permute(1, 0, 2).contiguous()
-                sd["state"][k] = st
-            elif tuple(st["exp_avg"].shape) != tuple(p.shape):
-                # same element count in another layout (a reference-shaped moment for a parameter this optimizer
-                # does not know to be node-major) would load silently permuted
-                raise L.MrgcnError(f"optimizer state {k}: moments of shape {tuple(st['exp_avg'].shape)} for a "
-                                   f"parameter of shape {tuple(p.shape)}")
-        super().load_state_dict(sd)
-        self._state_gen += 1
-        self._dev_step = {}  # re-seeded from the loaded `step` entries at the next step
-
-    def set_distributed(self, group, sharded_params):
-        """Node-partitioned training (mrgcn_amd.partition): `sharded_params` hold disjoint shards
-        per rank (their squared norms add up across ranks); every other parameter is replicated
-        and already carries the all-reduced gradient (counted once)."""
-        self._dist = (group, {id(p) for p in sharded_params})
-
-    def _dev_scratch(self, device):
-        s = self._scratch.get(device)
-        if s is None:
-            s = dict(accum=torch.zeros((), dtype=torch.float64, device=device),   # (self-cleaning: zero between steps)
-                     ticket=torch.zeros((), dtype=torch.int32, device=device),
-                     sumsq=torch.zeros((), dtype=torch.float64, device=device),
-                     sumsq_sharded=torch.zeros((), dtype=torch.float64, device=device),
-                     coef=torch.ones((), dtype=torch.float32, device=device),
-                     norm=torch.zeros((), dtype=torch.float32, device=device),
-                     # (block partials of the deterministic sums: written before they are read)
-                     partials=torch.empty(int(L.load().mrgcn_sumsq_det_workspace()) // 8, dtype=torch.float64,
-                                          device=device))
-            self._scratch[device] = s
-        return s
-
-    def _index_rows_ok(self, p, ent) -> bool:
-        """A compact-rows gradient (kind "index") may skip the rows outside its index set only while those rows hold no
-        moments: checked once per optimizer state (a loaded state, dense steps in between), with one host read."""
-        owner = (id(self), self._state_gen)
-        if ent.get("seeded_for") != owner:
-            if p.is_cuda and torch.cuda.is_current_stream_capturing():
-                raise L.MrgcnError("ClipAdam: the first step with a compact literal gradient looks at the moments "
-                                   "(a host read): run one step before capturing")
-            st = self.state.get(p)
-            ok = p.dim() == 2 and p.is_contiguous() and p.shape[1] % 4 == 0
-            if ok and st and int(st.get("step", 0)) > 0:
-                outside = torch.ones(p.shape[0], dtype=torch.bool, device=p.device)
-                outside[ent["index"]] = False
-                ok = not bool(((st["exp_avg"][outside] != 0).any() | (st["exp_avg_sq"][outside] != 0).any()).item())
-            ent["dense_only"] = not ok
-            ent["seeded_for"] = owner
-        return not ent["dense_only"]
-
-    def _new_state(self, p):
-        st = self.state[p]
-        if not st:
-            st["step"] = 0
-            st["exp_avg"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
-            st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
-        return st
-
-    def _dev_step_entry(self, key, device):
-        """The device step counter and bias corrections of one (beta1, beta2) (capturable)."""
-        ent = self._dev_step.get(key)
-        if ent is None:
-            # seeded with the steps already taken (a loaded checkpoint, eager steps before)
-            t0 = max([int(self.state[p].get("step", 0)) for g2 in self.param_groups
-                      if tuple(float(b) for b in g2["betas"]) == key for p in g2["params"]
-                      if self.state.get(p)] or [0])
-            ent = (torch.full((), t0, dtype=torch.int64, device=device),
-                   torch.ones(2, dtype=torch.float32, device=device))
-            self._dev_step[key] = ent
-        return ent
-
-    def init_state(self):
-        """What the first `step()` would allocate, without taking it: zero moments for every parameter that requires
-        a gradient and, with `capturable`, the device step counters — so that a DeviceEarlyStop built in front of the
-        first epoch has every buffer it snapshots.  A parameter that then never receives a gradient keeps its zero
-        moments (and an entry in `state_dict()`) where `step()` alone would have left it without state; its value is
-        the same either way."""
-        for group in self.param_groups:
-            for p in group["params"]:
-                if p.requires_grad:
-                    self._new_state(p)
-            if self.capturable and group["params"]:
-                self._dev_step_entry(tuple(float(b) for b in group["betas"]), group["params"][0].device)
-
-    def _reg_rows_ok(self, ent) -> bool:
-        """Can this row-sparse entry take the regularised row update (mrgcn_support_adam_rows_reg_f32)?  It needs the
-        backward to have run on a gradient support and a shape the kernels take."""
-        fz = ent.get("fused")
-        return (fz is not None and fz.get("sup") is not None and self._dist is None
-                and int(L.load().mrgcn_support_reg_norm_workspace(fz["sup"].handle, fz["B"], fz["F"])) >= 0)
-
-    @torch.no_grad()
-    def step(self, closure=None, *, l1_lambda=0.0, l2_lambda=0.0, reg_params=None):
-        """`l1_lambda` / `l2_lambda`: the reference's weight penalty (node_classification.py:172-188) on the parameters
-        the CALLER LEFT OUT of the penalty it put into the loss — `reg_params`, by default the node-major tables that
-        carry a row-sparse gradient.  The optimizer owns their penalty whichever route they end up on: r(p) =
-        l1 sign(p) + 2 l2 p joins the gradient in front of this step's clip (`max_norm`), the value
-        l1 sum|p| + l2 sum p^2 is left in `self.reg_loss` (a float32 device scalar; None when nothing was owned)."""
-        lib = L.load()
-        l1, l2 = float(l1_lambda), float(l2_lambda)
-        pen = l1 > 0 or l2 > 0
-        owned = {id(p) for p in reg_params} if (pen and reg_params is not None) else None
-        self.reg_loss = None
-        rowsparse = []  # gradient left on the parameter in row-sparse form (functional._ROW_SPARSE)
-        indexed = []    # ... as compact rows of a literal operand (functional._SpmmLiteral: kind "index")
-        regular = set()  # ids of the row-sparse entries that take the regularised update (decay and / or penalty)
-        torch_pen = []   # owned parameters on the dense route: their penalty is added with torch ops
-        for g in self.param_groups:
-            wd = float(g["weight_decay"])
-            for p in g["params"]:
-                ent = pop_row_grad(p)
-                if owned is not None:
-                    mine = id(p) in owned
-                else:
-                    mine = (pen and ent is not None and ent.get("kind") != "index"
-                            and getattr(p, "_mrgcn_node_major", False))
-                if ent is None:
-                    if mine:
-                        torch_pen.append(p)
-                    continue
-                if ent.get("kind") == "index":
-                    if (p.grad is None and wd == 0.0 and not mine and self._dist is None
-                            and self._index_rows_ok(p, ent)):
-                        indexed.append((g, p, ent))
-                        continue
-                    merge_row_grad(p, ent)
-                elif p.grad is None and wd == 0.0 and not mine:
-                    rowsparse.append((g, p, ent))
-                    continue
-                elif p.grad is None and self._reg_rows_ok(ent):
-                    # every node block moves (decay, penalty): the row update over all N nodes, the loss's gradient
-                    # still rebuilt from the support's dM
-                    rowsparse.append((g, p, ent))
-                    regular.add(id(ent))
-                    if mine:
-                        ent["pen"] = True
-                    continue
-                else:  # another term left a dense gradient on the same parameter (a regulariser): one dense step
-                    merge_row_grad(p, ent)
-                if mine:
-                    torch_pen.append(p)
-        for p in torch_pen:  # (no support, a shape outside the kernels, a dense gradient: today's route plus the penalty)
-            r = None
-            if l1 > 0:
-                r = l1 * torch.sign(p)
-                self.reg_loss = l1 * p.abs().sum() + (0 if self.reg_loss is None else self.reg_loss)
-            if l2 > 0:
-                r = (2.0 * l2) * p if r is None else r.add_(p, alpha=2.0 * l2)
-                self.reg_loss = l2 * (p * p).sum() + (0 if self.reg_loss is None else self.reg_loss)
-            p.grad = r if p.grad is None else p.grad.add_(r)
-        live = [(g, p) for g in self.param_groups for p in g["params"] if p.grad is not None]
-        if not live and not rowsparse and not indexed:
-            return None
-        device = (live[0][1] if live else (rowsparse or indexed)[0][1]).device
-        if not all(p.device == device for _, p in live):
-            raise L.MrgcnError("ClipAdam: all parameters must live on one GPU")
-        sc = self._dev_scratch(device)
-        s = _stream(device)
-        use_clip = self.max_norm is not None and self.max_norm > 0
-        # (contiguous and 16-byte aligned, as the vector kernels read them: a gradient that is a view into a flat
-        # bucket at an odd offset is copied)
-        grads = [p.grad if (p.grad.is_contiguous() and p.grad.data_ptr() % 16 == 0) else p.grad.contiguous().clone()
-                 for _, p in live]
-        # The dense parameters besides the node table are a handful of small tensors: their squared norms, the
-        # row-sparse gradients' norms, the clip coefficient and the device step counter take ONE launch
-        # (mrgcn_sumsq_clip_multi_f32) and their Adam updates another (mrgcn_adam_step_multi_f32) when every group
-        # shares (beta1, beta2, eps) — the reference's groups do (tasks/utils.py:8-45 vary lr / weight_decay only).
-        hyper = {(float(g["betas"][0]), float(g["betas"][1]), float(g["eps"])) for g, _ in live} | \
-                {(float(g["betas"][0]), float(g["betas"][1]), float(g["eps"])) for g, _, _ in rowsparse + indexed}
-        small = [i for i, g in enumerate(grads) if g.numel() <= _MULTI_MAX_NUMEL]
-        # (16 tensors per launch: a model with more — an MRGCN with encoders has ~40 — takes a few launches, not 2 x 40)
-        multi = (_MULTI and self._dist is None and len(hyper) == 1 and len(small) >= 1 and len(rowsparse) <= 16)
-        # torch.use_deterministic_algorithms(True): every squared norm summed in block order (the _det twins)
-        det = torch.are_deterministic_algorithms_enabled()
-        if det:
-            bump("deterministic.sumsq")
-        dp, dt = sc["partials"].data_ptr(), sc["ticket"].data_ptr()
-        # the penalty's share of the norm: one read of the table in front of the clip (weight decay needs none: torch
-        # adds wd . p inside Adam.step, after the clip) — sum (g + r)^2 then stands where the entry's ||g||^2 would
-        norm_of = {}
-        with torch.cuda.device(device):
-            for _, p, ent in rowsparse:
-                if not ent.pop("pen", False):
-                    continue
-                fz = ent["fused"]
-                nbytes = int(lib.mrgcn_support_reg_norm_workspace(fz["sup"].handle, fz["B"], fz["F"]))
-                ws = fz["sup"].workspace(("reg_norm", fz["B"], fz["F"]), (nbytes + 3) // 4)
-                out3 = ent.get("reg_sums")
-                if out3 is None or out3.device != device:
-                    out3 = ent["reg_sums"] = torch.empty(3, dtype=torch.float64, device=device)
-                L.check(lib.mrgcn_support_reg_norm_f32(
-                    fz["sup"].handle, fz["dM"].data_ptr(), fz["ld"], fz["comp"].data_ptr(), fz["B"], fz["F"],
-                    p.data_ptr(), l1, l2, out3.data_ptr(), ws.data_ptr(), nbytes, s), "mrgcn_support_reg_norm_f32")
-                norm_of[id(ent)] = out3
-                term = (l1 * out3[1] + l2 * out3[2]).float()
-                self.reg_loss = term if self.reg_loss is None else self.reg_loss + term
-        if self.reg_loss is not None and self.reg_loss.dtype != torch.float32:
-            self.reg_loss = self.reg_loss.float()
-
-        def row_sumsq(ent):  # the squared norm this entry brings to the clip (a 0-dim / 1-element double view)
-            o = norm_of.get(id(ent))
-            return ent["sumsq"] if o is None else o[:1]
-
-        def sumsq_accum(ptr, numel, acc):
-            if det:
-                L.check(lib.mrgcn_sumsq_accum_det_f32(ptr, numel, acc, dp, dt, s), "mrgcn_sumsq_accum_det_f32")
-            else:
-                L.check(lib.mrgcn_sumsq_accum_f32(ptr, numel, acc, s), "mrgcn_sumsq_accum_f32")
-        with torch.cuda.device(device):
-            bias = {}
-            if self.capturable:
-                for group in self.param_groups:  # one device counter per distinct (beta1, beta2)
-                    key = tuple(float(b) for b in group["betas"])
-                    if key in bias:
-                        continue
-                    bias[key] = self._dev_step_entry(key, device)[1]
-            if multi:
-                try:
-                    b1m, b2m, _ = next(iter(hyper))
-                    for i, g in enumerate(grads):
-                        if i not in small:  # (a large dense gradient: its own streaming pass into the same accumulator)
-                            sumsq_accum(g.data_ptr(), g.numel(), sc["accum"].data_ptr())
-                    for c0 in range(0, len(small) - 16, 16) if len(small) > 16 else ():
-                        part = small[c0:c0 + 16]
-                        gp_, gn_ = ((C.c_void_p * len(part))(*[grads[i].data_ptr() for i in part]),
-                                    (C.c_int64 * len(part))(*[grads[i].numel() for i in part]))
-                        if det:
-                            L.check(lib.mrgcn_sumsq_accum_multi_det_f32(len(part), gp_, gn_, sc["accum"].data_ptr(), dp,
-                                                                        dt, s), "mrgcn_sumsq_accum_multi_det_f32")
-                        else:
-                            L.check(lib.mrgcn_sumsq_accum_multi_f32(len(part), gp_, gn_, sc["accum"].data_ptr(), s),
-                                    "mrgcn_sumsq_accum_multi_f32")
-                    last = small[(len(small) - 1) // 16 * 16:]   # the launch that also closes the norm
-                    closing = [grads[i] for i in last]
-                    for _, _, ent in indexed:  # (a compact gradient: in the closing launch while it has room for it)
-                        if len(closing) < 16 and ent["g"].numel() <= 4 * _MULTI_MAX_NUMEL:
-                            closing.append(ent["g"])
-                        else:
-                            sumsq_accum(ent["g"].data_ptr(), ent["g"].numel(), sc["accum"].data_ptr())
-                    gp = (C.c_void_p * len(closing))(*[g.data_ptr() for g in closing])
-                    gn = (C.c_int64 * len(closing))(*[g.numel() for g in closing])
-                    ex = (C.c_void_p * max(len(rowsparse), 1))(*[row_sumsq(ent).data_ptr() for _, _, ent in rowsparse])
-                    dstep = self._dev_step.get((b1m, b2m)) if self.capturable else None
-                    args = (len(closing), gp, gn, len(rowsparse), ex, sc["accum"].data_ptr(), sc["ticket"].data_ptr(),
-                            float(self.max_norm) if use_clip else 0.0, sc["sumsq"].data_ptr(), sc["coef"].data_ptr(),
-                            sc["norm"].data_ptr(), dstep[0].data_ptr() if dstep else 0, b1m, b2m,
-                            dstep[1].data_ptr() if dstep else 0)
-                    if det:
-                        L.check(lib.mrgcn_sumsq_clip_multi_det_f32(*args, dp, s), "mrgcn_sumsq_clip_multi_det_f32")
-                    else:
-                        L.check(lib.mrgcn_sumsq_clip_multi_f32(*args, s), "mrgcn_sumsq_clip_multi_f32")
-                    for key, bc_t in bias.items():  # groups with other betas (no gradient this step): their counters too
-                        if key != (b1m, b2m):
-                            L.check(lib.mrgcn_adam_bias_f32(self._dev_step[key][0].data_ptr(), key[0], key[1],
-                                                            bc_t.data_ptr(), s), "mrgcn_adam_bias_f32")
-                except BaseException:
-                    # the scratch words are self-cleaning only when the closing launch ran: a failure in between must not
-                    # leak a partial sum into every later norm
-                    sc["accum"].zero_()
-                    sc["ticket"].zero_()
-                    raise
-            else:
-                sc["sumsq"].zero_()
-                sc["sumsq_sharded"].zero_()
-                sharded = self._dist[1] if self._dist else ()
-                for (_, p), g in zip(live, grads):
-                    acc = sc["sumsq_sharded"] if id(p) in sharded else sc["sumsq"]
-                    sumsq_accum(g.data_ptr(), g.numel(), acc.data_ptr())
-                for _, p, ent in rowsparse:  # ||g||^2 came for free with the gradient
-                    (sc["sumsq_sharded"] if id(p) in sharded else sc["sumsq"]).add_(row_sumsq(ent).reshape(()))
-                for _, _, ent in indexed:
-                    sumsq_accum(ent["g"].data_ptr(), ent["g"].numel(), sc["sumsq"].data_ptr())
-                if self._dist:
-                    from .partition import all_reduce_sum_
-                    all_reduce_sum_(sc["sumsq_sharded"], self._dist[0])
-                sc["sumsq"] += sc["sumsq_sharded"]
-                if use_clip:
-                    L.check(lib.mrgcn_clip_coef_f32(sc["sumsq"].data_ptr(), float(self.max_norm),
-                                                    sc["coef"].data_ptr(), sc["norm"].data_ptr(), s),
-                            "mrgcn_clip_coef_f32")
-                for key, bc_t in bias.items():
-                    L.check(lib.mrgcn_adam_bias_f32(self._dev_step[key][0].data_ptr(), key[0], key[1], bc_t.data_ptr(), s),
-                            "mrgcn_adam_bias_f32")
-            coef_ptr = step_coef_ptr = sc["coef"].data_ptr() if use_clip else 0
-            for group, p, ent in rowsparse:
-                st = self._new_state(p)
-                owner = (id(self), self._state_gen)
-                if ent.get("seeded_for") != owner:
-                    # these flags have not seen this optimizer's moments yet (a loaded or dense-built state,
-                    # a fresh gradient entry): every node that holds a non-zero moment counts as `ever`
-                    ent["ever"].zero_()
-                    ent["ever_in"] = None      # which row set the flags lie inside: None = none set yet
-                    if st["step"] > 0:   # (a parameter that never took a step has zero moments)
-                        nz = (st["exp_avg"] != 0).flatten(1).any(1) | (st["exp_avg_sq"] != 0).flatten(1).any(1)
-                        ent["ever"] |= nz.to(torch.uint8)
-                        ent["ever_in"] = "any"  # (moments from steps this entry has not seen)
-                    ent["seeded_for"] = owner
-                st["step"] += 1
-                b1, b2 = group["betas"]
-                bc = bias[(float(b1), float(b2))].data_ptr() if self.capturable else 0
-                nrows = p.shape[0]
-                fz = ent.get("fused")
-                # the coefficient of a clip that ran between backward and step (mrgcn_amd.optim.clip_grad_norm_)
-                pre = ent.pop("coef", None)
-                coef_ptr = pre.data_ptr() if pre is not None else step_coef_ptr
-                if fz is not None and fz.get("comp_version") is not None and fz["comp"]._version != fz["comp_version"]:
-                    raise L.MrgcnError("row-sparse weight_I gradient: weight_I_comp was modified between backward and "
-                                       "the node table's update (the fused update re-reads it)")
-                if id(ent) in regular:
-                    # all N nodes, gg = (g + r(p)) . coef + wd . p; r only where this optimizer owns the penalty.
-                    # Every node holds moments afterwards: a later plain step must look outside its support.
-                    mine = id(ent) in norm_of
-                    ent["ever_in"] = "any"
-                    bump("adam.reg")
-                    L.check(lib.mrgcn_support_adam_rows_reg_f32(
-                        fz["sup"].handle, fz["dM"].data_ptr(), fz["ld"], fz["comp"].data_ptr(), fz["B"], fz["F"],
-                        p.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(), ent["ever"].data_ptr(),
-                        float(group["lr"]), float(b1), float(b2), float(group["eps"]), float(group["weight_decay"]),
-                        l1 if mine else 0.0, l2 if mine else 0.0, int(st["step"]), bc, coef_ptr, s),
-                        "mrgcn_support_adam_rows_reg_f32")
-                    continue
-                if fz is not None and fz.get("sup") is not None:  # the same on the gradient support of the label set
-                    # every step since the flags were zeroed ran on THIS support: no node outside it holds moments and
-                    # the pass that looks for such nodes is not launched
-                    inside = ent.get("ever_in", "any")
-                    outside = 0 if (inside is None or inside is fz["sup"]) else 1
-                    ent["ever_in"] = fz["sup"] if not outside else "any"
-                    bump("adam.list")
-                    L.check(lib.mrgcn_support_adam_rows_fused_f32(
-                        fz["sup"].handle, fz["dM"].data_ptr(), fz["ld"], fz["comp"].data_ptr(), fz["B"], fz["F"],
-                        p.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(), ent["ever"].data_ptr(),
-                        float(group["lr"]), float(b1), float(b2), float(group["eps"]), int(st["step"]), bc, coef_ptr,
-                        outside, s), "mrgcn_support_adam_rows_fused_f32")
-                    continue
-                ent["ever_in"] = "any"
-                bump("adam.rows_fused" if fz is not None else "adam.rows")
-                if fz is not None:  # no gradient tensor: the blocks are rebuilt from dM inside the Adam pass
-                    L.check(lib.mrgcn_adam_step_rows_fused_f32(
-                        fz["plan"].handle, fz["dM"].data_ptr(), fz["ld"], fz["live"].data_ptr(), fz["comp"].data_ptr(),
-                        fz["B"], fz["F"], p.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(),
-                        ent["cur"].data_ptr(), ent["ever"].data_ptr(), float(group["lr"]), float(b1), float(b2),
-                        float(group["eps"]), int(st["step"]), bc, coef_ptr, s), "mrgcn_adam_step_rows_fused_f32")
-                    continue
-                L.check(lib.mrgcn_adam_step_rows_f32(
-                    p.data_ptr(), ent["g"].data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(),
-                    nrows, p.numel() // max(nrows, 1), ent["cur"].data_ptr(), ent["ever"].data_ptr(),
-                    float(group["lr"]), float(b1), float(b2), float(group["eps"]), int(st["step"]), bc, coef_ptr, s),
-                    "mrgcn_adam_step_rows_f32")
-            for group, p, ent in indexed:
-                st = self._new_state(p)
-                st["step"] += 1
-                b1, b2 = group["betas"]
-                bc = bias[(float(b1), float(b2))].data_ptr() if self.capturable else 0
-                pre = ent.pop("coef", None)
-                g = ent["g"]
-                bump("adam.index_rows")
-                L.check(lib.mrgcn_adam_step_index_rows_f32(
-                    p.data_ptr(), g.data_ptr(), g.stride(0), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(),
-                    ent["index_ptr"], g.shape[0], p.numel() // max(p.shape[0], 1), float(group["lr"]), float(b1),
-                    float(b2), float(group["eps"]), int(st["step"]), bc,
-                    pre.data_ptr() if pre is not None else step_coef_ptr, s), "mrgcn_adam_step_index_rows_f32")
-            coef_ptr = step_coef_ptr
-            for (group, p) in live:
-                st = self._new_state(p)
-                st["step"] += 1
-                rows = getattr(p, "_mrgcn_rows", None)
-                if rows is not None and not rows.get("dense_only"):
-                    rows["seeded_for"] = None  # a dense step may put moments where the row flags never looked
-            # (host-side bias corrections are per step count: the one launch needs the tensors to share it)
-            adam_multi = multi and (self.capturable or len({int(self.state[live[i][1]]["step"]) for i in small}) == 1)
-            if adam_multi:
-                b1m, b2m, epsm = next(iter(hyper))
-                for c0 in range(0, len(small), 16):
-                    sel = [(live[i][0], live[i][1], grads[i]) for i in small[c0:c0 + 16]]
-                    n = len(sel)
-                    arr = lambda ptrs: (C.c_void_p * n)(*ptrs)  # noqa: E731
-                    L.check(lib.mrgcn_adam_step_multi_f32(
-                        n, arr([p.data_ptr() for _, p, _ in sel]), arr([g.data_ptr() for _, _, g in sel]),
-                        arr([self.state[p]["exp_avg"].data_ptr() for _, p, _ in sel]),
-                        arr([self.state[p]["exp_avg_sq"].data_ptr() for _, p, _ in sel]),
-                        (C.c_int64 * n)(*[p.numel() for _, p, _ in sel]),
-                        (C.c_float * n)(*[float(g["lr"]) for g, _, _ in sel]),
-                        (C.c_float * n)(*[float(g["weight_decay"]) for g, _, _ in sel]), b1m, b2m, epsm,
-                        int(self.state[sel[0][1]]["step"]), bias[(b1m, b2m)].data_ptr() if self.capturable else 0,
-                        coef_ptr, s), "mrgcn_adam_step_multi_f32")
-            for i, ((group, p), g) in enumerate(zip(live, grads)):
-                if adam_multi and i in small:
-                    continue
-                st = self.state[p]
-                b1, b2 = group["betas"]
-                if self.capturable:
-                    L.check(lib.mrgcn_adam_step_dev_f32(
-                        p.data_ptr(), g.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(),
-                        p.numel(), float(group["lr"]), float(b1), float(b2), float(group["eps"]),
-                        float(group["weight_decay"]), bias[(float(b1), float(b2))].data_ptr(), coef_ptr, s),
-                        "mrgcn_adam_step_dev_f32")
-                    continue
-                L.check(lib.mrgcn_adam_step_f32(
-                    p.data_ptr(), g.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(),
-                    p.numel(), float(group["lr"]), float(b1), float(b2), float(group["eps"]),
-                    float(group["weight_decay"]), int(st["step"]), coef_ptr, s), "mrgcn_adam_step_f32")
-        # the kernels wrote through raw pointers: tell autograd (and every cache keyed by a tensor's version — the gate
-        # decisions of models.mrgcn) that these parameters changed, as an in-place torch update would
-        torch.autograd.graph.increment_version([p for _, p in live] + [p for _, p, _ in rowsparse + indexed])
-        return None
-
-    def last_grad_norm(self) -> float:
-        """Total gradient norm of the last step (synchronises)."""
-        dev = next(iter(self._scratch))
-        return float(self._scratch[dev]["norm"].item())
-
-
-def merge_row_grad(p, ent):
-    """Adds the gradient a row-sparse entry stands for (scaled by the clip coefficient it may carry) to `p.grad`."""
-    g = dense_from_rows(p, ent)
-    pre = ent.pop("coef", None)
-    if pre is not None:
-        g = g * pre
-    p.grad = g if p.grad is None else p.grad.add_(g)
 
 
 def weight_regularisation(model, l1_lambda: float = 0.0, l2_lambda: float = 0.0, skip=()):
