@@ -1137,6 +1137,30 @@ int64_t mrgcn_snapshot_block_bytes(void);
 int mrgcn_snapshot_if(const int32_t *flag, const mrgcn_copy_entry *table, int32_t n_entries, int64_t n_blocks,
                       int32_t restore, void *stream);
 
+/* ---- mini-batch node classification: one loss launch per batch, the epoch's means (csrc/nc_batches.hip) -----------
+ * Everything a training batch of node_classification.py:158-201 needs from its logits, in one pass over the rows
+ * logits[idx[i], :C]: `loss` = their mean cross-entropy (float64 sum in a fixed order, rounded once); `drows`
+ * (nullable: an evaluation batch, :229-256) = the compact gradient rows [n, C], bit for bit what
+ * mrgcn_softmax_xent_rows_f32 writes (mrgcn_softmax_xent_bwd_* consume them unchanged); `correct` = how many rows have
+ * their arg-max at target[i] and `labels` (nullable, [n]) the arg-max of each, by the rules of
+ * mrgcn_xent_eval_rows_f32: strict >, so the lowest class wins ties, and a target outside [0, C) poisons the loss
+ * (NaN) and reads nothing; `slot` (nullable) = two floats, {loss, (float)correct / (float)n}.
+ * n <= mrgcn_xent_train_eval_single_block_rows() is ONE launch and needs no workspace (NULL); more rows leave
+ * per-block parts in `workspace` (mrgcn_xent_train_eval_workspace() bytes, 16-byte aligned) that a second, one-thread
+ * launch adds in block order.  No atomics: equal inputs give equal bits.  idx may repeat rows; ld >= C. */
+int64_t mrgcn_xent_train_eval_workspace(void);
+int64_t mrgcn_xent_train_eval_single_block_rows(void);
+int mrgcn_xent_train_eval_rows_f32(const float *logits, int64_t ld, int32_t C, const int64_t *idx,
+                                   const int64_t *target, int64_t n, float *loss, float *drows, int64_t *correct,
+                                   int64_t *labels, float *slot, void *workspace, void *stream);
+/* The epoch's row of node_classification.py:203-204,:253-254 from the batches' slots ({loss, acc} pairs as the launch
+ * above writes them, contiguous [n, 2]): row4 = {mean train loss, mean train acc, mean valid loss, mean valid acc},
+ * each the float64 sum of its slots IN SLOT ORDER divided by the count and rounded once to float32 — unweighted means
+ * over batches, as np.mean of the reference's lists.  n_valid == 0 (valid_slots may be NULL) writes -1 for both
+ * validation values.  One thread; n_train > 0. */
+int mrgcn_batch_means_f32(const float *train_slots, int64_t n_train, const float *valid_slots, int64_t n_valid,
+                          float *row4, void *stream);
+
 /* ---- timing helpers (HIP events on the caller's stream; used by bench.py) ------ */
 int mrgcn_event_create(void **event);
 int mrgcn_event_destroy(void *event);

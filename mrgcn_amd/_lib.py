@@ -283,6 +283,10 @@ SIGNATURES = {
     "mrgcn_early_stop_record_row": (C.c_int, [_p, _p, C.c_double, _i32, _p, _i32, _p, _i64, _p]),
     "mrgcn_snapshot_block_bytes": (C.c_int64, []),
     "mrgcn_snapshot_if": (C.c_int, [_p, _p, _i32, _i64, _i32, _p]),
+    "mrgcn_xent_train_eval_workspace": (C.c_int64, []),
+    "mrgcn_xent_train_eval_single_block_rows": (C.c_int64, []),
+    "mrgcn_xent_train_eval_rows_f32": (C.c_int, [_p, _i64, _i32, _p, _p, _i64, _p, _p, _p, _p, _p, _p, _p]),
+    "mrgcn_batch_means_f32": (C.c_int, [_p, _i64, _p, _i64, _p, _p]),
     "mrgcn_event_create": (C.c_int, [C.POINTER(_p)]),
     "mrgcn_event_destroy": (C.c_int, [_p]),
     "mrgcn_event_record": (C.c_int, [_p, _p]),

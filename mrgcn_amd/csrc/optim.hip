@@ -9,6 +9,7 @@
 
 #include "common.hpp"
 #include "config.hpp"
+#include "xent_row.hpp"
 
 namespace mrgcn {
 namespace {
@@ -341,7 +342,6 @@ __global__ void k_adam(float *__restrict__ p, const float *__restrict__ g, float
 // The same with the gradient kept COMPACT: drows[i, :] = d loss / d logits[idx[i], :] (n x C) — the dense N x C
 // gradient (73 MB at the AM shape, all zeros but n rows) is only formed by the backward (k_xent_scatter), scaled by
 // the upstream gradient on the way: no dense multiply, and the rows that hold anything are known (row flags).
-using xf4 = __attribute__((ext_vector_type(4))) float;
 __global__ __launch_bounds__(1024) void k_xent_rows(const float *__restrict__ logits, int64_t ld, int C,
                                                     const int64_t *__restrict__ idx, const int64_t *__restrict__ target,
                                                     int64_t n, float *__restrict__ loss, float *__restrict__ drows,
@@ -360,56 +360,9 @@ __global__ __launch_bounds__(1024) void k_xent_rows(const float *__restrict__ lo
       row_n = idx[nx];
       t_n = target[nx];
     }
-    if (C <= 16) {  // the row in registers: all its loads in flight at once (a loop over z[c] waits for each)
-      float zz[16];
-      if (C >= 4) {
-        // four 16-byte pieces per row (dword-aligned addresses: rows may be 44 bytes), each starting inside the row
-        // (min(4p, C - 4)) and shifted into place — a quarter of the load instructions of sixteen 4-byte loads: the one
-        // block's CU is bound by its address unit when the rows are scattered (10 000 labelled rows: 155 us)
-        xf4 v[4];
-#pragma unroll
-        for (int p = 0; p < 4; ++p) v[p] = *reinterpret_cast<const xf4 *>(z + (4 * p < C - 4 ? 4 * p : C - 4));
-#pragma unroll
-        for (int p = 0; p < 4; ++p) {
-          const int shift = 4 * p - (4 * p < C - 4 ? 4 * p : C - 4);  // (wave uniform; > 3: the whole piece lies past C)
-          const xf4 w = v[p];
-          zz[4 * p] = shift == 0 ? w.x : shift == 1 ? w.y : shift == 2 ? w.z : w.w;
-          zz[4 * p + 1] = shift == 0 ? w.y : shift == 1 ? w.z : w.w;
-          zz[4 * p + 2] = shift == 0 ? w.z : w.w;
-          zz[4 * p + 3] = w.w;
-        }
-      } else {
-#pragma unroll
-        for (int c = 0; c < 16; ++c) zz[c] = z[c < C ? c : C - 1];  // (unconditional loads at clamped addresses:
-      }                                                             //  a load behind `c < C` waits for itself)
-#pragma unroll
-      for (int c = 0; c < 16; ++c) zz[c] = c < C ? zz[c] : -INFINITY;
-      float mx = zz[0];
-#pragma unroll
-      for (int c = 1; c < 16; ++c) mx = fmaxf(mx, zz[c]);
-      float se = 0.f, zt = 0.f;
-#pragma unroll
-      for (int c = 0; c < 16; ++c) {
-        if (c < C) se += expf(zz[c] - mx);
-        if (c == t) zt = zz[c];
-      }
-      const float lse = logf(se) + mx;
-      my += (lse - zt) * inv_n;
-      if (drows) {
-#pragma unroll
-        for (int c = 0; c < 16; ++c)
-          if (c < C) drows[i * C + c] = (expf(zz[c] - lse) - (c == t ? 1.f : 0.f)) * inv_n;
-      }
-      continue;
-    }
-    float mx = z[0];
-    for (int c = 1; c < C; ++c) mx = fmaxf(mx, z[c]);
-    float se = 0.f;
-    for (int c = 0; c < C; ++c) se += expf(z[c] - mx);
-    const float lse = logf(se) + mx;
-    my += (lse - z[t]) * inv_n;
-    if (drows)
-      for (int c = 0; c < C; ++c) drows[i * C + c] = (expf(z[c] - lse) - (c == t ? 1.f : 0.f)) * inv_n;
+    // (the row's loads, softmax and gradient row: xent_row.hpp, shared with nc_batches.hip)
+    const XentRow r = xent_row(z, C, t, inv_n, drows ? drows + i * C : nullptr);
+    my += (r.lse - r.zt) * inv_n;
   }
   // block sum over up to 16 waves
   __shared__ float s_part[16];

@@ -94,6 +94,12 @@ def categorical_crossentropy(Y_hat: torch.Tensor, idx: torch.Tensor, targets: to
     """`idx`, `targets`: int64 device tensors (the `Y.nonzero()` pair of the reference).  `sole_consumer`: nothing
     but this loss reads `Y_hat` (train_step): when `Y_hat` comes straight out of a layer whose backward goes by the
     row flags, the gradient's unlabelled rows are then not even zero-filled."""
+    flags, sparse = _loss_route(Y_hat, idx, targets, sole_consumer)
+    return _SoftmaxXent.apply(Y_hat, idx.contiguous(), targets.contiguous(), flags, sparse)
+
+
+def _loss_route(Y_hat, idx, targets, sole_consumer):
+    """(flags, sparse) of `_SoftmaxXent` for these logits and labels, and the counter of the route taken."""
     assert idx.dtype == torch.int64 and targets.dtype == torch.int64
     from .functional import _SUPPORT
     flags = sparse = None
@@ -104,7 +110,7 @@ def categorical_crossentropy(Y_hat: torch.Tensor, idx: torch.Tensor, targets: to
             sparse = bool(sole_consumer and ent[1] and getattr(Y_hat, "_mrgcn_sparse_grad_ok", False)
                           and Y_hat.grad_fn is not None and type(Y_hat.grad_fn).__name__ == "_RgcnLayerBackward")
     bump("loss.sparse_rows" if sparse else "loss.flagged" if flags is not None else "loss.plain")
-    return _SoftmaxXent.apply(Y_hat, idx.contiguous(), targets.contiguous(), flags, sparse)
+    return flags, sparse
 
 
 def categorical_accuracy(Y_hat, idx, targets):
@@ -146,18 +152,23 @@ def _ones_like_loss(loss):
 
 
 def train_step(model, forward_fn, idx, targets, optimizer, l1_lambda: float = 0.0, l2_lambda: float = 0.0,
-               row_sparse=None):
+               row_sparse=None, loss_fn=None):
     """One full-batch epoch.  `forward_fn()` returns the logits (e.g. `lambda: model(batch)`).
     Returns the loss as a device scalar (no host sync).  `row_sparse`: None = skip the rows of a node-major
     weight_I's gradient / Adam update that carry no gradient whenever that is exact (ClipAdam — `weight_I.grad`
     stays None for such a step, the gradient travels on the parameter; under weight decay or an L1 / L2 penalty the
     update visits every node but still rebuilds the loss's gradient from the support, and the returned loss includes
     the penalty the optimizer computed: DESIGN section 14); False = always the dense gradient in `.grad` and the dense
-    Adam kernel."""
+    Adam kernel.  `loss_fn(logits, idx, targets)`: another loss of the same contract in place of
+    `categorical_crossentropy(..., sole_consumer=True)` (tasks.node_classification: the batch's loss with its accuracy
+    out of the same launch)."""
     params = [p for g in optimizer.param_groups for p in g["params"]]
     clear_row_grads(params)
     logits = forward_fn()
-    loss = categorical_crossentropy(logits, idx, targets, sole_consumer=True)
+    if loss_fn is None:
+        loss = categorical_crossentropy(logits, idx, targets, sole_consumer=True)
+    else:
+        loss = loss_fn(logits, idx, targets)
     reg = l1_lambda > 0 or l2_lambda > 0
     # weight_I's gradient may stay unwritten where no node has any when the optimizer is the one that
     # knows how to read it.  Under weight decay or a penalty every node block moves, which the regularised row update

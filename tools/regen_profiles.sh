@@ -88,6 +88,9 @@ python3 tools/weight_reg_probe.py ${WEIGHT_REG_PARENT_JSON:+--parent $WEIGHT_REG
 # (10g) link prediction's run loop on the device: rank_both against the two rank calls, the replayed evaluating epoch
 # against the host loop, the replayed training epoch against GraphedStep
 python3 tools/lp_fit_probe.py --out $o/lp_fit_probe.json > $o/lp_fit_probe.txt 2> $o/lp_fit_probe.err
+# (10h) the mini-batch node-classification run loop at the AM/4 shape, batches of 1 024 and of 64: the replayed epoch, the
+# eager device epoch, the loop as the reference writes it, the fused loss launch against the two it replaces
+python3 tools/nc_minibatch_probe.py --out $o/nc_minibatch_probe.json > $o/nc_minibatch_probe.txt 2> $o/nc_minibatch_probe.err
 hipcc -O3 --offload-arch=gfx950 -std=c++17 tools/lab/copy_lab.hip -o /tmp/copy_lab 2>/dev/null && /tmp/copy_lab > $o/copy_lab.txt 2>&1
 python3 tools/lab/spmm_hot_lab.py > $o/spmm_hot_lab.txt 2>&1
 # the CPU suite last: the tree these artefacts describe is green
