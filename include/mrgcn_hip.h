@@ -1161,6 +1161,36 @@ int mrgcn_xent_train_eval_rows_f32(const float *logits, int64_t ld, int32_t C, c
 int mrgcn_batch_means_f32(const float *train_slots, int64_t n_train, const float *valid_slots, int64_t n_valid,
                           float *row4, void *stream);
 
+/* ---- mini-batch link prediction: one batch's ranks and metrics, the epoch's means (csrc/lp_batches.hip) -----------
+ * test_model of ONE batch (link_prediction.py:375-422 around compute_ranks_fast :593-643 and filter_scores_ :667-689):
+ * the batch's facts (int64 [num_facts, 3], batch-local ids, num_facts >= 1) ranked against the batch's own table
+ * E [num_nodes, H], raw and — with the four arrays of the filter lists, all or none — filtered, from ONE pass over
+ * the candidate scores.  ranks_raw / ranks_flt (nullable, int64 [2 num_facts]: tail ranks, then head ranks) are bit
+ * for bit what mrgcn_distmult_ranks writes without / with the lists: the same float32 score body (sequential over h,
+ * nothing contracted), the rule rank = greater + round_half_even((ties - 1) / 2) + 1, and the reference's quirk that
+ * facts at positions >= num_nodes stay unscored (:611-625: truth 0, every candidate ties).  slot [8] = raw mrr, hits@1,
+ * hits@3, hits@10, then the same four filtered (-1 each without lists, as test_model reports them, :383-389), each
+ * half what mrgcn_rank_metrics gives for that rank vector with one part (:403-407): a float64 sum in that kernel's
+ * order, rounded once.  Three launches (transpose + true scores; a block owns eight facts across all candidate tiles,
+ * counts as integers in LDS, and writes its own ranks; one wave per rank type for the metrics), stream ordered, no
+ * host memory, capturable, no float atomics: equal inputs give equal bits.  `workspace`: caller owned, 8-byte
+ * aligned, mrgcn_distmult_batch_eval_workspace(num_nodes, H, num_facts) bytes (-1 for sizes it does not take). */
+int64_t mrgcn_distmult_batch_eval_workspace(int64_t num_nodes, int32_t H, int64_t num_facts);
+int mrgcn_distmult_batch_eval(const float *E, int64_t ldE, int64_t num_nodes, const float *Rel, int64_t ldR, int32_t H,
+                              const int64_t *triples, int64_t num_facts, const int64_t *tail_ptr,
+                              const int32_t *tail_idx, const int64_t *head_ptr, const int32_t *head_idx,
+                              void *workspace, int64_t workspace_bytes, int64_t *ranks_raw, int64_t *ranks_flt,
+                              float *slot, void *stream);
+/* The epoch's row of the mini-batch loop from the batches' slots: row17[0] = np.mean(loss_lst) (:331) over the
+ * n_loss contiguous floats of loss_slots; row17[1:9] / row17[9:17] = per column the unweighted mean over the n_train /
+ * n_valid batches of their [n, 8] slots as mrgcn_distmult_batch_eval writes them (test_model :416-419; a column of -1
+ * stays -1, as np.mean of the reference's list of -1).  Each value is the float64 sum of its slots IN SLOT ORDER
+ * divided by the count and rounded once to float32; one thread.  score_out (nullable) = (float)(1 - mean validation
+ * raw mrr), the score train_model records (:363), taken from the float64 mean.  A count of 0 (its pointer may be
+ * NULL) leaves that set's columns — and, for n_valid, score_out — unwritten. */
+int mrgcn_lp_batch_means_f32(const float *loss_slots, int64_t n_loss, const float *train_slots, int64_t n_train,
+                             const float *valid_slots, int64_t n_valid, float *row17, float *score_out, void *stream);
+
 /* ---- timing helpers (HIP events on the caller's stream; used by bench.py) ------ */
 int mrgcn_event_create(void **event);
 int mrgcn_event_destroy(void *event);

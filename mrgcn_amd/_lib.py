@@ -287,6 +287,10 @@ SIGNATURES = {
     "mrgcn_xent_train_eval_single_block_rows": (C.c_int64, []),
     "mrgcn_xent_train_eval_rows_f32": (C.c_int, [_p, _i64, _i32, _p, _p, _i64, _p, _p, _p, _p, _p, _p, _p]),
     "mrgcn_batch_means_f32": (C.c_int, [_p, _i64, _p, _i64, _p, _p]),
+    "mrgcn_distmult_batch_eval_workspace": (C.c_int64, [_i64, _i32, _i64]),
+    "mrgcn_distmult_batch_eval": (C.c_int, [_p, _i64, _i64, _p, _i64, _i32, _p, _i64, _p, _p, _p, _p, _p, _i64, _p, _p,
+                                            _p, _p]),
+    "mrgcn_lp_batch_means_f32": (C.c_int, [_p, _i64, _p, _i64, _p, _i64, _p, _p, _p]),
     "mrgcn_event_create": (C.c_int, [C.POINTER(_p)]),
     "mrgcn_event_destroy": (C.c_int, [_p]),
     "mrgcn_event_record": (C.c_int, [_p, _p]),

@@ -1,6 +1,7 @@
 // The DistMult candidate scores shared by the rank kernel (distmult.hip: k_rank_counts) and the top-k kernel
 // (distmult_topk.hip: k_topk_tiles): ONE body, so that a fact that "ranks 3" sits at position 3 of the list
 // predict_topk returns — the same float32 products in the same order, bit for bit.
+// lp_score_tiles below is the same sum for several candidates per thread (lp_batches.hip: a batch's own small table).
 #pragma once
 
 #include "common.hpp"
@@ -88,6 +89,111 @@ __device__ __forceinline__ void lp_score_tile(const float *__restrict__ Et, int6
         }
       }
     }
+  }
+}
+
+// One h step of lp_score_tile's sum for CT candidates (values e[j]) and the block's kLpFB pairs: the same float32
+// operations in the same order.
+template <int CT, bool HEAD>
+__device__ __forceinline__ void lp_score_step(const float (*s_a)[kLpHT], const float (*s_b)[kLpHT], int h,
+                                              const float (&e)[CT], float (&acc)[CT][kLpFB]) {
+#pragma clang fp contract(off)
+#pragma unroll
+  for (int i = 0; i < kLpFB; ++i) {
+    const float a = s_a[i][h];
+    if (HEAD) {
+      const float b = s_b[i][h];
+#pragma unroll
+      for (int j = 0; j < CT; ++j) {
+        const float ep = e[j] * a;
+        const float epo = ep * b;
+        acc[j][i] = acc[j][i] + epo;
+      }
+    } else {
+#pragma unroll
+      for (int j = 0; j < CT; ++j) {
+        const float spe = a * e[j];
+        acc[j][i] = acc[j][i] + spe;
+      }
+    }
+  }
+}
+
+constexpr int kLpHC = 16;   // h values of a candidate fetched ahead of their use (lp_score_tiles)
+
+// The hn staged h values of one h tile for CT candidates: the candidates' values of kLpHC consecutive h are loaded
+// first, straight-line at clamped positions (kLpHC * CT loads in flight: a load per step behind its use pays a full
+// memory latency per h), then added in rising h.
+template <int CT, bool HEAD>
+__device__ __forceinline__ void lp_score_htile(const float *__restrict__ row, int64_t N, int hn,
+                                               const int64_t (&cc)[CT], const float (*s_a)[kLpHT],
+                                               const float (*s_b)[kLpHT], float (&acc)[CT][kLpFB]) {
+  for (int hc = 0; hc < hn; hc += kLpHC) {
+    float e[kLpHC][CT];
+#pragma unroll
+    for (int k = 0; k < kLpHC; ++k) {
+      const int h = (hc + k) < hn ? hc + k : hn - 1;
+#pragma unroll
+      for (int j = 0; j < CT; ++j) e[k][j] = row[(int64_t)h * N + cc[j]];
+    }
+    if (hc + kLpHC <= hn) {
+#pragma unroll
+      for (int k = 0; k < kLpHC; ++k) lp_score_step<CT, HEAD>(s_a, s_b, hc + k, e[k], acc);
+    } else {
+#pragma unroll
+      for (int k = 0; k < kLpHC; ++k)
+        if (hc + k < hn) lp_score_step<CT, HEAD>(s_a, s_b, hc + k, e[k], acc);
+    }
+  }
+}
+
+// lp_score_tile for CT candidates per thread at once — c, c + kLpTB, ..., c + (CT - 1) kLpTB — so that a block which owns
+// its pairs across several candidate tiles (lp_batches.hip) stages the pairs' vectors once and reads each staged value
+// from LDS once for all CT candidates: acc[j][i] = the score of candidate c + j kLpTB for pair i, by the SAME float32
+// operations in the same order as lp_score_tile (bit for bit; tests/test_gpu_lp_batches_kernels.py).  Candidates past
+// the table are read at the clamped id N - 1 (straight-line loads, no branch); their acc is not meaningful.
+template <int CT, class Ids>
+__device__ __forceinline__ void lp_score_tiles(const float *__restrict__ Et, int64_t N, int H,
+                                               const float *__restrict__ E, int64_t ldE,
+                                               const float *__restrict__ Rel, int64_t ldR, bool head, int64_t c,
+                                               int nfb, Ids ids, float (*s_a)[kLpHT], float (*s_b)[kLpHT],
+                                               float (&acc)[CT][kLpFB]) {
+#pragma clang fp contract(off)
+  int64_t cc[CT];
+#pragma unroll
+  for (int j = 0; j < CT; ++j) {
+    const int64_t cj = c + (int64_t)j * kLpTB;
+    cc[j] = cj < N ? cj : N - 1;
+#pragma unroll
+    for (int i = 0; i < kLpFB; ++i) acc[j][i] = 0.f;
+  }
+  for (int h0 = 0; h0 < H; h0 += kLpHT) {
+    const int hn = (H - h0) < kLpHT ? (H - h0) : kLpHT;
+    __syncthreads();
+    for (int i = threadIdx.x; i < kLpFB * kLpHT; i += kLpTB) {
+      const int fi = i / kLpHT, h = i % kLpHT;
+      float a = 0.f, b = 0.f;
+      if (fi < nfb && h < hn) {
+        int64_t anchor, rel;
+        ids(fi, anchor, rel);
+        const float pv = Rel[rel * ldR + h0 + h];
+        const float ev = E[anchor * ldE + h0 + h];
+        if (head) {
+          a = pv;
+          b = ev;
+        } else {
+          a = ev * pv;
+        }
+      }
+      s_a[fi][h] = a;
+      s_b[fi][h] = b;
+    }
+    __syncthreads();
+    const float *row = Et + (int64_t)h0 * N;
+    if (head)
+      lp_score_htile<CT, true>(row, N, hn, cc, s_a, s_b, acc);
+    else
+      lp_score_htile<CT, false>(row, N, hn, cc, s_a, s_b, acc);
   }
 }
 

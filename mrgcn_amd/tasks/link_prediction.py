@@ -3,8 +3,9 @@
 ranks :593-643, metrics :373-420), same function names and argument meaning, computed by the
 HIP kernels of `csrc/distmult.hip` through the C ABI.  The reference's mini-batch flow (mkbatches
 :477-530, train_model's batch loop :226-331, test_model :375-422) is mirrored further down, its
-full-batch run loop with evaluation and early stopping on the device (`fit`, csrc/lp_eval.hip) at the
-end of this file; logging and TSV writers are out of scope."""
+full-batch run loop with evaluation and early stopping on the device (`fit`, csrc/lp_eval.hip) and its mini-batch
+run loop (`fit_batches`, csrc/lp_batches.hip) at the end of this file; logging and TSV writers are out of scope
+(SURVEY §8)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -509,12 +510,12 @@ def _batch_state(batch, facts, device):
             batch.as_tensors_()
             batch.to({"relational": device})
         f = torch.as_tensor(np.asarray(facts), dtype=torch.int64).to(device).contiguous()
-        st = dict(device=device, facts=f, sampler=DeviceNegativeSampler(f), lists=None)
+        st = dict(device=device, facts=f, sampler=DeviceNegativeSampler(f), lists=None, eval_ws=None)
         batch._mrgcn_lp = st
     return st
 
 
-def train_batch_step(model, batch, facts, optimizer, negatives=None, clip=1.0):
+def train_batch_step(model, batch, facts, optimizer, negatives=None, clip=1.0, slot=None, sampler=None):
     """One batch of train_model (link_prediction.py:226-331): 20 % of the batch's facts corrupted inside the batch
     (half the heads, half the tails replaced by batch nodes, :239-263) — drawn on the device, or `negatives` (an
     [n // 5, 3] array of batch-local triples, e.g. the reference's draws) —, DistMult scores of facts + negatives, BCE,
@@ -522,12 +523,22 @@ def train_batch_step(model, batch, facts, optimizer, negatives=None, clip=1.0):
     `mrgcn_amd.train.ClipAdam` with a max_norm clips inside its own step; any other optimizer gets
     `mrgcn_amd.optim.clip_grad_norm_` first (torch's, unless a row-sparse weight_I gradient is among the parameters:
     `mrgcn_amd.optim.RowSparseAdam` then steps only the node blocks of the batch and the ones that ever had
-    gradient)."""
+    gradient).  `slot` (a float32 [1] piece of the epoch's loss table on the device): the loss also goes there.
+    `sampler`: any callable with `train_step`'s sampler contract — `triples, labels = sampler()`, the batch's facts
+    followed by their corrupted copies and the 1 / 0 labels on the device, without synchronising — in place of the
+    batch's own `DeviceNegativeSampler`."""
     from ..optim import clip_grad_norm_
     from ..train import ClipAdam
     E = _embed(model, batch)
     st = _batch_state(batch, facts, E.device)
-    if negatives is None:
+    if slot is not None and not (torch.is_tensor(slot) and slot.is_cuda and slot.dtype == torch.float32
+                                 and slot.numel() == 1):
+        raise _lib.MrgcnError("train_batch_step: slot is one float32 on the device")
+    if negatives is not None and sampler is not None:
+        raise _lib.MrgcnError("train_batch_step: negatives or a sampler, not both")
+    if sampler is not None:
+        triples, labels = sampler()
+    elif negatives is None:
         triples, labels = st["sampler"]()
     else:
         neg = torch.as_tensor(np.asarray(negatives), dtype=torch.int64).to(E.device)
@@ -540,7 +551,10 @@ def train_batch_step(model, batch, facts, optimizer, negatives=None, clip=1.0):
     if not (isinstance(optimizer, ClipAdam) and optimizer.max_norm is not None):
         clip_grad_norm_(model.parameters(), clip)
     optimizer.step()
-    return loss.detach()
+    loss = loss.detach()
+    if slot is not None:
+        slot.view(1).copy_(loss.view(1))
+    return loss
 
 
 def prepare_batches(batches, device):
@@ -1066,6 +1080,46 @@ class FitEpochs:
             self.model.train()
 
 
+def _run_schedule(run, sched, nepoch, poll, stopper):
+    """The host side of `fit` and `fit_batches`: the epochs of `sched` in windows of `poll` on `run` (`train_epoch`,
+    `eval_epoch`, `last_epoch`; `loss_ring`, `eval_ring`, `last`, `eval_ctr`), one look at the device per window, the
+    reference's tuples for the rows up to and including the record that latched a stop, `restore_()` after it."""
+    evals_before = 0     # evaluating epochs < nepoch in front of the current window = records at its start
+    epoch = 0
+    while epoch < nepoch:
+        window = sched[epoch:epoch + poll]
+        for e, eval_train, _, _ in window:
+            if e == nepoch:
+                run.last_epoch()
+            elif eval_train:
+                run.eval_epoch()
+            else:
+                run.train_epoch()
+        epoch += len(window)
+        st = run.eval_ctr.read()
+        losses, rows, last_host = run.loss_ring.cpu(), run.eval_ring.cpu(), run.last.cpu()
+        k = evals_before
+        for e, eval_train, eval_valid, _ in window:
+            tm = th = vm = vh = None
+            if eval_train and e < nepoch:
+                if k >= int(st.records):    # the stop was latched in front of this epoch
+                    break
+                r = rows[k % poll]
+                k += 1
+                tm, th = _unpack(r[1:9])
+                if eval_valid:
+                    vm, vh = _unpack(r[9:17])
+            elif eval_train:
+                tm, th = _unpack(last_host)
+            yield (e, float(losses[(e - 1) % poll][0]), tm, th, vm, vh)
+            if st.stop and k == int(st.records) and eval_train:
+                break
+        evals_before = k
+        if st.stop:
+            stopper.restore_()
+            return
+
+
 def fit(model, forward_fn, train_facts, valid_facts, optimizer, nepoch, eval_interval=1, mrr_batchsize=100,
         filter_ranks=True, early_stop=None, poll=8, graphed=True, sampler=None, warmup=3, static=None):
     """The reference's full-batch link-prediction loop (train_model, link_prediction.py:191-373, with test_model
@@ -1105,37 +1159,337 @@ def fit(model, forward_fn, train_facts, valid_facts, optimizer, nepoch, eval_int
     stopper = _as_device_stopper(early_stop, model, optimizer)
     run = FitEpochs(model, forward_fn, tparts, vparts, optimizer, stopper, poll, graphed, sampler, static, warmup)
     sched = eval_schedule(nepoch, eval_interval, vparts is not None)
-    evals_before = 0     # evaluating epochs < nepoch in front of the current window = records at its start
-    epoch = 0
-    while epoch < nepoch:
-        window = sched[epoch:epoch + poll]
-        for e, eval_train, _, _ in window:
-            if e == nepoch:
-                run.last_epoch()
-            elif eval_train:
-                run.eval_epoch()
-            else:
-                run.train_epoch()
-        epoch += len(window)
-        st = run.eval_ctr.read()
-        losses, rows, last_host = run.loss_ring.cpu(), run.eval_ring.cpu(), run.last.cpu()
-        k = evals_before
-        for e, eval_train, eval_valid, _ in window:
-            tm = th = vm = vh = None
-            if eval_train and e < nepoch:
-                if k >= int(st.records):    # the stop was latched in front of this epoch
-                    break
-                r = rows[k % poll]
-                k += 1
-                tm, th = _unpack(r[1:9])
-                if eval_valid:
-                    vm, vh = _unpack(r[9:17])
-            elif eval_train:
-                tm, th = _unpack(last_host)
-            yield (e, float(losses[(e - 1) % poll][0]), tm, th, vm, vh)
-            if st.stop and k == int(st.records) and eval_train:
-                break
-        evals_before = k
-        if st.stop:
-            stopper.restore_()
+    yield from _run_schedule(run, sched, nepoch, poll, stopper)
+
+
+# ---- the reference's mini-batch run loop on the device (link_prediction.py:224-422; csrc/lp_batches.hip) -----------
+def _check_lists(lists, nf, dev, who):
+    ls = list(lists)
+    if len(ls) != 4 or not all(torch.is_tensor(a) and a.is_cuda for a in ls):
+        raise _lib.MrgcnError(f"{who}: lists are the four device tensors of filter_lists")
+    if not (ls[0].dtype == ls[2].dtype == torch.int64 and ls[1].dtype == ls[3].dtype == torch.int32
+            and ls[0].numel() == ls[2].numel() == nf + 1):
+        raise _lib.MrgcnError(f"{who}: lists are (int64 [n + 1], int32, int64 [n + 1], int32)")
+    # (an empty tensor has no address; the lists are empty either way)
+    return [a.contiguous() if a.numel() else torch.zeros(1, dtype=a.dtype, device=dev) for a in ls]
+
+
+def batch_eval_workspace(num_nodes, H, num_facts, device):
+    """The workspace one `batch_eval` of that shape needs, as an int64 device tensor (kept by the caller)."""
+    nbytes = int(_lib.load().mrgcn_distmult_batch_eval_workspace(int(num_nodes), int(H), int(num_facts)))
+    if nbytes < 0:
+        raise _lib.MrgcnError("batch_eval: sizes outside mrgcn_distmult_batch_eval's limits (at least one node, one "
+                              "fact and one feature)")
+    return torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=device)
+
+
+def batch_eval(node_embeddings, edge_embeddings, facts, lists=None, slot=None, ranks=None, workspace=None):
+    """test_model's work on ONE batch (:392-414) in one call of three launches (mrgcn_distmult_batch_eval): the
+    batch's `facts` (a contiguous int64 [n, 3] device tensor of batch-local ids, n >= 1) ranked against the batch's own
+    `node_embeddings`, raw and — with `lists`, the four device tensors of `filter_lists(facts)` — filtered, and the
+    float32 `[8]` slot raw mrr, hits@1, hits@3, hits@10, then the same filtered (-1 each without lists).  The ranks
+    are `compute_ranks_fast`'s bit for bit (facts at positions >= the number of nodes unscored, as there), each slot
+    half is `rank_metrics`' of those ranks.  `slot`: the contiguous float32 [8] row to write (None: a new one);
+    `ranks`: a pair of contiguous int64 [2 n] device tensors (raw, flt; either may be None) that receive the ranks;
+    `workspace`: `batch_eval_workspace(...)` of this shape (None: allocated here).  Returns the slot.  No
+    synchronisation; capturable."""
+    E = _f32_rows(node_embeddings.detach(), "node_embeddings")
+    Rel = _f32_rows(edge_embeddings.detach(), "edge_embeddings")
+    dev = E.device
+    if not (torch.is_tensor(facts) and facts.is_cuda and facts.dtype == torch.int64 and facts.dim() == 2
+            and facts.shape[1] == 3 and facts.is_contiguous() and facts.shape[0] >= 1):
+        raise _lib.MrgcnError("batch_eval: facts is a contiguous, non-empty int64 [n, 3] tensor on the device")
+    nf, N, H = int(facts.shape[0]), int(E.shape[0]), int(E.shape[1])
+    if Rel.shape[1] != H:
+        raise ValueError("batch_eval: node and edge embeddings differ in width")
+    if N == 0:
+        raise ValueError("batch_eval: no nodes")
+    ls = _check_lists(lists, nf, dev, "batch_eval") if lists is not None else [None] * 4
+    if slot is None:
+        slot = torch.empty(8, dtype=torch.float32, device=dev)
+    elif not (torch.is_tensor(slot) and slot.is_cuda and slot.dtype == torch.float32 and tuple(slot.shape) == (8,)
+              and slot.is_contiguous()):
+        raise _lib.MrgcnError("batch_eval: slot is a contiguous float32 [8] tensor on the device")
+    raw, flt = ranks if ranks is not None else (None, None)
+    for r in (raw, flt):
+        if r is not None and not (torch.is_tensor(r) and r.is_cuda and r.dtype == torch.int64
+                                  and tuple(r.shape) == (2 * nf,) and r.is_contiguous()):
+            raise _lib.MrgcnError("batch_eval: ranks are contiguous int64 [2 * n] tensors on the device")
+    lib = _lib.load()
+    if workspace is None:
+        workspace = batch_eval_workspace(N, H, nf, dev)
+    ws_bytes = int(workspace.numel()) * workspace.element_size()
+    if not workspace.is_cuda or ws_bytes < int(lib.mrgcn_distmult_batch_eval_workspace(N, H, nf)):
+        raise _lib.MrgcnError("batch_eval: the workspace is too small for this batch (batch_eval_workspace)")
+    with torch.cuda.device(dev):
+        _lib.check(lib.mrgcn_distmult_batch_eval(_ptr(E), E.stride(0), N, _ptr(Rel), Rel.stride(0), H, _ptr(facts), nf,
+                                                 _ptr(ls[0]), _ptr(ls[1]), _ptr(ls[2]), _ptr(ls[3]), _ptr(workspace),
+                                                 ws_bytes, _ptr(raw), _ptr(flt), _ptr(slot), _stream()),
+                   "distmult_batch_eval")
+    return slot
+
+
+def _lp_batch_means(loss_slots, n_loss, train_slots, n_train, valid_slots, n_valid, row, score=None):
+    dev = row.device
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().mrgcn_lp_batch_means_f32(
+            _ptr(loss_slots) if n_loss else None, int(n_loss), _ptr(train_slots) if n_train else None, int(n_train),
+            _ptr(valid_slots) if n_valid else None, int(n_valid), _ptr(row), _ptr(score), _stream()),
+            "lp_batch_means")
+
+
+def _batch_lists(st, facts):
+    """The batch's filter lists on the device, built once (shared with `evaluate_batches`)."""
+    if st["lists"] is None:
+        dev = st["device"]
+        ls = [torch.from_numpy(a).to(dev) for a in filter_lists(np.asarray(facts))]
+        st["lists"] = [a if a.numel() else torch.zeros(1, dtype=a.dtype, device=dev) for a in ls]
+    return st["lists"]
+
+
+def _check_slots(slots, n, who):
+    if not (torch.is_tensor(slots) and slots.is_cuda and slots.dtype == torch.float32 and slots.dim() == 2
+            and slots.shape[1] == 8 and slots.is_contiguous() and slots.shape[0] >= n):
+        raise _lib.MrgcnError(f"{who}: slots is a contiguous float32 [batches, 8] table on the device")
+
+
+def eval_batches(model, batches, filtered=True, slots=None, ranks=None):
+    """test_model (:375-422) over prepared batches without the host: every batch's forward under `eval()` and
+    `no_grad` (the model's mode is put back on exit), then `batch_eval` into row i of `slots`.  A batch's filter lists
+    are built once and its workspace is allocated once; both stay with the batch.  Returns the float32 `[8]` device
+    vector of the unweighted means over the batches (:416-419; -1 for the filtered four when not `filtered`) — or,
+    with `slots` (the caller's float32 [batches, 8] table, e.g. `BatchFitEpochs`'), leaves the per-batch values there
+    and returns None: the means are the caller's business.  `ranks`: a pair of int64 device buffers of
+    `2 * sum(facts)` values (raw, flt; flt may be None when not `filtered`); batch i's ranks land at twice the facts in
+    front of it, the order `evaluate_batches` flattens to.  No synchronisation."""
+    batches = list(batches)
+    if not batches:
+        raise _lib.MrgcnError("eval_batches: no batches")
+    own = slots is None
+    raw_all, flt_all = ranks if ranks is not None else (None, None)
+    was_training = model.training
+    model.eval()
+    try:
+        with torch.no_grad():
+            Rel = _relations(model).detach()
+            at = 0
+            for i, (batch, facts) in enumerate(batches):
+                E = _embed(model, batch).detach()
+                st = _batch_state(batch, facts, E.device)
+                if i == 0:
+                    if own:
+                        slots = torch.empty((len(batches), 8), dtype=torch.float32, device=E.device)
+                    _check_slots(slots, len(batches), "eval_batches")
+                f = st["facts"]
+                nf, shape = int(f.shape[0]), (int(E.shape[0]), int(E.shape[1]), int(f.shape[0]))
+                ws = st.get("eval_ws")
+                if ws is None or ws[0] != shape:
+                    ws = st["eval_ws"] = (shape, batch_eval_workspace(*shape, E.device))
+                pair = None
+                if ranks is not None:
+                    pair = (raw_all[at:at + 2 * nf] if raw_all is not None else None,
+                            flt_all[at:at + 2 * nf] if flt_all is not None and filtered else None)
+                batch_eval(E, Rel, f, _batch_lists(st, facts) if filtered else None, slots[i], pair, ws[1])
+                at += 2 * nf
+    finally:
+        model.train(was_training)
+    if not own:
+        return None
+    row = torch.empty(EVAL_ROW, dtype=torch.float32, device=slots.device)
+    _lp_batch_means(None, 0, slots, len(batches), None, 0, row)
+    return row[1:9]
+
+
+def rank_batches(model, batches, filtered=True):
+    """`evaluate_batches`' result — `(mrr, hits_at_k, rankings)` as test_model returns them — from `eval_batches`:
+    the batches' ranks land in two device buffers, the means come from the batches' slots, and everything is read back
+    once, through pinned memory, after the last batch.  The rankings are `evaluate_batches`' exactly; its means are
+    float32 means of float32 values where these are float64 sums rounded once."""
+    batches = list(batches)
+    if not batches:
+        raise _lib.MrgcnError("rank_batches: no batches")
+    dev = next(model.parameters()).device
+    total = 2 * sum(int(np.asarray(f).shape[0]) if not torch.is_tensor(f) else int(f.shape[0]) for _, f in batches)
+    raw = torch.empty(total, dtype=torch.int64, device=dev)
+    flt = torch.empty(total, dtype=torch.int64, device=dev) if filtered else None
+    means = eval_batches(model, batches, filtered, ranks=(raw, flt))
+    means_h = torch.empty(8, dtype=torch.float32).pin_memory()
+    ranks_h = torch.empty((2 if filtered else 1, total), dtype=torch.int64).pin_memory()
+    means_h.copy_(means, non_blocking=True)
+    ranks_h[0].copy_(raw, non_blocking=True)
+    if filtered:
+        ranks_h[1].copy_(flt, non_blocking=True)
+    torch.cuda.current_stream(dev).synchronize()
+    mrr, hits_at_k = _unpack(means_h)
+    rankings = {"raw": ranks_h[0].tolist(), "flt": ranks_h[1].tolist() if filtered else [-1] * len(batches)}
+    return mrr, hits_at_k, rankings
+
+
+class BatchFitEpochs:
+    """The epochs `fit_batches` is made of, as callables on one set of device tables (see `fit_batches` for what they
+    do): `train_epoch()` — every training batch in order (`train_batch_step`, its loss into slot i), the mean of the
+    slots into row `epochs % poll` of `loss_ring` —, `eval_epoch()` — the same, then `eval_batches` of the training
+    batches and of the validation batches, the `EVAL_ROW` means into row `records % poll` of `eval_ring` by the
+    early-stop record, the snapshot behind its flag — and `last_epoch()`: a training epoch, then the training metrics
+    into `last`, eagerly.  `graphed=True`: the first two are one captured hipGraph each, under `GraphedBatchEpoch`'s
+    discipline — `warmup` real epochs on the capture stream (the last of them an evaluating one), `thread_local`
+    capture, a single chain on the one stream, counters and rings reset after the warm-up, the optimizer's
+    `_state_gen` compared and the supports' pair-sum tables refreshed in front of every replay."""
+
+    def __init__(self, model, train_batches, valid_batches, optimizer, stopper=None, poll=8, graphed=True,
+                 filter_ranks=True, samplers=None, warmup=3, clip=1.0):
+        from .. import functional as Fn
+        from ..train import _COUNT_ONLY, _StopState
+        train_batches, valid_batches = list(train_batches), list(valid_batches or [])
+        if not train_batches:
+            raise _lib.MrgcnError("fit_batches: no training batches")
+        if stopper is not None and not valid_batches:
+            raise _lib.MrgcnError("fit_batches: early stopping scores the validation MRR: pass valid_batches")
+        if graphed and not getattr(optimizer, "capturable", False):
+            raise _lib.MrgcnError("fit_batches(graphed=True) needs ClipAdam(..., capturable=True)")
+        dev = _batch_state(*train_batches[0], next(model.parameters()).device)["device"]
+        for batch, facts in train_batches + valid_batches:
+            if _batch_state(batch, facts, dev)["device"] != dev:
+                raise _lib.MrgcnError("fit_batches: the batches live on one device")
+        self.model, self.optimizer, self.stopper, self.poll = model, optimizer, stopper, poll
+        self.train_batches, self.valid_batches = train_batches, valid_batches
+        self.filter_ranks, self.clip = bool(filter_ranks), clip
+        self.samplers = [samplers(i, b, f) if samplers is not None else None for i, (b, f) in enumerate(train_batches)]
+        nt, nv = len(train_batches), len(valid_batches)
+        self.loss_ctr = _StopState(dev, 1, 0.0, _COUNT_ONLY)   # counts every epoch
+        self.eval_ctr = stopper.state if stopper is not None else _StopState(dev, 1, 0.0, _COUNT_ONLY)
+        self.loss_ring = torch.zeros((poll, 4), dtype=torch.float32, device=dev)
+        self.eval_ring = torch.zeros((poll, EVAL_ROW), dtype=torch.float32, device=dev)
+        self.loss_slots = torch.zeros(nt, dtype=torch.float32, device=dev)
+        self.train_slots = torch.zeros((nt, 8), dtype=torch.float32, device=dev)
+        self.valid_slots = torch.zeros((max(nv, 1), 8), dtype=torch.float32, device=dev)
+        self.row = torch.zeros(EVAL_ROW, dtype=torch.float32, device=dev)
+        self.score = torch.zeros((), dtype=torch.float32, device=dev)
+        self._last_row = torch.zeros(EVAL_ROW, dtype=torch.float32, device=dev)
+        self.last = self._last_row[1:9]
+        self.graphed = bool(graphed)
+        if not graphed:
+            self.reset()
             return
+        nw = max(int(warmup), 1)
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            for _ in range(nw - 1):
+                self._train_epoch()
+            self._eval_epoch()
+            self.reset()
+        torch.cuda.current_stream().wait_stream(side)
+        torch.cuda.synchronize()
+        self.warmup_steps = nw
+        self._graphs, self._pair_sums = [], []
+        for fn in (self._train_epoch, self._eval_epoch):
+            g = torch.cuda.CUDAGraph()
+            Fn.take_captured_pair_sums()
+            with torch.cuda.graph(g, stream=side, capture_error_mode="thread_local"):
+                fn()
+            self._pair_sums.append(Fn.take_captured_pair_sums())
+            self._graphs.append(g)
+        self._state_gen = optimizer._state_gen
+
+    def reset(self):
+        self.loss_ctr.reset()
+        self.eval_ctr.reset()
+        self.loss_ring.zero_()
+        self.eval_ring.zero_()
+
+    def _replay(self, i):
+        if self.optimizer._state_gen != self._state_gen:
+            raise _lib.MrgcnError("fit_batches: the optimizer's state was loaded after the capture (the captured "
+                                  "graphs still update the old moment buffers)")
+        for sup in self._pair_sums[i]:
+            sup.pair_sums_refresh()
+        self._graphs[i].replay()
+
+    def _train_epoch(self):
+        self.model.train()   # (:232)
+        for i, (batch, facts) in enumerate(self.train_batches):
+            train_batch_step(self.model, batch, facts, self.optimizer, clip=self.clip, slot=self.loss_slots[i:i + 1],
+                             sampler=self.samplers[i])
+        _lp_batch_means(self.loss_slots, len(self.train_batches), None, 0, None, 0, self.row)
+        self.loss_ctr.record(self.row[0:1], self.loss_ring, (self.row[0:1],))
+
+    def _eval_epoch(self):
+        self._train_epoch()
+        try:
+            nt, nv = len(self.train_batches), len(self.valid_batches)
+            eval_batches(self.model, self.train_batches, self.filter_ranks, slots=self.train_slots)
+            if nv:
+                eval_batches(self.model, self.valid_batches, self.filter_ranks, slots=self.valid_slots)
+            _lp_batch_means(None, 0, self.train_slots, nt, self.valid_slots, nv, self.row, self.score)
+        finally:
+            self.model.train()
+        (self.stopper if self.stopper is not None else self.eval_ctr).record_row(self.score, self.row, self.eval_ring)
+
+    def train_epoch(self):
+        if self.graphed:
+            self._replay(0)
+            bump("lp.batch_epoch.graphed")
+        else:
+            self._train_epoch()
+            bump("lp.batch_epoch.eager")
+
+    def eval_epoch(self):
+        if self.graphed:
+            self._replay(1)
+            bump("lp.batch_eval_epoch.graphed")
+        else:
+            self._eval_epoch()
+            bump("lp.batch_eval_epoch.eager")
+
+    def last_epoch(self):
+        self.train_epoch()
+        try:
+            eval_batches(self.model, self.train_batches, self.filter_ranks, slots=self.train_slots)
+            _lp_batch_means(None, 0, self.train_slots, len(self.train_batches), None, 0, self._last_row)
+        finally:
+            self.model.train()
+
+
+def fit_batches(model, train_batches, valid_batches, optimizer, nepoch, eval_interval=1, filter_ranks=True,
+                early_stop=None, poll=8, graphed=True, max_graph_batches=None, warmup=3, samplers=None):
+    """The reference's mini-batch link-prediction loop (train_model with gcn_batchsize > 0, link_prediction.py:224-373,
+    with test_model :375-422) as a generator over its tuples `(epoch, loss, train_mrr, train_hits_at_k, valid_mrr,
+    valid_hits_at_k)`, with `fit`'s contract row for row: the schedule (`eval_schedule`), the loss ring and the eval
+    ring of `poll` rows, the early-stop record on `1 - valid_mrr["raw"]`, the snapshot behind its flag, the latched stop
+    and what is yielded around it, `restore_()` on a stop, a run that reaches `nepoch` left with the LAST epoch's state,
+    and the eagerly evaluated last epoch.  The batches are prepared ones (`prepare_batches(mkbatches(...), device)`);
+    `valid_batches` None or empty: no validation (both validation fields are None; early stopping then raises).
+
+    A training epoch runs every training batch in `mkbatches`' order (`train_batch_step`, the batch's loss into its
+    slot), then the mean of the slots (`np.mean(loss_lst)`, :331) into the loss ring.  An evaluating epoch adds
+    `eval_batches` of the training batches, then of the validation batches — each batch's own forward under `eval()`,
+    its ranks and its eight metric values in three launches (mrgcn_distmult_batch_eval) —, then the unweighted means
+    over batches (mrgcn_lp_batch_means_f32, :416-419), then the record.  Nothing synchronises inside an epoch.
+    `samplers(i, batch, facts) -> sampler` supplies training batch i's negatives (`train_batch_step`'s `sampler`);
+    None draws the reference's 20 % in-batch corruptions on the device.
+
+    `graphed=True` captures the two epochs (`BatchFitEpochs`; needs `ClipAdam(capturable=True)`, and its `warmup`
+    epochs are REAL optimizer steps taken before epoch 1) when the evaluating epoch has at most `max_graph_batches`
+    batch passes — `2 * len(train_batches) + len(valid_batches)`; default `node_classification.MAX_GRAPH_BATCHES`, the
+    largest capture measured — and every batch has a fixed structure (masked or full batches).  Otherwise the eager
+    epochs run, which are equally free of synchronisation: FB15k-237's 1 011 batches run eagerly.
+
+    Out of scope: the loop's l1_lambda / l2_lambda (:306-322), literal-encoder batches inside a capture, the
+    partitioned engines."""
+    from ..train import _as_device_stopper
+    from .node_classification import MAX_GRAPH_BATCHES, _is_fixed_structure
+    train_batches, valid_batches = list(train_batches), list(valid_batches or [])
+    nepoch, poll = int(nepoch), max(int(poll), 1)
+    if early_stop is not None and not valid_batches:
+        raise _lib.MrgcnError("fit_batches: early stopping scores the validation MRR: pass valid_batches")
+    if graphed and not getattr(optimizer, "capturable", False):
+        raise _lib.MrgcnError("fit_batches(graphed=True) needs ClipAdam(..., capturable=True)")
+    cap = MAX_GRAPH_BATCHES if max_graph_batches is None else int(max_graph_batches)
+    capture = bool(graphed and 2 * len(train_batches) + len(valid_batches) <= cap
+                   and all(_is_fixed_structure(b) for b, _ in train_batches + valid_batches))
+    stopper = _as_device_stopper(early_stop, model, optimizer)
+    run = BatchFitEpochs(model, train_batches, valid_batches, optimizer, stopper, poll, capture, filter_ranks, samplers,
+                         warmup)
+    sched = eval_schedule(nepoch, eval_interval, bool(valid_batches))
+    yield from _run_schedule(run, sched, nepoch, poll, stopper)

@@ -91,6 +91,9 @@ python3 tools/lp_fit_probe.py --out $o/lp_fit_probe.json > $o/lp_fit_probe.txt 2
 # (10h) the mini-batch node-classification run loop at the AM/4 shape, batches of 1 024 and of 64: the replayed epoch, the
 # eager device epoch, the loop as the reference writes it, the fused loss launch against the two it replaces
 python3 tools/nc_minibatch_probe.py --out $o/nc_minibatch_probe.json > $o/nc_minibatch_probe.txt 2> $o/nc_minibatch_probe.err
+# (10i) the mini-batch link-prediction run loop at the FB15k-237 shape: batch_eval against the two sequences it replaces,
+# eval_batches against evaluate_batches, the eager device epochs against the host loop
+python3 tools/lp_minibatch_fit_probe.py --out $o/lp_minibatch_fit_probe.json > $o/lp_minibatch_fit_probe.txt 2> $o/lp_minibatch_fit_probe.err
 hipcc -O3 --offload-arch=gfx950 -std=c++17 tools/lab/copy_lab.hip -o /tmp/copy_lab 2>/dev/null && /tmp/copy_lab > $o/copy_lab.txt 2>&1
 python3 tools/lab/spmm_hot_lab.py > $o/spmm_hot_lab.txt 2>&1
 # the CPU suite last: the tree these artefacts describe is green
