@@ -753,6 +753,30 @@ int mrgcn_adam_step_multi_f32(int32_t n_tensors, float *const *params, const flo
                               float *const *exp_avg, float *const *exp_avg_sq, const int64_t *numel, const float *lr,
                               const float *weight_decay, float beta1, float beta2, float eps, int64_t step,
                               const float *bc_dev, const float *grad_scale, void *stream);
+/* The L1 / L2 weight penalty of the link-prediction loop (tasks/link_prediction.py:306-326: l1 sum|p| + l2 sum p^2 over
+ * the `weight*` parameters joins the loss, is differentiated, clipped with it by clip_grad_norm_ and stepped) on
+ * <= 16 float32 tensors per launch, without rewriting a gradient.  Tensor t: params[t], grads[t] (nullable: no
+ * gradient this step), numel[t], and — with row_flags (nullable array) — row_flags[t] (nullable uint8 [numel / row_len])
+ * and row_len[t]: row i of the gradient buffer counts only where row_flags[t][i] != 0; its other rows are never read.
+ * r(p) = l1 sgn(p) + 2 l2 p, sgn(0) = 0.
+ * mrgcn_penalty_norm_multi_f32 ADDS sum (g + r(p))^2, sum |p| and sum p^2 into the device doubles out3[0..2] (zeroed by
+ * the caller; several launches chain into one out3) in a fixed order — a fixed float tree per block, double partials
+ * added in block order by the block that arrives last, a grid that depends on the sizes only: the same bits on every
+ * run.  `partials`: device scratch of mrgcn_penalty_norm_workspace() BYTES (fully written before it is read);
+ * `ticket`: a uint32 that is zero at the first call, left zero.  A tensor above 2^20 elements takes a launch of its
+ * own.
+ * mrgcn_adam_step_reg_multi_f32: mrgcn_adam_step_multi_f32's update of every element on
+ * gg = (g + r(p)) * *grad_scale + weight_decay * p (torch's order: the penalty is clipped, the decay is not).
+ * 16-byte accesses where every base is 16-byte aligned and flagged rows hold whole pieces, scalar ones otherwise. */
+int64_t mrgcn_penalty_norm_workspace(void);
+int mrgcn_penalty_norm_multi_f32(int32_t n_tensors, const float *const *params, const float *const *grads,
+                                 const int64_t *numel, const uint8_t *const *row_flags, const int32_t *row_len, float l1,
+                                 float l2, double *out3, double *partials, uint32_t *ticket, void *stream);
+int mrgcn_adam_step_reg_multi_f32(int32_t n_tensors, float *const *params, const float *const *grads,
+                                  const int64_t *numel, const uint8_t *const *row_flags, const int32_t *row_len,
+                                  float *const *exp_avg, float *const *exp_avg_sq, const float *lr,
+                                  const float *weight_decay, float l1, float l2, float beta1, float beta2, float eps,
+                                  int64_t step, const float *bc_dev, const float *grad_scale, void *stream);
 /* torch.optim.Adam step (node_classification.py:35-37, :193) on one tensor; the gradient is
  * multiplied by *grad_scale (device float, nullable) first, i.e. the clip is folded in. */
 int mrgcn_adam_step_f32(float *param, const float *grad, float *exp_avg, float *exp_avg_sq,

@@ -617,6 +617,247 @@ __global__ __launch_bounds__(kTB) void k_adam_multi(MultiAdam a, float b1, float
   }
 }
 
+// ---- L1 / L2 weight penalties on dense and flagged-row parameters (tasks/link_prediction.py:306-326) -----------------
+// The reference adds l1 sum|p| + l2 sum p^2 over the `weight*` parameters to the loss, so r(p) = l1 sgn(p) + 2 l2 p is
+// part of every such gradient when clip_grad_norm_ looks at it.  Two launches over a list of <= kMultiMax tensors do
+// that without touching the gradients: k_penalty_norm_multi sums (g + r(p))^2, |p| and p^2; k_adam_reg_multi is
+// k_adam_multi's update on gg = (g + r(p)) scale + wd p.  A tensor may carry row flags: row i of its gradient buffer
+// counts only where flags[i] != 0, and the other rows of the buffer are never read (a flagged-off load reads the
+// parameter's own piece instead and a select drops it).  Both are one-shot over their tensors: a block owns a
+// contiguous tile whose size depends on the tensor's size only, every load of a step is issued before the first use.
+constexpr int kPenMaxBlocks = 4096;         // blocks of one norm launch (its partials: 3 doubles each)
+constexpr int kPenTensorBlocks = 1024;      // blocks one tensor may take of them
+constexpr int64_t kPenTile = 4 * 4 * kTB;   // floats of a block's smallest tile: four 16-byte pieces per thread
+constexpr int kPenSumChunk = 1024;          // partials per sum the last block stages in LDS at a time
+struct MultiPen {
+  const float *p[kMultiMax];
+  const float *g[kMultiMax];          // nullable: no gradient this step
+  const uint8_t *flags[kMultiMax];    // nullable: every row counts
+  int64_t n[kMultiMax];
+  int64_t per_block[kMultiMax];       // floats per block: a multiple of kPenTile
+  int32_t row_len[kMultiMax];
+  int32_t vec[kMultiMax];             // 16-byte pieces (aligned bases, rows of whole pieces)
+  int32_t blk0[kMultiMax + 1];
+  int32_t n_tensors;
+};
+__device__ __forceinline__ float pen_grad(float p, float l1, float l2x2) {  // l1 sgn(p) + 2 l2 p, sgn(0) = 0
+  const float sg = (float)(p > 0.f) - (float)(p < 0.f);
+  return fmaf(l2x2, p, l1 * sg);
+}
+// the row of 16-byte piece q (rows of rl4 pieces) / of element i
+__device__ __forceinline__ int64_t pen_row(int64_t i, int32_t len) {
+  return i <= 0x7fffffffLL ? (int64_t)((uint32_t)i / (uint32_t)len) : i / len;
+}
+
+__global__ __launch_bounds__(kTB) void k_penalty_norm_multi(MultiPen a, float l1, float l2x2, int pen,
+                                                            double *__restrict__ out3, double *__restrict__ partials,
+                                                            unsigned int *__restrict__ ticket) {
+  int t = 0;
+  while (t + 1 < a.n_tensors && (int)blockIdx.x >= a.blk0[t + 1]) ++t;
+  const int b = blockIdx.x - a.blk0[t];
+  const float *__restrict__ p = a.p[t];
+  const float *__restrict__ g = a.g[t];
+  const uint8_t *__restrict__ fl = a.flags[t];
+  const int64_t n = a.n[t], per = a.per_block[t];
+  const int32_t len = a.row_len[t];
+  float s0 = 0.f, s1 = 0.f, s2 = 0.f;
+  auto add = [&](float pp, float gg) {
+    const float x = pen ? gg + pen_grad(pp, l1, l2x2) : gg;
+    s0 = fmaf(x, x, s0);
+    s1 += fabsf(pp);
+    s2 = fmaf(pp, pp, s2);
+  };
+  if (a.vec[t]) {
+    const int64_t nv = n >> 2, q0 = ((int64_t)b * per) >> 2, q1 = min(q0 + (per >> 2), nv);
+    const int32_t rl4 = len >> 2;
+    const float4 *p4 = reinterpret_cast<const float4 *>(p);
+    const float4 *g4 = reinterpret_cast<const float4 *>(g);
+    for (int64_t q = q0 + threadIdx.x; q < q1; q += 4 * kTB) {
+      int64_t qq[4];
+      bool on[4];
+      float4 P[4], G[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) qq[u] = q + u * kTB < q1 ? q + u * kTB : q;
+#pragma unroll
+      for (int u = 0; u < 4; ++u) on[u] = g != nullptr && (fl == nullptr || fl[pen_row(qq[u], rl4)] != 0);
+#pragma unroll
+      for (int u = 0; u < 4; ++u) P[u] = p4[qq[u]];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) G[u] = (on[u] ? g4 : p4)[qq[u]];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        if (q + u * kTB < q1) {
+          add(P[u].x, on[u] ? G[u].x : 0.f);
+          add(P[u].y, on[u] ? G[u].y : 0.f);
+          add(P[u].z, on[u] ? G[u].z : 0.f);
+          add(P[u].w, on[u] ? G[u].w : 0.f);
+        }
+      }
+    }
+    if (b == 0)  // (a flagged tensor has rows of whole pieces: no tail)
+      for (int64_t i = (nv << 2) + threadIdx.x; i < n; i += kTB) add(p[i], g ? g[i] : 0.f);
+  } else {
+    const int64_t e0 = (int64_t)b * per, e1 = min(e0 + per, n);
+    for (int64_t i = e0 + threadIdx.x; i < e1; i += 4 * kTB) {
+      int64_t ii[4];
+      bool on[4];
+      float P[4], G[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) ii[u] = i + u * kTB < e1 ? i + u * kTB : i;
+#pragma unroll
+      for (int u = 0; u < 4; ++u) on[u] = g != nullptr && (fl == nullptr || fl[pen_row(ii[u], len)] != 0);
+#pragma unroll
+      for (int u = 0; u < 4; ++u) P[u] = p[ii[u]];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) G[u] = (on[u] ? g : p)[ii[u]];
+#pragma unroll
+      for (int u = 0; u < 4; ++u)
+        if (i + u * kTB < e1) add(P[u], on[u] ? G[u] : 0.f);
+    }
+  }
+  // the *_det scheme: a fixed float tree per block -> double partials -> added in block order by the last block
+  const float t0 = block_sum(s0), t1 = block_sum(s1), t2 = block_sum(s2);
+  __shared__ int s_last;
+  __shared__ double s_stage[3][kPenSumChunk];
+  const unsigned int nb = gridDim.x;
+  if (threadIdx.x == 0) {
+    partials[(int64_t)nb + blockIdx.x] = (double)t1;
+    partials[2 * (int64_t)nb + blockIdx.x] = (double)t2;
+    s_last = det_last_block((double)t0, partials, ticket) ? 1 : 0;  // (its release covers the two stores above)
+  }
+  __syncthreads();
+  if (!s_last) return;
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+  double tot = 0.0;
+  for (unsigned int c0 = 0; c0 < nb; c0 += kPenSumChunk) {
+    const unsigned int m = min(nb - c0, (unsigned int)kPenSumChunk);
+    __syncthreads();
+    for (unsigned int k = threadIdx.x; k < 3 * m; k += kTB) s_stage[k / m][k % m] = partials[(int64_t)(k / m) * nb + c0 + k % m];
+    __syncthreads();
+    if (threadIdx.x < 3)
+      for (unsigned int k = 0; k < m; ++k) tot += s_stage[threadIdx.x][k];
+  }
+  if (threadIdx.x < 3) out3[threadIdx.x] += tot;
+  if (threadIdx.x == 0) __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+struct MultiAdamReg {
+  float *p[kMultiMax];
+  const float *g[kMultiMax];
+  const uint8_t *flags[kMultiMax];
+  float *m[kMultiMax];
+  float *v[kMultiMax];
+  int64_t n[kMultiMax];
+  float lr[kMultiMax], wd[kMultiMax];
+  int32_t row_len[kMultiMax];
+  int32_t vec[kMultiMax];
+  int64_t blk0[kMultiMax + 1];
+  int32_t n_tensors;
+};
+constexpr int kAdamRegPieces = 2;  // 16-byte pieces (or floats, on the scalar path) per thread
+__global__ __launch_bounds__(kTB) void k_adam_reg_multi(MultiAdamReg a, float l1, float l2x2, int pen, float b1, float b2,
+                                                        float eps, float bc1, float bc2_sqrt,
+                                                        const float *__restrict__ scale,
+                                                        const float *__restrict__ bc_dev) {
+  if (bc_dev) {
+    bc1 = bc_dev[0];
+    bc2_sqrt = bc_dev[1];
+  }
+  int t = 0;
+  while (t + 1 < a.n_tensors && (int64_t)blockIdx.x >= a.blk0[t + 1]) ++t;
+  const int64_t b = (int64_t)blockIdx.x - a.blk0[t];
+  float *__restrict__ p = a.p[t];
+  const float *__restrict__ g = a.g[t];
+  const uint8_t *__restrict__ fl = a.flags[t];
+  float *__restrict__ m = a.m[t];
+  float *__restrict__ v = a.v[t];
+  const int64_t n = a.n[t];
+  const int32_t len = a.row_len[t];
+  const float sc = scale ? *scale : 1.f, wd = a.wd[t];
+  const float step = a.lr[t] / bc1;
+  auto upd = [&](float &pp, float g0, float &mm, float &vv) {  // k_adam_multi's update on (g + r(p)) scale + wd p
+    float gg = (pen ? g0 + pen_grad(pp, l1, l2x2) : g0) * sc;
+    if (wd != 0.f) gg = fmaf(wd, pp, gg);
+    mm = fmaf(b1, mm, (1.f - b1) * gg);
+    vv = fmaf(b2, vv, (1.f - b2) * gg * gg);
+    const float denom = sqrtf(vv) / bc2_sqrt + eps;
+    pp -= step * (mm / denom);
+  };
+  constexpr int U = kAdamRegPieces;
+  if (a.vec[t]) {
+    const int64_t nv = n >> 2, q = b * (U * kTB) + threadIdx.x;
+    const int32_t rl4 = len >> 2;
+    float4 *p4 = reinterpret_cast<float4 *>(p);
+    const float4 *g4 = reinterpret_cast<const float4 *>(g);
+    float4 *m4 = reinterpret_cast<float4 *>(m);
+    float4 *v4 = reinterpret_cast<float4 *>(v);
+    if (q < nv) {
+      int64_t qq[U];
+      bool on[U];
+      float4 P[U], G[U], M[U], V[U];
+#pragma unroll
+      for (int u = 0; u < U; ++u) qq[u] = q + u * kTB < nv ? q + u * kTB : q;
+#pragma unroll
+      for (int u = 0; u < U; ++u) on[u] = g != nullptr && (fl == nullptr || fl[pen_row(qq[u], rl4)] != 0);
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        P[u] = p4[qq[u]];
+        M[u] = m4[qq[u]];
+        V[u] = v4[qq[u]];
+      }
+#pragma unroll
+      for (int u = 0; u < U; ++u) G[u] = (on[u] ? g4 : reinterpret_cast<const float4 *>(p))[qq[u]];
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        if (u == 0 || q + u * kTB < nv) {
+          upd(P[u].x, on[u] ? G[u].x : 0.f, M[u].x, V[u].x);
+          upd(P[u].y, on[u] ? G[u].y : 0.f, M[u].y, V[u].y);
+          upd(P[u].z, on[u] ? G[u].z : 0.f, M[u].z, V[u].z);
+          upd(P[u].w, on[u] ? G[u].w : 0.f, M[u].w, V[u].w);
+          p4[qq[u]] = P[u];
+          m4[qq[u]] = M[u];
+          v4[qq[u]] = V[u];
+        }
+      }
+    }
+    if (b == 0)
+      for (int64_t i = (nv << 2) + threadIdx.x; i < n; i += kTB) {
+        float P = p[i], M = m[i], V = v[i];
+        upd(P, g ? g[i] : 0.f, M, V);
+        p[i] = P;
+        m[i] = M;
+        v[i] = V;
+      }
+  } else {
+    const int64_t i = b * (U * kTB) + threadIdx.x;
+    if (i >= n) return;
+    int64_t ii[U];
+    bool on[U];
+    float P[U], G[U], M[U], V[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) ii[u] = i + u * kTB < n ? i + u * kTB : i;
+#pragma unroll
+    for (int u = 0; u < U; ++u) on[u] = g != nullptr && (fl == nullptr || fl[pen_row(ii[u], len)] != 0);
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      P[u] = p[ii[u]];
+      M[u] = m[ii[u]];
+      V[u] = v[ii[u]];
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) G[u] = (on[u] ? g : (const float *)p)[ii[u]];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      if (u == 0 || i + u * kTB < n) {
+        upd(P[u], on[u] ? G[u] : 0.f, M[u], V[u]);
+        p[ii[u]] = P[u];
+        m[ii[u]] = M[u];
+        v[ii[u]] = V[u];
+      }
+    }
+  }
+}
+
 // mean cross-entropy over labelled rows + its gradient w.r.t. the logits.
 // one thread per labelled row (C is small: the number of classes)
 __global__ void k_xent(const float *__restrict__ logits, int64_t ld, int C,
@@ -1144,6 +1385,90 @@ int mrgcn_adam_step_multi_f32(int32_t n_tensors, float *const *params, const flo
   const double bc2 = bc_dev ? 1.0 : 1.0 - pow((double)beta2, (double)step);
   mrgcn::k_adam_multi<<<dim3(blk), dim3(kTB), 0, (hipStream_t)stream>>>(a, beta1, beta2, eps, (float)bc1,
                                                                        (float)sqrt(bc2), grad_scale, bc_dev);
+  MRGCN_HIP_TRY(hipGetLastError());
+  return MRGCN_OK;
+}
+
+// ---- L1 / L2 penalties on dense and flagged-row parameters ------------------------------------------------------------
+int64_t mrgcn_penalty_norm_workspace(void) { return (int64_t)mrgcn::kPenMaxBlocks * 3 * (int64_t)sizeof(double); }
+
+// one tensor of a penalty list: sizes, and whether it moves as 16-byte pieces (`others`: its further base addresses)
+static int penalty_tensor(const void *param, const void *grad, uintptr_t others, int64_t numel, const uint8_t *flags,
+                          int32_t row_len, int32_t &vec) {
+  MRGCN_REQUIRE(param && numel >= 0, "parameter: NULL / numel");
+  MRGCN_REQUIRE(!flags || (row_len > 0 && numel % row_len == 0), "row flags need row_len > 0 that divides numel");
+  vec = ((((uintptr_t)param | (uintptr_t)grad | others) & 15) == 0) && (!flags || row_len % 4 == 0);
+  return MRGCN_OK;
+}
+
+int mrgcn_penalty_norm_multi_f32(int32_t n_tensors, const float *const *params, const float *const *grads,
+                                 const int64_t *numel, const uint8_t *const *row_flags, const int32_t *row_len, float l1,
+                                 float l2, double *out3, double *partials, uint32_t *ticket, void *stream) {
+  MRGCN_REQUIRE(n_tensors >= 1 && n_tensors <= mrgcn::kMultiMax, "1..16 tensors per call");
+  MRGCN_REQUIRE(params && grads && numel && out3 && partials && ticket && (!row_flags || row_len), "NULL");
+  MRGCN_REQUIRE(l1 >= 0.f && l2 >= 0.f, "l1 / l2 must not be negative");
+  mrgcn::MultiPen a{};
+  a.n_tensors = n_tensors;
+  int64_t blk = 0;
+  for (int t = 0; t < n_tensors; ++t) {
+    const uint8_t *fl = row_flags ? row_flags[t] : nullptr;
+    const int32_t len = fl ? row_len[t] : 0;
+    if (int rc = penalty_tensor(params[t], grads[t], 0, numel[t], fl, len, a.vec[t])) return rc;
+    a.p[t] = params[t]; a.g[t] = grads[t]; a.flags[t] = fl; a.n[t] = numel[t]; a.row_len[t] = len;
+    int64_t per = mrgcn::kPenTile;
+    int64_t nb = (numel[t] + per - 1) / per;
+    if (nb > mrgcn::kPenTensorBlocks) {  // (sizes only: the same grid on every device and run)
+      per = ((numel[t] + mrgcn::kPenTensorBlocks - 1) / mrgcn::kPenTensorBlocks + mrgcn::kPenTile - 1) /
+            mrgcn::kPenTile * mrgcn::kPenTile;
+      nb = (numel[t] + per - 1) / per;
+    }
+    a.per_block[t] = per;
+    a.blk0[t] = (int32_t)blk;
+    blk += nb < 1 ? 1 : nb;
+  }
+  a.blk0[n_tensors] = (int32_t)blk;
+  MRGCN_REQUIRE(blk <= mrgcn::kPenMaxBlocks, "too many elements for one launch (a tensor above 2^20 elements: its own)");
+  mrgcn::k_penalty_norm_multi<<<dim3((unsigned)blk), dim3(kTB), 0, (hipStream_t)stream>>>(
+      a, l1, 2.f * l2, (l1 > 0.f || l2 > 0.f) ? 1 : 0, out3, partials, ticket);
+  MRGCN_HIP_TRY(hipGetLastError());
+  return MRGCN_OK;
+}
+
+int mrgcn_adam_step_reg_multi_f32(int32_t n_tensors, float *const *params, const float *const *grads,
+                                  const int64_t *numel, const uint8_t *const *row_flags, const int32_t *row_len,
+                                  float *const *exp_avg, float *const *exp_avg_sq, const float *lr,
+                                  const float *weight_decay, float l1, float l2, float beta1, float beta2, float eps,
+                                  int64_t step, const float *bc_dev, const float *grad_scale, void *stream) {
+  MRGCN_REQUIRE(n_tensors >= 1 && n_tensors <= mrgcn::kMultiMax, "1..16 tensors per call");
+  MRGCN_REQUIRE(params && grads && numel && exp_avg && exp_avg_sq && lr && weight_decay && (!row_flags || row_len),
+                "NULL");
+  MRGCN_REQUIRE(step >= 1 || bc_dev, "step counts from 1");
+  MRGCN_REQUIRE(l1 >= 0.f && l2 >= 0.f, "l1 / l2 must not be negative");
+  mrgcn::MultiAdamReg a{};
+  a.n_tensors = n_tensors;
+  int64_t blk = 0;
+  const int64_t per_thread_block = (int64_t)mrgcn::kAdamRegPieces * kTB;
+  for (int t = 0; t < n_tensors; ++t) {
+    MRGCN_REQUIRE(exp_avg[t] && exp_avg_sq[t], "NULL moments");
+    const uint8_t *fl = row_flags ? row_flags[t] : nullptr;
+    const int32_t len = fl ? row_len[t] : 0;
+    if (int rc = penalty_tensor(params[t], grads[t], (uintptr_t)exp_avg[t] | (uintptr_t)exp_avg_sq[t], numel[t], fl, len,
+                                a.vec[t]))
+      return rc;
+    a.p[t] = params[t]; a.g[t] = grads[t]; a.flags[t] = fl; a.m[t] = exp_avg[t]; a.v[t] = exp_avg_sq[t];
+    a.n[t] = numel[t]; a.lr[t] = lr[t]; a.wd[t] = weight_decay[t]; a.row_len[t] = len;
+    const int64_t units = a.vec[t] ? (numel[t] >> 2) : numel[t];
+    const int64_t nb = (units + per_thread_block - 1) / per_thread_block;
+    a.blk0[t] = blk;
+    blk += nb < 1 ? 1 : nb;
+  }
+  a.blk0[n_tensors] = blk;
+  MRGCN_REQUIRE(blk <= 0x7fffffff, "too many elements for one launch");
+  const double bc1 = bc_dev ? 1.0 : 1.0 - pow((double)beta1, (double)step);
+  const double bc2 = bc_dev ? 1.0 : 1.0 - pow((double)beta2, (double)step);
+  mrgcn::k_adam_reg_multi<<<dim3((unsigned)blk), dim3(kTB), 0, (hipStream_t)stream>>>(
+      a, l1, 2.f * l2, (l1 > 0.f || l2 > 0.f) ? 1 : 0, beta1, beta2, eps, (float)bc1, (float)sqrt(bc2), grad_scale,
+      bc_dev);
   MRGCN_HIP_TRY(hipGetLastError());
   return MRGCN_OK;
 }

@@ -57,6 +57,12 @@ def _from_reference_layout(t, shape):
     return t.view(B, N, F).permute(1, 0, 2).contiguous()
 
 
+def _penalty_kernel_takes(p) -> bool:
+    """May the penalty kernels step `p`?  float32, contiguous, on the GPU, dense storage."""
+    return bool(p.is_cuda and p.dtype == torch.float32 and p.is_contiguous() and not p.is_sparse
+                and (p.grad is None or not p.grad.is_sparse))
+
+
 def merge_row_grad(p, ent):
     """Adds the gradient a row-sparse entry stands for (scaled by the clip coefficient it may carry) to `p.grad`."""
     g = dense_from_rows(p, ent)
@@ -247,54 +253,69 @@ class ClipAdam(torch.optim.Optimizer):
 
     # -- step(): the phases ------------------------------------------------------------------------------------------
     @torch.no_grad()
-    def step(self, closure=None, *, l1_lambda=0.0, l2_lambda=0.0, reg_params=None):
+    def step(self, closure=None, *, l1_lambda=0.0, l2_lambda=0.0, reg_params=None, dense_penalty="torch"):
         """`l1_lambda` / `l2_lambda`: the reference's weight penalty (node_classification.py:172-188) on the parameters
         the CALLER LEFT OUT of the penalty it put into the loss — `reg_params`, by default the node-major tables that
         carry a row-sparse gradient.  The optimizer owns their penalty whichever route they end up on: r(p) =
         l1 sign(p) + 2 l2 p joins the gradient in front of this step's clip (`max_norm`), the value
-        l1 sum|p| + l2 sum p^2 is left in `self.reg_loss` (a float32 device scalar; None when nothing was owned)."""
+        l1 sum|p| + l2 sum p^2 is left in `self.reg_loss` (a float32 device scalar; None when nothing was owned).
+        `dense_penalty`: what an owned parameter off the regularised row update gets — "torch": r(p) is added to a
+        dense `p.grad` with torch ops (a row-sparse entry is densified first); "kernel": the gradient stays as the
+        backward left it (dense, or the flagged rows of a node-kind entry) and two multi-tensor launches do the
+        penalty's share of the clip and the update (csrc/optim.hip: mrgcn_penalty_norm_multi_f32,
+        mrgcn_adam_step_reg_multi_f32), in a fixed summation order."""
+        if dense_penalty not in ("torch", "kernel"):
+            raise ValueError(f"dense_penalty must be 'torch' or 'kernel', not {dense_penalty!r}")
         l1, l2 = float(l1_lambda), float(l2_lambda)
         pen = l1 > 0 or l2 > 0
         self.reg_loss = None
-        rows, indexed, dense, torch_pen = self._route(pen, {id(p) for p in reg_params}
-                                                      if (pen and reg_params is not None) else None)
+        rows, indexed, dense, torch_pen, kernel_pen = self._route(
+            pen, {id(p) for p in reg_params} if (pen and reg_params is not None) else None,
+            pen and dense_penalty == "kernel")
         self._add_torch_penalties(torch_pen, l1, l2)
-        if not dense and not rows and not indexed:
+        if not dense and not rows and not indexed and not kernel_pen:
             return None
-        device = (dense[0][1] if dense else (rows or indexed)[0][1]).device
-        if not all(p.device == device for _, p in dense):
+        device = (dense[0][1] if dense else (rows or indexed or kernel_pen)[0][1]).device
+        if not all(p.device == device for _, p in dense) or not all(p.device == device for _, p, _ in kernel_pen):
             raise L.MrgcnError("ClipAdam: all parameters must live on one GPU")
         sc, s = self._dev_scratch(device), _stream(device)
         # (contiguous and 16-byte aligned, as the vector kernels read them: a gradient that is a view into a flat
         # bucket at an odd offset is copied)
         grads = [p.grad if (p.grad.is_contiguous() and p.grad.data_ptr() % 16 == 0) else p.grad.contiguous().clone()
                  for _, p in dense]
-        how = self._launch_plan(dense, grads, rows, indexed)
+        how = self._launch_plan(dense, grads, rows, indexed, kernel_pen)
         with torch.cuda.device(device):
             row_sumsq = self._penalty_prepass(rows, l1, l2, device, s)
+            if kernel_pen:  # one more squared norm for the clip: sum (g + r(p))^2 over the penalised tensors
+                row_sumsq = row_sumsq + [self._penalty_norm(kernel_pen, l1, l2, sc, s)]
             # capturable: one device counter (and its bias corrections) per distinct (beta1, beta2)
             betas = dict.fromkeys(tuple(float(b) for b in g["betas"]) for g in self.param_groups)
             bias = {key: self._dev_step_entry(key, device)[1] for key in betas} if self.capturable else {}
             if how.multi:
-                self._norm_in_one_launch(sc, s, how, grads, len(rows), row_sumsq, indexed, bias)
+                self._norm_in_one_launch(sc, s, how, grads, len(row_sumsq), row_sumsq, indexed, bias)
             else:
                 self._norm_per_tensor(sc, s, how, dense, grads, rows, row_sumsq, indexed, bias)
             coef_ptr = sc["coef"].data_ptr() if how.use_clip else 0
             self._step_rows(rows, bias, coef_ptr, l1, l2, s)
             self._step_indexed(indexed, bias, coef_ptr, s)
             self._step_dense(dense, grads, how, bias, coef_ptr, s)
+            self._step_penalised(kernel_pen, bias, coef_ptr, l1, l2, s)
         # the kernels wrote through raw pointers: tell autograd (and every cache keyed by a tensor's version — the gate
         # decisions of models.mrgcn) that these parameters changed, as an in-place torch update would
-        torch.autograd.graph.increment_version([p for _, p in dense] + [r.p for r in rows] + [p for _, p, _ in indexed])
+        torch.autograd.graph.increment_version([p for _, p in dense] + [r.p for r in rows] + [p for _, p, _ in indexed]
+                                               + [p for _, p, _ in kernel_pen])
 
-    def _route(self, pen, owned):
+    def _route(self, pen, owned, kernel=False):
         """Pops every row-sparse entry and sends each parameter to one update -> (`rows`: _RowGrad, `indexed`:
         (group, p, entry) of compact literal rows, `dense`: (group, p) stepped from `p.grad`, `torch_pen`: those of them
-        whose penalty this optimizer owns).  An entry stays row-sparse only while it is the parameter's whole gradient
+        whose penalty this optimizer owns, `kernel_pen`: (group, p, entry or None) — with `kernel`, the owned
+        parameters that would have been `torch_pen`, stepped by the penalty kernels and not part of `dense`).  An
+        entry stays row-sparse only while it is the parameter's whole gradient
         (`alone`); `plain` = and nothing but that gradient moves the parameter (no decay, no owned penalty).  Anything
         else is merged into `p.grad`: another term left a dense gradient there (a regulariser), no support, a shape
-        outside the kernels."""
-        rows, indexed, dense, torch_pen = [], [], [], []
+        outside the kernels — except that a node-kind entry with its own gradient buffer and flags (`g` / `cur`, no
+        `fused`) goes to `kernel_pen` as it is."""
+        rows, indexed, dense, torch_pen, kernel_pen = [], [], [], [], []
         for g in self.param_groups:
             wd = float(g["weight_decay"])
             for p in g["params"]:
@@ -312,6 +333,12 @@ class ClipAdam(torch.optim.Optimizer):
                     # every node block moves (decay, penalty): the row update over all N nodes, the loss's gradient
                     # still rebuilt from the support's dM
                     rows.append(_RowGrad(g, p, ent, True, mine))
+                elif kernel and mine and _penalty_kernel_takes(p):
+                    flagged = (ent is not None and not index and alone and ent.get("fused") is None
+                               and ent.get("g") is not None and ent.get("cur") is not None and "coef" not in ent)
+                    if ent is not None and not flagged:
+                        merge_row_grad(p, ent)
+                    kernel_pen.append((g, p, ent if flagged else None))
                 else:
                     if ent is not None:
                         merge_row_grad(p, ent)
@@ -319,7 +346,7 @@ class ClipAdam(torch.optim.Optimizer):
                         torch_pen.append(p)
                     if mine or p.grad is not None:
                         dense.append((g, p))
-        return rows, indexed, dense, torch_pen
+        return rows, indexed, dense, torch_pen, kernel_pen
 
     def _add_torch_penalties(self, torch_pen, l1, l2):
         """The owned parameters on the dense route: r(p) joins `p.grad` and the value `self.reg_loss` with torch ops."""
@@ -333,16 +360,18 @@ class ClipAdam(torch.optim.Optimizer):
                 self.reg_loss = l2 * (p * p).sum() + (0 if self.reg_loss is None else self.reg_loss)
             p.grad = r if p.grad is None else p.grad.add_(r)
 
-    def _launch_plan(self, dense, grads, rows, indexed) -> _Launch:
+    def _launch_plan(self, dense, grads, rows, indexed, kernel_pen=()) -> _Launch:
         # The dense parameters besides the node table are a handful of small tensors: their squared norms, the
         # row-sparse gradients' norms, the clip coefficient and the device step counter take ONE launch
         # (mrgcn_sumsq_clip_multi_f32) and their Adam updates another (mrgcn_adam_step_multi_f32) when every group
         # shares (beta1, beta2, eps) — the reference's groups do (tasks/utils.py:8-45 vary lr / weight_decay only).
-        groups = [g for g, _ in dense] + [r.group for r in rows] + [g for g, _, _ in indexed]
+        groups = [g for g, _ in dense] + [r.group for r in rows] + [g for g, _, _ in indexed] + \
+            [g for g, _, _ in kernel_pen]
         hyper = {(float(g["betas"][0]), float(g["betas"][1]), float(g["eps"])) for g in groups}
         small = [i for i, g in enumerate(grads) if g.numel() <= _MULTI_MAX_NUMEL]
         # (16 tensors per launch: a model with more — an MRGCN with encoders has ~40 — takes a few launches, not 2 x 40)
-        multi = _MULTI and self._dist is None and len(hyper) == 1 and len(small) >= 1 and len(rows) <= 16
+        multi = (_MULTI and self._dist is None and len(hyper) == 1 and len(small) >= 1
+                 and len(rows) + bool(kernel_pen) <= 16)
         # torch.use_deterministic_algorithms(True): every squared norm summed in block order (the _det twins)
         det = torch.are_deterministic_algorithms_enabled()
         if det:
@@ -374,6 +403,88 @@ class ClipAdam(torch.optim.Optimizer):
         if self.reg_loss is not None and self.reg_loss.dtype != torch.float32:
             self.reg_loss = self.reg_loss.float()
         return out
+
+    @staticmethod
+    def _penalty_args(items):
+        """The tensor list of one penalty launch as ctypes arrays: gradients (NULL: none this step), sizes, row flags."""
+        n = len(items)
+        gs, fl, rl = [], [], []
+        for _, p, ent in items:
+            if ent is not None:   # the flagged rows of a node-kind entry: rows off the flags are never read
+                gs.append(ent["g"].data_ptr())
+                fl.append(ent["cur"].data_ptr())
+                rl.append(p.numel() // max(p.shape[0], 1))
+            else:
+                gs.append(p.grad.data_ptr() if p.grad is not None else None)
+                fl.append(None)
+                rl.append(0)
+        return (n, (C.c_void_p * n)(*[p.data_ptr() for _, p, _ in items]), (C.c_void_p * n)(*gs),
+                (C.c_int64 * n)(*[p.numel() for _, p, _ in items]), (C.c_void_p * n)(*fl), (C.c_int32 * n)(*rl))
+
+    @staticmethod
+    def _penalty_launches(items):
+        """<= 16 tensors a launch; a tensor above _MULTI_MAX_NUMEL takes one of its own."""
+        small = [it for it in items if it[1].numel() <= _MULTI_MAX_NUMEL]
+        return [[it] for it in items if it[1].numel() > _MULTI_MAX_NUMEL] + \
+            [small[c0:c0 + 16] for c0 in range(0, len(small), 16)]
+
+    def _penalty_norm(self, kernel_pen, l1, l2, sc, s):
+        """-> the 1-element double sum (g + r(p))^2 over the penalised tensors (mrgcn_penalty_norm_multi_f32: block
+        order, the same bits on every run); l1 sum|p| + l2 sum p^2 joins `self.reg_loss`.  No gradient is rewritten."""
+        lib = L.load()
+        for _, p, ent in kernel_pen:
+            if ent is None and p.grad is not None and not (p.grad.is_contiguous() and p.grad.dtype == torch.float32):
+                p.grad = p.grad.float().contiguous()
+        if "pen3" not in sc:
+            dev = kernel_pen[0][1].device
+            sc["pen3"] = torch.zeros(3, dtype=torch.float64, device=dev)
+            sc["pen_ws"] = torch.empty(int(lib.mrgcn_penalty_norm_workspace()) // 8, dtype=torch.float64, device=dev)
+            sc["pen_ticket"] = torch.zeros((), dtype=torch.int32, device=dev)
+        out3 = sc["pen3"]
+        out3.zero_()   # (a device op inside the step: a captured step zeroes it at every replay)
+        for part in self._penalty_launches(kernel_pen):
+            n, pp, gp, nn_, fl, rl = self._penalty_args(part)
+            L.check(lib.mrgcn_penalty_norm_multi_f32(n, pp, gp, nn_, fl, rl, l1, l2, out3.data_ptr(),
+                                                     sc["pen_ws"].data_ptr(), sc["pen_ticket"].data_ptr(), s),
+                    "mrgcn_penalty_norm_multi_f32")
+        term = (l1 * out3[1] + l2 * out3[2]).float()
+        self.reg_loss = term if self.reg_loss is None else self.reg_loss + term
+        return out3[:1]
+
+    def _step_penalised(self, kernel_pen, bias, coef_ptr, l1, l2, s):
+        """Adam on the penalised tensors, every element: gg = (g + r(p)) . coef + wd . p (mrgcn_adam_step_reg_multi_f32)."""
+        if not kernel_pen:
+            return
+        lib = L.load()
+        bump("adam.reg_dense")
+        by_hyper = {}
+        for group, p, ent in kernel_pen:
+            st = self._new_state(p)
+            if ent is not None:
+                self._seed_row_flags(ent, st)
+            st["step"] += 1
+            if ent is not None:   # every node holds moments afterwards (as the regularised row update leaves it)
+                ent["ever"].fill_(1)
+                ent["ever_in"] = "any"
+            else:
+                rows = getattr(p, "_mrgcn_rows", None)
+                if rows is not None and not rows.get("dense_only"):
+                    rows["seeded_for"] = None
+            b1, b2 = group["betas"]
+            key = (float(b1), float(b2), float(group["eps"]), None if self.capturable else int(st["step"]))
+            by_hyper.setdefault(key, []).append((group, p, ent))
+        for (b1, b2, eps, _), items in by_hyper.items():
+            for c0 in range(0, len(items), 16):
+                part = items[c0:c0 + 16]
+                n, pp, gp, nn_, fl, rl = self._penalty_args(part)
+                L.check(lib.mrgcn_adam_step_reg_multi_f32(
+                    n, pp, gp, nn_, fl, rl,
+                    (C.c_void_p * n)(*[self.state[p]["exp_avg"].data_ptr() for _, p, _ in part]),
+                    (C.c_void_p * n)(*[self.state[p]["exp_avg_sq"].data_ptr() for _, p, _ in part]),
+                    (C.c_float * n)(*[float(g["lr"]) for g, _, _ in part]),
+                    (C.c_float * n)(*[float(g["weight_decay"]) for g, _, _ in part]), l1, l2, b1, b2, eps,
+                    int(self.state[part[0][1]]["step"]), bias[(b1, b2)].data_ptr() if self.capturable else 0,
+                    coef_ptr, s), "mrgcn_adam_step_reg_multi_f32")
 
     def _norm_in_one_launch(self, sc, s, how, grads, n_rows, row_sumsq, indexed, bias):
         """Total norm, clip coefficient and the device step counters when one multi-tensor launch can close the norm:
@@ -435,6 +546,8 @@ class ClipAdam(torch.optim.Optimizer):
             sums.accum(g.data_ptr(), g.numel(), sharded_sum if id(p) in sharded else sumsq, s, how.det)
         for r, sq in zip(rows, row_sumsq):  # ||g||^2 came for free with the gradient
             (sharded_sum if id(r.p) in sharded else sumsq).add_(sq.reshape(()))
+        for sq in row_sumsq[len(rows):]:    # (the penalised tensors' sum (g + r(p))^2: never sharded)
+            sumsq.add_(sq.reshape(()))
         for _, _, ent in indexed:
             sums.accum(ent["g"].data_ptr(), ent["g"].numel(), sumsq, s, how.det)
         if self._dist:

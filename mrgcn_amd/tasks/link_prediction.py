@@ -515,7 +515,44 @@ def _batch_state(batch, facts, device):
     return st
 
 
-def train_batch_step(model, batch, facts, optimizer, negatives=None, clip=1.0, slot=None, sampler=None):
+def penalty_owners(model, optimizer, on_device=True):
+    """The parameters whose L1 / L2 penalty (link_prediction.py:306-322) the optimizer's own step takes over
+    (`ClipAdam.step(l1_lambda=, l2_lambda=, reg_params=, dense_penalty="kernel")`): those whose NAME contains `weight`
+    (a bare RGCN's `layers.0.weight_I`, or the same under an `rgcn.` prefix), that the optimizer steps, that require a
+    gradient and that are float32, contiguous and — `on_device` — on the GPU; none unless the optimizer is a `ClipAdam`
+    that clips inside its own step (`max_norm` set) and is not distributed.  Everything else keeps its penalty in the
+    loss."""
+    from ..optim import ClipAdam
+    if not (isinstance(optimizer, ClipAdam) and optimizer.max_norm is not None and optimizer._dist is None):
+        return []
+    stepped = {id(p) for g in optimizer.param_groups for p in g["params"]}
+    return [p for name, p in model.named_parameters()
+            if "weight" in name and id(p) in stepped and p.requires_grad and p.dtype == torch.float32
+            and p.is_contiguous() and (p.is_cuda or not on_device)]
+
+
+def _penalised_backward_and_step(model, optimizer, loss, clip, l1_lambda, l2_lambda):
+    """backward, clip and step of a loss that carries the loop's weight penalty (:306-326) -> BCE + penalty as a device
+    scalar, the penalty taken from the parameters before the step.  The optimizer owns the penalty of
+    `penalty_owners`; the others' stays in the loss (`weight_regularisation`), so every route steps the same thing."""
+    from ..optim import clip_grad_norm_
+    from ..train import ClipAdam, weight_regularisation
+    owned = penalty_owners(model, optimizer)
+    term = weight_regularisation(model, l1_lambda, l2_lambda, skip=owned)
+    if term is not None:
+        loss = loss + term
+    loss.backward()
+    if not (isinstance(optimizer, ClipAdam) and optimizer.max_norm is not None):
+        clip_grad_norm_(model.parameters(), clip)
+    if not owned:
+        optimizer.step()
+        return loss.detach()
+    optimizer.step(l1_lambda=l1_lambda, l2_lambda=l2_lambda, reg_params=owned, dense_penalty="kernel")
+    return loss.detach() if optimizer.reg_loss is None else loss.detach() + optimizer.reg_loss
+
+
+def train_batch_step(model, batch, facts, optimizer, negatives=None, clip=1.0, slot=None, sampler=None,
+                     l1_lambda=0.0, l2_lambda=0.0):
     """One batch of train_model (link_prediction.py:226-331): 20 % of the batch's facts corrupted inside the batch
     (half the heads, half the tails replaced by batch nodes, :239-263) — drawn on the device, or `negatives` (an
     [n // 5, 3] array of batch-local triples, e.g. the reference's draws) —, DistMult scores of facts + negatives, BCE,
@@ -526,7 +563,10 @@ def train_batch_step(model, batch, facts, optimizer, negatives=None, clip=1.0, s
     gradient).  `slot` (a float32 [1] piece of the epoch's loss table on the device): the loss also goes there.
     `sampler`: any callable with `train_step`'s sampler contract — `triples, labels = sampler()`, the batch's facts
     followed by their corrupted copies and the 1 / 0 labels on the device, without synchronising — in place of the
-    batch's own `DeviceNegativeSampler`."""
+    batch's own `DeviceNegativeSampler`.  `l1_lambda` / `l2_lambda` (:306-322): l1 sum|p| + l2 sum p^2 over the
+    parameters named `weight*` joins the loss, is clipped with it and is part of the returned loss; a `ClipAdam` with
+    a max_norm takes the penalty of the weights it steps into its own step (`penalty_owners`), without an autograd
+    graph over them."""
     from ..optim import clip_grad_norm_
     from ..train import ClipAdam
     E = _embed(model, batch)
@@ -547,11 +587,14 @@ def train_batch_step(model, batch, facts, optimizer, negatives=None, clip=1.0, s
         labels[st["facts"].shape[0]:] = 0
     optimizer.zero_grad()
     loss = binary_crossentropy(score_distmult_bc(triples, E, _relations(model)), labels)
-    loss.backward()
-    if not (isinstance(optimizer, ClipAdam) and optimizer.max_norm is not None):
-        clip_grad_norm_(model.parameters(), clip)
-    optimizer.step()
-    loss = loss.detach()
+    if l1_lambda > 0 or l2_lambda > 0:
+        loss = _penalised_backward_and_step(model, optimizer, loss, clip, l1_lambda, l2_lambda)
+    else:
+        loss.backward()
+        if not (isinstance(optimizer, ClipAdam) and optimizer.max_norm is not None):
+            clip_grad_norm_(model.parameters(), clip)
+        optimizer.step()
+        loss = loss.detach()
     if slot is not None:
         slot.view(1).copy_(loss.view(1))
     return loss
@@ -564,11 +607,12 @@ def prepare_batches(batches, device):
     return batches
 
 
-def train_epoch(batches, model, optimizer, clip=1.0):
+def train_epoch(batches, model, optimizer, clip=1.0, l1_lambda=0.0, l2_lambda=0.0):
     """One epoch of train_model (:226-331): every batch once, in the fixed order of `mkbatches`; the mean of the batch
-    losses (:326-331), read back once after the last step."""
+    losses (:326-331), read back once after the last step.  `l1_lambda` / `l2_lambda`: see `train_batch_step`."""
     model.train()
-    losses = [train_batch_step(model, batch, facts, optimizer, clip=clip) for batch, facts in batches]
+    losses = [train_batch_step(model, batch, facts, optimizer, clip=clip, l1_lambda=l1_lambda, l2_lambda=l2_lambda)
+              for batch, facts in batches]
     return float(np.mean([float(x) for x in torch.stack(losses).cpu().numpy()])) if losses else float("nan")
 
 
@@ -945,19 +989,22 @@ def eval_schedule(nepoch, eval_interval, has_valid):
     return out
 
 
-def train_step(model, forward_fn, sampler, optimizer, static=None, clip=1.0):
+def train_step(model, forward_fn, sampler, optimizer, static=None, clip=1.0, l1_lambda=0.0, l2_lambda=0.0):
     """One full-batch epoch of train_model (:231-326): `triples, labels = sampler()` (a `DeviceNegativeSampler`, or any
     callable that returns the facts followed by their corrupted copies and the 1 / 0 labels on the device without
     synchronising), `forward_fn()` for the node embeddings (e.g. `lambda: model(None, A)`), DistMult scores, BCE,
     backward, the gradient clipped at `clip` — inside the step of a `ClipAdam` that has a `max_norm`, by
     `clip_grad_norm_` otherwise — and the optimizer step.  `static`: the `SortedTriples` of the facts the triples start
-    with.  Returns the loss as a device scalar; no host read, so a graph captures it."""
+    with.  `l1_lambda` / `l2_lambda`: the loop's weight penalty, as in `train_batch_step`.  Returns the loss (BCE +
+    penalty) as a device scalar; no host read, so a graph captures it."""
     from ..optim import clip_grad_norm_
     from ..train import ClipAdam
     triples, labels = sampler()
     emb = forward_fn()
     loss = binary_crossentropy(score_distmult_bc(triples, emb, _relations(model), static=static), labels)
     optimizer.zero_grad(set_to_none=True)
+    if l1_lambda > 0 or l2_lambda > 0:
+        return _penalised_backward_and_step(model, optimizer, loss, clip, l1_lambda, l2_lambda)
     loss.backward()
     if not (isinstance(optimizer, ClipAdam) and optimizer.max_norm is not None):
         clip_grad_norm_(model.parameters(), clip)
@@ -981,7 +1028,7 @@ class FitEpochs:
     (the last of them an evaluating epoch), after which the counters and rings are reset."""
 
     def __init__(self, model, forward_fn, tparts, vparts, optimizer, stopper=None, poll=8, graphed=True, sampler=None,
-                 static=None, warmup=3):
+                 static=None, warmup=3, l1_lambda=0.0, l2_lambda=0.0):
         from .. import functional as Fn
         from ..train import _COUNT_ONLY, _StopState
         dev = tparts.facts.device
@@ -1000,6 +1047,7 @@ class FitEpochs:
                 static = SortedTriples(sampler.facts, num_nodes, int(_relations(model).shape[0]))
         self.model, self.forward_fn, self.tparts, self.vparts = model, forward_fn, tparts, vparts
         self.optimizer, self.stopper, self.sampler, self.static, self.poll = optimizer, stopper, sampler, static, poll
+        self.l1_lambda, self.l2_lambda = float(l1_lambda), float(l2_lambda)
         self.loss_ctr = _StopState(dev, 1, 0.0, _COUNT_ONLY)   # counts every epoch
         self.eval_ctr = stopper.state if stopper is not None else _StopState(dev, 1, 0.0, _COUNT_ONLY)
         self.loss_ring = torch.zeros((poll, 4), dtype=torch.float32, device=dev)
@@ -1049,7 +1097,8 @@ class FitEpochs:
 
     def _train_epoch(self):
         self.model.train()
-        loss = train_step(self.model, self.forward_fn, self.sampler, self.optimizer, self.static)
+        loss = train_step(self.model, self.forward_fn, self.sampler, self.optimizer, self.static,
+                          l1_lambda=self.l1_lambda, l2_lambda=self.l2_lambda)
         self.loss_ctr.record(loss, self.loss_ring, (loss,))
         return loss
 
@@ -1121,7 +1170,8 @@ def _run_schedule(run, sched, nepoch, poll, stopper):
 
 
 def fit(model, forward_fn, train_facts, valid_facts, optimizer, nepoch, eval_interval=1, mrr_batchsize=100,
-        filter_ranks=True, early_stop=None, poll=8, graphed=True, sampler=None, warmup=3, static=None):
+        filter_ranks=True, early_stop=None, poll=8, graphed=True, sampler=None, warmup=3, static=None,
+        l1_lambda=0.0, l2_lambda=0.0):
     """The reference's full-batch link-prediction loop (train_model, link_prediction.py:191-373, with test_model
     :375-422) as a generator over its tuples `(epoch, loss, train_mrr, train_hits_at_k, valid_mrr, valid_hits_at_k)`
     — epochs from 1, `loss` a float, an mrr `{"raw", "flt"}`, hits `{"raw": [h@1, h@3, h@10], "flt": [...]}`, None
@@ -1130,7 +1180,9 @@ def fit(model, forward_fn, train_facts, valid_facts, optimizer, nepoch, eval_int
     facts are evaluated in parts of `mrr_batchsize` (`FactParts`), `valid_facts` (None: no validation) likewise; the
     early stop scores `1 - valid_mrr["raw"]` (:363).  `early_stop`: None, a DeviceEarlyStop, or a host EarlyStop as
     its configuration.  `sampler`: see `train_step`; None draws the reference's 20 % in-batch negatives on the device
-    (`DeviceNegativeSampler`, with the stored orders of the facts for the decoder's backward).
+    (`DeviceNegativeSampler`, with the stored orders of the facts for the decoder's backward).  `l1_lambda` /
+    `l2_lambda`: the loop's weight penalty (:306-322, `train_batch_step`), part of every step — captured ones too —
+    and of the yielded loss.
 
     An epoch is one of two step functions, chosen on the host from the epoch number (no device read):
     a training epoch — `train_step`, its loss into a device ring — and an evaluating epoch — the same, then ONE
@@ -1157,7 +1209,8 @@ def fit(model, forward_fn, train_facts, valid_facts, optimizer, nepoch, eval_int
     tparts = FactParts(train_facts, mrr_batchsize, filter_ranks, device=dev)
     vparts = FactParts(valid_facts, mrr_batchsize, filter_ranks, device=dev) if valid_facts is not None else None
     stopper = _as_device_stopper(early_stop, model, optimizer)
-    run = FitEpochs(model, forward_fn, tparts, vparts, optimizer, stopper, poll, graphed, sampler, static, warmup)
+    run = FitEpochs(model, forward_fn, tparts, vparts, optimizer, stopper, poll, graphed, sampler, static, warmup,
+                    l1_lambda, l2_lambda)
     sched = eval_schedule(nepoch, eval_interval, vparts is not None)
     yield from _run_schedule(run, sched, nepoch, poll, stopper)
 
@@ -1337,7 +1390,7 @@ class BatchFitEpochs:
     `_state_gen` compared and the supports' pair-sum tables refreshed in front of every replay."""
 
     def __init__(self, model, train_batches, valid_batches, optimizer, stopper=None, poll=8, graphed=True,
-                 filter_ranks=True, samplers=None, warmup=3, clip=1.0):
+                 filter_ranks=True, samplers=None, warmup=3, clip=1.0, l1_lambda=0.0, l2_lambda=0.0):
         from .. import functional as Fn
         from ..train import _COUNT_ONLY, _StopState
         train_batches, valid_batches = list(train_batches), list(valid_batches or [])
@@ -1354,6 +1407,7 @@ class BatchFitEpochs:
         self.model, self.optimizer, self.stopper, self.poll = model, optimizer, stopper, poll
         self.train_batches, self.valid_batches = train_batches, valid_batches
         self.filter_ranks, self.clip = bool(filter_ranks), clip
+        self.l1_lambda, self.l2_lambda = float(l1_lambda), float(l2_lambda)
         self.samplers = [samplers(i, b, f) if samplers is not None else None for i, (b, f) in enumerate(train_batches)]
         nt, nv = len(train_batches), len(valid_batches)
         self.loss_ctr = _StopState(dev, 1, 0.0, _COUNT_ONLY)   # counts every epoch
@@ -1410,7 +1464,7 @@ class BatchFitEpochs:
         self.model.train()   # (:232)
         for i, (batch, facts) in enumerate(self.train_batches):
             train_batch_step(self.model, batch, facts, self.optimizer, clip=self.clip, slot=self.loss_slots[i:i + 1],
-                             sampler=self.samplers[i])
+                             sampler=self.samplers[i], l1_lambda=self.l1_lambda, l2_lambda=self.l2_lambda)
         _lp_batch_means(self.loss_slots, len(self.train_batches), None, 0, None, 0, self.row)
         self.loss_ctr.record(self.row[0:1], self.loss_ring, (self.row[0:1],))
 
@@ -1452,7 +1506,8 @@ class BatchFitEpochs:
 
 
 def fit_batches(model, train_batches, valid_batches, optimizer, nepoch, eval_interval=1, filter_ranks=True,
-                early_stop=None, poll=8, graphed=True, max_graph_batches=None, warmup=3, samplers=None):
+                early_stop=None, poll=8, graphed=True, max_graph_batches=None, warmup=3, samplers=None,
+                l1_lambda=0.0, l2_lambda=0.0):
     """The reference's mini-batch link-prediction loop (train_model with gcn_batchsize > 0, link_prediction.py:224-373,
     with test_model :375-422) as a generator over its tuples `(epoch, loss, train_mrr, train_hits_at_k, valid_mrr,
     valid_hits_at_k)`, with `fit`'s contract row for row: the schedule (`eval_schedule`), the loss ring and the eval
@@ -1475,8 +1530,10 @@ def fit_batches(model, train_batches, valid_batches, optimizer, nepoch, eval_int
     largest capture measured — and every batch has a fixed structure (masked or full batches).  Otherwise the eager
     epochs run, which are equally free of synchronisation: FB15k-237's 1 011 batches run eagerly.
 
-    Out of scope: the loop's l1_lambda / l2_lambda (:306-322), literal-encoder batches inside a capture, the
-    partitioned engines."""
+    `l1_lambda` / `l2_lambda`: the loop's weight penalty (:306-322) in every batch step, eager or captured, and in
+    every recorded loss (`train_batch_step`).
+
+    Out of scope: literal-encoder batches inside a capture, the partitioned engines."""
     from ..train import _as_device_stopper
     from .node_classification import MAX_GRAPH_BATCHES, _is_fixed_structure
     train_batches, valid_batches = list(train_batches), list(valid_batches or [])
@@ -1490,6 +1547,6 @@ def fit_batches(model, train_batches, valid_batches, optimizer, nepoch, eval_int
                    and all(_is_fixed_structure(b) for b, _ in train_batches + valid_batches))
     stopper = _as_device_stopper(early_stop, model, optimizer)
     run = BatchFitEpochs(model, train_batches, valid_batches, optimizer, stopper, poll, capture, filter_ranks, samplers,
-                         warmup)
+                         warmup, l1_lambda=l1_lambda, l2_lambda=l2_lambda)
     sched = eval_schedule(nepoch, eval_interval, bool(valid_batches))
     yield from _run_schedule(run, sched, nepoch, poll, stopper)

@@ -94,6 +94,10 @@ python3 tools/nc_minibatch_probe.py --out $o/nc_minibatch_probe.json > $o/nc_min
 # (10i) the mini-batch link-prediction run loop at the FB15k-237 shape: batch_eval against the two sequences it replaces,
 # eval_batches against evaluate_batches, the eager device epochs against the host loop
 python3 tools/lp_minibatch_fit_probe.py --out $o/lp_minibatch_fit_probe.json > $o/lp_minibatch_fit_probe.txt 2> $o/lp_minibatch_fit_probe.err
+# (10j) the L1 / L2 weight penalty of the link-prediction loops at the FB15k-237 shape: the step, a whole training epoch
+# and a replayed full-batch epoch without penalties, with the penalty inside the optimizer's step, and with it written
+# into the loss by hand
+python3 tools/lp_penalty_probe.py --out $o/lp_penalty_probe.json > $o/lp_penalty_probe.txt 2> $o/lp_penalty_probe.err
 hipcc -O3 --offload-arch=gfx950 -std=c++17 tools/lab/copy_lab.hip -o /tmp/copy_lab 2>/dev/null && /tmp/copy_lab > $o/copy_lab.txt 2>&1
 python3 tools/lab/spmm_hot_lab.py > $o/spmm_hot_lab.txt 2>&1
 # the CPU suite last: the tree these artefacts describe is green
