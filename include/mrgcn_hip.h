@@ -1106,6 +1106,29 @@ int mrgcn_row_scale_f32(float *Y, int64_t ld, int64_t rows, int32_t F, const flo
 int mrgcn_row_scale_live_f32(const float *dY, int64_t ld_dY, int64_t rows, int32_t F, const float *m,
                              const uint8_t *row_flags, int32_t zero_dead, float *out, int64_t ld_out, void *stream);
 
+/* ---- keyed, filtered negatives for the link-prediction decoder (csrc/lp_negatives.hip) ----------------------------
+ * The reference corrupts 20 % of a batch's facts with nodes of the batch and never checks a draw against the known
+ * facts (mrgcn/tasks/link_prediction.py:247-264; mrgcn_corrupt_triples_i64 above is that scheme).  Here every fact
+ * i < n gets `rate` negatives, negative j of fact i in row k = i * rate + j of `out` ([n * rate, 3]): a copy of the
+ * fact whose head or tail is replaced by a candidate.  `side`: 0 = bit 0 of word z of attempt 0's block decides (set:
+ * the head), 1 = tails only, 2 = heads only.  Attempt a = 0 .. MRGCN_NEG_MAX_ATTEMPTS - 1 takes the Philox4x32-10 block
+ * of counter (k lo 32, (k >> 32) | (a << 24), position lo, position hi) under key (seed lo, seed hi ^ 0x4E454753), forms
+ * h = x << 32 | y and picks candidate c = (h * n_cand) >> 64: cand[c], or c itself when `cand` is NULL.  The attempt is
+ * refused when the pick equals the end it replaces, and — with `known_keys`, n_known ascending keys — when the key of the
+ * corrupted triple is among them: key(s, p, o) = (s * num_relations + p) * num_nodes + o on GLOBAL ids, an id of `facts`
+ * / `cand` being mapped through `to_global` when that is given (a batch's local ids).  The first accepted attempt is
+ * written and unresolved[k] (nullable, [n * rate]) = 0; when all are refused the last draw stands and unresolved[k] = 1.
+ * `state` is two int64 in DEVICE memory, {seed, position}, read by the draw; a one-thread launch behind it adds one to
+ * the position in stream order, so a captured call draws new negatives at every replay.  One thread per negative, no
+ * atomics: the result depends on the arguments and the state only.  n * rate < 2^56 (and < 2^39: one grid),
+ * num_nodes * num_relations * num_nodes < 2^63; the ids in facts / cand / to_global are the caller's to keep in range.
+ * (mrgcn_amd/host.py: negatives_draw is the bit-exact host mirror.) */
+#define MRGCN_NEG_MAX_ATTEMPTS 8
+int mrgcn_negatives_draw_i64(const int64_t *facts, int64_t n, int32_t rate, const int64_t *cand, int64_t n_cand,
+                             const int64_t *to_global, const int64_t *known_keys, int64_t n_known, int64_t num_nodes,
+                             int64_t num_relations, int32_t side, int64_t *state, int64_t *out, uint8_t *unresolved,
+                             void *stream);
+
 /* ---- validation and early stopping inside a replayed epoch (csrc/early_stop.hip) ---------------------------------
  * Evaluation of a label set: loss_out = mean cross-entropy of the rows logits[idx[i], :C] (max-subtracted
  * log-sum-exp, as mrgcn_softmax_xent_rows_f32), correct_out = how many of those rows have their arg-max at target[i]

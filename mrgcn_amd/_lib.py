@@ -280,6 +280,7 @@ SIGNATURES = {
     "mrgcn_node_dropout_draw_f32": (C.c_int, [_p, _i64, _i64, _i32, _i32, _i64, C.c_float, _p, _i32, _p]),
     "mrgcn_row_scale_f32": (C.c_int, [_p, _i64, _i64, _i32, _p, _p]),
     "mrgcn_row_scale_live_f32": (C.c_int, [_p, _i64, _i64, _i32, _p, _p, _i32, _p, _i64, _p]),
+    "mrgcn_negatives_draw_i64": (C.c_int, [_p, _i64, _i32, _p, _i64, _p, _p, _i64, _i64, _i64, _i32, _p, _p, _p, _p]),
     "mrgcn_xent_eval_workspace": (C.c_int64, []),
     "mrgcn_xent_eval_single_block_rows": (C.c_int64, []),
     "mrgcn_xent_eval_rows_f32": (C.c_int, [_p, _i64, _i32, _p, _p, _i64, _p, _p, _p, _p, _p]),

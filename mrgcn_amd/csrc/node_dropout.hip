@@ -2,7 +2,7 @@
 // rows scaled by it).
 //
 //   mrgcn_node_dropout_draw_f32   the masks of one step, drawn with Philox4x32-10 (Salmon et al., SC'11 — the public
-//                                 counter-based generator, written out below) from a seed and a stream position that
+//                                 counter-based generator, written out in philox.hpp) from a seed and a stream position that
 //                                 live in device memory; the position is advanced by a one-thread launch behind the
 //                                 draw, so a replayed hipGraph draws fresh masks on every replay
 //   mrgcn_row_scale_f32           Y[r, 0:F] *= m[r] in place on rows with a leading dimension (the forward)
@@ -10,37 +10,14 @@
 //
 // All three are one-shot grids of 16-byte accesses: a thread owns one float4 and leaves.
 #include "common.hpp"
+#include "philox.hpp"
 
 namespace mrgcn {
 namespace {
 
 constexpr int kTB = 256;
 
-// ---- Philox4x32-10 -------------------------------------------------------------------------------------------------
-constexpr uint32_t kPhiloxM0 = 0xD2511F53u, kPhiloxM1 = 0xCD9E8D57u;
-constexpr uint32_t kPhiloxW0 = 0x9E3779B9u, kPhiloxW1 = 0xBB67AE85u;
-
-struct U4 {
-  uint32_t x, y, z, w;
-};
-
-__device__ __forceinline__ U4 philox4x32_10(U4 c, uint32_t k0, uint32_t k1) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const uint64_t p0 = (uint64_t)kPhiloxM0 * c.x;
-    const uint64_t p1 = (uint64_t)kPhiloxM1 * c.z;
-    U4 n;
-    n.x = (uint32_t)(p1 >> 32) ^ c.y ^ k0;
-    n.y = (uint32_t)p1;
-    n.z = (uint32_t)(p0 >> 32) ^ c.w ^ k1;
-    n.w = (uint32_t)p0;
-    c = n;
-    k0 += kPhiloxW0;
-    k1 += kPhiloxW1;
-  }
-  return c;
-}
-
+// ---- the draw (Philox4x32-10: philox.hpp) ----------------------------------------------------------------------------
 // One thread draws the four nodes 4g .. 4g+3 of one layer: counter (g, layer, position lo, position hi), key (seed lo,
 // seed hi) — a node's value depends on nothing else, whatever the grid.  A node is dropped when its 32-bit word is
 // below `threshold` (= floor(p * 2^32): 0 keeps every node, 2^32 drops every node).

@@ -79,3 +79,83 @@ def node_dropout_mask(n: int, p: float, seed: int, position: int, layer: int):
     u = np.stack(words, axis=1).reshape(-1)[:n]
     return np.where(u < np.uint64(node_dropout_threshold(p)), np.float32(0.0), node_dropout_keep_value(p)).astype(
         np.float32)
+
+
+# ---- keyed, filtered negatives: the host mirror of mrgcn_negatives_draw_i64 (csrc/lp_negatives.hip) -------------------
+NEG_MAX_ATTEMPTS = 8     # include/mrgcn_hip.h: MRGCN_NEG_MAX_ATTEMPTS
+NEG_KEY_TAG = 0x4E454753  # xor-ed into the key's high word: another stream than node dropout's under the same seed
+NEG_SIDES = {"both": 0, "tail": 1, "head": 2}
+
+
+def fact_keys(known, num_nodes: int, num_relations: int):
+    """key(s, p, o) = (s * num_relations + p) * num_nodes + o of every row of `known` ([m, 3]), sorted ascending, as
+    uint64 — the fact index a draw is checked against."""
+    import numpy as np
+    N, R = int(num_nodes), int(num_relations)
+    if N < 1 or R < 1 or N * R * N >= 1 << 63:
+        raise ValueError("fact_keys: num_nodes * num_relations * num_nodes has to stay below 2^63")
+    k = np.asarray(known, dtype=np.int64).reshape(-1, 3).astype(np.uint64)
+    return np.sort((k[:, 0] * np.uint64(R) + k[:, 1]) * np.uint64(N) + k[:, 2])
+
+
+def _mul_hi64(h, n: int):
+    """(h * n) >> 64 for uint64 `h` and 1 <= n < 2^63."""
+    import numpy as np
+    if n < 1 << 32:   # h = x << 32 | y:  h n = (x n << 32) + y n, both products below 2^64
+        x, y = h >> np.uint64(32), h & np.uint64(0xFFFFFFFF)
+        return (x * np.uint64(n) + ((y * np.uint64(n)) >> np.uint64(32))) >> np.uint64(32)
+    return np.array([(int(v) * n) >> 64 for v in h], dtype=np.uint64)
+
+
+def negatives_draw(facts, rate, n_cand, num_nodes, num_relations, known_keys, seed, position, side=0, cand=None,
+                   to_global=None):
+    """`mrgcn_negatives_draw_i64` in numpy: (out int64 [n * rate, 3], unresolved uint8 [n * rate]) for the state
+    (seed, position).  Negative k = i * rate + j of fact i: attempt a < NEG_MAX_ATTEMPTS takes the Philox block of
+    counter (k lo, (k >> 32) | (a << 24), position lo, position hi) under key (seed lo, seed hi ^ NEG_KEY_TAG), picks
+    candidate ((x << 32 | y) * n_cand) >> 64 (through `cand` when given) and is refused when the pick is the end it
+    replaces or the corrupted triple's key — on global ids, through `to_global` when given — is in `known_keys` (sorted;
+    None or False: no such check).  `side`: 0 = bit 0 of word z of attempt 0 (set: the head), 1 = tails, 2 = heads."""
+    import numpy as np
+    facts = np.asarray(facts, dtype=np.int64).reshape(-1, 3)
+    n, rate, n_cand, N, R = facts.shape[0], int(rate), int(n_cand), int(num_nodes), int(num_relations)
+    side = NEG_SIDES.get(side, side)
+    if rate < 1 or n_cand < 1 or n * rate >= 1 << 56 or side not in (0, 1, 2):
+        raise ValueError("negatives_draw: rate >= 1, n_cand >= 1, n * rate < 2^56, side 0 / 1 / 2")
+    seed, position = int(seed) & 0xFFFFFFFFFFFFFFFF, int(position) & 0xFFFFFFFFFFFFFFFF
+    key = (seed & 0xFFFFFFFF, (seed >> 32) ^ NEG_KEY_TAG)
+    keys = None if known_keys is None or known_keys is False else np.asarray(known_keys, dtype=np.uint64)
+    if keys is not None and keys.size == 0:
+        keys = None
+    cand = None if cand is None else np.asarray(cand, dtype=np.int64)
+    G = (lambda v: v) if to_global is None or keys is None else (lambda v, t=np.asarray(to_global, np.int64): t[v])
+    total = n * rate
+    k = np.arange(total, dtype=np.uint64)
+    src = facts[np.arange(total) // rate]
+    s, p, o = src[:, 0].copy(), src[:, 1], src[:, 2].copy()
+    head = np.full(total, side == 2)
+    pick = np.zeros(total, dtype=np.int64)
+    pending = np.arange(total)
+    for a in range(NEG_MAX_ATTEMPTS):
+        if pending.size == 0:
+            break
+        kk = k[pending]
+        x, y, z, _ = philox4x32_10((kk & np.uint64(0xFFFFFFFF), (kk >> np.uint64(32)) | np.uint64(a << 24),
+                                    position & 0xFFFFFFFF, position >> 32), key)
+        if a == 0 and side == 0:
+            head = (z & np.uint64(1)) != 0
+        c = _mul_hi64((x << np.uint64(32)) | y, n_cand).astype(np.int64)
+        pk = c if cand is None else cand[c]
+        pick[pending] = pk
+        hd, ss, pp, oo = head[pending], s[pending], p[pending], o[pending]
+        refused = pk == np.where(hd, ss, oo)
+        if keys is not None:
+            gp, gs, go = G(pk).astype(np.uint64), G(ss).astype(np.uint64), G(oo).astype(np.uint64)
+            pr = pp.astype(np.uint64)
+            ck = np.where(hd, (gp * np.uint64(R) + pr) * np.uint64(N) + go, (gs * np.uint64(R) + pr) * np.uint64(N) + gp)
+            at = np.minimum(np.searchsorted(keys, ck), keys.size - 1)
+            refused |= keys[at] == ck
+        pending = pending[refused]
+    out = np.stack([np.where(head, pick, s), p, np.where(head, o, pick)], axis=1).astype(np.int64)
+    unresolved = np.zeros(total, dtype=np.uint8)
+    unresolved[pending] = 1
+    return out, unresolved

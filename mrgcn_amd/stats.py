@@ -25,7 +25,9 @@ def stats() -> dict:
     `weight_I.wide_feat` (wide masked layers with a feature term, and those of them with an input term),
     `node_dropout.device` (layers that applied a node-dropout mask on the device: `RGCN.set_node_dropout("device")`).
     `backward.dw_pair_sums` (layer backwards whose dW read the table of per-(row, relation) sums of a constant input
-    instead of gathering X rows), `dw_pair_sums.build` (how often such a table was built or rebuilt).
+    instead of gathering X rows), `dw_pair_sums.build` (how often such a table was built or rebuilt),
+    `lp.negatives.keyed` (calls of a `tasks.link_prediction.NegativeSampler`: keyed, filtered negatives drawn on the
+    device; a call inside a stream capture counts once, its replays do not).
     Under `torch.use_deterministic_algorithms(True)`: `deterministic.distmult_bwd` (DistMult backwards on the owner
     form), `deterministic.bce` (BCE losses summed in block order), `deterministic.sumsq` (clips whose squared norms were
     summed in block order: ClipAdam steps and `optim.clip_grad_norm_` calls), `deterministic.wide_input` (wide

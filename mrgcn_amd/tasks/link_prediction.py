@@ -365,6 +365,118 @@ class DeviceNegativeSampler:
         return self.buf, self.labels
 
 
+def _fact_keys_device(triples: torch.Tensor, num_nodes: int, num_relations: int, to_global=None) -> torch.Tensor:
+    """`host.fact_keys` with torch ops on the triples' device (built once per sampler: no kernel of its own)."""
+    s_, p_, o_ = triples[:, 0], triples[:, 1], triples[:, 2]
+    if to_global is not None:
+        s_, o_ = to_global[s_], to_global[o_]
+    return torch.sort((s_ * int(num_relations) + p_) * int(num_nodes) + o_).values.contiguous()
+
+
+class NegativeSampler:
+    """`rate` negatives per fact, corrupted against `candidates` (None: every node 0 .. num_nodes - 1) and refused when
+    they are known facts — what the reference's sampler (link_prediction.py:247-264: 20 % of the facts, nodes of the
+    batch, never checked; `DeviceNegativeSampler`) does not offer.  `DeviceNegativeSampler`'s contract: the facts sit at
+    the head of one [n * (1 + rate), 3] buffer (`.facts`, `.buf`), `.labels` (n ones, n * rate zeros) is built once,
+    `triples, labels = sampler()` is two launches (mrgcn_negatives_draw_i64: the draw and the move of its position) and
+    returns the same tensors every call, nothing synchronised — capturable; negative j of fact i is row n + i * rate + j.
+
+    `known`: None — the facts themselves —, an [m, 3] array or tensor of GLOBAL triples (train + valid + test,
+    typically) or False (unfiltered: only the fact's own end is refused); their sorted keys are built here, once.
+    `to_global` (an id tensor): the facts and candidates hold local ids, position i standing for node to_global[i] of
+    the graph the keys speak of.  `side`: "both" (a random bit per negative), "tail" or "head".  `seed` (None:
+    `torch.initial_seed()`) and the position live in `.state`, two int64 on the device; `reseed` rewrites them in place,
+    also under a captured graph.  `.unresolved` flags the negatives whose MRGCN_NEG_MAX_ATTEMPTS draws were all refused
+    (the last draw stands: it may be a known fact with label 0); `num_unresolved()` reads the count back."""
+
+    def __init__(self, facts, num_nodes, num_relations, rate=1, known=None, candidates=None, to_global=None,
+                 side="both", seed=None):
+        from .. import functional as Fn
+        from ..host import NEG_SIDES
+        facts = torch.as_tensor(np.asarray(facts) if not torch.is_tensor(facts) else facts).long()
+        if facts.dim() != 2 or facts.shape[1] != 3:
+            raise ValueError("NegativeSampler: facts must be [n, 3]")
+        if not facts.is_cuda:
+            facts = facts.cuda()
+        dev = facts.device
+        if side not in NEG_SIDES:
+            raise ValueError(f"NegativeSampler: side is one of {sorted(NEG_SIDES)}, not {side!r}")
+        n, rate = int(facts.shape[0]), int(rate)
+        N, R = int(num_nodes), int(num_relations)
+        if rate < 1 or N < 1 or R < 1 or N * R * N >= 1 << 63:
+            raise ValueError("NegativeSampler: rate >= 1 and num_nodes * num_relations * num_nodes < 2^63")
+        self.n, self.rate, self.num_nodes, self.num_relations, self.side = n, rate, N, R, NEG_SIDES[side]
+        self.buf = torch.empty((n * (1 + rate), 3), dtype=torch.int64, device=dev)
+        self.buf[:n] = facts
+        self.facts = self.buf[:n]
+        self.labels = torch.ones(n * (1 + rate), dtype=torch.float32, device=dev)
+        self.labels[n:] = 0
+        self.unresolved = torch.zeros(n * rate, dtype=torch.uint8, device=dev)
+        self.to_global = None if to_global is None else torch.as_tensor(to_global).long().to(dev).contiguous()
+        if candidates is None:
+            self.candidates, self.n_cand = None, (N if self.to_global is None else int(self.to_global.numel()))
+        else:
+            self.candidates = torch.as_tensor(candidates).long().to(dev).contiguous()
+            self.n_cand = int(self.candidates.numel())
+        if self.n_cand < 1:
+            raise ValueError("NegativeSampler: no candidates")
+        if known is False:
+            self.keys = None
+        elif known is None:
+            self.keys = _fact_keys_device(self.facts, N, R, self.to_global)
+        else:
+            self.keys = _fact_keys_device(_triples(known.cpu().numpy() if torch.is_tensor(known) else known, dev), N, R)
+        if self.keys is not None and self.keys.numel() == 0:
+            self.keys = None
+        self.state = Fn.node_dropout_state(torch.initial_seed() if seed is None else seed, 0, dev)
+
+    def reseed(self, seed, position=0):
+        """Rewrites {seed, position} in place (a copy into `.state`: the captured launches read the same memory)."""
+        from .. import functional as Fn
+        self.state.copy_(Fn.node_dropout_state(seed, position, self.state.device))
+
+    def num_unresolved(self) -> int:
+        return int(self.unresolved.sum())
+
+    def __call__(self):
+        with torch.cuda.device(self.buf.device):
+            _lib.check(_lib.load().mrgcn_negatives_draw_i64(
+                _ptr(self.buf), self.n, self.rate, _ptr(self.candidates), self.n_cand, _ptr(self.to_global),
+                _ptr(self.keys), int(self.keys.numel()) if self.keys is not None else 0, self.num_nodes,
+                self.num_relations, self.side, _ptr(self.state), C.c_void_p(self.buf.data_ptr() + 24 * self.n),
+                _ptr(self.unresolved), _stream()), "negatives_draw")
+        bump("lp.negatives.keyed")
+        return self.buf, self.labels
+
+
+def batch_negative_samplers(num_nodes, num_relations, rate=1, known=None, side="both", seed=None):
+    """The `samplers` factory of `fit_batches` / `BatchFitEpochs` for keyed negatives: `samplers(i, batch, facts)` is a
+    `NegativeSampler` over training batch i's facts whose candidates are the batch's local ids
+    0 .. len(batch.node_index) - 1 (the nodes the batch has embeddings for) and whose filter is the GLOBAL one — local
+    ids go through `batch.node_index`; a batch's facts keep their global relation ids (`mkbatches`).  `known`: None —
+    each batch's own facts —, global triples, or False, as `NegativeSampler`'s.  Sampler i draws under `seed + i`
+    (None: `torch.initial_seed()`)."""
+    base = torch.initial_seed() if seed is None else int(seed)
+    shared: dict = {}   # device -> the sorted keys of `known`, built once for all batches
+
+    def samplers(i, batch, facts):
+        st = getattr(batch, "_mrgcn_lp", None)
+        dev = st["device"] if st is not None else torch.device("cuda", torch.cuda.current_device())
+        f = st["facts"] if st is not None else torch.as_tensor(np.asarray(facts), dtype=torch.int64).to(dev)
+        node_index = torch.as_tensor(np.asarray(batch.node_index) if not torch.is_tensor(batch.node_index)
+                                     else batch.node_index).long().to(dev)
+        own = known if known is None or known is False else False
+        smp = NegativeSampler(f, num_nodes, num_relations, rate=rate, known=own, to_global=node_index, side=side,
+                              seed=base + i)
+        if known is not None and known is not False:
+            if dev not in shared:
+                shared[dev] = _fact_keys_device(
+                    _triples(known.cpu().numpy() if torch.is_tensor(known) else known, dev), num_nodes, num_relations)
+            smp.keys = shared[dev] if shared[dev].numel() else None
+        return smp
+    return samplers
+
+
 def filter_lists(data: np.ndarray):
     """The filter of compute_ranks_fast(filtered=True) (truedicts :568-591 + filter_scores_
     :667-689) as CSR lists: per fact, the sorted nodes that are other true objects of (s, p)

@@ -98,6 +98,12 @@ python3 tools/lp_minibatch_fit_probe.py --out $o/lp_minibatch_fit_probe.json > $
 # and a replayed full-batch epoch without penalties, with the penalty inside the optimizer's step, and with it written
 # into the loss by hand
 python3 tools/lp_penalty_probe.py --out $o/lp_penalty_probe.json > $o/lp_penalty_probe.txt 2> $o/lp_penalty_probe.err
+# (10k) keyed, filtered negatives at the FB15k-237 shape: the sampler call at 1 and 10 negatives per fact, filtered and
+# unfiltered, next to the default sampler's; the replayed training epoch of fit with each.  The parent rows of DESIGN
+# section 19 are the PARENT commit's on the same box: check the parent out beside this tree, build it, copy
+# tools/lp_negatives_probe.py into it and run `python3 tools/lp_negatives_probe.py --rows default --out <file>` there
+# first; LP_NEGATIVES_PARENT_JSON=<file> then puts them into the result.  Without it the file holds this tree's rows only.
+python3 tools/lp_negatives_probe.py ${LP_NEGATIVES_PARENT_JSON:+--parent $LP_NEGATIVES_PARENT_JSON} --out $o/lp_negatives_probe.json > $o/lp_negatives_probe.txt 2> $o/lp_negatives_probe.err
 hipcc -O3 --offload-arch=gfx950 -std=c++17 tools/lab/copy_lab.hip -o /tmp/copy_lab 2>/dev/null && /tmp/copy_lab > $o/copy_lab.txt 2>&1
 python3 tools/lab/spmm_hot_lab.py > $o/spmm_hot_lab.txt 2>&1
 # the CPU suite last: the tree these artefacts describe is green
