@@ -1129,6 +1129,43 @@ int mrgcn_negatives_draw_i64(const int64_t *facts, int64_t n, int32_t rate, cons
                              int64_t num_relations, int32_t side, int64_t *state, int64_t *out, uint8_t *unresolved,
                              void *stream);
 
+/* ---- grouped DistMult loss over a fact's keyed negatives (csrc/distmult_group.hip) --------------------------------
+ * The decoder of mrgcn/tasks/link_prediction.py:645-665 (scores) and :550-554 (loss) for triples in the layout of
+ * mrgcn_negatives_draw_i64's sampler: rows [0, n) the facts, row n + i * rate + j negative j of fact i, which has fact
+ * i's predicate and one of its ends.  A negative whose column 0 differs from the fact's subject counts as
+ * head-corrupted, any other as tail-corrupted (so a negative equal to its fact is a tail negative with the fact's own
+ * object).  A wave owns a group: the fact's three rows are read once, one row per negative.
+ * _supported: 1 when the group kernels take the shape — rows of whole 16-byte pieces (H % 4 == 0, H <= 256, ldE / ldR
+ *   multiples of 4, 16-byte aligned bases), ids and n * (1 + rate) below 2^31 —, else 0 (the caller scores the flat
+ *   triples instead).
+ * _fwd: scores [n (1 + rate)] (bit for bit mrgcn_distmult_score_f32's on the same rows), dscores = dloss / dscore in
+ *   the same layout and *loss WRITTEN: block partials added in a fixed order, no float atomic.  loss_kind
+ *   MRGCN_GROUP_LOSS_BCE: BCEWithLogitsLoss(pos_weight), mean over all n (1 + rate) scores — term
+ *   (1 - y) x + (1 + (w - 1) y) (log1p(exp(-|x|)) + max(-x, 0)), gradient ((1 + (w - 1) y) sigmoid(x) - w y) / count.
+ *   MRGCN_GROUP_LOSS_SOFTMAX: the mean over facts of -log softmax of the fact's score among its 1 + rate scores
+ *   (pos_weight unread).  workspace: mrgcn_distmult_group_fwd_workspace() bytes.
+ * _bwd: dE / dRel += the gradients for dscores times *upstream (a float in DEVICE memory: no host read).  Without the
+ *   orders (all three NULL) everything is added by row atomics (mini-batches).  With the three orders of the FACTS by
+ *   subject / predicate / object (SortedTriples) the group pass stores three rows per fact to scratch, which are summed
+ *   along the orders, and the negatives' own rows are summed along a radix sort by their changed end over the bits of
+ *   num_nodes - 1; workspace then: 16-byte aligned, mrgcn_distmult_group_bwd_workspace(n, rate, H) bytes (-1 for sizes
+ *   it does not take).  Float atomics at run ends: not bit-reproducible.  No host synchronisation; capturable. */
+#define MRGCN_GROUP_LOSS_BCE 0
+#define MRGCN_GROUP_LOSS_SOFTMAX 1
+int32_t mrgcn_distmult_group_supported(const float *E, int64_t ldE, const float *Rel, int64_t ldR, int32_t H,
+                                       int64_t num_nodes, int64_t num_relations, int64_t n, int32_t rate);
+int64_t mrgcn_distmult_group_fwd_workspace(void);
+int mrgcn_distmult_group_fwd_f32(const float *E, int64_t ldE, const float *Rel, int64_t ldR, int32_t H,
+                                 const int64_t *triples, int64_t n, int32_t rate, int32_t loss_kind, float pos_weight,
+                                 float *scores, float *dscores, float *loss, void *workspace, int64_t workspace_bytes,
+                                 void *stream);
+int64_t mrgcn_distmult_group_bwd_workspace(int64_t n, int32_t rate, int32_t H);
+int mrgcn_distmult_group_bwd_f32(const float *E, int64_t ldE, const float *Rel, int64_t ldR, int32_t H,
+                                 const int64_t *triples, int64_t n, int32_t rate, const float *dscores,
+                                 const float *upstream, int64_t num_nodes, const int64_t *order_s,
+                                 const int64_t *order_p, const int64_t *order_o, float *dE, int64_t lddE, float *dRel,
+                                 int64_t lddR, void *workspace, int64_t workspace_bytes, void *stream);
+
 /* ---- validation and early stopping inside a replayed epoch (csrc/early_stop.hip) ---------------------------------
  * Evaluation of a label set: loss_out = mean cross-entropy of the rows logits[idx[i], :C] (max-subtracted
  * log-sum-exp, as mrgcn_softmax_xent_rows_f32), correct_out = how many of those rows have their arg-max at target[i]

@@ -281,6 +281,13 @@ SIGNATURES = {
     "mrgcn_row_scale_f32": (C.c_int, [_p, _i64, _i64, _i32, _p, _p]),
     "mrgcn_row_scale_live_f32": (C.c_int, [_p, _i64, _i64, _i32, _p, _p, _i32, _p, _i64, _p]),
     "mrgcn_negatives_draw_i64": (C.c_int, [_p, _i64, _i32, _p, _i64, _p, _p, _i64, _i64, _i64, _i32, _p, _p, _p, _p]),
+    "mrgcn_distmult_group_supported": (_i32, [_p, _i64, _p, _i64, _i32, _i64, _i64, _i64, _i32]),
+    "mrgcn_distmult_group_fwd_workspace": (C.c_int64, []),
+    "mrgcn_distmult_group_fwd_f32": (C.c_int, [_p, _i64, _p, _i64, _i32, _p, _i64, _i32, _i32, C.c_float, _p, _p, _p, _p,
+                                               _i64, _p]),
+    "mrgcn_distmult_group_bwd_workspace": (C.c_int64, [_i64, _i32, _i32]),
+    "mrgcn_distmult_group_bwd_f32": (C.c_int, [_p, _i64, _p, _i64, _i32, _p, _i64, _i32, _p, _p, _i64, _p, _p, _p, _p,
+                                               _i64, _p, _i64, _p, _i64, _p]),
     "mrgcn_xent_eval_workspace": (C.c_int64, []),
     "mrgcn_xent_eval_single_block_rows": (C.c_int64, []),
     "mrgcn_xent_eval_rows_f32": (C.c_int, [_p, _i64, _i32, _p, _p, _i64, _p, _p, _p, _p, _p]),

@@ -27,7 +27,9 @@ def stats() -> dict:
     `backward.dw_pair_sums` (layer backwards whose dW read the table of per-(row, relation) sums of a constant input
     instead of gathering X rows), `dw_pair_sums.build` (how often such a table was built or rebuilt),
     `lp.negatives.keyed` (calls of a `tasks.link_prediction.NegativeSampler`: keyed, filtered negatives drawn on the
-    device; a call inside a stream capture counts once, its replays do not).
+    device; a call inside a stream capture counts once, its replays do not), `lp.decoder.grouped` (calls of
+    `tasks.link_prediction.group_loss`, counted the same way) / `lp.decoder.grouped.fallback` (those of them that scored
+    the flat triples and took torch's loss: rows the group kernels do not take, or the deterministic flag).
     Under `torch.use_deterministic_algorithms(True)`: `deterministic.distmult_bwd` (DistMult backwards on the owner
     form), `deterministic.bce` (BCE losses summed in block order), `deterministic.sumsq` (clips whose squared norms were
     summed in block order: ClipAdam steps and `optim.clip_grad_norm_` calls), `deterministic.wide_input` (wide

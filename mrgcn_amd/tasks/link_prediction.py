@@ -279,6 +279,222 @@ def binary_crossentropy(Y_hat, Y, criterion=None):
     return _BceLogits.apply(Y_hat.float(), Y.to(Y_hat.device).float().contiguous())
 
 
+# ---- the grouped decoder: a fact and its keyed negatives scored and differentiated as one group ---------------------
+GROUP_LOSSES = {"bce": 0, "softmax": 1}   # include/mrgcn_hip.h: MRGCN_GROUP_LOSS_*
+_GROUP_SORTED_MIN = 1024   # facts from which the backward sums stored rows along the stored orders (below: row atomics)
+
+
+def check_groups(triples, num_facts, rate):
+    """The layout contract of the grouped decoder, as torch ops (CPU or GPU tensors; synchronises): `triples` is int64
+    [num_facts * (1 + rate), 3], rows [0, num_facts) the facts, row num_facts + i * rate + j negative j of fact i, which
+    has fact i's predicate and at least one of its two ends.  Raises `MrgcnError` naming the first offending row."""
+    n, rate = int(num_facts), int(rate)
+    t = torch.as_tensor(triples)
+    if n < 1 or rate < 1:
+        raise _lib.MrgcnError("check_groups: num_facts >= 1 and rate >= 1")
+    if t.dim() != 2 or t.shape[1] != 3 or t.dtype != torch.int64:
+        raise _lib.MrgcnError("check_groups: triples are int64 [num_facts * (1 + rate), 3]")
+    if t.shape[0] != n * (1 + rate):
+        raise _lib.MrgcnError(f"check_groups: {t.shape[0]} rows for {n} facts at rate {rate}: "
+                              f"{n * (1 + rate)} expected")
+    facts = t[:n].repeat_interleave(rate, dim=0)
+    neg = t[n:]
+    bad_p = neg[:, 1] != facts[:, 1]
+    bad_e = (neg[:, 0] != facts[:, 0]) & (neg[:, 2] != facts[:, 2])
+    bad = bad_p | bad_e
+    if bool(bad.any()):
+        k = int(torch.nonzero(bad)[0])
+        what = "another predicate than" if bool(bad_p[k]) else "neither end of"
+        raise _lib.MrgcnError(f"check_groups: row {n + k} (negative {k % rate} of fact {k // rate}) has {what} its fact: "
+                              f"{tuple(int(v) for v in neg[k])} against {tuple(int(v) for v in t[k // rate])}")
+
+
+def _check_group_ids(t, E, Rel, who):
+    """The ids of the triples address rows of the embeddings (the kernels do not look; synchronises)."""
+    lo, hi = t.min(0).values.tolist(), t.max(0).values.tolist()
+    if min(lo) < 0 or max(hi[0], hi[2]) >= E.shape[0] or hi[1] >= Rel.shape[0]:
+        raise _lib.MrgcnError(f"{who}: an id of the triples is outside the embeddings")
+
+
+def _group_ws(owner, device, what: str, nbytes: int) -> torch.Tensor:
+    """Scratch of the grouped decoder, allocated once and kept: on the facts' `SortedTriples` when there is one
+    (`owner`), else with the deterministic entries' scratch (fully written before it is read)."""
+    if owner is None:
+        return _det_scratch(device, what, nbytes)
+    ws = owner.__dict__.setdefault("_group_ws", {})
+    t = ws.get(what)
+    if t is None or t.numel() < nbytes:
+        t = ws[what] = torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=device)
+    return t
+
+
+class _GroupLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, E, Rel, triples, n, rate, kind, weight, static):
+        lib = _lib.load()
+        total = triples.shape[0]
+        scores = torch.empty(total, dtype=torch.float32, device=E.device)
+        g = torch.empty(total, dtype=torch.float32, device=E.device)
+        loss = torch.empty((), dtype=torch.float32, device=E.device)
+        ws = _group_ws(static, E.device, "group_fwd", int(lib.mrgcn_distmult_group_fwd_workspace()))
+        _lib.check(lib.mrgcn_distmult_group_fwd_f32(
+            _ptr(E), E.stride(0), _ptr(Rel), Rel.stride(0), E.shape[1], _ptr(triples), n, rate, kind, weight,
+            _ptr(scores), _ptr(g), _ptr(loss), _ptr(ws), ws.numel(), _stream()), "distmult_group_fwd")
+        ctx.save_for_backward(E, Rel, triples, g)
+        ctx.group = (n, rate, static)
+        ctx.mark_non_differentiable(scores)
+        return loss, scores
+
+    @staticmethod
+    def backward(ctx, gl, _gs):
+        E, Rel, triples, g = ctx.saved_tensors
+        n, rate, st = ctx.group
+        lib = _lib.load()
+        gl = gl.contiguous().float()
+        # (both gradients out of ONE zeroed buffer, as the flat decoder's backward)
+        off = (E.numel() + 3) // 4 * 4
+        buf = torch.zeros(off + Rel.numel(), dtype=torch.float32, device=E.device)
+        dE, dR = buf[:E.numel()].view(E.shape), buf[off:].view(Rel.shape)
+        if st is not None and n >= _GROUP_SORTED_MIN and st.covers(triples):
+            ws = _group_ws(st, E.device, "group_bwd", int(lib.mrgcn_distmult_group_bwd_workspace(n, rate, E.shape[1])))
+            orders, wsp, wsn = [_ptr(o) for o in st.order], _ptr(ws), ws.numel()
+        else:
+            orders, wsp, wsn = [None] * 3, None, 0
+        _lib.check(lib.mrgcn_distmult_group_bwd_f32(
+            _ptr(E), E.stride(0), _ptr(Rel), Rel.stride(0), E.shape[1], _ptr(triples), n, rate, _ptr(g), _ptr(gl),
+            E.shape[0], orders[0], orders[1], orders[2], _ptr(dE), dE.stride(0), _ptr(dR), dR.stride(0), wsp, wsn,
+            _stream()), "distmult_group_bwd")
+        return (dE if ctx.needs_input_grad[0] else None, dR if ctx.needs_input_grad[1] else None,
+                None, None, None, None, None, None)
+
+
+def _group_args(loss, pos_weight, who):
+    """(loss kind, positive weight as a host float) of the grouped decoder's keywords; a one-element tensor is read
+    here, once, outside the step."""
+    if loss not in GROUP_LOSSES:
+        raise _lib.MrgcnError(f"{who}: loss is one of {sorted(GROUP_LOSSES)}, not {loss!r}")
+    if pos_weight is None:
+        return GROUP_LOSSES[loss], 1.0
+    if loss == "softmax":
+        raise _lib.MrgcnError(f"{who}: pos_weight belongs to loss='bce' (the softmax loss has no labels to weigh)")
+    if torch.is_tensor(pos_weight):
+        if pos_weight.numel() != 1:
+            raise _lib.MrgcnError(f"{who}: pos_weight is one number")
+        if pos_weight.is_cuda and torch.cuda.is_current_stream_capturing():
+            raise _lib.MrgcnError(f"{who}: a pos_weight tensor is read on the host: pass it outside a stream capture")
+        pos_weight = float(pos_weight)
+    w = float(pos_weight)
+    if not (w > 0.0 and np.isfinite(w)):
+        raise _lib.MrgcnError(f"{who}: pos_weight is a positive finite number")
+    return GROUP_LOSSES[loss], w
+
+
+def group_loss(triples, node_embeddings, edge_embeddings, num_facts, rate, loss="bce", pos_weight=None, static=None):
+    """The DistMult loss (link_prediction.py:645-665, :550-554) of facts and their keyed negatives, scored and
+    differentiated group by group (csrc/distmult_group.hip): a float32 device scalar carrying autograd to both embedding
+    tensors; never synchronises, so a hipGraph captures it.  `triples`: int64 [num_facts * (1 + rate), 3] in
+    `NegativeSampler`'s layout — rows [0, n) the facts, row n + i * rate + j negative j of fact i, with fact i's
+    predicate and at least one of its ends (`check_groups`, run once per triples tensor outside stream captures).  A
+    negative counts as head-corrupted when its column 0 differs from the fact's subject and as tail-corrupted
+    otherwise: one equal to its fact is a tail negative with the fact's own object.
+
+    `loss="bce"`: `BCEWithLogitsLoss(pos_weight=w)`, mean over all n (1 + rate) scores; `pos_weight` a host float or a
+    one-element tensor (read once, here), None = 1.  `loss="softmax"`: the mean over facts of -log softmax of the fact's
+    score among its 1 + rate scores — `cross_entropy` of the [n, 1 + rate] score matrix with target 0; takes no
+    `pos_weight`.  `static`: the `SortedTriples` of the facts: from 1 024 facts on the backward then sums along the
+    stored orders instead of by row atomics, and keeps its scratch there.
+
+    Shapes the group kernels do not take — H % 4 != 0, H > 256, rows not 16-byte aligned, ids past 2^31 — and
+    `torch.use_deterministic_algorithms(True)` go through `score_distmult_bc(..., static=...)` and torch's loss on its
+    scores (`stats()["lp.decoder.grouped.fallback"]`): under the flag the fixed-order backward runs."""
+    import torch.nn.functional as F
+    kind, w = _group_args(loss, pos_weight, "group_loss")
+    E = _f32_rows(node_embeddings, "node_embeddings")
+    Rel = _f32_rows(edge_embeddings, "edge_embeddings")
+    n, rate = int(num_facts), int(rate)
+    t = triples if torch.is_tensor(triples) and triples.is_cuda and triples.dtype == torch.int64 \
+        and triples.is_contiguous() else _triples(triples, E.device)
+    if getattr(t, "_mrgcn_groups", None) != (n, rate):
+        if torch.cuda.is_current_stream_capturing():
+            if t.dim() != 2 or t.shape[0] != n * (1 + rate) or n < 1 or rate < 1:
+                raise _lib.MrgcnError("group_loss: triples are [num_facts * (1 + rate), 3]")
+        else:
+            check_groups(t, n, rate)
+            _check_group_ids(t, E, Rel, "group_loss")
+            try:
+                t._mrgcn_groups = (n, rate)
+            except AttributeError:
+                pass
+    bump("lp.decoder.grouped")
+    lib = _lib.load()
+    if torch.are_deterministic_algorithms_enabled() or not lib.mrgcn_distmult_group_supported(
+            _ptr(E), E.stride(0), _ptr(Rel), Rel.stride(0), E.shape[1], E.shape[0], Rel.shape[0], n, rate):
+        bump("lp.decoder.grouped.fallback")
+        scores = score_distmult_bc(t, E, Rel, static=static)
+        if kind == GROUP_LOSSES["softmax"]:
+            x = torch.cat([scores[:n, None], scores[n:].view(n, rate)], 1)
+            return F.cross_entropy(x, torch.zeros(n, dtype=torch.int64, device=E.device))
+        y = torch.zeros_like(scores)
+        y[:n] = 1
+        pw = None if pos_weight is None else torch.full((), w, dtype=torch.float32, device=E.device)
+        return F.binary_cross_entropy_with_logits(scores, y, pos_weight=pw)
+    return _GroupLoss.apply(E, Rel, t, n, rate, kind, w, static)[0]
+
+
+def group_scores(triples, node_embeddings, edge_embeddings, num_facts, rate):
+    """The scores the group kernels write for `triples` (float32 [num_facts * (1 + rate)], no autograd): bit for bit
+    `score_distmult_bc`'s.  Raises where the group kernels do not take the shape."""
+    E = _f32_rows(node_embeddings, "node_embeddings")
+    Rel = _f32_rows(edge_embeddings, "edge_embeddings")
+    n, rate = int(num_facts), int(rate)
+    t = _triples(triples, E.device)
+    check_groups(t, n, rate)
+    _check_group_ids(t, E, Rel, "group_scores")
+    if not _lib.load().mrgcn_distmult_group_supported(_ptr(E), E.stride(0), _ptr(Rel), Rel.stride(0), E.shape[1],
+                                                      E.shape[0], Rel.shape[0], n, rate):
+        raise _lib.MrgcnError("group_scores: the group kernels do not take this shape")
+    with torch.no_grad():
+        return _GroupLoss.apply(E.detach(), Rel.detach(), t, n, rate, 0, 1.0, None)[1]
+
+
+def _decoder_args(decoder, loss, pos_weight, samplers, who):
+    """The run loops' `decoder` / `loss` / `pos_weight` keywords, checked before any kernel is touched -> (grouped?,
+    loss, pos_weight as a host float or None)."""
+    if decoder not in ("triples", "grouped"):
+        raise _lib.MrgcnError(f"{who}: decoder is 'triples' or 'grouped', not {decoder!r}")
+    if decoder == "triples":
+        if loss != "bce" or pos_weight is not None:
+            raise _lib.MrgcnError(f"{who}: loss={loss!r} / pos_weight need decoder='grouped' (the flat decoder has the "
+                                  "plain BCE only)")
+        return False, "bce", None
+    _, w = _group_args(loss, pos_weight, who)
+    for smp in samplers:
+        if not isinstance(smp, NegativeSampler):
+            raise _lib.MrgcnError(f"{who}: decoder='grouped' takes NegativeSampler's layout (rate negatives behind "
+                                  f"every fact): pass NegativeSampler(s), not {type(smp).__name__}")
+    return True, loss, (None if pos_weight is None else w)
+
+
+def _sampler_static(sampler, num_nodes, num_relations):
+    """The `SortedTriples` of a `NegativeSampler`'s facts, built once per sampler (outside stream captures) and kept."""
+    st = getattr(sampler, "_static", None)
+    if st is None:
+        if torch.cuda.is_current_stream_capturing():
+            raise _lib.MrgcnError("decoder='grouped': the facts' orders are built on first use, outside a stream capture")
+        st = sampler._static = SortedTriples(sampler.facts, num_nodes, num_relations)
+    return st
+
+
+def _decoder_loss(triples, labels, E, Rel, static, sampler=None, decoder="triples", loss="bce", pos_weight=None):
+    """The decoder line of every step and run loop: the flat BCE of `score_distmult_bc`, or the grouped loss over
+    `sampler`'s groups (`static` None: the sampler's own stored orders)."""
+    if decoder != "grouped":
+        return binary_crossentropy(score_distmult_bc(triples, E, Rel, static=static), labels)
+    if static is None:
+        static = _sampler_static(sampler, int(E.shape[0]), int(Rel.shape[0]))
+    return group_loss(triples, E, Rel, sampler.n, sampler.rate, loss=loss, pos_weight=pos_weight, static=static)
+
+
 def sample_negatives(batch_data: np.ndarray, rng=np.random):
     """train_model's within-batch corruption (link_prediction.py:239-263): 20 % of the positives
     are copied, half get a random in-batch head, half a random in-batch tail.  Returns
@@ -664,7 +880,7 @@ def _penalised_backward_and_step(model, optimizer, loss, clip, l1_lambda, l2_lam
 
 
 def train_batch_step(model, batch, facts, optimizer, negatives=None, clip=1.0, slot=None, sampler=None,
-                     l1_lambda=0.0, l2_lambda=0.0):
+                     l1_lambda=0.0, l2_lambda=0.0, decoder="triples", loss="bce", pos_weight=None):
     """One batch of train_model (link_prediction.py:226-331): 20 % of the batch's facts corrupted inside the batch
     (half the heads, half the tails replaced by batch nodes, :239-263) — drawn on the device, or `negatives` (an
     [n // 5, 3] array of batch-local triples, e.g. the reference's draws) —, DistMult scores of facts + negatives, BCE,
@@ -678,9 +894,11 @@ def train_batch_step(model, batch, facts, optimizer, negatives=None, clip=1.0, s
     batch's own `DeviceNegativeSampler`.  `l1_lambda` / `l2_lambda` (:306-322): l1 sum|p| + l2 sum p^2 over the
     parameters named `weight*` joins the loss, is clipped with it and is part of the returned loss; a `ClipAdam` with
     a max_norm takes the penalty of the weights it steps into its own step (`penalty_owners`), without an autograd
-    graph over them."""
+    graph over them.  `decoder="grouped"` (with a `NegativeSampler` as `sampler`): the grouped loss (`group_loss`) in
+    place of the flat scores and BCE — `loss` "bce" (with `pos_weight`) or "softmax"; everything else unchanged."""
     from ..optim import clip_grad_norm_
     from ..train import ClipAdam
+    grouped, group_kind, pos_weight = _decoder_args(decoder, loss, pos_weight, [sampler], "train_batch_step")
     E = _embed(model, batch)
     st = _batch_state(batch, facts, E.device)
     if slot is not None and not (torch.is_tensor(slot) and slot.is_cuda and slot.dtype == torch.float32
@@ -698,7 +916,7 @@ def train_batch_step(model, batch, facts, optimizer, negatives=None, clip=1.0, s
         labels = torch.ones(triples.shape[0], dtype=torch.float32, device=E.device)
         labels[st["facts"].shape[0]:] = 0
     optimizer.zero_grad()
-    loss = binary_crossentropy(score_distmult_bc(triples, E, _relations(model)), labels)
+    loss = _decoder_loss(triples, labels, E, _relations(model), None, sampler, decoder, group_kind, pos_weight)
     if l1_lambda > 0 or l2_lambda > 0:
         loss = _penalised_backward_and_step(model, optimizer, loss, clip, l1_lambda, l2_lambda)
     else:
@@ -719,12 +937,21 @@ def prepare_batches(batches, device):
     return batches
 
 
-def train_epoch(batches, model, optimizer, clip=1.0, l1_lambda=0.0, l2_lambda=0.0):
+def train_epoch(batches, model, optimizer, clip=1.0, l1_lambda=0.0, l2_lambda=0.0, samplers=None, decoder="triples",
+                loss="bce", pos_weight=None):
     """One epoch of train_model (:226-331): every batch once, in the fixed order of `mkbatches`; the mean of the batch
-    losses (:326-331), read back once after the last step.  `l1_lambda` / `l2_lambda`: see `train_batch_step`."""
+    losses (:326-331), read back once after the last step.  `l1_lambda` / `l2_lambda`: see `train_batch_step`.
+    `samplers`: one sampler per batch (None: each batch's own `DeviceNegativeSampler`); `decoder` / `loss` /
+    `pos_weight`: see `train_batch_step` — the grouped decoder needs `NegativeSampler`s."""
+    batches = list(batches)
+    smps = list(samplers) if samplers is not None else [None] * len(batches)
+    if len(smps) != len(batches):
+        raise _lib.MrgcnError("train_epoch: one sampler per batch")
+    _decoder_args(decoder, loss, pos_weight, smps, "train_epoch")
     model.train()
-    losses = [train_batch_step(model, batch, facts, optimizer, clip=clip, l1_lambda=l1_lambda, l2_lambda=l2_lambda)
-              for batch, facts in batches]
+    losses = [train_batch_step(model, batch, facts, optimizer, clip=clip, l1_lambda=l1_lambda, l2_lambda=l2_lambda,
+                               sampler=smp, decoder=decoder, loss=loss, pos_weight=pos_weight)
+              for (batch, facts), smp in zip(batches, smps)]
     return float(np.mean([float(x) for x in torch.stack(losses).cpu().numpy()])) if losses else float("nan")
 
 
@@ -1101,19 +1328,24 @@ def eval_schedule(nepoch, eval_interval, has_valid):
     return out
 
 
-def train_step(model, forward_fn, sampler, optimizer, static=None, clip=1.0, l1_lambda=0.0, l2_lambda=0.0):
+def train_step(model, forward_fn, sampler, optimizer, static=None, clip=1.0, l1_lambda=0.0, l2_lambda=0.0,
+               decoder="triples", loss="bce", pos_weight=None):
     """One full-batch epoch of train_model (:231-326): `triples, labels = sampler()` (a `DeviceNegativeSampler`, or any
     callable that returns the facts followed by their corrupted copies and the 1 / 0 labels on the device without
     synchronising), `forward_fn()` for the node embeddings (e.g. `lambda: model(None, A)`), DistMult scores, BCE,
     backward, the gradient clipped at `clip` — inside the step of a `ClipAdam` that has a `max_norm`, by
     `clip_grad_norm_` otherwise — and the optimizer step.  `static`: the `SortedTriples` of the facts the triples start
     with.  `l1_lambda` / `l2_lambda`: the loop's weight penalty, as in `train_batch_step`.  Returns the loss (BCE +
-    penalty) as a device scalar; no host read, so a graph captures it."""
+    penalty) as a device scalar; no host read, so a graph captures it.  `decoder="grouped"` (`sampler` a
+    `NegativeSampler`): `group_loss` over the sampler's groups — `loss` "bce" (with `pos_weight`, a host float) or
+    "softmax" — in place of the flat scores and BCE; `static` None then means the sampler's own stored orders, built
+    on first use outside a capture."""
     from ..optim import clip_grad_norm_
     from ..train import ClipAdam
+    _, group_kind, pos_weight = _decoder_args(decoder, loss, pos_weight, [sampler], "train_step")
     triples, labels = sampler()
     emb = forward_fn()
-    loss = binary_crossentropy(score_distmult_bc(triples, emb, _relations(model), static=static), labels)
+    loss = _decoder_loss(triples, labels, emb, _relations(model), static, sampler, decoder, group_kind, pos_weight)
     optimizer.zero_grad(set_to_none=True)
     if l1_lambda > 0 or l2_lambda > 0:
         return _penalised_backward_and_step(model, optimizer, loss, clip, l1_lambda, l2_lambda)
@@ -1140,9 +1372,11 @@ class FitEpochs:
     (the last of them an evaluating epoch), after which the counters and rings are reset."""
 
     def __init__(self, model, forward_fn, tparts, vparts, optimizer, stopper=None, poll=8, graphed=True, sampler=None,
-                 static=None, warmup=3, l1_lambda=0.0, l2_lambda=0.0):
+                 static=None, warmup=3, l1_lambda=0.0, l2_lambda=0.0, decoder="triples", loss="bce", pos_weight=None):
         from .. import functional as Fn
         from ..train import _COUNT_ONLY, _StopState
+        _, loss, pos_weight = _decoder_args(decoder, loss, pos_weight, [sampler], "fit")
+        self.decoder = dict(decoder=decoder, loss=loss, pos_weight=pos_weight)
         dev = tparts.facts.device
         if stopper is not None and vparts is None:
             raise _lib.MrgcnError("fit: early stopping scores the validation MRR: pass valid_facts")
@@ -1210,7 +1444,7 @@ class FitEpochs:
     def _train_epoch(self):
         self.model.train()
         loss = train_step(self.model, self.forward_fn, self.sampler, self.optimizer, self.static,
-                          l1_lambda=self.l1_lambda, l2_lambda=self.l2_lambda)
+                          l1_lambda=self.l1_lambda, l2_lambda=self.l2_lambda, **self.decoder)
         self.loss_ctr.record(loss, self.loss_ring, (loss,))
         return loss
 
@@ -1283,7 +1517,7 @@ def _run_schedule(run, sched, nepoch, poll, stopper):
 
 def fit(model, forward_fn, train_facts, valid_facts, optimizer, nepoch, eval_interval=1, mrr_batchsize=100,
         filter_ranks=True, early_stop=None, poll=8, graphed=True, sampler=None, warmup=3, static=None,
-        l1_lambda=0.0, l2_lambda=0.0):
+        l1_lambda=0.0, l2_lambda=0.0, decoder="triples", loss="bce", pos_weight=None):
     """The reference's full-batch link-prediction loop (train_model, link_prediction.py:191-373, with test_model
     :375-422) as a generator over its tuples `(epoch, loss, train_mrr, train_hits_at_k, valid_mrr, valid_hits_at_k)`
     — epochs from 1, `loss` a float, an mrr `{"raw", "flt"}`, hits `{"raw": [h@1, h@3, h@10], "flt": [...]}`, None
@@ -1294,7 +1528,8 @@ def fit(model, forward_fn, train_facts, valid_facts, optimizer, nepoch, eval_int
     its configuration.  `sampler`: see `train_step`; None draws the reference's 20 % in-batch negatives on the device
     (`DeviceNegativeSampler`, with the stored orders of the facts for the decoder's backward).  `l1_lambda` /
     `l2_lambda`: the loop's weight penalty (:306-322, `train_batch_step`), part of every step — captured ones too —
-    and of the yielded loss.
+    and of the yielded loss.  `decoder="grouped"` (`sampler` a `NegativeSampler`), `loss`, `pos_weight`: the grouped
+    loss in every step (`train_step`, `group_loss`); a `pos_weight` tensor is read once, here.
 
     An epoch is one of two step functions, chosen on the host from the epoch number (no device read):
     a training epoch — `train_step`, its loss into a device ring — and an evaluating epoch — the same, then ONE
@@ -1316,13 +1551,14 @@ def fit(model, forward_fn, train_facts, valid_facts, optimizer, nepoch, eval_int
     Under `torch.use_deterministic_algorithms(True)` the step takes the deterministic decoder kernels; what is added
     here (ranks: integer counts; metrics: a fixed-order float64 sum; records) has no float atomics."""
     from ..train import _as_device_stopper
+    _decoder_args(decoder, loss, pos_weight, [sampler], "fit")
     dev = next(model.parameters()).device
     nepoch, poll = int(nepoch), max(int(poll), 1)
     tparts = FactParts(train_facts, mrr_batchsize, filter_ranks, device=dev)
     vparts = FactParts(valid_facts, mrr_batchsize, filter_ranks, device=dev) if valid_facts is not None else None
     stopper = _as_device_stopper(early_stop, model, optimizer)
     run = FitEpochs(model, forward_fn, tparts, vparts, optimizer, stopper, poll, graphed, sampler, static, warmup,
-                    l1_lambda, l2_lambda)
+                    l1_lambda, l2_lambda, decoder, loss, pos_weight)
     sched = eval_schedule(nepoch, eval_interval, vparts is not None)
     yield from _run_schedule(run, sched, nepoch, poll, stopper)
 
@@ -1502,9 +1738,11 @@ class BatchFitEpochs:
     `_state_gen` compared and the supports' pair-sum tables refreshed in front of every replay."""
 
     def __init__(self, model, train_batches, valid_batches, optimizer, stopper=None, poll=8, graphed=True,
-                 filter_ranks=True, samplers=None, warmup=3, clip=1.0, l1_lambda=0.0, l2_lambda=0.0):
+                 filter_ranks=True, samplers=None, warmup=3, clip=1.0, l1_lambda=0.0, l2_lambda=0.0,
+                 decoder="triples", loss="bce", pos_weight=None):
         from .. import functional as Fn
         from ..train import _COUNT_ONLY, _StopState
+        _decoder_args(decoder, loss, pos_weight, [None] if samplers is None else [], "fit_batches")
         train_batches, valid_batches = list(train_batches), list(valid_batches or [])
         if not train_batches:
             raise _lib.MrgcnError("fit_batches: no training batches")
@@ -1521,6 +1759,8 @@ class BatchFitEpochs:
         self.filter_ranks, self.clip = bool(filter_ranks), clip
         self.l1_lambda, self.l2_lambda = float(l1_lambda), float(l2_lambda)
         self.samplers = [samplers(i, b, f) if samplers is not None else None for i, (b, f) in enumerate(train_batches)]
+        _, loss, pos_weight = _decoder_args(decoder, loss, pos_weight, self.samplers, "fit_batches")
+        self.decoder = dict(decoder=decoder, loss=loss, pos_weight=pos_weight)
         nt, nv = len(train_batches), len(valid_batches)
         self.loss_ctr = _StopState(dev, 1, 0.0, _COUNT_ONLY)   # counts every epoch
         self.eval_ctr = stopper.state if stopper is not None else _StopState(dev, 1, 0.0, _COUNT_ONLY)
@@ -1576,7 +1816,8 @@ class BatchFitEpochs:
         self.model.train()   # (:232)
         for i, (batch, facts) in enumerate(self.train_batches):
             train_batch_step(self.model, batch, facts, self.optimizer, clip=self.clip, slot=self.loss_slots[i:i + 1],
-                             sampler=self.samplers[i], l1_lambda=self.l1_lambda, l2_lambda=self.l2_lambda)
+                             sampler=self.samplers[i], l1_lambda=self.l1_lambda, l2_lambda=self.l2_lambda,
+                             **self.decoder)
         _lp_batch_means(self.loss_slots, len(self.train_batches), None, 0, None, 0, self.row)
         self.loss_ctr.record(self.row[0:1], self.loss_ring, (self.row[0:1],))
 
@@ -1619,7 +1860,7 @@ class BatchFitEpochs:
 
 def fit_batches(model, train_batches, valid_batches, optimizer, nepoch, eval_interval=1, filter_ranks=True,
                 early_stop=None, poll=8, graphed=True, max_graph_batches=None, warmup=3, samplers=None,
-                l1_lambda=0.0, l2_lambda=0.0):
+                l1_lambda=0.0, l2_lambda=0.0, decoder="triples", loss="bce", pos_weight=None):
     """The reference's mini-batch link-prediction loop (train_model with gcn_batchsize > 0, link_prediction.py:224-373,
     with test_model :375-422) as a generator over its tuples `(epoch, loss, train_mrr, train_hits_at_k, valid_mrr,
     valid_hits_at_k)`, with `fit`'s contract row for row: the schedule (`eval_schedule`), the loss ring and the eval
@@ -1643,11 +1884,13 @@ def fit_batches(model, train_batches, valid_batches, optimizer, nepoch, eval_int
     epochs run, which are equally free of synchronisation: FB15k-237's 1 011 batches run eagerly.
 
     `l1_lambda` / `l2_lambda`: the loop's weight penalty (:306-322) in every batch step, eager or captured, and in
-    every recorded loss (`train_batch_step`).
+    every recorded loss (`train_batch_step`).  `decoder="grouped"` (with `samplers` that make `NegativeSampler`s,
+    e.g. `batch_negative_samplers`), `loss`, `pos_weight`: the grouped loss in every batch step (`group_loss`).
 
     Out of scope: literal-encoder batches inside a capture, the partitioned engines."""
     from ..train import _as_device_stopper
     from .node_classification import MAX_GRAPH_BATCHES, _is_fixed_structure
+    _decoder_args(decoder, loss, pos_weight, [None] if samplers is None else [], "fit_batches")
     train_batches, valid_batches = list(train_batches), list(valid_batches or [])
     nepoch, poll = int(nepoch), max(int(poll), 1)
     if early_stop is not None and not valid_batches:
@@ -1659,6 +1902,7 @@ def fit_batches(model, train_batches, valid_batches, optimizer, nepoch, eval_int
                    and all(_is_fixed_structure(b) for b, _ in train_batches + valid_batches))
     stopper = _as_device_stopper(early_stop, model, optimizer)
     run = BatchFitEpochs(model, train_batches, valid_batches, optimizer, stopper, poll, capture, filter_ranks, samplers,
-                         warmup, l1_lambda=l1_lambda, l2_lambda=l2_lambda)
+                         warmup, l1_lambda=l1_lambda, l2_lambda=l2_lambda, decoder=decoder, loss=loss,
+                         pos_weight=pos_weight)
     sched = eval_schedule(nepoch, eval_interval, bool(valid_batches))
     yield from _run_schedule(run, sched, nepoch, poll, stopper)

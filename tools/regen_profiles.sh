@@ -104,6 +104,13 @@ python3 tools/lp_penalty_probe.py --out $o/lp_penalty_probe.json > $o/lp_penalty
 # tools/lp_negatives_probe.py into it and run `python3 tools/lp_negatives_probe.py --rows default --out <file>` there
 # first; LP_NEGATIVES_PARENT_JSON=<file> then puts them into the result.  Without it the file holds this tree's rows only.
 python3 tools/lp_negatives_probe.py ${LP_NEGATIVES_PARENT_JSON:+--parent $LP_NEGATIVES_PARENT_JSON} --out $o/lp_negatives_probe.json > $o/lp_negatives_probe.txt 2> $o/lp_negatives_probe.err
+# (10l) the grouped decoder next to the flat one at the FB15k-237 shape, 1 and 10 keyed negatives per fact: the replayed
+# training epoch of fit (also with a positive weight and with the softmax loss), scores + loss alone, the backward alone,
+# the median mini-batch's step.  The parent rows of DESIGN section 20 are the PARENT commit's on the same box: check the
+# parent out beside this tree, build it, copy tools/lp_grouped_probe.py into it and run
+# `python3 tools/lp_grouped_probe.py --rows triples --out <file>` there first; LP_GROUPED_PARENT_JSON=<file> then puts
+# them into the result.  Without it the file holds this tree's rows only.
+python3 tools/lp_grouped_probe.py ${LP_GROUPED_PARENT_JSON:+--parent $LP_GROUPED_PARENT_JSON} --out $o/lp_grouped_probe.json > $o/lp_grouped_probe.txt 2> $o/lp_grouped_probe.err
 hipcc -O3 --offload-arch=gfx950 -std=c++17 tools/lab/copy_lab.hip -o /tmp/copy_lab 2>/dev/null && /tmp/copy_lab > $o/copy_lab.txt 2>&1
 python3 tools/lab/spmm_hot_lab.py > $o/spmm_hot_lab.txt 2>&1
 # the CPU suite last: the tree these artefacts describe is green
