@@ -901,6 +901,45 @@ int mrgcn_distmult_topk(const float *E, int64_t ldE, int64_t num_nodes, const fl
                         const int32_t *excl_idx, int32_t k, void *workspace, int64_t workspace_bytes,
                         int64_t *out_idx, float *out_score, void *stream);
 
+/* ComplEx beside DistMult (Trouillon et al., "Complex Embeddings for Simple Link Prediction", ICML 2016, eq. 11; the
+ * reference has DistMult only): score = Re sum_k e_s[k] r[k] conj(e_o[k]) over K = H / 2 complex numbers, a row's first
+ * K columns the real parts and its last K the imaginary parts.  H must be even.  Same triple layout as the DistMult
+ * entries.
+ * _score: lanes over k, a fixed shuffle tree per triple; a pure function of its inputs (equal inputs, equal bits), held to float64 by a
+ *   tolerance.
+ * _score_bwd: dE / dRel (nullable) ACCUMULATED into.  With g = dscores and a row x = (xr | xi):
+ *     dE[s] += g (rr or + ri oi | rr oi - ri or)   dE[o] += g (sr rr - si ri | si rr + sr ri)
+ *     dRel[p] += g (sr or + si oi | sr oi - si or)
+ *   order_s / _p / _o: STABLE sorts of the triples by column (SortedTriples, mrgcn_distmult_orders; with the counting
+ *   sort's the sums are right but their order, and so their last bits, may change from run to run).  Runs of equal
+ *   targets are summed in registers along the orders; every row has one owner per pass, runs that cross a wave's span
+ *   meet in a slab and are added in wave order: no float atomics, equal bits on every run.  workspace:
+ *   mrgcn_complex_bwd_workspace(n, H) bytes (-1 for an odd H).
+ * _ranks_both / _topk: mrgcn_distmult_ranks_both's and mrgcn_distmult_topk's contracts word for word, with the
+ *   candidate score sum_h q[h] E[c,h], sequential over h = 0 .. H-1 in float32, uncontracted, where for k < K
+ *     tail side (anchor s)   q[k] = sr rr - si ri    q[K+k] = si rr + sr ri
+ *     head side (anchor o)   q[k] = rr or + ri oi    q[K+k] = rr oi - ri or
+ *   each product rounded, then the sum or difference rounded once.  The two sides round differently, so the ranks keep
+ *   the fact's own score per side (truth [2 nf] in the workspace).  One score body serves both entries. */
+int mrgcn_complex_score_f32(const float *E, int64_t ldE, const float *Rel, int64_t ldR, int32_t H,
+                            const int64_t *triples, int64_t n, float *scores, void *stream);
+int64_t mrgcn_complex_bwd_workspace(int64_t n, int32_t H);
+int mrgcn_complex_score_bwd_f32(const float *E, int64_t ldE, const float *Rel, int64_t ldR, int32_t H,
+                                const int64_t *triples, int64_t n, const float *dscores, const int64_t *order_s,
+                                const int64_t *order_p, const int64_t *order_o, float *dE, int64_t lddE, float *dRel,
+                                int64_t lddR, void *workspace, int64_t workspace_bytes, void *stream);
+int64_t mrgcn_complex_ranks_both_workspace(int64_t num_nodes, int32_t H, int64_t num_facts);
+int mrgcn_complex_ranks_both(const float *E, int64_t ldE, int64_t num_nodes, const float *Rel, int64_t ldR, int32_t H,
+                             const int64_t *triples, int64_t num_facts, const int64_t *tail_ptr,
+                             const int32_t *tail_idx, const int64_t *head_ptr, const int32_t *head_idx,
+                             const int64_t *part_ptr, int64_t num_parts, int64_t slice_facts, void *workspace,
+                             int64_t workspace_bytes, int64_t *ranks_raw, int64_t *ranks_flt, void *stream);
+int64_t mrgcn_complex_topk_workspace(int64_t num_nodes, int32_t H, int64_t num_queries, int32_t k);
+int mrgcn_complex_topk(const float *E, int64_t ldE, int64_t num_nodes, const float *Rel, int64_t ldR, int32_t H,
+                       const int64_t *queries, int64_t num_queries, int32_t head, const int64_t *excl_ptr,
+                       const int32_t *excl_idx, int32_t k, void *workspace, int64_t workspace_bytes,
+                       int64_t *out_idx, float *out_score, void *stream);
+
 /* Graph-capturable Adam (torch.optim.Adam(capturable=True) semantics): the step counter and the
  * bias corrections live in device memory, so a captured epoch replays with the right step.
  * mrgcn_adam_bias_f32: ++*step_dev; bc_dev[0] = 1 - beta1^step, bc_dev[1] = sqrt(1 - beta2^step).

@@ -197,6 +197,16 @@ SIGNATURES = {
     "mrgcn_distmult_topk_workspace": (C.c_int64, [_i64, _i32, _i64, _i32]),
     "mrgcn_distmult_topk": (C.c_int, [_p, _i64, _i64, _p, _i64, _i32, _p, _i64, _i32, _p, _p, _i32, _p, _i64, _p, _p,
                                       _p]),
+    "mrgcn_complex_score_f32": (C.c_int, [_p, _i64, _p, _i64, _i32, _p, _i64, _p, _p]),
+    "mrgcn_complex_bwd_workspace": (C.c_int64, [_i64, _i32]),
+    "mrgcn_complex_score_bwd_f32": (C.c_int, [_p, _i64, _p, _i64, _i32, _p, _i64, _p, _p, _p, _p, _p, _i64, _p, _i64,
+                                              _p, _i64, _p]),
+    "mrgcn_complex_ranks_both_workspace": (C.c_int64, [_i64, _i32, _i64]),
+    "mrgcn_complex_ranks_both": (C.c_int, [_p, _i64, _i64, _p, _i64, _i32, _p, _i64, _p, _p, _p, _p, _p, _i64, _i64,
+                                           _p, _i64, _p, _p, _p]),
+    "mrgcn_complex_topk_workspace": (C.c_int64, [_i64, _i32, _i64, _i32]),
+    "mrgcn_complex_topk": (C.c_int, [_p, _i64, _i64, _p, _i64, _i32, _p, _i64, _i32, _p, _p, _i32, _p, _i64, _p, _p,
+                                     _p]),
     "mrgcn_adam_bias_f32": (C.c_int, [_p, C.c_float, C.c_float, _p, _p]),
     "mrgcn_adam_step_dev_f32": (C.c_int, [_p, _p, _p, _p, _i64, C.c_float, C.c_float, C.c_float, C.c_float,
                                           C.c_float, _p, _p, _p]),

@@ -30,6 +30,7 @@ __device__ __forceinline__ uint64_t topk_key(float score, int64_t c) {
 }
 
 // grid (candidate tiles, query tiles).  part[(q * ntiles + tile) * k + j] = key j of the tile's sorted list
+template <int SC>
 __global__ __launch_bounds__(kLpTB) void k_topk_tiles(
     const float *__restrict__ Et, int64_t N, int H, const float *__restrict__ E, int64_t ldE,
     const float *__restrict__ Rel, int64_t ldR, const int64_t *__restrict__ queries, int64_t nq, int head_,
@@ -44,7 +45,7 @@ __global__ __launch_bounds__(kLpTB) void k_topk_tiles(
   const int nfb = (int)((nq - q0) < kLpFB ? (nq - q0) : kLpFB);
   const bool live = c < N;
   float acc[kLpFB];
-  lp_score_tile(Et, N, H, E, ldE, Rel, ldR, head, c, live, nfb,
+  lp_score_tile<SC>(Et, N, H, E, ldE, Rel, ldR, head, c, live, nfb,
                 [&](int fi, int64_t &anchor, int64_t &rel) {
                   const int64_t a = queries[2 * (q0 + fi)];
                   anchor = a < 0 ? 0 : a >= N ? N - 1 : a;  // (ids are the caller's contract; never a read past E)
@@ -125,6 +126,47 @@ inline int64_t et_bytes(int64_t N, int32_t H) { return ((int64_t)sizeof(float) *
 
 using namespace mrgcn;
 
+extern "C" int64_t mrgcn_distmult_topk_workspace(int64_t num_nodes, int32_t H, int64_t num_queries, int32_t k);
+
+namespace {
+template <int SC>
+int topk_run(const char *who_, const float *E, int64_t ldE, int64_t num_nodes, const float *Rel, int64_t ldR, int32_t H,
+                        const int64_t *queries, int64_t num_queries, int32_t head, const int64_t *excl_ptr,
+                        const int32_t *excl_idx, int32_t k, void *workspace, int64_t workspace_bytes, int64_t *out_idx,
+                        float *out_score, void *stream) {
+  const std::string who(who_);
+  MRGCN_REQUIRE(k >= 1 && k <= kTopkMax, who + ": k must be in [1, 256]");
+  MRGCN_REQUIRE(num_queries >= 0 && num_queries < ((int64_t)1 << 31), who + ": 0 <= queries < 2^31");
+  if (num_queries == 0) return MRGCN_OK;
+  MRGCN_REQUIRE(E && Rel && queries && out_idx && out_score && workspace && H > 0 && num_nodes > 0 &&
+                    num_nodes < ((int64_t)1 << 31) && (head == 0 || head == 1),
+                who + ": bad argument");
+  MRGCN_REQUIRE((excl_ptr == nullptr) == (excl_idx == nullptr),
+                who + ": give both exclusion arrays (ptr, idx) or neither");
+  MRGCN_REQUIRE(workspace_bytes >= mrgcn_distmult_topk_workspace(num_nodes, H, num_queries, k),
+                who + ": workspace too small");
+  hipStream_t st = (hipStream_t)stream;
+  float *Et = (float *)workspace;
+  uint64_t *part = (uint64_t *)((char *)workspace + et_bytes(num_nodes, H));
+  MRGCN_HIP_TRY(lp_transpose(E, ldE, num_nodes, H, Et, st));
+  const int64_t ntiles = (num_nodes + kLpTB - 1) / kLpTB;
+  // (a grid's y extent ends at 65 535 query tiles: more queries go out in several launches)
+  const int64_t per_launch = (int64_t)65535 * kLpFB;
+  for (int64_t q0 = 0; q0 < num_queries; q0 += per_launch) {
+    const int64_t n = std::min(per_launch, num_queries - q0);
+    dim3 grid((unsigned)ntiles, (unsigned)((n + kLpFB - 1) / kLpFB));
+    k_topk_tiles<SC><<<grid, kLpTB, 0, st>>>(Et, num_nodes, H, E, ldE, Rel, ldR, queries + 2 * q0, n, head,
+                                         excl_ptr ? excl_ptr + q0 : nullptr, excl_idx, k, ntiles,
+                                         part + q0 * ntiles * k);
+  }
+  int K = 1;
+  while (K < k) K <<= 1;
+  k_topk_merge<<<(unsigned)num_queries, std::max(K, kWave), 0, st>>>(part, ntiles, k, K, out_idx, out_score);
+  MRGCN_HIP_TRY(hipGetLastError());
+  return MRGCN_OK;
+}
+}  // namespace
+
 extern "C" {
 
 int64_t mrgcn_distmult_topk_workspace(int64_t num_nodes, int32_t H, int64_t num_queries, int32_t k) {
@@ -140,35 +182,23 @@ int mrgcn_distmult_topk(const float *E, int64_t ldE, int64_t num_nodes, const fl
                         const int64_t *queries, int64_t num_queries, int32_t head, const int64_t *excl_ptr,
                         const int32_t *excl_idx, int32_t k, void *workspace, int64_t workspace_bytes, int64_t *out_idx,
                         float *out_score, void *stream) {
-  MRGCN_REQUIRE(k >= 1 && k <= kTopkMax, "distmult_topk: k must be in [1, 256]");
-  MRGCN_REQUIRE(num_queries >= 0 && num_queries < ((int64_t)1 << 31), "distmult_topk: 0 <= queries < 2^31");
-  if (num_queries == 0) return MRGCN_OK;
-  MRGCN_REQUIRE(E && Rel && queries && out_idx && out_score && workspace && H > 0 && num_nodes > 0 &&
-                    num_nodes < ((int64_t)1 << 31) && (head == 0 || head == 1),
-                "distmult_topk: bad argument");
-  MRGCN_REQUIRE((excl_ptr == nullptr) == (excl_idx == nullptr),
-                "distmult_topk: give both exclusion arrays (ptr, idx) or neither");
-  MRGCN_REQUIRE(workspace_bytes >= mrgcn_distmult_topk_workspace(num_nodes, H, num_queries, k),
-                "distmult_topk: workspace too small");
-  hipStream_t st = (hipStream_t)stream;
-  float *Et = (float *)workspace;
-  uint64_t *part = (uint64_t *)((char *)workspace + et_bytes(num_nodes, H));
-  MRGCN_HIP_TRY(lp_transpose(E, ldE, num_nodes, H, Et, st));
-  const int64_t ntiles = (num_nodes + kLpTB - 1) / kLpTB;
-  // (a grid's y extent ends at 65 535 query tiles: more queries go out in several launches)
-  const int64_t per_launch = (int64_t)65535 * kLpFB;
-  for (int64_t q0 = 0; q0 < num_queries; q0 += per_launch) {
-    const int64_t n = std::min(per_launch, num_queries - q0);
-    dim3 grid((unsigned)ntiles, (unsigned)((n + kLpFB - 1) / kLpFB));
-    k_topk_tiles<<<grid, kLpTB, 0, st>>>(Et, num_nodes, H, E, ldE, Rel, ldR, queries + 2 * q0, n, head,
-                                         excl_ptr ? excl_ptr + q0 : nullptr, excl_idx, k, ntiles,
-                                         part + q0 * ntiles * k);
-  }
-  int K = 1;
-  while (K < k) K <<= 1;
-  k_topk_merge<<<(unsigned)num_queries, std::max(K, kWave), 0, st>>>(part, ntiles, k, K, out_idx, out_score);
-  MRGCN_HIP_TRY(hipGetLastError());
-  return MRGCN_OK;
+  return topk_run<kLpDistMult>("distmult_topk", E, ldE, num_nodes, Rel, ldR, H, queries, num_queries, head, excl_ptr,
+                               excl_idx, k, workspace, workspace_bytes, out_idx, out_score, stream);
+}
+
+// The ComplEx twins (Trouillon et al. 2016): the same contract and workspace; scores are the ComplEx rank kernel's, bit
+// for bit (lp_score.hpp: one body).
+int64_t mrgcn_complex_topk_workspace(int64_t num_nodes, int32_t H, int64_t num_queries, int32_t k) {
+  return H % 2 == 0 ? mrgcn_distmult_topk_workspace(num_nodes, H, num_queries, k) : -1;
+}
+
+int mrgcn_complex_topk(const float *E, int64_t ldE, int64_t num_nodes, const float *Rel, int64_t ldR, int32_t H,
+                       const int64_t *queries, int64_t num_queries, int32_t head, const int64_t *excl_ptr,
+                       const int32_t *excl_idx, int32_t k, void *workspace, int64_t workspace_bytes, int64_t *out_idx,
+                       float *out_score, void *stream) {
+  MRGCN_REQUIRE(H > 0 && H % 2 == 0, "complex_topk: H must be even (H / 2 complex numbers per row)");
+  return topk_run<kLpComplEx>("complex_topk", E, ldE, num_nodes, Rel, ldR, H, queries, num_queries, head, excl_ptr,
+                              excl_idx, k, workspace, workspace_bytes, out_idx, out_score, stream);
 }
 
 }  // extern "C"

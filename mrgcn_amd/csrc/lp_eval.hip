@@ -25,6 +25,10 @@ constexpr int64_t kSliceFacts = (int64_t)32768 * kFB;      // the default slice:
 
 // truth[f] as k_true_scores writes it.  The reference leaves the facts at positions >= num_nodes OF ITS CALL unscored
 // (link_prediction.py:611-617); a call here stands for one call per part, so the position is the one inside the part.
+// SC == kLpComplEx: the two sides round differently (lp_score.hpp: lp_stage), so the fact's own score is kept PER SIDE,
+// truth[f] by the tail side's operations and truth[nf + f] by the head side's — the fact's own answer then ties with
+// itself exactly, as lp_rank_of assumes.
+template <int SC>
 __global__ void k_truth_both(const float *__restrict__ E, int64_t ldE, const float *__restrict__ Rel, int64_t ldR,
                              int H, const int64_t *__restrict__ tr, int64_t nf, int64_t N,
                              const int64_t *__restrict__ part_ptr, int64_t nparts, float *__restrict__ truth,
@@ -44,7 +48,23 @@ __global__ void k_truth_both(const float *__restrict__ E, int64_t ldE, const flo
     pos = f - part_ptr[lo];
   }
   float acc = 0.f;
-  if (pos < N) {
+  if constexpr (SC == kLpComplEx) {
+    float acc_h = 0.f;
+    if (pos < N) {
+      const int64_t si = tr[3 * f], pi = tr[3 * f + 1], oi = tr[3 * f + 2];
+      const float *s = E + si * ldE, *o = E + oi * ldE;
+      for (int h = 0; h < H; ++h) {
+        float qt, qh, unused;
+        lp_stage<SC>(E, ldE, Rel, ldR, H, false, si, pi, h, qt, unused);
+        lp_stage<SC>(E, ldE, Rel, ldR, H, true, oi, pi, h, qh, unused);
+        const float pt = qt * o[h];
+        const float ph = qh * s[h];
+        acc = acc + pt;
+        acc_h = acc_h + ph;
+      }
+    }
+    truth[nf + f] = acc_h;
+  } else if (pos < N) {
     const float *s = E + tr[3 * f] * ldE, *p = Rel + tr[3 * f + 1] * ldR, *o = E + tr[3 * f + 2] * ldE;
     for (int h = 0; h < H; ++h) {
       const float sp = s[h] * p[h];
@@ -57,6 +77,7 @@ __global__ void k_truth_both(const float *__restrict__ E, int64_t ldE, const flo
 }
 
 // grid (candidate tiles, fact tiles of this slice, 2 directions): k_rank_counts' grid, facts from f_begin on.
+template <int SC>
 __global__ __launch_bounds__(kTB) void k_rank_counts_both(
     const float *__restrict__ Et, int64_t N, int H, const float *__restrict__ E, int64_t ldE,
     const float *__restrict__ Rel, int64_t ldR, const int64_t *__restrict__ tr, int64_t nf, int64_t f_begin,
@@ -74,7 +95,7 @@ __global__ __launch_bounds__(kTB) void k_rank_counts_both(
   const bool live = c < N;
   float acc[kFB];
   if (threadIdx.x < kFB * 4) s_cnt[threadIdx.x >> 2][threadIdx.x & 3] = 0;
-  lp_score_tile(Et, N, H, E, ldE, Rel, ldR, head, c, live, nfb,
+  lp_score_tile<SC>(Et, N, H, E, ldE, Rel, ldR, head, c, live, nfb,
                 [&](int fi, int64_t &anchor, int64_t &rel) {
                   const int64_t f = f0 + fi;
                   anchor = tr[3 * f + (head ? 2 : 0)];
@@ -90,7 +111,7 @@ __global__ __launch_bounds__(kTB) void k_rank_counts_both(
     if (i < nfb && live) {
       const int64_t f = f0 + i;
       const float sc = scored[f] ? acc[i] : 0.f;
-      const float t = truth[f];
+      const float t = truth[(SC == kLpComplEx && head ? nf : 0) + f];
       gt = sc > t;
       eq = sc == t;
       // (a candidate below the true score counts nowhere: its list is not searched)
@@ -197,6 +218,57 @@ __global__ void k_early_stop_record_row(mrgcn_early_stop_state *__restrict__ st,
   early_stop_book(st, score, tolerance, patience_default);
 }
 
+// Et [H, N] floats | truth [sides nf] floats | scored [nf] int32 | counts [8 nf] int32
+inline int64_t ranks_both_bytes(int64_t num_nodes, int32_t H, int64_t num_facts, int sides) {
+  if (num_nodes < 0 || H <= 0 || num_facts < 0) return -1;
+  return (int64_t)sizeof(float) * ((int64_t)H * num_nodes + sides * num_facts) +
+         (int64_t)sizeof(int32_t) * 9 * num_facts;
+}
+
+template <int SC>
+int ranks_both_run(const char *who_, const float *E, int64_t ldE, int64_t num_nodes, const float *Rel, int64_t ldR,
+                   int32_t H, const int64_t *triples, int64_t num_facts, const int64_t *tail_ptr,
+                   const int32_t *tail_idx, const int64_t *head_ptr, const int32_t *head_idx, const int64_t *part_ptr,
+                   int64_t num_parts, int64_t slice_facts, void *workspace, int64_t workspace_bytes,
+                   int64_t *ranks_raw, int64_t *ranks_flt, void *stream) {
+  const std::string who(who_);
+  constexpr int kSides = SC == kLpComplEx ? 2 : 1;
+  MRGCN_REQUIRE(E && Rel && triples && ranks_raw && workspace && H > 0 && num_nodes > 0 && num_facts >= 0,
+                who + ": bad argument");
+  MRGCN_REQUIRE((tail_ptr == nullptr) == (head_ptr == nullptr) && (tail_ptr == nullptr) == (tail_idx == nullptr) &&
+                    (head_ptr == nullptr) == (head_idx == nullptr),
+                who + ": give all four filter arrays or none");
+  MRGCN_REQUIRE(tail_ptr == nullptr || ranks_flt != nullptr, who + ": filter lists without ranks_flt");
+  MRGCN_REQUIRE(part_ptr == nullptr || num_parts > 0, who + ": part_ptr without parts");
+  MRGCN_REQUIRE(slice_facts >= 0 && slice_facts <= kMaxSliceFacts, who + ": slice_facts");
+  MRGCN_REQUIRE(workspace_bytes >= ranks_both_bytes(num_nodes, H, num_facts, kSides), who + ": workspace too small");
+  if (num_facts == 0) return MRGCN_OK;
+  hipStream_t st = (hipStream_t)stream;
+  float *Et = (float *)workspace;
+  float *truth = Et + (int64_t)H * num_nodes;
+  int32_t *scored = (int32_t *)(truth + kSides * num_facts);
+  int32_t *counts = scored + num_facts;
+  MRGCN_HIP_TRY(lp_transpose(E, ldE, num_nodes, H, Et, st));
+  k_truth_both<SC><<<(unsigned)((num_facts + 127) / 128), 128, 0, st>>>(E, ldE, Rel, ldR, H, triples, num_facts,
+                                                                         num_nodes, part_ptr, num_parts, truth, scored,
+                                                                         counts);
+  MRGCN_HIP_TRY(hipGetLastError());
+  int64_t slice = slice_facts > 0 ? slice_facts : kSliceFacts;
+  slice = (slice + kFB - 1) / kFB * kFB;   // whole fact tiles
+  const bool filtered = tail_ptr != nullptr;
+  for (int64_t f0 = 0; f0 < num_facts; f0 += slice) {
+    const int64_t m = (num_facts - f0) < slice ? (num_facts - f0) : slice;
+    dim3 rg((unsigned)((num_nodes + kTB - 1) / kTB), (unsigned)((m + kFB - 1) / kFB), 2);
+    k_rank_counts_both<SC><<<rg, kTB, 0, st>>>(Et, num_nodes, H, E, ldE, Rel, ldR, triples, num_facts, f0, truth,
+                                               scored, tail_ptr, tail_idx, head_ptr, head_idx, counts);
+    MRGCN_HIP_TRY(hipGetLastError());
+  }
+  k_rank_final_both<<<(unsigned)((2 * num_facts + 255) / 256), 256, 0, st>>>(counts, num_facts, ranks_raw,
+                                                                            filtered ? ranks_flt : nullptr);
+  MRGCN_HIP_TRY(hipGetLastError());
+  return MRGCN_OK;
+}
+
 }  // namespace
 }  // namespace mrgcn
 
@@ -207,9 +279,7 @@ extern "C" {
 int64_t mrgcn_distmult_ranks_both_slice(void) { return kSliceFacts; }
 
 int64_t mrgcn_distmult_ranks_both_workspace(int64_t num_nodes, int32_t H, int64_t num_facts) {
-  if (num_nodes < 0 || H <= 0 || num_facts < 0) return -1;
-  // Et [H, N] floats | truth [nf] floats | scored [nf] int32 | counts [8 nf] int32
-  return (int64_t)sizeof(float) * ((int64_t)H * num_nodes + num_facts) + (int64_t)sizeof(int32_t) * 9 * num_facts;
+  return ranks_both_bytes(num_nodes, H, num_facts, 1);
 }
 
 int mrgcn_distmult_ranks_both(const float *E, int64_t ldE, int64_t num_nodes, const float *Rel, int64_t ldR, int32_t H,
@@ -217,41 +287,26 @@ int mrgcn_distmult_ranks_both(const float *E, int64_t ldE, int64_t num_nodes, co
                               const int32_t *tail_idx, const int64_t *head_ptr, const int32_t *head_idx,
                               const int64_t *part_ptr, int64_t num_parts, int64_t slice_facts, void *workspace,
                               int64_t workspace_bytes, int64_t *ranks_raw, int64_t *ranks_flt, void *stream) {
-  MRGCN_REQUIRE(E && Rel && triples && ranks_raw && workspace && H > 0 && num_nodes > 0 && num_facts >= 0,
-                "distmult_ranks_both: bad argument");
-  MRGCN_REQUIRE((tail_ptr == nullptr) == (head_ptr == nullptr) && (tail_ptr == nullptr) == (tail_idx == nullptr) &&
-                    (head_ptr == nullptr) == (head_idx == nullptr),
-                "distmult_ranks_both: give all four filter arrays or none");
-  MRGCN_REQUIRE(tail_ptr == nullptr || ranks_flt != nullptr, "distmult_ranks_both: filter lists without ranks_flt");
-  MRGCN_REQUIRE(part_ptr == nullptr || num_parts > 0, "distmult_ranks_both: part_ptr without parts");
-  MRGCN_REQUIRE(slice_facts >= 0 && slice_facts <= kMaxSliceFacts, "distmult_ranks_both: slice_facts");
-  MRGCN_REQUIRE(workspace_bytes >= mrgcn_distmult_ranks_both_workspace(num_nodes, H, num_facts),
-                "distmult_ranks_both: workspace too small");
-  if (num_facts == 0) return MRGCN_OK;
-  hipStream_t st = (hipStream_t)stream;
-  float *Et = (float *)workspace;
-  float *truth = Et + (int64_t)H * num_nodes;
-  int32_t *scored = (int32_t *)(truth + num_facts);
-  int32_t *counts = scored + num_facts;
-  MRGCN_HIP_TRY(lp_transpose(E, ldE, num_nodes, H, Et, st));
-  k_truth_both<<<(unsigned)((num_facts + 127) / 128), 128, 0, st>>>(E, ldE, Rel, ldR, H, triples, num_facts,
-                                                                     num_nodes, part_ptr, num_parts, truth, scored,
-                                                                     counts);
-  MRGCN_HIP_TRY(hipGetLastError());
-  int64_t slice = slice_facts > 0 ? slice_facts : kSliceFacts;
-  slice = (slice + kFB - 1) / kFB * kFB;   // whole fact tiles
-  const bool filtered = tail_ptr != nullptr;
-  for (int64_t f0 = 0; f0 < num_facts; f0 += slice) {
-    const int64_t m = (num_facts - f0) < slice ? (num_facts - f0) : slice;
-    dim3 rg((unsigned)((num_nodes + kTB - 1) / kTB), (unsigned)((m + kFB - 1) / kFB), 2);
-    k_rank_counts_both<<<rg, kTB, 0, st>>>(Et, num_nodes, H, E, ldE, Rel, ldR, triples, num_facts, f0, truth, scored,
-                                           tail_ptr, tail_idx, head_ptr, head_idx, counts);
-    MRGCN_HIP_TRY(hipGetLastError());
-  }
-  k_rank_final_both<<<(unsigned)((2 * num_facts + 255) / 256), 256, 0, st>>>(counts, num_facts, ranks_raw,
-                                                                            filtered ? ranks_flt : nullptr);
-  MRGCN_HIP_TRY(hipGetLastError());
-  return MRGCN_OK;
+  return ranks_both_run<kLpDistMult>("distmult_ranks_both", E, ldE, num_nodes, Rel, ldR, H, triples, num_facts,
+                                     tail_ptr, tail_idx, head_ptr, head_idx, part_ptr, num_parts, slice_facts,
+                                     workspace, workspace_bytes, ranks_raw, ranks_flt, stream);
+}
+
+// The ComplEx twins (Trouillon et al. 2016): the same contract word for word; the scores are lp_stage<kLpComplEx>'s and
+// the fact's own score is kept per side (truth [2 nf]).
+int64_t mrgcn_complex_ranks_both_workspace(int64_t num_nodes, int32_t H, int64_t num_facts) {
+  return ranks_both_bytes(num_nodes, H, num_facts, 2);
+}
+
+int mrgcn_complex_ranks_both(const float *E, int64_t ldE, int64_t num_nodes, const float *Rel, int64_t ldR, int32_t H,
+                             const int64_t *triples, int64_t num_facts, const int64_t *tail_ptr,
+                             const int32_t *tail_idx, const int64_t *head_ptr, const int32_t *head_idx,
+                             const int64_t *part_ptr, int64_t num_parts, int64_t slice_facts, void *workspace,
+                             int64_t workspace_bytes, int64_t *ranks_raw, int64_t *ranks_flt, void *stream) {
+  MRGCN_REQUIRE(H > 0 && H % 2 == 0, "complex_ranks_both: H must be even (H / 2 complex numbers per row)");
+  return ranks_both_run<kLpComplEx>("complex_ranks_both", E, ldE, num_nodes, Rel, ldR, H, triples, num_facts,
+                                    tail_ptr, tail_idx, head_ptr, head_idx, part_ptr, num_parts, slice_facts,
+                                    workspace, workspace_bytes, ranks_raw, ranks_flt, stream);
 }
 
 int mrgcn_rank_metrics(const int64_t *ranks, int64_t num_facts, const int64_t *part_ptr, int64_t num_parts, float *out4,

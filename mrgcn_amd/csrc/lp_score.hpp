@@ -2,6 +2,8 @@
 // (distmult_topk.hip: k_topk_tiles): ONE body, so that a fact that "ranks 3" sits at position 3 of the list
 // predict_topk returns — the same float32 products in the same order, bit for bit.
 // lp_score_tiles below is the same sum for several candidates per thread (lp_batches.hip: a batch's own small table).
+// The body takes a scorer (template parameter SC, lp_stage below): DistMult, whose instantiation is the arithmetic it
+// always was, and ComplEx, which stages one pair vector per side and runs the tail side's inner loop on both.
 #pragma once
 
 #include "common.hpp"
@@ -34,18 +36,60 @@ __device__ __forceinline__ int64_t lp_rank_of(int64_t gt, int64_t eq) {
   return gt + half + 1;
 }
 
+// The scoring functions a candidate body serves.  DistMult (link_prediction.py:645-665): sum_h (E[s,h] Rel[p,h]) E[o,h].
+// ComplEx (Trouillon et al. 2016, eq. 11): Re sum_k e_s[k] r[k] conj(e_o[k]) over K = H / 2 complex numbers, a row's
+// first K columns the real and its last K the imaginary parts.
+constexpr int kLpDistMult = 0;
+constexpr int kLpComplEx = 1;
+
+// The staged values of column hh for one (anchor, relation) pair.  DistMult: tail side a = E[anchor,hh] Rel[rel,hh];
+// head side a = Rel[rel,hh], b = E[anchor,hh] (the candidate is multiplied in first, as the reference associates).
+// ComplEx: a = q[hh], the pair vector whose plain dot product with a candidate's row IS the score, on either side
+// (b unused) — with x the anchor's row, r the relation's, k = hh mod K:
+//   tail (anchor = s)   q[k] = xr rr - xi ri     q[K + k] = xi rr + xr ri
+//   head (anchor = o)   q[k] = rr xr + ri xi     q[K + k] = rr xi - ri xr
+// each product rounded to float32, then the sum or difference rounded once (nothing contracted).  Column hh reads its
+// partner column hh +- K of both rows from global memory; K need not be a multiple of the h tile.
+template <int SC>
+__device__ __forceinline__ void lp_stage(const float *__restrict__ E, int64_t ldE, const float *__restrict__ Rel,
+                                         int64_t ldR, int H, bool head, int64_t anchor, int64_t rel, int hh, float &a,
+                                         float &b) {
+#pragma clang fp contract(off)
+  if constexpr (SC == kLpComplEx) {
+    const int K = H >> 1;
+    const bool im = hh >= K;
+    const int k = im ? hh - K : hh;
+    const float *x = E + anchor * ldE, *r = Rel + rel * ldR;
+    const float xr = x[k], xi = x[K + k], rr = r[k], ri = r[K + k];
+    const float p1 = im ? xi * rr : xr * rr;
+    const float p2 = im ? xr * ri : xi * ri;
+    a = (im != head) ? p1 + p2 : p1 - p2;
+    b = 0.f;
+  } else {
+    const float pv = Rel[rel * ldR + hh];
+    const float ev = E[anchor * ldE + hh];
+    if (head) {
+      a = pv;
+      b = ev;
+    } else {
+      a = ev * pv;
+    }
+  }
+}
+
 // acc[i] = the score of candidate c (this thread's; `live` = c < N) for pair i < nfb of the block, candidates read
 // coalesced from the transposed table.  head == false: the candidate fills the tail slot,
 // acc += (E[anchor,h] Rel[rel,h]) * E[c,h]; head == true: the head slot, acc += (E[c,h] Rel[rel,h]) * E[anchor,h];
 // sequential over h = 0 .. H-1, nothing contracted.  ids(i, anchor, rel) names pair i's rows.  Every thread of the
 // block must call it (barriers); s_a / s_b are the block's [kLpFB][kLpHT] staging arrays.
-template <class Ids>
+template <int SC = kLpDistMult, class Ids>
 __device__ __forceinline__ void lp_score_tile(const float *__restrict__ Et, int64_t N, int H,
                                               const float *__restrict__ E, int64_t ldE,
                                               const float *__restrict__ Rel, int64_t ldR, bool head, int64_t c,
                                               bool live, int nfb, Ids ids, float (*s_a)[kLpHT], float (*s_b)[kLpHT],
                                               float (&acc)[kLpFB]) {
 #pragma clang fp contract(off)
+  const bool two = head && SC == kLpDistMult;   // two products per h (the ComplEx pair vector is staged whole)
 #pragma unroll
   for (int i = 0; i < kLpFB; ++i) acc[i] = 0.f;
   for (int h0 = 0; h0 < H; h0 += kLpHT) {
@@ -57,14 +101,7 @@ __device__ __forceinline__ void lp_score_tile(const float *__restrict__ Et, int6
       if (fi < nfb && h < hn) {
         int64_t anchor, rel;
         ids(fi, anchor, rel);
-        const float pv = Rel[rel * ldR + h0 + h];
-        const float ev = E[anchor * ldE + h0 + h];
-        if (head) {
-          a = pv;
-          b = ev;
-        } else {
-          a = ev * pv;
-        }
+        lp_stage<SC>(E, ldE, Rel, ldR, H, head, anchor, rel, h0 + h, a, b);
       }
       s_a[fi][h] = a;
       s_b[fi][h] = b;
@@ -73,7 +110,7 @@ __device__ __forceinline__ void lp_score_tile(const float *__restrict__ Et, int6
     if (live) {
       for (int h = 0; h < hn; ++h) {
         const float e = Et[(int64_t)(h0 + h) * N + c];
-        if (head) {
+        if (two) {
 #pragma unroll
           for (int i = 0; i < kLpFB; ++i) {
             const float ep = e * s_a[i][h];
@@ -152,7 +189,7 @@ __device__ __forceinline__ void lp_score_htile(const float *__restrict__ row, in
 // from LDS once for all CT candidates: acc[j][i] = the score of candidate c + j kLpTB for pair i, by the SAME float32
 // operations in the same order as lp_score_tile (bit for bit; tests/test_gpu_lp_batches_kernels.py).  Candidates past
 // the table are read at the clamped id N - 1 (straight-line loads, no branch); their acc is not meaningful.
-template <int CT, class Ids>
+template <int CT, int SC = kLpDistMult, class Ids>
 __device__ __forceinline__ void lp_score_tiles(const float *__restrict__ Et, int64_t N, int H,
                                                const float *__restrict__ E, int64_t ldE,
                                                const float *__restrict__ Rel, int64_t ldR, bool head, int64_t c,
@@ -176,21 +213,14 @@ __device__ __forceinline__ void lp_score_tiles(const float *__restrict__ Et, int
       if (fi < nfb && h < hn) {
         int64_t anchor, rel;
         ids(fi, anchor, rel);
-        const float pv = Rel[rel * ldR + h0 + h];
-        const float ev = E[anchor * ldE + h0 + h];
-        if (head) {
-          a = pv;
-          b = ev;
-        } else {
-          a = ev * pv;
-        }
+        lp_stage<SC>(E, ldE, Rel, ldR, H, head, anchor, rel, h0 + h, a, b);
       }
       s_a[fi][h] = a;
       s_b[fi][h] = b;
     }
     __syncthreads();
     const float *row = Et + (int64_t)h0 * N;
-    if (head)
+    if (head && SC == kLpDistMult)
       lp_score_htile<CT, true>(row, N, hn, cc, s_a, s_b, acc);
     else
       lp_score_htile<CT, false>(row, N, hn, cc, s_a, s_b, acc);

@@ -159,3 +159,48 @@ def negatives_draw(facts, rate, n_cand, num_nodes, num_relations, known_keys, se
     unresolved = np.zeros(total, dtype=np.uint8)
     unresolved[pending] = 1
     return out, unresolved
+
+
+def complex_candidate_scores(E, Rel, anchors, rels, side):
+    """The ComplEx candidate scores of `mrgcn_complex_ranks_both` / `mrgcn_complex_topk` (csrc/lp_score.hpp:
+    lp_stage<kLpComplEx>), restated in numpy with exactly their float32 operations: float32 [nq, N], row i the scores
+    of all N nodes as the missing end of pair i = (anchors[i], rels[i]).  With K = H / 2, x the anchor's row and r the
+    relation's, the pair vector is
+        side "tail" (anchor = s)   q[k] = xr rr - xi ri     q[K + k] = xi rr + xr ri
+        side "head" (anchor = o)   q[k] = rr xr + ri xi     q[K + k] = rr xi - ri xr
+    each product rounded to float32, then the sum or difference rounded once, and the score of candidate c is
+    sum_h q[h] E[c, h], sequential over h = 0 .. H - 1, each product rounded before it is added.  The statement the
+    kernels equal bit for bit."""
+    import numpy as np
+    if side not in ("tail", "head"):
+        raise ValueError(f"side must be 'tail' or 'head', not {side!r}")
+    E = np.ascontiguousarray(E, dtype=np.float32)
+    Rel = np.ascontiguousarray(Rel, dtype=np.float32)
+    H = E.shape[1]
+    if H % 2 or Rel.shape[1] != H:
+        raise ValueError("complex_candidate_scores: rows of an even, equal width")
+    K = H // 2
+    x, r = E[np.asarray(anchors, dtype=np.int64)], Rel[np.asarray(rels, dtype=np.int64)]
+    xr, xi, rr, ri = x[:, :K], x[:, K:], r[:, :K], r[:, K:]
+    if side == "tail":
+        q = np.concatenate([xr * rr - xi * ri, xi * rr + xr * ri], axis=1)
+    else:
+        q = np.concatenate([rr * xr + ri * xi, rr * xi - ri * xr], axis=1)
+    assert q.dtype == np.float32
+    acc = np.zeros((x.shape[0], E.shape[0]), dtype=np.float32)
+    for h in range(H):
+        acc = acc + q[:, h:h + 1] * E[None, :, h]
+    return acc
+
+
+def complex_scores64(triples, E, Rel):
+    """Re sum_k e_s[k] r[k] conj(e_o[k]) of every triple in numpy complex128 (Trouillon et al. 2016, eq. 11): the
+    formulation the float32 kernels and mirrors are held to by a tolerance, independent of their real-valued one."""
+    import numpy as np
+    t = np.asarray(triples, dtype=np.int64).reshape(-1, 3)
+    E, Rel = np.asarray(E, dtype=np.float64), np.asarray(Rel, dtype=np.float64)
+    K = E.shape[1] // 2
+    if E.shape[1] % 2 or Rel.shape[1] != E.shape[1]:
+        raise ValueError("complex_scores64: rows of an even, equal width")
+    Ec, Rc = E[:, :K] + 1j * E[:, K:], Rel[:, :K] + 1j * Rel[:, K:]
+    return np.real(np.sum(Ec[t[:, 0]] * Rc[t[:, 1]] * np.conj(Ec[t[:, 2]]), axis=1))

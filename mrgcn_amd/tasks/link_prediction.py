@@ -244,6 +244,98 @@ def score_distmult_bc(data, node_embeddings, edge_embeddings, static: "SortedTri
     return _DistMultScore.apply(E, Rel, _triples(data, E.device), static)
 
 
+# ---- the ComplEx scorer beside DistMult (Trouillon et al. 2016; csrc/complex.hip) ---------------------------------
+SCORERS = ("distmult", "complex")
+
+
+def _scorer(scorer, who: str) -> bool:
+    """The `scorer` keyword, checked before any kernel is touched -> is it ComplEx?"""
+    if scorer not in SCORERS:
+        raise _lib.MrgcnError(f"{who}: scorer is 'distmult' or 'complex', not {scorer!r}")
+    return scorer == "complex"
+
+
+def _complex_width(H: int, who: str):
+    if int(H) % 2:
+        raise _lib.MrgcnError(f"{who}: scorer='complex' reads a row as H / 2 complex numbers: the width {int(H)} is odd")
+
+
+def _no_complex(scorer, who: str):
+    """The entries whose ComplEx form is not built yet (csrc/lp_batches.hip's fused batch evaluation and run loop)."""
+    if _scorer(scorer, who):
+        raise _lib.MrgcnError(f"{who}: scorer='complex' is not available in the mini-batch run loop and its fused "
+                              "batch evaluation (csrc/lp_batches.hip scores DistMult only); use train_epoch / "
+                              "evaluate_batches, or the full-batch `fit`")
+
+
+class _ComplexScore(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, E, Rel, triples, static=None):
+        ctx.static = static
+        lib = _lib.load()
+        n, H = triples.shape[0], E.shape[1]
+        scores = torch.empty(n, dtype=torch.float32, device=E.device)
+        _lib.check(lib.mrgcn_complex_score_f32(_ptr(E), E.stride(0), _ptr(Rel), Rel.stride(0), H, _ptr(triples), n,
+                                               _ptr(scores), _stream()), "complex_score")
+        ctx.save_for_backward(E, Rel, triples)
+        return scores
+
+    @staticmethod
+    def backward(ctx, g):
+        # ONE route (DESIGN: "ComplEx"): runs of equal targets summed in registers along STABLE orders, every row by
+        # one owner — the stored facts of `static` through their stored orders, the triples behind them (or all of
+        # them) through the stable radix sort.  No float atomics with or without torch's deterministic flag.
+        E, Rel, triples = ctx.saved_tensors
+        lib = _lib.load()
+        g = g.contiguous().float()
+        dE = torch.zeros_like(E, memory_format=torch.contiguous_format) if ctx.needs_input_grad[0] else None
+        dR = torch.zeros_like(Rel, memory_format=torch.contiguous_format) if ctx.needs_input_grad[1] else None
+        if dE is None and dR is None:
+            return None, None, None, None
+        if torch.are_deterministic_algorithms_enabled():
+            bump("deterministic.complex_bwd")
+        n, H, dev, st = triples.shape[0], E.shape[1], E.device, ctx.static
+        lddE, lddR = (dE.stride(0) if dE is not None else 0), (dR.stride(0) if dR is not None else 0)
+
+        def run(tr, m, gm, orders):
+            ws = _det_scratch(dev, "complex_bwd", int(lib.mrgcn_complex_bwd_workspace(m, H)))
+            _lib.check(lib.mrgcn_complex_score_bwd_f32(
+                _ptr(E), E.stride(0), _ptr(Rel), Rel.stride(0), H, tr, m, gm, _ptr(orders[0]), _ptr(orders[1]),
+                _ptr(orders[2]), _ptr(dE), lddE, _ptr(dR), lddR, _ptr(ws), ws.numel(), _stream()), "complex_score_bwd")
+
+        ns = 0
+        if st is not None and st.covers(triples):
+            ns = len(st)
+            run(_ptr(triples), ns, _ptr(g), st.order)
+        m = n - ns
+        if m > 0:
+            tr, gm = C.c_void_p(triples.data_ptr() + 24 * ns), C.c_void_p(g.data_ptr() + 4 * ns)
+            if ns:
+                bufs = st.tail_orders_stable(m, E.shape[0], Rel.shape[0])
+            else:
+                bufs = [torch.empty(m, dtype=torch.int64, device=dev) for _ in range(3)]
+                bufs.append(torch.empty(int(lib.mrgcn_distmult_orders_workspace(m)), dtype=torch.uint8, device=dev))
+            _lib.check(lib.mrgcn_distmult_orders(tr, m, E.shape[0], Rel.shape[0], _ptr(bufs[0]), _ptr(bufs[1]),
+                                                 _ptr(bufs[2]), _ptr(bufs[3]), bufs[3].numel(), _stream()),
+                       "distmult_orders")
+            run(tr, m, gm, bufs[:3])
+        return dE, dR, None, None
+
+
+def score_complex_bc(data, node_embeddings, edge_embeddings, static: "SortedTriples | None" = None):
+    """`score_distmult_bc`'s twin for ComplEx (Trouillon et al. 2016): Re sum_k e_s[k] r[k] conj(e_o[k]) over the
+    H / 2 complex numbers of a row (real parts first), with autograd.  Same triples, same `static` (the stored orders
+    of the facts the triples START with; the triples behind them — freshly drawn negatives — are sorted anew by the
+    stable radix sort).  An odd width raises `MrgcnError`."""
+    H = int(node_embeddings.shape[-1])
+    _complex_width(H, "score_complex_bc")
+    E = _f32_rows(node_embeddings, "node_embeddings")
+    Rel = _f32_rows(edge_embeddings, "edge_embeddings")
+    if Rel.shape[1] != H:
+        raise ValueError("score_complex_bc: node and edge embeddings differ in width")
+    return _ComplexScore.apply(E, Rel, _triples(data, E.device), static)
+
+
 class _BceLogits(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, y):
@@ -457,11 +549,15 @@ def group_scores(triples, node_embeddings, edge_embeddings, num_facts, rate):
         return _GroupLoss.apply(E.detach(), Rel.detach(), t, n, rate, 0, 1.0, None)[1]
 
 
-def _decoder_args(decoder, loss, pos_weight, samplers, who):
-    """The run loops' `decoder` / `loss` / `pos_weight` keywords, checked before any kernel is touched -> (grouped?,
-    loss, pos_weight as a host float or None)."""
+def _decoder_args(decoder, loss, pos_weight, samplers, who, scorer="distmult"):
+    """The run loops' `decoder` / `loss` / `pos_weight` / `scorer` keywords, checked before any kernel is touched ->
+    (grouped?, loss, pos_weight as a host float or None)."""
+    cx = _scorer(scorer, who)
     if decoder not in ("triples", "grouped"):
         raise _lib.MrgcnError(f"{who}: decoder is 'triples' or 'grouped', not {decoder!r}")
+    if cx and decoder == "grouped":
+        raise _lib.MrgcnError(f"{who}: decoder='grouped' scores DistMult only: scorer='complex' takes the flat "
+                              "decoder (decoder='triples')")
     if decoder == "triples":
         if loss != "bce" or pos_weight is not None:
             raise _lib.MrgcnError(f"{who}: loss={loss!r} / pos_weight need decoder='grouped' (the flat decoder has the "
@@ -485,11 +581,14 @@ def _sampler_static(sampler, num_nodes, num_relations):
     return st
 
 
-def _decoder_loss(triples, labels, E, Rel, static, sampler=None, decoder="triples", loss="bce", pos_weight=None):
-    """The decoder line of every step and run loop: the flat BCE of `score_distmult_bc`, or the grouped loss over
-    `sampler`'s groups (`static` None: the sampler's own stored orders)."""
+def _decoder_loss(triples, labels, E, Rel, static, sampler=None, decoder="triples", loss="bce", pos_weight=None,
+                  scorer="distmult"):
+    """The decoder line of every step and run loop: the flat BCE of `score_distmult_bc` (`scorer="complex"`: of
+    `score_complex_bc`), or the grouped loss over `sampler`'s groups (`static` None: the sampler's own stored
+    orders)."""
     if decoder != "grouped":
-        return binary_crossentropy(score_distmult_bc(triples, E, Rel, static=static), labels)
+        score = score_complex_bc if scorer == "complex" else score_distmult_bc
+        return binary_crossentropy(score(triples, E, Rel, static=static), labels)
     if static is None:
         static = _sampler_static(sampler, int(E.shape[0]), int(Rel.shape[0]))
     return group_loss(triples, E, Rel, sampler.n, sampler.rate, loss=loss, pos_weight=pos_weight, static=static)
@@ -736,16 +835,25 @@ def filter_lists(data: np.ndarray):
     return tp, ti, hp, hi
 
 
-def compute_ranks_fast(data, node_embeddings, edge_embeddings, batch_size=100, filtered=False):
+def compute_ranks_fast(data, node_embeddings, edge_embeddings, batch_size=100, filtered=False, scorer="distmult"):
     """link_prediction.py:593-643.  Returns the int64 [2 * num_facts] ranks (tail corruption
     then head corruption) on the embeddings' device.  `batch_size` (the reference's
     mrr_batchsize, a memory knob for its [facts, nodes] score matrix) is accepted and unused:
-    scores are never materialised here."""
+    scores are never materialised here.  `scorer="complex"`: ComplEx scores (`rank_both` over one part; an odd width
+    raises `MrgcnError`)."""
+    if _scorer(scorer, "compute_ranks_fast"):
+        _complex_width(node_embeddings.shape[-1], "compute_ranks_fast")
     E = _f32_rows(node_embeddings.detach(), "node_embeddings")
     Rel = _f32_rows(edge_embeddings.detach(), "edge_embeddings")
     lib = _lib.load()
     dev = E.device
     facts_np = data.cpu().numpy() if torch.is_tensor(data) else np.asarray(data)
+    if scorer == "complex":
+        if len(facts_np) == 0:
+            return torch.empty(0, dtype=torch.int64, device=dev)
+        lists = [torch.from_numpy(a).to(dev) for a in filter_lists(facts_np)] if filtered else None
+        raw, flt = rank_both(facts_np, E, Rel, lists=lists, scorer=scorer)
+        return flt if filtered else raw
     tr = _triples(facts_np, dev)
     nf, N, H = tr.shape[0], E.shape[0], E.shape[1]
     ranks = torch.empty(2 * nf, dtype=torch.int64, device=dev)
@@ -880,7 +988,7 @@ def _penalised_backward_and_step(model, optimizer, loss, clip, l1_lambda, l2_lam
 
 
 def train_batch_step(model, batch, facts, optimizer, negatives=None, clip=1.0, slot=None, sampler=None,
-                     l1_lambda=0.0, l2_lambda=0.0, decoder="triples", loss="bce", pos_weight=None):
+                     l1_lambda=0.0, l2_lambda=0.0, decoder="triples", loss="bce", pos_weight=None, scorer="distmult"):
     """One batch of train_model (link_prediction.py:226-331): 20 % of the batch's facts corrupted inside the batch
     (half the heads, half the tails replaced by batch nodes, :239-263) — drawn on the device, or `negatives` (an
     [n // 5, 3] array of batch-local triples, e.g. the reference's draws) —, DistMult scores of facts + negatives, BCE,
@@ -895,10 +1003,11 @@ def train_batch_step(model, batch, facts, optimizer, negatives=None, clip=1.0, s
     parameters named `weight*` joins the loss, is clipped with it and is part of the returned loss; a `ClipAdam` with
     a max_norm takes the penalty of the weights it steps into its own step (`penalty_owners`), without an autograd
     graph over them.  `decoder="grouped"` (with a `NegativeSampler` as `sampler`): the grouped loss (`group_loss`) in
-    place of the flat scores and BCE — `loss` "bce" (with `pos_weight`) or "softmax"; everything else unchanged."""
+    place of the flat scores and BCE — `loss` "bce" (with `pos_weight`) or "softmax"; everything else unchanged.
+    `scorer="complex"`: ComplEx scores (`score_complex_bc`) under the flat BCE; not with the grouped decoder."""
     from ..optim import clip_grad_norm_
     from ..train import ClipAdam
-    grouped, group_kind, pos_weight = _decoder_args(decoder, loss, pos_weight, [sampler], "train_batch_step")
+    grouped, group_kind, pos_weight = _decoder_args(decoder, loss, pos_weight, [sampler], "train_batch_step", scorer)
     E = _embed(model, batch)
     st = _batch_state(batch, facts, E.device)
     if slot is not None and not (torch.is_tensor(slot) and slot.is_cuda and slot.dtype == torch.float32
@@ -916,7 +1025,8 @@ def train_batch_step(model, batch, facts, optimizer, negatives=None, clip=1.0, s
         labels = torch.ones(triples.shape[0], dtype=torch.float32, device=E.device)
         labels[st["facts"].shape[0]:] = 0
     optimizer.zero_grad()
-    loss = _decoder_loss(triples, labels, E, _relations(model), None, sampler, decoder, group_kind, pos_weight)
+    loss = _decoder_loss(triples, labels, E, _relations(model), None, sampler, decoder, group_kind, pos_weight,
+                         scorer)
     if l1_lambda > 0 or l2_lambda > 0:
         loss = _penalised_backward_and_step(model, optimizer, loss, clip, l1_lambda, l2_lambda)
     else:
@@ -938,29 +1048,30 @@ def prepare_batches(batches, device):
 
 
 def train_epoch(batches, model, optimizer, clip=1.0, l1_lambda=0.0, l2_lambda=0.0, samplers=None, decoder="triples",
-                loss="bce", pos_weight=None):
+                loss="bce", pos_weight=None, scorer="distmult"):
     """One epoch of train_model (:226-331): every batch once, in the fixed order of `mkbatches`; the mean of the batch
     losses (:326-331), read back once after the last step.  `l1_lambda` / `l2_lambda`: see `train_batch_step`.
     `samplers`: one sampler per batch (None: each batch's own `DeviceNegativeSampler`); `decoder` / `loss` /
-    `pos_weight`: see `train_batch_step` — the grouped decoder needs `NegativeSampler`s."""
+    `pos_weight` / `scorer`: see `train_batch_step` — the grouped decoder needs `NegativeSampler`s."""
     batches = list(batches)
     smps = list(samplers) if samplers is not None else [None] * len(batches)
     if len(smps) != len(batches):
         raise _lib.MrgcnError("train_epoch: one sampler per batch")
-    _decoder_args(decoder, loss, pos_weight, smps, "train_epoch")
+    _decoder_args(decoder, loss, pos_weight, smps, "train_epoch", scorer)
     model.train()
     losses = [train_batch_step(model, batch, facts, optimizer, clip=clip, l1_lambda=l1_lambda, l2_lambda=l2_lambda,
-                               sampler=smp, decoder=decoder, loss=loss, pos_weight=pos_weight)
+                               sampler=smp, decoder=decoder, loss=loss, pos_weight=pos_weight, scorer=scorer)
               for (batch, facts), smp in zip(batches, smps)]
     return float(np.mean([float(x) for x in torch.stack(losses).cpu().numpy()])) if losses else float("nan")
 
 
-def evaluate_batches(batches, model, filtered=True):
+def evaluate_batches(batches, model, filtered=True, scorer="distmult"):
     """test_model (link_prediction.py:375-422): every batch's facts ranked against that batch's embeddings only
     (mrgcn_distmult_ranks), raw and — `filtered` — filtered by the true facts of that batch (truedicts(batch facts),
     computed once per batch and kept).  Returns (mrr, hits_at_k, rankings) as test_model does: {"raw", "flt"} means
     over the batches of the batches' MRR and hits@{1, 3, 10} (-1 for "flt" when not `filtered`), and the ranks of all
-    batches flattened."""
+    batches flattened.  `scorer="complex"`: ComplEx scores (`rank_both` per batch)."""
+    cx = _scorer(scorer, "evaluate_batches")
     lib = _lib.load()
     model.eval()
     K = [1, 3, 10]
@@ -989,7 +1100,10 @@ def evaluate_batches(batches, model, filtered=True):
                         st["lists"] = [a if a.numel() else torch.zeros(1, dtype=a.dtype, device=dev) for a in ls]
                     lists = st["lists"]
                 ranks = torch.empty(2 * nf, dtype=torch.int64, device=dev)
-                if nf:
+                if nf and cx:
+                    _complex_width(H, "evaluate_batches")
+                    ranks = rank_both(tr, E, Rel, lists=lists if flt else None, scorer=scorer)[1 if flt else 0]
+                elif nf:
                     ws_bytes = lib.mrgcn_distmult_ranks_workspace(N, H, nf)
                     ws = torch.empty((ws_bytes + 3) // 4, dtype=torch.int32, device=dev)
                     _lib.check(lib.mrgcn_distmult_ranks(_ptr(E), E.stride(0), N, _ptr(Rel), Rel.stride(0), H, _ptr(tr),
@@ -1074,7 +1188,7 @@ def _check_ids(queries, num_nodes: int, num_relations: int):
                          f"found {lo_r} .. {hi_r}")
 
 
-def predict_topk(queries, node_embeddings, edge_embeddings, k, side="tail", known=None):
+def predict_topk(queries, node_embeddings, edge_embeddings, k, side="tail", known=None, scorer="distmult"):
     """The k best completions of every query: `queries` [nq, 2] rows (anchor node, relation) — numpy or a tensor —,
     side="tail" ranks the nodes c of (anchor, relation, c), side="head" those of (c, relation, anchor).  Returns
     (idx int64 [nq, k], scores float32 [nq, k]) on the embeddings' device: score descending, equal scores (-0 == +0) by
@@ -1084,8 +1198,12 @@ def predict_topk(queries, node_embeddings, edge_embeddings, k, side="tail", know
     array of facts whose completions are excluded (`known_lists` builds the lists), or a ready (ptr, idx) pair of
     device tensors (int64 [nq + 1], int32) — with it and `queries` as a device tensor a call builds nothing on the host
     and can be captured in a graph (ids are then checked outside captures only).  1 <= k <= 256.  Embeddings must be
-    finite; results with NaN are undefined."""
+    finite; results with NaN are undefined.  `scorer="complex"`: ComplEx scores — those of the ComplEx ranks, bit for
+    bit, and of `mrgcn_amd.host.complex_candidate_scores` (mrgcn_complex_topk); an odd width raises `MrgcnError`."""
     head = _side(side)
+    cx = _scorer(scorer, "predict_topk")
+    if cx:
+        _complex_width(node_embeddings.shape[-1], "predict_topk")
     if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= TOPK_MAX:
         raise ValueError(f"predict_topk: k must be an integer in [1, {TOPK_MAX}], not {k!r}")
     k = int(k)
@@ -1130,28 +1248,30 @@ def predict_topk(queries, node_embeddings, edge_embeddings, k, side="tail", know
     if nq == 0:
         return out_idx, out_score
     lib = _lib.load()
-    ws_bytes = int(lib.mrgcn_distmult_topk_workspace(N, H, nq, k))
+    ws_bytes = int((lib.mrgcn_complex_topk_workspace if cx else lib.mrgcn_distmult_topk_workspace)(N, H, nq, k))
     if ws_bytes < 0:
         raise _lib.MrgcnError("predict_topk: sizes outside mrgcn_distmult_topk's limits")
     ws = torch.empty((ws_bytes + 7) // 8, dtype=torch.int64, device=dev)
     with torch.cuda.device(dev):
-        _lib.check(lib.mrgcn_distmult_topk(_ptr(E), E.stride(0), N, _ptr(Rel), Rel.stride(0), H, _ptr(q), nq, head,
+        _lib.check((lib.mrgcn_complex_topk if cx else lib.mrgcn_distmult_topk)(_ptr(E), E.stride(0), N, _ptr(Rel), Rel.stride(0), H, _ptr(q), nq, head,
                                            _ptr(ptr), _ptr(idx), k, _ptr(ws), ws_bytes, _ptr(out_idx),
-                                           _ptr(out_score), _stream()), "distmult_topk")
+                                           _ptr(out_score), _stream()), "complex_topk" if cx else "distmult_topk")
     return out_idx, out_score
 
 
-def predict_links(model, batch, queries, k, side="tail", known=None):
+def predict_links(model, batch, queries, k, side="tail", known=None, scorer="distmult"):
     """`predict_topk` on a model's own embeddings: `model.eval()`, then — without gradients — the batch's node
     embeddings (`_embed`: an MRGCN's forward, or a bare RGCN on the batch structure) against the model's relation
     embeddings.  `batch`: a FullBatch or a masked / sliced MiniBatch.  With a mini-batch the node ids of `queries`,
     `known` and the result are the BATCH-LOCAL ones (positions in `batch.node_index`, as in the facts `mkbatches`
-    returns); map results back with `batch.node_index[idx]`.  The model is left in eval mode."""
+    returns); map results back with `batch.node_index[idx]`.  The model is left in eval mode.  `scorer`: see
+    `predict_topk`."""
     _side(side)
+    _scorer(scorer, "predict_links")
     model.eval()
     with torch.no_grad():
         E = _embed(model, batch)
-        return predict_topk(queries, E, _relations(model), k, side=side, known=known)
+        return predict_topk(queries, E, _relations(model), k, side=side, known=known, scorer=scorer)
 
 
 # ---- the reference's full-batch run loop on the device (link_prediction.py:191-422; csrc/lp_eval.hip) ---------------
@@ -1206,7 +1326,7 @@ def rank_both_slice() -> int:
     return int(_lib.load().mrgcn_distmult_ranks_both_slice())
 
 
-def rank_both(facts, node_embeddings, edge_embeddings, lists=None, part_ptr=None, slice_facts=0):
+def rank_both(facts, node_embeddings, edge_embeddings, lists=None, part_ptr=None, slice_facts=0, scorer="distmult"):
     """Raw and filtered ranks of `facts` from ONE pass over the candidate scores (mrgcn_distmult_ranks_both): `(raw,
     flt)`, each what `compute_ranks_fast` returns without / with the filter, bit for bit; `flt` is None without lists.
     `facts`: an [n, 3] array, or a `FactParts` (its lists and parts are then taken).  `lists`: the four device tensors
@@ -1214,7 +1334,11 @@ def rank_both(facts, node_embeddings, edge_embeddings, lists=None, part_ptr=None
     stands for one `compute_ranks_fast` per part — the reference leaves facts at positions >= the number of nodes of a
     call unscored, and the position is then the one inside the part.  `slice_facts`: facts per launch of the scoring
     grid (0: `rank_both_slice()`).  With device tensors nothing is copied from or to the host, nothing synchronises and
-    a graph captures the call."""
+    a graph captures the call.  `scorer="complex"`: ComplEx scores (mrgcn_complex_ranks_both: the same contract, the
+    fact's own score kept per side, because the two sides round differently); an odd width raises `MrgcnError`."""
+    cx = _scorer(scorer, "rank_both")
+    if cx:
+        _complex_width(node_embeddings.shape[-1], "rank_both")
     if isinstance(facts, FactParts):
         lists = facts.lists if lists is None else lists
         part_ptr = facts.part_ptr if part_ptr is None else part_ptr
@@ -1251,13 +1375,13 @@ def rank_both(facts, node_embeddings, edge_embeddings, lists=None, part_ptr=None
             raise _lib.MrgcnError("rank_both: part_ptr is a device int64 [nparts + 1] tensor")
         part_ptr, nparts = part_ptr.contiguous(), int(part_ptr.numel()) - 1
     lib = _lib.load()
-    ws_bytes = int(lib.mrgcn_distmult_ranks_both_workspace(N, H, nf))
+    ws_bytes = int((lib.mrgcn_complex_ranks_both_workspace if cx else lib.mrgcn_distmult_ranks_both_workspace)(N, H, nf))
     ws = torch.empty((ws_bytes + 3) // 4, dtype=torch.int32, device=dev)
     with torch.cuda.device(dev):
-        _lib.check(lib.mrgcn_distmult_ranks_both(_ptr(E), E.stride(0), N, _ptr(Rel), Rel.stride(0), H, _ptr(tr), nf,
+        _lib.check((lib.mrgcn_complex_ranks_both if cx else lib.mrgcn_distmult_ranks_both)(_ptr(E), E.stride(0), N, _ptr(Rel), Rel.stride(0), H, _ptr(tr), nf,
                                                  _ptr(ls[0]), _ptr(ls[1]), _ptr(ls[2]), _ptr(ls[3]), _ptr(part_ptr),
                                                  nparts, int(slice_facts), _ptr(ws), ws_bytes, _ptr(raw), _ptr(flt),
-                                                 _stream()), "distmult_ranks_both")
+                                                 _stream()), "complex_ranks_both" if cx else "distmult_ranks_both")
     return raw, flt
 
 
@@ -1293,18 +1417,19 @@ def rank_metrics(ranks, part_ptr=None, out=None, score=None):
 
 
 def evaluate_facts(node_embeddings, edge_embeddings, parts: FactParts, want_ranks=False, out=None, score=None,
-                   slice_facts=0):
+                   slice_facts=0, scorer="distmult"):
     """test_model (:375-422) of the parts of a `FactParts` against ONE set of embeddings (full-batch mode: every part
     sees the whole graph's), without the host: `rank_both` and one `rank_metrics` per rank type.  Returns the float32
     `[8]` device vector raw mrr, hits@1, hits@3, hits@10, then the same filtered (-1 each when the parts carry no
     lists, as test_model reports them) — `out`, when given — and with `want_ranks` also `(raw, flt)`, the ranks of all
     parts as `rank_both` lays them out.  `score` (a float32 device scalar) receives `1 - raw mrr`.  No
-    synchronisation; capturable."""
+    synchronisation; capturable.  `scorer`: see `rank_both`."""
+    _scorer(scorer, "evaluate_facts")
     ptr = parts.part_ptr_host
     if not (ptr[0] == 0 and ptr[-1] == parts.n == parts.facts.shape[0] and bool(np.all(np.diff(ptr) > 0))
             and parts.part_ptr.numel() == len(ptr)):
         raise _lib.MrgcnError("evaluate_facts: part_ptr must rise from 0 to the number of facts, no part empty")
-    raw, flt = rank_both(parts, node_embeddings, edge_embeddings, slice_facts=slice_facts)
+    raw, flt = rank_both(parts, node_embeddings, edge_embeddings, slice_facts=slice_facts, scorer=scorer)
     if out is None:
         out = torch.empty(8, dtype=torch.float32, device=raw.device)
     rank_metrics(raw, parts.part_ptr, out[:4], score)
@@ -1329,7 +1454,7 @@ def eval_schedule(nepoch, eval_interval, has_valid):
 
 
 def train_step(model, forward_fn, sampler, optimizer, static=None, clip=1.0, l1_lambda=0.0, l2_lambda=0.0,
-               decoder="triples", loss="bce", pos_weight=None):
+               decoder="triples", loss="bce", pos_weight=None, scorer="distmult"):
     """One full-batch epoch of train_model (:231-326): `triples, labels = sampler()` (a `DeviceNegativeSampler`, or any
     callable that returns the facts followed by their corrupted copies and the 1 / 0 labels on the device without
     synchronising), `forward_fn()` for the node embeddings (e.g. `lambda: model(None, A)`), DistMult scores, BCE,
@@ -1339,13 +1464,15 @@ def train_step(model, forward_fn, sampler, optimizer, static=None, clip=1.0, l1_
     penalty) as a device scalar; no host read, so a graph captures it.  `decoder="grouped"` (`sampler` a
     `NegativeSampler`): `group_loss` over the sampler's groups — `loss` "bce" (with `pos_weight`, a host float) or
     "softmax" — in place of the flat scores and BCE; `static` None then means the sampler's own stored orders, built
-    on first use outside a capture."""
+    on first use outside a capture.  `scorer="complex"`: ComplEx scores (`score_complex_bc`) under the flat BCE; not
+    with the grouped decoder."""
     from ..optim import clip_grad_norm_
     from ..train import ClipAdam
-    _, group_kind, pos_weight = _decoder_args(decoder, loss, pos_weight, [sampler], "train_step")
+    _, group_kind, pos_weight = _decoder_args(decoder, loss, pos_weight, [sampler], "train_step", scorer)
     triples, labels = sampler()
     emb = forward_fn()
-    loss = _decoder_loss(triples, labels, emb, _relations(model), static, sampler, decoder, group_kind, pos_weight)
+    loss = _decoder_loss(triples, labels, emb, _relations(model), static, sampler, decoder, group_kind, pos_weight,
+                         scorer)
     optimizer.zero_grad(set_to_none=True)
     if l1_lambda > 0 or l2_lambda > 0:
         return _penalised_backward_and_step(model, optimizer, loss, clip, l1_lambda, l2_lambda)
@@ -1372,11 +1499,13 @@ class FitEpochs:
     (the last of them an evaluating epoch), after which the counters and rings are reset."""
 
     def __init__(self, model, forward_fn, tparts, vparts, optimizer, stopper=None, poll=8, graphed=True, sampler=None,
-                 static=None, warmup=3, l1_lambda=0.0, l2_lambda=0.0, decoder="triples", loss="bce", pos_weight=None):
+                 static=None, warmup=3, l1_lambda=0.0, l2_lambda=0.0, decoder="triples", loss="bce", pos_weight=None,
+                 scorer="distmult"):
         from .. import functional as Fn
         from ..train import _COUNT_ONLY, _StopState
-        _, loss, pos_weight = _decoder_args(decoder, loss, pos_weight, [sampler], "fit")
-        self.decoder = dict(decoder=decoder, loss=loss, pos_weight=pos_weight)
+        _, loss, pos_weight = _decoder_args(decoder, loss, pos_weight, [sampler], "fit", scorer)
+        self.decoder = dict(decoder=decoder, loss=loss, pos_weight=pos_weight, scorer=scorer)
+        self.scorer = scorer
         dev = tparts.facts.device
         if stopper is not None and vparts is None:
             raise _lib.MrgcnError("fit: early stopping scores the validation MRR: pass valid_facts")
@@ -1452,7 +1581,7 @@ class FitEpochs:
         self.model.eval()
         with torch.no_grad():
             E, Rel = self.forward_fn(), _relations(self.model)
-            evaluate_facts(E, Rel, self.tparts, out=out)
+            evaluate_facts(E, Rel, self.tparts, out=out, scorer=self.scorer)
         return E, Rel
 
     def _eval_epoch(self):
@@ -1461,7 +1590,7 @@ class FitEpochs:
         try:
             E, Rel = self._evaluate_train(self.row[1:9])
             if self.vparts is not None:   # (against the same embeddings)
-                evaluate_facts(E, Rel, self.vparts, out=self.row[9:17], score=self.score)
+                evaluate_facts(E, Rel, self.vparts, out=self.row[9:17], score=self.score, scorer=self.scorer)
         finally:
             self.model.train()
         (self.stopper if self.stopper is not None else self.eval_ctr).record_row(self.score, self.row, self.eval_ring)
@@ -1517,7 +1646,7 @@ def _run_schedule(run, sched, nepoch, poll, stopper):
 
 def fit(model, forward_fn, train_facts, valid_facts, optimizer, nepoch, eval_interval=1, mrr_batchsize=100,
         filter_ranks=True, early_stop=None, poll=8, graphed=True, sampler=None, warmup=3, static=None,
-        l1_lambda=0.0, l2_lambda=0.0, decoder="triples", loss="bce", pos_weight=None):
+        l1_lambda=0.0, l2_lambda=0.0, decoder="triples", loss="bce", pos_weight=None, scorer="distmult"):
     """The reference's full-batch link-prediction loop (train_model, link_prediction.py:191-373, with test_model
     :375-422) as a generator over its tuples `(epoch, loss, train_mrr, train_hits_at_k, valid_mrr, valid_hits_at_k)`
     — epochs from 1, `loss` a float, an mrr `{"raw", "flt"}`, hits `{"raw": [h@1, h@3, h@10], "flt": [...]}`, None
@@ -1529,7 +1658,9 @@ def fit(model, forward_fn, train_facts, valid_facts, optimizer, nepoch, eval_int
     (`DeviceNegativeSampler`, with the stored orders of the facts for the decoder's backward).  `l1_lambda` /
     `l2_lambda`: the loop's weight penalty (:306-322, `train_batch_step`), part of every step — captured ones too —
     and of the yielded loss.  `decoder="grouped"` (`sampler` a `NegativeSampler`), `loss`, `pos_weight`: the grouped
-    loss in every step (`train_step`, `group_loss`); a `pos_weight` tensor is read once, here.
+    loss in every step (`train_step`, `group_loss`); a `pos_weight` tensor is read once, here.  `scorer="complex"`:
+    ComplEx in place of DistMult, in the steps' flat BCE (eager and captured) and in both evaluations of an evaluating
+    epoch; not with the grouped decoder.
 
     An epoch is one of two step functions, chosen on the host from the epoch number (no device read):
     a training epoch — `train_step`, its loss into a device ring — and an evaluating epoch — the same, then ONE
@@ -1551,14 +1682,14 @@ def fit(model, forward_fn, train_facts, valid_facts, optimizer, nepoch, eval_int
     Under `torch.use_deterministic_algorithms(True)` the step takes the deterministic decoder kernels; what is added
     here (ranks: integer counts; metrics: a fixed-order float64 sum; records) has no float atomics."""
     from ..train import _as_device_stopper
-    _decoder_args(decoder, loss, pos_weight, [sampler], "fit")
+    _decoder_args(decoder, loss, pos_weight, [sampler], "fit", scorer)
     dev = next(model.parameters()).device
     nepoch, poll = int(nepoch), max(int(poll), 1)
     tparts = FactParts(train_facts, mrr_batchsize, filter_ranks, device=dev)
     vparts = FactParts(valid_facts, mrr_batchsize, filter_ranks, device=dev) if valid_facts is not None else None
     stopper = _as_device_stopper(early_stop, model, optimizer)
     run = FitEpochs(model, forward_fn, tparts, vparts, optimizer, stopper, poll, graphed, sampler, static, warmup,
-                    l1_lambda, l2_lambda, decoder, loss, pos_weight)
+                    l1_lambda, l2_lambda, decoder, loss, pos_weight, scorer)
     sched = eval_schedule(nepoch, eval_interval, vparts is not None)
     yield from _run_schedule(run, sched, nepoch, poll, stopper)
 
@@ -1584,7 +1715,8 @@ def batch_eval_workspace(num_nodes, H, num_facts, device):
     return torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=device)
 
 
-def batch_eval(node_embeddings, edge_embeddings, facts, lists=None, slot=None, ranks=None, workspace=None):
+def batch_eval(node_embeddings, edge_embeddings, facts, lists=None, slot=None, ranks=None, workspace=None,
+               scorer="distmult"):
     """test_model's work on ONE batch (:392-414) in one call of three launches (mrgcn_distmult_batch_eval): the
     batch's `facts` (a contiguous int64 [n, 3] device tensor of batch-local ids, n >= 1) ranked against the batch's own
     `node_embeddings`, raw and — with `lists`, the four device tensors of `filter_lists(facts)` — filtered, and the
@@ -1593,7 +1725,8 @@ def batch_eval(node_embeddings, edge_embeddings, facts, lists=None, slot=None, r
     half is `rank_metrics`' of those ranks.  `slot`: the contiguous float32 [8] row to write (None: a new one);
     `ranks`: a pair of contiguous int64 [2 n] device tensors (raw, flt; either may be None) that receive the ranks;
     `workspace`: `batch_eval_workspace(...)` of this shape (None: allocated here).  Returns the slot.  No
-    synchronisation; capturable."""
+    synchronisation; capturable.  `scorer`: "distmult" only (`scorer="complex"` raises `MrgcnError`)."""
+    _no_complex(scorer, "batch_eval")
     E = _f32_rows(node_embeddings.detach(), "node_embeddings")
     Rel = _f32_rows(edge_embeddings.detach(), "edge_embeddings")
     dev = E.device
@@ -1654,7 +1787,7 @@ def _check_slots(slots, n, who):
         raise _lib.MrgcnError(f"{who}: slots is a contiguous float32 [batches, 8] table on the device")
 
 
-def eval_batches(model, batches, filtered=True, slots=None, ranks=None):
+def eval_batches(model, batches, filtered=True, slots=None, ranks=None, scorer="distmult"):
     """test_model (:375-422) over prepared batches without the host: every batch's forward under `eval()` and
     `no_grad` (the model's mode is put back on exit), then `batch_eval` into row i of `slots`.  A batch's filter lists
     are built once and its workspace is allocated once; both stay with the batch.  Returns the float32 `[8]` device
@@ -1662,7 +1795,9 @@ def eval_batches(model, batches, filtered=True, slots=None, ranks=None):
     with `slots` (the caller's float32 [batches, 8] table, e.g. `BatchFitEpochs`'), leaves the per-batch values there
     and returns None: the means are the caller's business.  `ranks`: a pair of int64 device buffers of
     `2 * sum(facts)` values (raw, flt; flt may be None when not `filtered`); batch i's ranks land at twice the facts in
-    front of it, the order `evaluate_batches` flattens to.  No synchronisation."""
+    front of it, the order `evaluate_batches` flattens to.  No synchronisation.  `scorer`: "distmult" only
+    (`scorer="complex"` raises `MrgcnError`; `evaluate_batches` ranks with ComplEx)."""
+    _no_complex(scorer, "eval_batches")
     batches = list(batches)
     if not batches:
         raise _lib.MrgcnError("eval_batches: no batches")
@@ -1701,11 +1836,13 @@ def eval_batches(model, batches, filtered=True, slots=None, ranks=None):
     return row[1:9]
 
 
-def rank_batches(model, batches, filtered=True):
+def rank_batches(model, batches, filtered=True, scorer="distmult"):
     """`evaluate_batches`' result — `(mrr, hits_at_k, rankings)` as test_model returns them — from `eval_batches`:
     the batches' ranks land in two device buffers, the means come from the batches' slots, and everything is read back
     once, through pinned memory, after the last batch.  The rankings are `evaluate_batches`' exactly; its means are
-    float32 means of float32 values where these are float64 sums rounded once."""
+    float32 means of float32 values where these are float64 sums rounded once.  `scorer`: "distmult" only
+    (`scorer="complex"` raises `MrgcnError`)."""
+    _no_complex(scorer, "rank_batches")
     batches = list(batches)
     if not batches:
         raise _lib.MrgcnError("rank_batches: no batches")
@@ -1739,9 +1876,10 @@ class BatchFitEpochs:
 
     def __init__(self, model, train_batches, valid_batches, optimizer, stopper=None, poll=8, graphed=True,
                  filter_ranks=True, samplers=None, warmup=3, clip=1.0, l1_lambda=0.0, l2_lambda=0.0,
-                 decoder="triples", loss="bce", pos_weight=None):
+                 decoder="triples", loss="bce", pos_weight=None, scorer="distmult"):
         from .. import functional as Fn
         from ..train import _COUNT_ONLY, _StopState
+        _no_complex(scorer, "BatchFitEpochs")
         _decoder_args(decoder, loss, pos_weight, [None] if samplers is None else [], "fit_batches")
         train_batches, valid_batches = list(train_batches), list(valid_batches or [])
         if not train_batches:
@@ -1860,7 +1998,7 @@ class BatchFitEpochs:
 
 def fit_batches(model, train_batches, valid_batches, optimizer, nepoch, eval_interval=1, filter_ranks=True,
                 early_stop=None, poll=8, graphed=True, max_graph_batches=None, warmup=3, samplers=None,
-                l1_lambda=0.0, l2_lambda=0.0, decoder="triples", loss="bce", pos_weight=None):
+                l1_lambda=0.0, l2_lambda=0.0, decoder="triples", loss="bce", pos_weight=None, scorer="distmult"):
     """The reference's mini-batch link-prediction loop (train_model with gcn_batchsize > 0, link_prediction.py:224-373,
     with test_model :375-422) as a generator over its tuples `(epoch, loss, train_mrr, train_hits_at_k, valid_mrr,
     valid_hits_at_k)`, with `fit`'s contract row for row: the schedule (`eval_schedule`), the loss ring and the eval
@@ -1887,9 +2025,11 @@ def fit_batches(model, train_batches, valid_batches, optimizer, nepoch, eval_int
     every recorded loss (`train_batch_step`).  `decoder="grouped"` (with `samplers` that make `NegativeSampler`s,
     e.g. `batch_negative_samplers`), `loss`, `pos_weight`: the grouped loss in every batch step (`group_loss`).
 
-    Out of scope: literal-encoder batches inside a capture, the partitioned engines."""
+    Out of scope: literal-encoder batches inside a capture, the partitioned engines, and `scorer="complex"` (raises
+    `MrgcnError`: the fused batch evaluation scores DistMult only)."""
     from ..train import _as_device_stopper
     from .node_classification import MAX_GRAPH_BATCHES, _is_fixed_structure
+    _no_complex(scorer, "fit_batches")
     _decoder_args(decoder, loss, pos_weight, [None] if samplers is None else [], "fit_batches")
     train_batches, valid_batches = list(train_batches), list(valid_batches or [])
     nepoch, poll = int(nepoch), max(int(poll), 1)

@@ -111,6 +111,10 @@ python3 tools/lp_negatives_probe.py ${LP_NEGATIVES_PARENT_JSON:+--parent $LP_NEG
 # `python3 tools/lp_grouped_probe.py --rows triples --out <file>` there first; LP_GROUPED_PARENT_JSON=<file> then puts
 # them into the result.  Without it the file holds this tree's rows only.
 python3 tools/lp_grouped_probe.py ${LP_GROUPED_PARENT_JSON:+--parent $LP_GROUPED_PARENT_JSON} --out $o/lp_grouped_probe.json > $o/lp_grouped_probe.txt 2> $o/lp_grouped_probe.err
+# (10m) the ComplEx scorer next to DistMult at the FB15k-237 shape: flat scores + BCE, the backward alone (DistMult's
+# default and deterministic routes, ComplEx's one fixed-order route), rank_both over the validation-sized fact set,
+# predict_topk of 500 queries at k = 10, the replayed training epoch of fit; DistMult's rows again at the end
+python3 tools/lp_complex_probe.py --out $o/lp_complex_probe.json > $o/lp_complex_probe.txt 2> $o/lp_complex_probe.err
 hipcc -O3 --offload-arch=gfx950 -std=c++17 tools/lab/copy_lab.hip -o /tmp/copy_lab 2>/dev/null && /tmp/copy_lab > $o/copy_lab.txt 2>&1
 python3 tools/lab/spmm_hot_lab.py > $o/spmm_hot_lab.txt 2>&1
 # the CPU suite last: the tree these artefacts describe is green
