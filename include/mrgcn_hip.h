@@ -1205,6 +1205,41 @@ int mrgcn_distmult_group_bwd_f32(const float *E, int64_t ldE, const float *Rel, 
                                  const int64_t *order_p, const int64_t *order_o, float *dE, int64_t lddE, float *dRel,
                                  int64_t lddR, void *workspace, int64_t workspace_bytes, void *stream);
 
+/* ---- 1-vs-all softmax decoder on the matrix cores (csrc/lp_all.hip) -----------------------------------------------
+ * Every query vector Q[q] scored against ALL rows of the candidate table E under a softmax cross-entropy:
+ * x[q][c] = Q[q] . E[c], loss = (1/m) sum_q (log sum_c exp x[q][c] - x[q][target[q]]) — the objective of Kadlec, Bajgar,
+ * Kleindienst ("Knowledge Base Completion: Baselines Strike Back", 2017), Lacroix, Usunier, Obozinski ("Canonical
+ * Tensor Decomposition for Knowledge Base Completion", ICML 2018) and Ruffinelli, Broscheit, Gemulla ("You CAN Teach an
+ * Old Dog New Tricks! On Training Knowledge Graph Embeddings", ICLR 2020); the reference has the sampled BCE only
+ * (mrgcn/tasks/link_prediction.py:645-665, :550-554), so the papers stand where a reference call site would.  The
+ * unit does not know the scorer: the caller builds the query vectors (tasks/link_prediction.py: pair_vectors).  The
+ * [m, N] score matrix is never stored; all three kernels compute 64 x 64 score tiles with v_mfma_f32_16x16x4_f32
+ * (exact fp32).  Q [m, H] and E [N, H] are float32 with row strides ldQ / ldE; target int64 [m], 0 <= target < N (not
+ * checked here).
+ * _supported: 1 when the kernels take the shape — H % 4 == 0, 4 <= H <= 256, 1 <= m, N < 2^31, ldQ / ldE >= H and
+ *   multiples of 4, 16-byte aligned bases —, else 0 (the caller materialises the scores instead).
+ * _chunk: the candidates per forward chunk: with fewer than 256 query tiles of 64 the forward cuts the candidates
+ *   into chunks of this many over gridDim.y and merges the chunks' (max, sum) pairs in chunk order.
+ * _workspace: the bytes _fwd needs (-1 for sizes it does not take); _bwd needs none.
+ * _fwd: lse [2 m]: lse[q] = log sum_c exp x[q][c] by an online max / sum, rounded to float32 from the float64 it is
+ *   merged in, and lse[m + q] what that rounding left (the backward subtracts both: exp(x - lse) then does not carry
+ *   half an ulp of lse); xt [m] = x[q][target[q]] from the same tile arithmetic (lse - xt >= 0 in bits when N == 1);
+ *   *loss WRITTEN: lse - xt summed as float64 in a fixed order, divided by m and rounded once.
+ * _bwd: lse as _fwd wrote it ([2 m]); with G[q][c] = (exp(x[q][c] - lse[q]) - [c == target[q]]) * *gl / m (gl: a float in DEVICE memory, no host
+ *   read), dQ = G . E and dE = G^T . Q are WRITTEN (every output row has one owning block; nothing is added); either
+ *   may be NULL and its kernel is skipped.  Both recompute the scores.
+ * No float atomics: equal inputs give equal bits.  Stream ordered, no allocation, capturable. */
+int32_t mrgcn_lp_all_supported(const float *Q, int64_t ldQ, int64_t m, const float *E, int64_t ldE, int64_t N,
+                               int32_t H);
+int64_t mrgcn_lp_all_chunk(void);
+int64_t mrgcn_lp_all_workspace(int64_t m, int64_t N, int32_t H);
+int mrgcn_lp_all_fwd_f32(const float *Q, int64_t ldQ, int64_t m, const float *E, int64_t ldE, int64_t N, int32_t H,
+                         const int64_t *target, float *lse, float *xt, float *loss, void *workspace,
+                         int64_t workspace_bytes, void *stream);
+int mrgcn_lp_all_bwd_f32(const float *Q, int64_t ldQ, int64_t m, const float *E, int64_t ldE, int64_t N, int32_t H,
+                         const int64_t *target, const float *lse, const float *gl, float *dQ, int64_t lddQ, float *dE,
+                         int64_t lddE, void *workspace, int64_t workspace_bytes, void *stream);
+
 /* ---- validation and early stopping inside a replayed epoch (csrc/early_stop.hip) ---------------------------------
  * Evaluation of a label set: loss_out = mean cross-entropy of the rows logits[idx[i], :C] (max-subtracted
  * log-sum-exp, as mrgcn_softmax_xent_rows_f32), correct_out = how many of those rows have their arg-max at target[i]

@@ -204,3 +204,78 @@ def complex_scores64(triples, E, Rel):
         raise ValueError("complex_scores64: rows of an even, equal width")
     Ec, Rc = E[:, :K] + 1j * E[:, K:], Rel[:, :K] + 1j * Rel[:, K:]
     return np.real(np.sum(Ec[t[:, 0]] * Rc[t[:, 1]] * np.conj(Ec[t[:, 2]]), axis=1))
+
+
+# ---- the 1-vs-all softmax decoder (csrc/lp_all.hip; tasks/link_prediction.py: pair_vectors, all_loss) -------------
+ALL_SIDES = ("both", "tail", "head")
+
+
+def _pair_vectors_np(facts, E, Rel, side, scorer, dtype):
+    import numpy as np
+    if side not in ALL_SIDES:
+        raise ValueError(f"side is one of {ALL_SIDES}, not {side!r}")
+    if scorer not in ("distmult", "complex"):
+        raise ValueError(f"scorer is 'distmult' or 'complex', not {scorer!r}")
+    t = np.asarray(facts, dtype=np.int64).reshape(-1, 3)
+    E, Rel = np.asarray(E, dtype=dtype), np.asarray(Rel, dtype=dtype)
+    H = E.shape[1]
+    if Rel.shape[1] != H or (scorer == "complex" and H % 2):
+        raise ValueError("pair_vectors: rows of an equal (ComplEx: even) width")
+    K = H // 2
+    q, tg = [], []
+    if side in ("both", "tail"):
+        x, r = E[t[:, 0]], Rel[t[:, 1]]
+        if scorer == "distmult":
+            q.append(x * r)
+        else:
+            xr, xi, rr, ri = x[:, :K], x[:, K:], r[:, :K], r[:, K:]
+            q.append(np.concatenate([xr * rr - xi * ri, xi * rr + xr * ri], axis=1))
+        tg.append(t[:, 2])
+    if side in ("both", "head"):
+        x, r = E[t[:, 2]], Rel[t[:, 1]]
+        if scorer == "distmult":
+            q.append(r * x)
+        else:
+            xr, xi, rr, ri = x[:, :K], x[:, K:], r[:, :K], r[:, K:]
+            q.append(np.concatenate([rr * xr + ri * xi, rr * xi - ri * xr], axis=1))
+        tg.append(t[:, 0])
+    return np.concatenate(q, axis=0), np.concatenate(tg, axis=0)
+
+
+def pair_vectors64(facts, E, Rel, side="both", scorer="distmult"):
+    """`link_prediction.pair_vectors` in numpy float64 -> (Q [m, H], target [m]): the vector whose plain dot product
+    with a candidate's row is the score of the fact with that candidate as its missing end.  DistMult: tail
+    q = E[s] * Rel[p], target o; head q = Rel[p] * E[o], target s.  ComplEx: csrc/lp_score.hpp's pair vectors (real
+    parts first).  `side="both"`: the tail queries, then the head queries (m = 2 n)."""
+    import numpy as np
+    return _pair_vectors_np(facts, E, Rel, side, scorer, np.float64)
+
+
+def all_loss64(Q, E, target, upstream=1.0):
+    """The mean 1-vs-all softmax cross-entropy of the scores x = Q E^T in numpy float64, with a max-shifted logsumexp
+    -> (loss, lse [m], dQ [m, H], dE [N, H]), the gradients for the upstream scalar `upstream`."""
+    import numpy as np
+    Q, E = np.asarray(Q, dtype=np.float64), np.asarray(E, dtype=np.float64)
+    tg = np.asarray(target, dtype=np.int64)
+    m = Q.shape[0]
+    x = Q @ E.T
+    mx = x.max(axis=1, keepdims=True)
+    lse = mx[:, 0] + np.log(np.exp(x - mx).sum(axis=1))
+    loss = float(np.mean(lse - x[np.arange(m), tg]))
+    G = np.exp(x - lse[:, None])
+    G[np.arange(m), tg] -= 1.0
+    G *= float(upstream) / m
+    return loss, lse, G @ E, G.T @ Q
+
+
+def all_lse32(Q, E, target):
+    """`all_loss64`'s forward in float32 — a float32 matmul plus a float32 max-shifted logsumexp -> (lse [m], xt [m]):
+    what the kernel differs from in summation order only."""
+    import numpy as np
+    Q, E = np.ascontiguousarray(Q, dtype=np.float32), np.ascontiguousarray(E, dtype=np.float32)
+    tg = np.asarray(target, dtype=np.int64)
+    x = Q @ E.T
+    mx = x.max(axis=1, keepdims=True)
+    lse = mx[:, 0] + np.log(np.exp(x - mx).sum(axis=1, dtype=np.float32))
+    assert lse.dtype == np.float32
+    return lse, x[np.arange(Q.shape[0]), tg]

@@ -549,12 +549,178 @@ def group_scores(triples, node_embeddings, edge_embeddings, num_facts, rate):
         return _GroupLoss.apply(E.detach(), Rel.detach(), t, n, rate, 0, 1.0, None)[1]
 
 
+# ---- the 1-vs-all softmax decoder (csrc/lp_all.hip) ----------------------------------------------------------------
+# Every fact scored against ALL candidates on both sides under a softmax cross-entropy — the objective DistMult and
+# ComplEx are normally trained with (Kadlec et al. 2017; Lacroix et al. 2018; Ruffinelli et al. 2020) — without the
+# [queries, nodes] score matrix ever being stored.
+ALL_SIDES = ("both", "tail", "head")
+
+
+def _all_side(side, who):
+    if side not in ALL_SIDES:
+        raise _lib.MrgcnError(f"{who}: side is one of {ALL_SIDES}, not {side!r}")
+    return side
+
+
+def pair_vectors(facts, E, Rel, side="both", scorer="distmult"):
+    """(Q [m, H], target [m]) of the facts (an int64 [n, 3] tensor on E's device), as torch ops under autograd
+    (index_select and elementwise work, O(m H)): Q[i] is the vector whose plain dot product with a candidate's row is
+    the score of fact i with that candidate as its missing end, target[i] the fact's own end.  DistMult: tail
+    q = E[s] * Rel[p], target o; head q = Rel[p] * E[o], target s.  ComplEx: csrc/lp_score.hpp's pair vectors, real
+    parts first — tail (xr rr - xi ri | xi rr + xr ri), head (rr xr + ri xi | rr xi - ri xr).  `side="both"`: the tail
+    queries, then the head queries (m = 2 n).  `host.pair_vectors64` is the float64 mirror."""
+    cx = _scorer(scorer, "pair_vectors")
+    _all_side(side, "pair_vectors")
+    H = int(E.shape[1])
+    if cx:
+        _complex_width(H, "pair_vectors")
+    K = H // 2
+    s, p, o = facts[:, 0], facts[:, 1], facts[:, 2]
+    r = Rel.index_select(0, p)
+    q, tg = [], []
+    if side in ("both", "tail"):
+        x = E.index_select(0, s)
+        if cx:
+            xr, xi, rr, ri = x[:, :K], x[:, K:], r[:, :K], r[:, K:]
+            q.append(torch.cat([xr * rr - xi * ri, xi * rr + xr * ri], 1))
+        else:
+            q.append(x * r)
+        tg.append(o)
+    if side in ("both", "head"):
+        x = E.index_select(0, o)
+        if cx:
+            xr, xi, rr, ri = x[:, :K], x[:, K:], r[:, :K], r[:, K:]
+            q.append(torch.cat([rr * xr + ri * xi, rr * xi - ri * xr], 1))
+        else:
+            q.append(r * x)
+        tg.append(s)
+    if len(q) == 1:
+        return q[0], tg[0].contiguous()
+    return torch.cat(q, 0), torch.cat(tg, 0)
+
+
+def _all_supported(lib, Q, E) -> bool:
+    return bool(Q.shape[0] >= 1 and E.shape[0] >= 1 and lib.mrgcn_lp_all_supported(
+        _ptr(Q), Q.stride(0), Q.shape[0], _ptr(E), E.stride(0), E.shape[0], E.shape[1]))
+
+
+def _all_fwd(lib, Q, E, target):
+    m, N, H = Q.shape[0], E.shape[0], E.shape[1]
+    out = torch.empty(3 * m + 1, dtype=torch.float32, device=E.device)
+    lse, xt, loss = out[:2 * m], out[2 * m:3 * m], out[3 * m:].view(())   # (lse: the float32 values, then their remainders)
+    ws = _det_scratch(E.device, "lp_all", int(lib.mrgcn_lp_all_workspace(m, N, H)))
+    _lib.check(lib.mrgcn_lp_all_fwd_f32(_ptr(Q), Q.stride(0), m, _ptr(E), E.stride(0), N, H, _ptr(target), _ptr(lse),
+                                        _ptr(xt), _ptr(loss), _ptr(ws), ws.numel(), _stream()), "lp_all_fwd")
+    return lse, xt, loss
+
+
+class _AllLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, Q, E, target):
+        lse, _, loss = _all_fwd(_lib.load(), Q, E, target)
+        ctx.save_for_backward(Q, E, target, lse)
+        return loss
+
+    @staticmethod
+    def backward(ctx, gl):
+        Q, E, target, lse = ctx.saved_tensors
+        gl = gl.contiguous().float()
+        dQ = torch.empty(Q.shape, dtype=torch.float32, device=Q.device) if ctx.needs_input_grad[0] else None
+        dE = torch.empty(E.shape, dtype=torch.float32, device=E.device) if ctx.needs_input_grad[1] else None
+        _lib.check(_lib.load().mrgcn_lp_all_bwd_f32(
+            _ptr(Q), Q.stride(0), Q.shape[0], _ptr(E), E.stride(0), E.shape[0], E.shape[1], _ptr(target), _ptr(lse),
+            _ptr(gl), _ptr(dQ), Q.shape[1], _ptr(dE), E.shape[1], None, 0, _stream()), "lp_all_bwd")
+        return dQ, dE, None
+
+
+def all_pairs_loss(Q, E, target):
+    """The mean softmax cross-entropy of the scores Q E^T against `target` (float32 [m, H] and [N, H] on the device,
+    int64 [m]) as a float32 device scalar carrying autograd to Q and E — `F.cross_entropy(Q @ E.T, target)` without the
+    [m, N] matrix (csrc/lp_all.hip); never synchronises.  Shapes the kernels do not take — H % 4 != 0, H > 256, rows
+    not 16-byte aligned — materialise the matrix (`stats()["lp.decoder.all.fallback"]`)."""
+    import torch.nn.functional as F
+    Q, E = _f32_rows(Q, "Q"), _f32_rows(E, "E")
+    if Q.shape[1] != E.shape[1] or target.shape[0] != Q.shape[0]:
+        raise _lib.MrgcnError("all_pairs_loss: Q [m, H], E [N, H], target [m]")
+    target = target.contiguous()
+    if not _all_supported(_lib.load(), Q, E):
+        bump("lp.decoder.all.fallback")
+        return F.cross_entropy(Q @ E.t(), target)
+    return _AllLoss.apply(Q, E, target)
+
+
+def all_lse(Q, E, target):
+    """(lse [m], xt [m]) as the forward kernel writes them — lse[q] = log sum_c exp(Q[q] . E[c]),
+    xt[q] = Q[q] . E[target[q]] — without autograd, for tests and tools.  Raises where the kernels do not take the
+    shape."""
+    Q, E = _f32_rows(Q, "Q"), _f32_rows(E, "E")
+    lib = _lib.load()
+    if Q.shape[1] != E.shape[1] or target.shape[0] != Q.shape[0] or not _all_supported(lib, Q, E):
+        raise _lib.MrgcnError("all_lse: the 1-vs-all kernels do not take this shape")
+    with torch.no_grad():
+        lse, xt, _ = _all_fwd(lib, Q.detach(), E.detach(), target.contiguous())
+    return lse[:Q.shape[0]], xt
+
+
+def all_loss(facts, node_embeddings, edge_embeddings, side="both", scorer="distmult"):
+    """The mean 1-vs-all softmax cross-entropy of the facts: every fact scored against ALL rows of `node_embeddings` as
+    its missing tail and — `side="both"` — as its missing head (`side`: "both", "tail" or "head"), the fact's own end
+    the target.  A float32 device scalar carrying autograd to both embedding tensors; never synchronises, so a hipGraph
+    captures it.  `facts`: an int64 [n, 3] array or device tensor, n >= 1; its ids are checked once per tensor, outside
+    stream captures.  `scorer`: "distmult" or "complex" (`pair_vectors` builds the query vectors; the kernels of
+    csrc/lp_all.hip do not know the scorer).  Known answers other than the fact's own stay in the denominator (no
+    filtering), there is no label smoothing.  Shapes the kernels do not take go through
+    `F.cross_entropy(Q @ E.T, target)` (`stats()["lp.decoder.all.fallback"]`)."""
+    _scorer(scorer, "all_loss")
+    _all_side(side, "all_loss")
+    E = _f32_rows(node_embeddings, "node_embeddings")
+    Rel = _f32_rows(edge_embeddings, "edge_embeddings")
+    t = facts if torch.is_tensor(facts) and facts.is_cuda and facts.dtype == torch.int64 and facts.dim() == 2 \
+        and facts.is_contiguous() else _triples(facts, E.device)
+    if t.shape[0] < 1:
+        raise _lib.MrgcnError("all_loss: facts are [n, 3] with n >= 1")
+    shape = (int(E.shape[0]), int(Rel.shape[0]))
+    if getattr(t, "_mrgcn_all", None) != shape and not torch.cuda.is_current_stream_capturing():
+        _check_group_ids(t, E, Rel, "all_loss")
+        try:
+            t._mrgcn_all = shape
+        except AttributeError:
+            pass
+    bump("lp.decoder.all")
+    Q, target = pair_vectors(t, E, Rel, side, scorer)
+    return all_pairs_loss(Q, E, target)
+
+
+def _all_facts(sampler, fallback, who):
+    """The facts of the 1-vs-all decoder: `sampler.facts` (both device samplers have it; the sampler is NOT called, no
+    negatives are drawn), else `fallback`."""
+    if sampler is None:
+        return fallback
+    facts = getattr(sampler, "facts", None)
+    if facts is None:
+        raise _lib.MrgcnError(f"{who}: decoder='all' reads the facts from `sampler.facts` (DeviceNegativeSampler and "
+                              f"NegativeSampler have it), which {type(sampler).__name__} lacks")
+    return facts
+
+
 def _decoder_args(decoder, loss, pos_weight, samplers, who, scorer="distmult"):
     """The run loops' `decoder` / `loss` / `pos_weight` / `scorer` keywords, checked before any kernel is touched ->
     (grouped?, loss, pos_weight as a host float or None)."""
     cx = _scorer(scorer, who)
-    if decoder not in ("triples", "grouped"):
-        raise _lib.MrgcnError(f"{who}: decoder is 'triples' or 'grouped', not {decoder!r}")
+    if decoder not in ("triples", "grouped", "all"):
+        raise _lib.MrgcnError(f"{who}: decoder is 'triples', 'grouped' or 'all', not {decoder!r}")
+    if decoder == "all":
+        if loss == "bce":
+            raise _lib.MrgcnError(f"{who}: decoder='all' is the 1-vs-all softmax cross-entropy: pass loss='softmax' "
+                                  "(a 1-vs-all BCE is not built)")
+        if loss != "softmax":
+            raise _lib.MrgcnError(f"{who}: decoder='all' takes loss='softmax', not {loss!r}")
+        if pos_weight is not None:
+            raise _lib.MrgcnError(f"{who}: pos_weight belongs to loss='bce' (the 1-vs-all softmax has no labels to "
+                                  "weigh)")
+        for smp in samplers:
+            _all_facts(smp, None, who)
+        return False, "softmax", None
     if cx and decoder == "grouped":
         raise _lib.MrgcnError(f"{who}: decoder='grouped' scores DistMult only: scorer='complex' takes the flat "
                               "decoder (decoder='triples')")
@@ -585,7 +751,10 @@ def _decoder_loss(triples, labels, E, Rel, static, sampler=None, decoder="triple
                   scorer="distmult"):
     """The decoder line of every step and run loop: the flat BCE of `score_distmult_bc` (`scorer="complex"`: of
     `score_complex_bc`), or the grouped loss over `sampler`'s groups (`static` None: the sampler's own stored
-    orders)."""
+    orders), or — `decoder="all"`, `triples` then the facts alone — the 1-vs-all softmax cross-entropy on both sides
+    (`all_loss`)."""
+    if decoder == "all":
+        return all_loss(triples, E, Rel, side="both", scorer=scorer)
     if decoder != "grouped":
         score = score_complex_bc if scorer == "complex" else score_distmult_bc
         return binary_crossentropy(score(triples, E, Rel, static=static), labels)
@@ -1004,7 +1173,9 @@ def train_batch_step(model, batch, facts, optimizer, negatives=None, clip=1.0, s
     a max_norm takes the penalty of the weights it steps into its own step (`penalty_owners`), without an autograd
     graph over them.  `decoder="grouped"` (with a `NegativeSampler` as `sampler`): the grouped loss (`group_loss`) in
     place of the flat scores and BCE — `loss` "bce" (with `pos_weight`) or "softmax"; everything else unchanged.
-    `scorer="complex"`: ComplEx scores (`score_complex_bc`) under the flat BCE; not with the grouped decoder."""
+    `scorer="complex"`: ComplEx scores (`score_complex_bc`) under the flat BCE; not with the grouped decoder.
+    `decoder="all"` with `loss="softmax"`: the 1-vs-all softmax cross-entropy (`all_loss`) of the batch's facts —
+    `sampler.facts` when there is a sampler, which is not called — against the batch's own nodes, on both sides."""
     from ..optim import clip_grad_norm_
     from ..train import ClipAdam
     grouped, group_kind, pos_weight = _decoder_args(decoder, loss, pos_weight, [sampler], "train_batch_step", scorer)
@@ -1015,7 +1186,11 @@ def train_batch_step(model, batch, facts, optimizer, negatives=None, clip=1.0, s
         raise _lib.MrgcnError("train_batch_step: slot is one float32 on the device")
     if negatives is not None and sampler is not None:
         raise _lib.MrgcnError("train_batch_step: negatives or a sampler, not both")
-    if sampler is not None:
+    if decoder == "all":
+        if negatives is not None:
+            raise _lib.MrgcnError("train_batch_step: decoder='all' scores every node of the batch: it takes no negatives")
+        triples, labels = _all_facts(sampler, st["facts"], "train_batch_step"), None
+    elif sampler is not None:
         triples, labels = sampler()
     elif negatives is None:
         triples, labels = st["sampler"]()
@@ -1465,11 +1640,18 @@ def train_step(model, forward_fn, sampler, optimizer, static=None, clip=1.0, l1_
     `NegativeSampler`): `group_loss` over the sampler's groups — `loss` "bce" (with `pos_weight`, a host float) or
     "softmax" — in place of the flat scores and BCE; `static` None then means the sampler's own stored orders, built
     on first use outside a capture.  `scorer="complex"`: ComplEx scores (`score_complex_bc`) under the flat BCE; not
-    with the grouped decoder."""
+    with the grouped decoder.  `decoder="all"` with `loss="softmax"`: the 1-vs-all softmax cross-entropy (`all_loss`)
+    of `sampler.facts` against every row of the embeddings, on both sides, with either scorer; the sampler is not
+    called and no negatives are drawn."""
     from ..optim import clip_grad_norm_
     from ..train import ClipAdam
     _, group_kind, pos_weight = _decoder_args(decoder, loss, pos_weight, [sampler], "train_step", scorer)
-    triples, labels = sampler()
+    if decoder == "all":   # (the sampler is not called: no negatives are drawn)
+        if sampler is None:
+            raise _lib.MrgcnError("train_step: decoder='all' reads the facts from `sampler.facts`: pass a sampler")
+        triples, labels = _all_facts(sampler, None, "train_step"), None
+    else:
+        triples, labels = sampler()
     emb = forward_fn()
     loss = _decoder_loss(triples, labels, emb, _relations(model), static, sampler, decoder, group_kind, pos_weight,
                          scorer)
@@ -1513,7 +1695,7 @@ class FitEpochs:
             raise _lib.MrgcnError("fit(graphed=True) needs ClipAdam(..., capturable=True)")
         if sampler is None:
             sampler = DeviceNegativeSampler(tparts.facts)
-            if static is None:
+            if static is None and decoder != "all":   # (the 1-vs-all decoder has no stored orders to walk)
                 was = model.training
                 model.eval()
                 with torch.no_grad():
@@ -1660,7 +1842,8 @@ def fit(model, forward_fn, train_facts, valid_facts, optimizer, nepoch, eval_int
     and of the yielded loss.  `decoder="grouped"` (`sampler` a `NegativeSampler`), `loss`, `pos_weight`: the grouped
     loss in every step (`train_step`, `group_loss`); a `pos_weight` tensor is read once, here.  `scorer="complex"`:
     ComplEx in place of DistMult, in the steps' flat BCE (eager and captured) and in both evaluations of an evaluating
-    epoch; not with the grouped decoder.
+    epoch; not with the grouped decoder.  `decoder="all"` with `loss="softmax"`: the 1-vs-all softmax cross-entropy
+    (`all_loss`) of the training facts against all nodes in every step, with either scorer; no negatives are drawn.
 
     An epoch is one of two step functions, chosen on the host from the epoch number (no device read):
     a training epoch — `train_step`, its loss into a device ring — and an evaluating epoch — the same, then ONE
@@ -2024,6 +2207,8 @@ def fit_batches(model, train_batches, valid_batches, optimizer, nepoch, eval_int
     `l1_lambda` / `l2_lambda`: the loop's weight penalty (:306-322) in every batch step, eager or captured, and in
     every recorded loss (`train_batch_step`).  `decoder="grouped"` (with `samplers` that make `NegativeSampler`s,
     e.g. `batch_negative_samplers`), `loss`, `pos_weight`: the grouped loss in every batch step (`group_loss`).
+    `decoder="all"` with `loss="softmax"`: the 1-vs-all softmax cross-entropy (`all_loss`) of every batch's facts
+    against that batch's own nodes; `samplers` may stay None, and a sampler that is given is not called.
 
     Out of scope: literal-encoder batches inside a capture, the partitioned engines, and `scorer="complex"` (raises
     `MrgcnError`: the fused batch evaluation scores DistMult only)."""

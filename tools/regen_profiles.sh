@@ -115,6 +115,11 @@ python3 tools/lp_grouped_probe.py ${LP_GROUPED_PARENT_JSON:+--parent $LP_GROUPED
 # default and deterministic routes, ComplEx's one fixed-order route), rank_both over the validation-sized fact set,
 # predict_topk of 500 queries at k = 10, the replayed training epoch of fit; DistMult's rows again at the end
 python3 tools/lp_complex_probe.py --out $o/lp_complex_probe.json > $o/lp_complex_probe.txt 2> $o/lp_complex_probe.err
+# (10n) the 1-vs-all softmax decoder at the FB15k-237 shape: all_loss forward / backward and its three kernels alone
+# (with their TFLOP/s) at 4 096, 32 768 and all 272 115 facts next to F.cross_entropy on the materialised matrix where
+# that fits, the replayed training epoch of fit with decoder="all" against decoder="grouped" at 10 negatives, the median
+# mini-batch's step; every leg in a child process under its own time limit
+python3 tools/lp_all_probe.py --out $o/lp_all_probe.json > $o/lp_all_probe.txt 2> $o/lp_all_probe.err
 hipcc -O3 --offload-arch=gfx950 -std=c++17 tools/lab/copy_lab.hip -o /tmp/copy_lab 2>/dev/null && /tmp/copy_lab > $o/copy_lab.txt 2>&1
 python3 tools/lab/spmm_hot_lab.py > $o/spmm_hot_lab.txt 2>&1
 # the CPU suite last: the tree these artefacts describe is green
