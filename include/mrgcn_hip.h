@@ -1240,6 +1240,37 @@ int mrgcn_lp_all_bwd_f32(const float *Q, int64_t ldQ, int64_t m, const float *E,
                          const int64_t *target, const float *lse, const float *gl, float *dQ, int64_t lddQ, float *dE,
                          int64_t lddE, void *workspace, int64_t workspace_bytes, void *stream);
 
+/* ---- block-diagonal relation transform (csrc/block_xform.hip) ------------------------------------------------------
+ * Schlichtkrull et al. 2018, "Modeling Relational Data with Graph Convolutional Networks", eq. 4:
+ * W_r = blockdiag(Q_r[0], ..., Q_r[NB-1]), NB blocks of ki x fo = (K / NB) x (F / NB); input columns b ki .. b ki + ki - 1
+ * feed output columns b fo .. b fo + fo - 1 only.  W: [R][NB][ki][fo].  Per compact column c = (j_c, r_c), f = b fo + q:
+ *     Out[o(c), f] = sum_{k < ki} X[j_c, b ki + k] . W[r_c, b, k, q]
+ * with o(c) = c or MPOS[c] (`operand_order` != 0) and the whole padded row written (zeros in [F, ldOut), nothing else),
+ * as mrgcn_rel_transform_fwd_f32 does.  The sum runs over k rising from +0, every product and every sum rounded to
+ * float32 on its own (no fused multiply-add): the result is one statement of float32 operations, equal to its numpy
+ * mirror (mrgcn_amd.host.block_transform32) bit for bit.
+ * Backward from dM [ncols, ldM] in plain compact order (the TRANSPOSED view's output); either output nullable:
+ *     dX[j, b ki + k] = sum_{c in NPTR[j] .. NPTR[j+1]} sum_{q < fo} W[r_c, b, k, q] . dM[c, b fo + q]
+ *                       (a node's columns in four consecutive runs, each added with c rising and q rising inside it, the
+ *                       four partial rows added in run order; every row written, zeros for a node without a column)
+ *     dW[r, b, k, q]  = sum_{c : r_c = r} X[j_c, b ki + k] . dM[c, b fo + q]
+ *                       (units of 256 columns of RPERM inside one (band, relation) group write partial slabs of K fo
+ *                       floats to the workspace, a second launch adds a relation's slabs in a fixed order; a relation
+ *                       without columns gets zeros)
+ * No float atomics: equal inputs give equal bits on every run.  X is not read when dW is NULL, W not when dX is NULL.
+ * Limits (_supported): NB divides K and F, 1 <= ki, fo <= 64, K, F <= 256, K fo 4 <= 64 KB, fewer than 65536
+ * relations; the calls also need ldX >= K, ldOut >= F, ldM >= F, lddX >= K.  A shape outside them, or a workspace
+ * smaller than _bwd_workspace(...) floats, is MRGCN_ERR_INVALID. */
+int32_t mrgcn_block_transform_supported(const mrgcn_plan_t *plan, int32_t K, int32_t F, int32_t NB);
+int mrgcn_block_transform_fwd_f32(const mrgcn_plan_t *plan, const float *X, int64_t ldX, int32_t K, const float *W,
+                                  int32_t NB, int32_t F, float *Out, int64_t ldOut, int32_t operand_order,
+                                  void *stream);
+int64_t mrgcn_block_transform_bwd_workspace(const mrgcn_plan_t *plan, int32_t K, int32_t F, int32_t NB,
+                                            int32_t need_dX, int32_t need_dW); /* floats */
+int mrgcn_block_transform_bwd_f32(const mrgcn_plan_t *plan, const float *dM, int64_t ldM, const float *X, int64_t ldX,
+                                  int32_t K, const float *W, int32_t NB, int32_t F, float *dX, int64_t lddX, float *dW,
+                                  float *workspace, int64_t workspace_floats, void *stream);
+
 /* ---- validation and early stopping inside a replayed epoch (csrc/early_stop.hip) ---------------------------------
  * Evaluation of a label set: loss_out = mean cross-entropy of the rows logits[idx[i], :C] (max-subtracted
  * log-sum-exp, as mrgcn_softmax_xent_rows_f32), correct_out = how many of those rows have their arg-max at target[i]

@@ -304,6 +304,11 @@ SIGNATURES = {
     "mrgcn_lp_all_fwd_f32": (C.c_int, [_p, _i64, _i64, _p, _i64, _i64, _i32, _p, _p, _p, _p, _p, _i64, _p]),
     "mrgcn_lp_all_bwd_f32": (C.c_int, [_p, _i64, _i64, _p, _i64, _i64, _i32, _p, _p, _p, _p, _i64, _p, _i64, _p,
                                        _i64, _p]),
+    "mrgcn_block_transform_supported": (_i32, [_p, _i32, _i32, _i32]),
+    "mrgcn_block_transform_fwd_f32": (C.c_int, [_p, _p, _i64, _i32, _p, _i32, _i32, _p, _i64, _i32, _p]),
+    "mrgcn_block_transform_bwd_workspace": (C.c_int64, [_p, _i32, _i32, _i32, _i32, _i32]),
+    "mrgcn_block_transform_bwd_f32": (C.c_int, [_p, _p, _i64, _p, _i64, _i32, _p, _i32, _i32, _p, _i64, _p, _p, _i64,
+                                                _p]),
     "mrgcn_xent_eval_workspace": (C.c_int64, []),
     "mrgcn_xent_eval_single_block_rows": (C.c_int64, []),
     "mrgcn_xent_eval_rows_f32": (C.c_int, [_p, _i64, _i32, _p, _p, _i64, _p, _p, _p, _p, _p]),

@@ -1432,6 +1432,8 @@ def masked_layer_supported(sup, layer, K: int, need_dX: bool = False) -> bool:
     featureless input layer with 1 to 4 bases.)"""
     if getattr(layer, "operand_dtype", "f32") != "f32":
         return False
+    if getattr(layer, "num_blocks", -1) > 0:
+        return False   # (the masked pass has no block-diagonal feature term)
     if layer.outdim > 16:
         if not (layer.input_layer and layer.featureless):
             return K >= 1 and _masked_wide_feat(sup, layer)
@@ -1499,6 +1501,90 @@ class _BasisContract(torch.autograd.Function):
         return dcomp, dV
 
 
+class _BlockLayer(torch.autograd.Function):
+    """Y = relu?( A' . M + b ),  M[c, b fo + q] = sum_k X[j_c, b ki + k] . W_F[r_c, b, k, q]: the feature term with
+    block-diagonal relation weights (Schlichtkrull et al. 2018, eq. 4; csrc/block_xform.hip), W_F the layer's
+    (R, NB, ki, fo) parameter.  The backward takes any dense output gradient (a note of the layer above about an applied
+    ReLU mask is honoured) and returns plain dense gradients without a note of its own."""
+
+    @staticmethod
+    def forward(ctx, plan: GraphPlan, F: int, X, W_F, bias, relu: bool, owner=None, row_scale=None):
+        lib = L.load()
+        dev = plan.device
+        if X.dtype != torch.float32 or X.dim() != 2:
+            raise L.MrgcnError("a block-diagonal layer reads a 2-D fp32 input")
+        Xc = X if X.stride(1) == 1 else X.contiguous()   # row-strided X is taken as it is
+        Wc = W_F.contiguous()
+        NB, K = int(Wc.shape[1]), int(Xc.shape[1])
+        ld = _ld_for(F)
+        M = torch.empty((plan.nop, ld), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            L.check(lib.mrgcn_block_transform_fwd_f32(plan.handle, Xc.data_ptr(), Xc.stride(0), K, Wc.data_ptr(), NB, F,
+                                                      M.data_ptr(), ld, 1, _stream(dev)),
+                    "mrgcn_block_transform_fwd_f32")
+        plan.replicate(M)
+        Y = plan.spmm(L.VIEW_COMPACT, M, F=F, bias=bias, relu=relu,
+                      padded_rows=bool(getattr(owner, "padded_output", False)))
+        ctx.row_scale = _check_row_scale(row_scale, Y.shape[0], Y.device)
+        if ctx.row_scale is not None:
+            row_scale_(Y, ctx.row_scale)   # (node dropout: behind the ReLU epilogue, m >= 0)
+        ctx.plan, ctx.F, ctx.NB, ctx.relu, ctx.has_bias = plan, F, NB, relu, bias is not None
+        ctx.save_for_backward(Xc, Wc, Y if relu else None)
+        return Y
+
+    @staticmethod
+    def backward(ctx, dY):
+        lib = L.load()
+        plan, F, NB = ctx.plan, ctx.F, ctx.NB
+        X, W_F, Y = ctx.saved_tensors
+        dev = plan.device
+        dY = dY.contiguous()
+        meta = _grad_meta(dY)
+        if meta and meta.get("sparse_rows"):
+            raise L.MrgcnError("internal: an output gradient with unwritten rows reached a block-diagonal layer")
+        if ctx.relu and not (meta and meta["relu_applied"]):
+            dY = relu_bwd(dY, Y)
+        if ctx.row_scale is not None:
+            dY = row_scale_live(dY, ctx.row_scale)
+        dbias = _bias_grad(dY) if ctx.has_bias else None
+        need_dX, need_dW = ctx.needs_input_grad[2], ctx.needs_input_grad[3]
+        dX = dW = None
+        if need_dX or need_dW:
+            K = X.shape[1]
+            # dM = A'^T dY over touched columns, plain compact order
+            ldm = (F + 3) // 4 * 4
+            dM = torch.empty((plan.ncols, ldm), dtype=torch.float32, device=dev)
+            plan.spmm(L.VIEW_TRANSPOSED, dY, F=F, out=dM)
+            if need_dX:
+                dX = torch.empty((X.shape[0], K), dtype=torch.float32, device=dev)
+            if need_dW:
+                dW = torch.empty_like(W_F)
+            nws = int(lib.mrgcn_block_transform_bwd_workspace(plan.handle, K, F, NB, int(need_dX), int(need_dW)))
+            ws = torch.empty((nws,), dtype=torch.float32, device=dev) if nws > 0 else None
+            with torch.cuda.device(dev):
+                L.check(lib.mrgcn_block_transform_bwd_f32(
+                    plan.handle, dM.data_ptr(), ldm, X.data_ptr(), X.stride(0), K, W_F.data_ptr(), NB, F,
+                    dX.data_ptr() if need_dX else 0, K, dW.data_ptr() if need_dW else 0,
+                    ws.data_ptr() if ws is not None else 0, nws, _stream(dev)), "mrgcn_block_transform_bwd_f32")
+        return None, None, dX, dW, dbias, None, None, None
+
+
+def _block_feature_term(plan: GraphPlan, layer, X, bias, relu: bool, row_scale):
+    """The feature term of a layer with `num_blocks > 0`: the block transform's kernels inside their limits, else the
+    literal formula on the dense form of the blocks (counted in `stats()["layer.block.fallback"]`)."""
+    F, W_F = layer.outdim, layer.weight_F
+    NB, K = int(W_F.shape[1]), int(X.shape[1])
+    if K != NB * int(W_F.shape[2]):
+        raise L.MrgcnError(f"a block-diagonal layer of {NB * int(W_F.shape[2])} inputs got rows of {K}")
+    if X.dtype == torch.float32 and L.load().mrgcn_block_transform_supported(plan.handle, K, F, NB):
+        bump("layer.block")
+        return _BlockLayer.apply(plan, F, X, W_F, bias, relu, layer, row_scale)
+    bump("layer.block.fallback")
+    from .layers.graph import _relation_transform, block_weight_dense
+    FW = _relation_transform(X, block_weight_dense(W_F)).reshape(plan.num_relations * X.shape[0], F)
+    return spmm_literal(plan, FW, bias=bias, relu=relu, row_scale=row_scale)
+
+
 def rgcn_layer(plan: GraphPlan, layer, X, relu: bool = False, input_term: bool = True,
                feature_term: bool = True, use_bias: bool = True, row_scale=None) -> torch.Tensor:
     """Fused forward of one `GraphConvolution` (graph.py:62-102).  `input_term` / `feature_term`
@@ -1506,6 +1592,24 @@ def rgcn_layer(plan: GraphPlan, layer, X, relu: bool = False, input_term: bool =
     (fp32, one value >= 0 per output row), applied to the output rows inside the layer's autograd function."""
     F = layer.outdim
     B = layer.num_bases
+    if getattr(layer, "num_blocks", -1) > 0 and feature_term and not (layer.input_layer and layer.featureless):
+        # block-diagonal feature term (csrc/block_xform.hip); an input layer's node-table term runs through the
+        # route below and the two products are added, as the slice walk adds its own
+        if getattr(layer, "operand_dtype", "f32") != "f32":
+            raise L.MrgcnError("num_blocks: the block-diagonal feature term has no bf16 operand (operand_dtype 'f32')")
+        if X is None:
+            raise L.MrgcnError("rgcn_layer: the feature term needs X")
+        bias = layer.b if (layer.bias and use_bias) else None
+        if not (layer.input_layer and input_term):
+            Y = _block_feature_term(plan, layer, X, bias, relu, row_scale)
+            if relu:
+                Y._mrgcn_relu_out = True
+            return Y
+        Y = rgcn_layer(plan, layer, None, feature_term=False, use_bias=False)
+        Y = Y + _block_feature_term(plan, layer, X, bias, False, None)
+        if relu:
+            Y = torch.relu(Y)
+        return Y if row_scale is None else _RowScale.apply(Y, row_scale)
     weight_I = comp_I = W_F = None
     if layer.input_layer and input_term:
         weight_I = layer.weight_I

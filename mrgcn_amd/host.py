@@ -279,3 +279,82 @@ def all_lse32(Q, E, target):
     lse = mx[:, 0] + np.log(np.exp(x - mx).sum(axis=1, dtype=np.float32))
     assert lse.dtype == np.float32
     return lse, x[np.arange(Q.shape[0]), tg]
+
+
+# ---- block-diagonal relation transform (csrc/block_xform.hip; Schlichtkrull et al. 2018, eq. 4) ----------------------
+# W: (R, NB, ki, fo), W_r = blockdiag(W[r, 0], ..., W[r, NB-1]); a compact column c is the pair (node[c], rel[c]).
+def block_weight_dense64(W):
+    """The dense `(R, NB ki, NB fo)` form of the blocks in numpy float64."""
+    import numpy as np
+    W = np.asarray(W, dtype=np.float64)
+    R, NB, ki, fo = W.shape
+    D = np.zeros((R, NB * ki, NB * fo), dtype=np.float64)
+    for b in range(NB):
+        D[:, b * ki:(b + 1) * ki, b * fo:(b + 1) * fo] = W[:, b]
+    return D
+
+
+def _block_transform_np(X, W, node, rel, dtype):
+    import numpy as np
+    X, W = np.ascontiguousarray(X, dtype=dtype), np.ascontiguousarray(W, dtype=dtype)
+    node, rel = np.asarray(node, dtype=np.int64), np.asarray(rel, dtype=np.int64)
+    R, NB, ki, fo = W.shape
+    if X.shape[1] != NB * ki:
+        raise ValueError("block_transform: X has NB * ki columns")
+    Xc = X[node].reshape(node.shape[0], NB, ki)       # [ncols, NB, ki]
+    Wc = W[rel]                                        # [ncols, NB, ki, fo]
+    acc = np.zeros((node.shape[0], NB, fo), dtype=dtype)
+    for k in range(ki):   # k rising; the product is rounded before it is added
+        acc = acc + Xc[:, :, k, None] * Wc[:, :, k, :]
+    assert acc.dtype == dtype
+    return acc.reshape(node.shape[0], NB * fo)
+
+
+def block_transform32(X, W, node, rel):
+    """`mrgcn_block_transform_fwd_f32` restated in numpy with exactly its float32 operations -> float32 [ncols, F] in
+    plain compact order: Out[c, b fo + q] = sum_k X[node[c], b ki + k] * W[rel[c], b, k, q], k rising from +0, every
+    product and every sum rounded to float32 on its own.  The statement the kernel equals bit for bit."""
+    import numpy as np
+    return _block_transform_np(X, W, node, rel, np.float32)
+
+
+def block_transform64(X, W, node, rel):
+    """The same sums in numpy float64."""
+    import numpy as np
+    return _block_transform_np(X, W, node, rel, np.float64)
+
+
+def _block_transform_bwd_np(dM, X, W, node, rel, num_nodes, dtype):
+    import numpy as np
+    X, W = np.ascontiguousarray(X, dtype=dtype), np.ascontiguousarray(W, dtype=dtype)
+    node, rel = np.asarray(node, dtype=np.int64), np.asarray(rel, dtype=np.int64)
+    R, NB, ki, fo = W.shape
+    n = node.shape[0]
+    G = np.ascontiguousarray(np.asarray(dM, dtype=dtype)[:, :NB * fo]).reshape(n, NB, fo)
+    Z = np.zeros((n, NB, ki), dtype=dtype)             # Z[c, b, k] = sum_q W[rel[c], b, k, q] G[c, b, q]
+    Wc = W[rel]
+    for q in range(fo):
+        Z = Z + Wc[:, :, :, q] * G[:, :, None, q]
+    dX = np.zeros((int(num_nodes), NB * ki), dtype=dtype)
+    dW = np.zeros((R, NB, ki, fo), dtype=dtype)
+    Xc = X[node].reshape(n, NB, ki)
+    for c in range(n):    # columns in rising compact id
+        dX[node[c]] = dX[node[c]] + Z[c].reshape(-1)
+        dW[rel[c]] = dW[rel[c]] + Xc[c][:, :, None] * G[c][:, None, :]
+    assert dX.dtype == dtype and dW.dtype == dtype
+    return dX, dW
+
+
+def block_transform_bwd64(dM, X, W, node, rel, num_nodes):
+    """The block transform's gradients in numpy float64 -> (dX [num_nodes, K], dW (R, NB, ki, fo)):
+    dX[j, b ki + k] = sum_{c: node[c] = j} sum_q W[rel[c], b, k, q] dM[c, b fo + q],
+    dW[r, b, k, q] = sum_{c: rel[c] = r} X[node[c], b ki + k] dM[c, b fo + q]."""
+    import numpy as np
+    return _block_transform_bwd_np(dM, X, W, node, rel, num_nodes, np.float64)
+
+
+def block_transform_bwd32(dM, X, W, node, rel, num_nodes):
+    """The same sums with every operation in float32 (columns in rising compact id, q rising inside one): what the
+    kernels differ from in summation order only — the yardstick of their tolerance."""
+    import numpy as np
+    return _block_transform_bwd_np(dM, X, W, node, rel, num_nodes, np.float32)

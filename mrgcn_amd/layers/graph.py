@@ -22,6 +22,10 @@ hands out and `load_state_dict()` takes the reference's shape (checkpoints are i
 the reference's shape and order (same seed, same initial values).  In this layout the forward, the
 backward and Adam touch a node's weights as one 4*B*out-byte run, and a node without gradient is
 skipped as a whole.  Without bases `weight_I` is `(R*N, out)` exactly as in the reference.
+
+`num_blocks = NB > 0` (not in the reference): the block-diagonal decomposition of Schlichtkrull et al. 2018, eq. 4, for
+the FEATURE term — `weight_F` is `(R, NB, indim/NB, outdim/NB)`, `W_r = blockdiag(weight_F[r, 0], ...)`.  The fused
+engine runs it on csrc/block_xform.hip (functional._BlockLayer), the literal engine on `block_weight_dense`.
 """
 from __future__ import annotations
 
@@ -59,13 +63,35 @@ def _relation_transform(X, W_F):
     return torch.cat([torch.matmul(X.unsqueeze(0), W_F[r0:r0 + step]) for r0 in range(0, R, step)], dim=0)
 
 
+def block_weight_dense(weight_F):
+    """The dense equivalent `(R, indim, outdim)` of a block-diagonal `weight_F` of shape `(R, NB, ki, fo)`:
+    `W_r = blockdiag(weight_F[r, 0], ..., weight_F[r, NB-1])` (Schlichtkrull et al. 2018, eq. 4), built with plain,
+    differentiable torch ops.  Correct and slow on purpose: the literal engine, the fused engine's fallback and the
+    tests' torch reference use it; the fused engine itself never forms it."""
+    R, NB, ki, fo = weight_F.shape
+    eye = torch.eye(NB, dtype=weight_F.dtype, device=weight_F.device)
+    # W[r, b*ki + k, c*fo + q] = weight_F[r, b, k, q] * [b == c]
+    return (weight_F.unsqueeze(3) * eye.view(1, NB, 1, NB, 1)).reshape(R, NB * ki, NB * fo)
+
+
 class GraphConvolution(nn.Module):
     def __init__(self, indim, outdim, num_relations, num_nodes, num_bases=-1, bias=False,
-                 input_layer=False, featureless=False, shared_bases_weights=False):
+                 input_layer=False, featureless=False, shared_bases_weights=False, num_blocks=-1):
         super().__init__()
         self.indim, self.outdim = indim, outdim
         self.num_relations, self.num_nodes = num_relations, num_nodes
         self.num_bases = num_bases
+        # block-diagonal decomposition of the feature term (Schlichtkrull et al. 2018, eq. 4): weight_F is
+        # (R, NB, indim/NB, outdim/NB) and takes no bases; `num_bases` keeps its meaning for the node table
+        self.num_blocks = int(num_blocks) if num_blocks is not None and num_blocks > 0 else -1
+        if self.num_blocks > 0:
+            from .._lib import MrgcnError
+            if featureless:
+                raise MrgcnError("num_blocks: a featureless layer has no feature term to decompose")
+            if shared_bases_weights:
+                raise MrgcnError("num_blocks: the block-diagonal feature term takes no bases (shared_bases_weights)")
+            if indim % self.num_blocks or outdim % self.num_blocks:
+                raise MrgcnError(f"num_blocks={self.num_blocks} has to divide indim={indim} and outdim={outdim}")
         self.input_layer, self.featureless, self.bias = input_layer, featureless, bias
         self.engine = DEFAULT_ENGINE
         # storage type of the fused engine's compact operand: "f32" (parity default) or "bf16"
@@ -75,14 +101,16 @@ class GraphConvolution(nn.Module):
         use_bases = num_bases > 0
         S = num_bases if use_bases else num_relations  # graph.py:33-36
         wants_F = not featureless
+        NB = self.num_blocks
 
         # registration order fixes the RNG stream of reset_parameters (graph.py:38-57):
         # weight_I_comp, weight_F_comp, weight_I, weight_F, b
+        shape_F = (num_relations, NB, indim // NB, outdim // NB) if NB > 0 else (S, indim, outdim)
         shapes = [
             ("weight_I_comp", (num_relations, num_bases) if use_bases and input_layer else None),
-            ("weight_F_comp", (num_relations, num_bases) if use_bases and wants_F else None),
+            ("weight_F_comp", (num_relations, num_bases) if use_bases and wants_F and NB <= 0 else None),
             ("weight_I", (S * num_nodes, outdim) if input_layer else None),
-            ("weight_F", (S, indim, outdim) if wants_F else None),
+            ("weight_F", shape_F if wants_F else None),
             ("b", (outdim,) if bias else None),
         ]
         self.weight_I_node_major = bool(use_bases and input_layer)
@@ -132,6 +160,11 @@ class GraphConvolution(nn.Module):
                 nn.init.xavier_uniform_(ref)
                 with torch.no_grad():
                     param.copy_(ref.view(B, N, out).permute(1, 0, 2))
+            elif name == "weight_F" and getattr(self, "num_blocks", -1) > 0:
+                # Glorot on one block: an output sees ki inputs, an input feeds fo outputs
+                ki, fo = param.shape[2], param.shape[3]
+                bound = (6.0 / (ki + fo)) ** 0.5
+                nn.init.uniform_(param, -bound, bound)
             else:
                 nn.init.xavier_uniform_(param)
 
@@ -142,6 +175,16 @@ class GraphConvolution(nn.Module):
             N, B, out = W.shape
             W = W.permute(1, 0, 2).reshape(B * N, out)
         return W
+
+    def weight_F_dense(self):
+        """The feature term's weights as the literal formula multiplies them, `(R, indim, outdim)`: the basis
+        contraction of graph.py:83-85, or the dense form of the blocks; differentiable."""
+        W_F = self.weight_F
+        if getattr(self, "num_blocks", -1) > 0:
+            return block_weight_dense(W_F)
+        if self.num_bases > 0:
+            W_F = (self.weight_F_comp @ W_F.view(self.num_bases, -1)).view(self.num_relations, self.indim, self.outdim)
+        return W_F
 
     # ------------------------------------------------------------------------------
     def forward(self, X, A, A_idx=None):
@@ -164,9 +207,7 @@ class GraphConvolution(nn.Module):
             Y = Fn.spmm_literal(plan, W_I, bias=self.b if (last and self.bias) else None)
             if last:
                 return Y
-        W_F = self.weight_F
-        if B > 0:
-            W_F = (self.weight_F_comp @ W_F.view(B, -1)).view(R, self.indim, out)
+        W_F = self.weight_F_dense()
         FW = _relation_transform(X, W_F).reshape(R * X.shape[0], out)
         AFW = Fn.spmm_literal(plan, FW, bias=self.b if self.bias else None)
         return AFW if Y is None else Y + AFW
@@ -200,9 +241,7 @@ class GraphConvolution(nn.Module):
             if self.featureless:  # graph.py:77-81: the input term (+ bias) is the whole layer
                 return Y
         if self.engine == "literal":
-            W_F = self.weight_F
-            if B > 0:
-                W_F = (self.weight_F_comp @ W_F.view(B, -1)).view(R, self.indim, out)
+            W_F = self.weight_F_dense()
             FW = _relation_transform(X, W_F).reshape(R * n_b, out)
             YF = Fn.spmm_literal(plan_F, FW, bias=self.b if self.bias else None)
         else:

@@ -74,7 +74,7 @@ def _pick_device(want_gpu: bool):
 class MRGCN(nn.Module):
     def __init__(self, modules, embedding_modules, num_relations, num_nodes, num_bases=-1,
                  p_dropout=0.0, featureless=False, bias=False, link_prediction=False,
-                 gcn_gpu_acceleration=False, gated=True):
+                 gcn_gpu_acceleration=False, gated=True, num_blocks=-1):
         super().__init__()
         assert len(modules) > 0
 
@@ -141,7 +141,7 @@ class MRGCN(nn.Module):
             self.gate_weights.requires_grad = False
 
         self.rgcn = RGCN(modules, num_relations, num_nodes, num_bases, p_dropout, featureless, bias,
-                         link_prediction)
+                         link_prediction, num_blocks=num_blocks)
         # The R-GCN of this package only computes on the GPU.  With the flag off the module is
         # still built (state dicts, CPU-side tooling) but moved to the GPU lazily at first use.
         device = _pick_device(gcn_gpu_acceleration or torch.cuda.is_available())

@@ -14,7 +14,7 @@ from ..plan import build_plans_parallel, plan_of
 
 class RGCN(nn.Module):
     def __init__(self, modules, num_relations, num_nodes, num_bases, p_dropout, featureless, bias,
-                 link_prediction):
+                 link_prediction, num_blocks=-1):
         super().__init__()
         assert len(modules) > 0
 
@@ -24,10 +24,13 @@ class RGCN(nn.Module):
         self.activations = nn.ModuleDict()
         for i, (indim, outdim, _ltype, f_activation) in enumerate(modules):
             first = i == 0  # rgcn.py:30-37: only layer 0 is an input layer / may be featureless
+            # block-diagonal weights (num_blocks > 0) go to every layer that has a feature term; a featureless
+            # layer 0 keeps its bases
+            has_F = not (first and featureless)
             self.layers[f"layer_{i}"] = GraphConvolution(
                 indim=indim, outdim=outdim, num_relations=num_relations, num_nodes=num_nodes,
                 num_bases=num_bases, featureless=featureless if first else False,
-                input_layer=first, bias=bias)
+                input_layer=first, bias=bias, num_blocks=num_blocks if has_F else -1)
             self.activations[f"layer_{i}"] = f_activation
         self.num_layers = len(self.layers)
         # hidden layers keep their output in rows padded to whole 16-byte pieces (plan.spmm: the product stores whole

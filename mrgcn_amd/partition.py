@@ -248,8 +248,12 @@ class PartitionedRGCN(nn.Module):
     rank constructs it with the same seed; `load_full_state` shards a reference-shaped state."""
 
     def __init__(self, modules, num_relations, num_nodes, num_bases, featureless, bias, part: NodePartition,
-                 group=None, link_prediction=False):
+                 group=None, link_prediction=False, num_blocks=-1):
         super().__init__()
+        if num_blocks is not None and num_blocks > 0:
+            from ._lib import MrgcnError
+            raise MrgcnError("num_blocks: the partitioned engines have no block-diagonal feature term (models.rgcn.RGCN "
+                               "runs it on one device)")
         if link_prediction:  # DistMult relation embeddings (rgcn.py:55-61): small, replicated
             self.relations = nn.Parameter(torch.empty((num_relations, modules[-1][1])))
             nn.init.xavier_uniform_(self.relations)

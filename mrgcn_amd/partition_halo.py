@@ -637,8 +637,11 @@ class HaloPartitionedRGCN(nn.Module):
     parameters as `partition.PartitionedRGCN`."""
 
     def __init__(self, modules, num_relations, num_nodes, num_bases, featureless, bias, part: NodePartition, group=None,
-                 link_prediction=False):
+                 link_prediction=False, num_blocks=-1):
         super().__init__()
+        if num_blocks is not None and num_blocks > 0:
+            raise L.MrgcnError("num_blocks: the partitioned engines have no block-diagonal feature term (models.rgcn.RGCN "
+                               "runs it on one device)")
         if link_prediction:
             self.relations = nn.Parameter(torch.empty((num_relations, modules[-1][1])))
             nn.init.xavier_uniform_(self.relations)

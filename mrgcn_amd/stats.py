@@ -30,6 +30,8 @@ def stats() -> dict:
     device; a call inside a stream capture counts once, its replays do not), `lp.decoder.grouped` (calls of
     `tasks.link_prediction.group_loss`, counted the same way) / `lp.decoder.grouped.fallback` (those of them that scored
     the flat triples and took torch's loss: rows the group kernels do not take, or the deterministic flag).
+    `layer.block` (feature terms with block-diagonal weights served by csrc/block_xform.hip) / `layer.block.fallback`
+    (those outside its limits: the literal formula on `layers.graph.block_weight_dense`).
     Under `torch.use_deterministic_algorithms(True)`: `deterministic.distmult_bwd` (DistMult backwards on the owner
     form), `deterministic.bce` (BCE losses summed in block order), `deterministic.sumsq` (clips whose squared norms were
     summed in block order: ClipAdam steps and `optim.clip_grad_norm_` calls), `deterministic.wide_input` (wide

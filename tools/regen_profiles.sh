@@ -120,6 +120,9 @@ python3 tools/lp_complex_probe.py --out $o/lp_complex_probe.json > $o/lp_complex
 # that fits, the replayed training epoch of fit with decoder="all" against decoder="grouped" at 10 negatives, the median
 # mini-batch's step; every leg in a child process under its own time limit
 python3 tools/lp_all_probe.py --out $o/lp_all_probe.json > $o/lp_all_probe.txt 2> $o/lp_all_probe.err
+# (10o) a block-diagonal hidden layer (200 -> 200, 40 blocks) at the FB15k-237 shape: its five passes alone, the layer on
+# the fused engine against the literal engine on the dense expansion (with peak memory), the replayed two-layer fit epoch
+python3 tools/block_layer_probe.py --out $o/block_layer_probe.json > $o/block_layer_probe.txt 2> $o/block_layer_probe.err
 hipcc -O3 --offload-arch=gfx950 -std=c++17 tools/lab/copy_lab.hip -o /tmp/copy_lab 2>/dev/null && /tmp/copy_lab > $o/copy_lab.txt 2>&1
 python3 tools/lab/spmm_hot_lab.py > $o/spmm_hot_lab.txt 2>&1
 # the CPU suite last: the tree these artefacts describe is green
