@@ -940,6 +940,66 @@ int mrgcn_complex_topk(const float *E, int64_t ldE, int64_t num_nodes, const flo
                        const int32_t *excl_idx, int32_t k, void *workspace, int64_t workspace_bytes,
                        int64_t *out_idx, float *out_score, void *stream);
 
+/* ---- type-constrained ranks and top-k (csrc/lp_typed.hip, csrc/distmult_topk.hip; Krompass et al., ISWC 2015) ------
+ * Candidates per relation and side instead of every node: cand_ptr (int64 [2 R + 1]) / cand_idx (int32, each list
+ * ascending, duplicate free, ids in [0, num_nodes)) as in mrgcn_negatives_draw_typed_i64 — slot 2 p the tails of
+ * relation p, slot 2 p + 1 its heads.  The host groups the facts (queries) by relation: order (int64 [n]) lists their
+ * indices relation by relation, tile_ptr (int64 [num_tiles + 1], rising from 0 to n) cuts that sequence into tiles of
+ * at most 8 facts OF ONE RELATION, tile_rel (int32 [num_tiles]) names each tile's relation.  A block takes one work item
+ * of `work` (int32 [num_work, 2]) and scores one tile against 256 positions of its slot; candidate scores are
+ * mrgcn_distmult_ranks_both's / mrgcn_complex_ranks_both's bit for bit (one shared body, called with the gathered id).
+ * All arrays are device memory; what the host built is trusted (tiles and items outside their ranges are skipped).
+ *
+ * _typed_ranks: work item {2 tile + side, candidate tile} for every tile, side (0 tail, 1 head) and candidate tile
+ *   below ceil(slot length / 256).  ranks_raw / ranks_flt [2 nf]: tail ranks, then head ranks, in the order of
+ *   `triples` (NOT the grouped order); rank = #greater + round_half_even((#ties - 1) / 2) + 1 counted over the slot's
+ *   candidates — the fact's own answer must be one of them —, for ranks_flt without the candidates of the fact's filter
+ *   list (tail_* / head_* as in mrgcn_distmult_ranks_both, indexed by the fact's position in `triples`; all four NULL:
+ *   raw ranks only).  EVERY fact is scored: the reference's rule that facts at positions >= num_nodes of a call stay
+ *   unscored (link_prediction.py:611-617) is compute_ranks_fast's and is not carried over; there is no part_ptr.
+ *   workspace: mrgcn_*_typed_ranks_workspace() bytes (Et [H, N], truth [nf] — [2 nf] for ComplEx —, counts [8 nf]).
+ * _typed_topk: mrgcn_distmult_topk's contract (queries [nq, 2], head, exclusions, k, result order, (-1, -inf) tails)
+ *   over the nodes of the query relation's slot on the asked side; work item {tile, candidate tile}; q_tiles (int32
+ *   [nq]) = ceil(slot length / 256) of each query (0: an empty slot, a row of (-1, -inf)); max_slot = the longest slot
+ *   among the queries'.  Rows come back in the order of `queries`; excl_ptr is indexed by it too.  workspace = H N
+ *   floats (the transposed table the gather reads) + nq * k * max(1, ceil(max_slot / 256)) 64-bit keys: the tile lists
+ *   are sized by the longest slot, not by num_nodes.  No host synchronisation; capturable; pure functions of their
+ *   inputs (the counts are integer atomics: any order, one sum). */
+int64_t mrgcn_distmult_typed_ranks_workspace(int64_t num_nodes, int32_t H, int64_t num_facts);
+int mrgcn_distmult_typed_ranks(const float *E, int64_t ldE, int64_t num_nodes, const float *Rel, int64_t ldR, int32_t H,
+                               const int64_t *triples, int64_t num_facts, const int64_t *order,
+                               const int64_t *tile_ptr, const int32_t *tile_rel, int64_t num_tiles, const int32_t *work,
+                               int64_t num_work, const int64_t *cand_ptr, const int32_t *cand_idx,
+                               const int64_t *tail_ptr, const int32_t *tail_idx, const int64_t *head_ptr,
+                               const int32_t *head_idx, void *workspace, int64_t workspace_bytes, int64_t *ranks_raw,
+                               int64_t *ranks_flt, void *stream);
+int64_t mrgcn_complex_typed_ranks_workspace(int64_t num_nodes, int32_t H, int64_t num_facts);
+int mrgcn_complex_typed_ranks(const float *E, int64_t ldE, int64_t num_nodes, const float *Rel, int64_t ldR, int32_t H,
+                              const int64_t *triples, int64_t num_facts, const int64_t *order,
+                              const int64_t *tile_ptr, const int32_t *tile_rel, int64_t num_tiles, const int32_t *work,
+                              int64_t num_work, const int64_t *cand_ptr, const int32_t *cand_idx,
+                              const int64_t *tail_ptr, const int32_t *tail_idx, const int64_t *head_ptr,
+                              const int32_t *head_idx, void *workspace, int64_t workspace_bytes, int64_t *ranks_raw,
+                              int64_t *ranks_flt, void *stream);
+int64_t mrgcn_distmult_typed_topk_workspace(int64_t num_nodes, int32_t H, int64_t num_queries, int32_t k,
+                                            int64_t max_slot);
+int mrgcn_distmult_typed_topk(const float *E, int64_t ldE, int64_t num_nodes, const float *Rel, int64_t ldR, int32_t H,
+                              const int64_t *queries, int64_t num_queries, int32_t head, const int64_t *order,
+                              const int64_t *tile_ptr, const int32_t *tile_rel, int64_t num_tiles, const int32_t *work,
+                              int64_t num_work, const int32_t *q_tiles, const int64_t *cand_ptr,
+                              const int32_t *cand_idx, int64_t max_slot, const int64_t *excl_ptr,
+                              const int32_t *excl_idx, int32_t k, void *workspace, int64_t workspace_bytes,
+                              int64_t *out_idx, float *out_score, void *stream);
+int64_t mrgcn_complex_typed_topk_workspace(int64_t num_nodes, int32_t H, int64_t num_queries, int32_t k,
+                                           int64_t max_slot);
+int mrgcn_complex_typed_topk(const float *E, int64_t ldE, int64_t num_nodes, const float *Rel, int64_t ldR, int32_t H,
+                             const int64_t *queries, int64_t num_queries, int32_t head, const int64_t *order,
+                             const int64_t *tile_ptr, const int32_t *tile_rel, int64_t num_tiles, const int32_t *work,
+                             int64_t num_work, const int32_t *q_tiles, const int64_t *cand_ptr,
+                             const int32_t *cand_idx, int64_t max_slot, const int64_t *excl_ptr,
+                             const int32_t *excl_idx, int32_t k, void *workspace, int64_t workspace_bytes,
+                             int64_t *out_idx, float *out_score, void *stream);
+
 /* Graph-capturable Adam (torch.optim.Adam(capturable=True) semantics): the step counter and the
  * bias corrections live in device memory, so a captured epoch replays with the right step.
  * mrgcn_adam_bias_f32: ++*step_dev; bc_dev[0] = 1 - beta1^step, bc_dev[1] = sqrt(1 - beta2^step).
@@ -1167,6 +1227,21 @@ int mrgcn_negatives_draw_i64(const int64_t *facts, int64_t n, int32_t rate, cons
                              const int64_t *to_global, const int64_t *known_keys, int64_t n_known, int64_t num_nodes,
                              int64_t num_relations, int32_t side, int64_t *state, int64_t *out, uint8_t *unresolved,
                              void *stream);
+/* The type-constrained draw (Krompass, Baier, Tresp, "Type-Constrained Representation Learning in Knowledge Graphs",
+ * ISWC 2015): mrgcn_negatives_draw_i64's contract word for word — the same counter, key and tag, the same side bit from
+ * attempt 0's word z, the same refusals, flags and state —, with the candidates of the fact's relation p and the drawn
+ * side in place of (cand, n_cand): cand_ptr (int64 [2 num_relations + 1], rising) and cand_idx (int32, every list
+ * ascending and duplicate free) are a CSR over 2 num_relations slots, slot 2 p the relation's tail candidates (its
+ * range), slot 2 p + 1 its head candidates (its domain).  The pick is cand_idx[cand_ptr[slot] + ((h * len) >> 64)], len
+ * the slot's length: with every slot 0 .. num_nodes - 1 the output equals mrgcn_negatives_draw_i64's (cand NULL, n_cand
+ * = num_nodes) bit for bit.  A slot whose only node is the end it replaces is refused at all attempts: the draw stands
+ * and the negative is flagged.  An empty slot (or a relation outside [0, num_relations)) reads nothing: the fact's own
+ * end stands, flagged; the caller keeps such facts out (tasks.link_prediction.NegativeSampler raises).  The lists hold
+ * GLOBAL ids: there is no to_global.  (mrgcn_amd/host.py: negatives_draw(typed=...) is the bit-exact host mirror.) */
+int mrgcn_negatives_draw_typed_i64(const int64_t *facts, int64_t n, int32_t rate, const int64_t *cand_ptr,
+                                   const int32_t *cand_idx, const int64_t *known_keys, int64_t n_known,
+                                   int64_t num_nodes, int64_t num_relations, int32_t side, int64_t *state, int64_t *out,
+                                   uint8_t *unresolved, void *stream);
 
 /* ---- grouped DistMult loss over a fact's keyed negatives (csrc/distmult_group.hip) --------------------------------
  * The decoder of mrgcn/tasks/link_prediction.py:645-665 (scores) and :550-554 (loss) for triples in the layout of

@@ -291,6 +291,19 @@ SIGNATURES = {
     "mrgcn_row_scale_f32": (C.c_int, [_p, _i64, _i64, _i32, _p, _p]),
     "mrgcn_row_scale_live_f32": (C.c_int, [_p, _i64, _i64, _i32, _p, _p, _i32, _p, _i64, _p]),
     "mrgcn_negatives_draw_i64": (C.c_int, [_p, _i64, _i32, _p, _i64, _p, _p, _i64, _i64, _i64, _i32, _p, _p, _p, _p]),
+    "mrgcn_negatives_draw_typed_i64": (C.c_int, [_p, _i64, _i32, _p, _p, _p, _i64, _i64, _i64, _i32, _p, _p, _p, _p]),
+    "mrgcn_distmult_typed_ranks_workspace": (C.c_int64, [_i64, _i32, _i64]),
+    "mrgcn_distmult_typed_ranks": (C.c_int, [_p, _i64, _i64, _p, _i64, _i32, _p, _i64, _p, _p, _p, _i64, _p, _i64, _p, _p,
+                                             _p, _p, _p, _p, _p, _i64, _p, _p, _p]),
+    "mrgcn_complex_typed_ranks_workspace": (C.c_int64, [_i64, _i32, _i64]),
+    "mrgcn_complex_typed_ranks": (C.c_int, [_p, _i64, _i64, _p, _i64, _i32, _p, _i64, _p, _p, _p, _i64, _p, _i64, _p, _p,
+                                            _p, _p, _p, _p, _p, _i64, _p, _p, _p]),
+    "mrgcn_distmult_typed_topk_workspace": (C.c_int64, [_i64, _i32, _i64, _i32, _i64]),
+    "mrgcn_distmult_typed_topk": (C.c_int, [_p, _i64, _i64, _p, _i64, _i32, _p, _i64, _i32, _p, _p, _p, _i64, _p, _i64,
+                                            _p, _p, _p, _i64, _p, _p, _i32, _p, _i64, _p, _p, _p]),
+    "mrgcn_complex_typed_topk_workspace": (C.c_int64, [_i64, _i32, _i64, _i32, _i64]),
+    "mrgcn_complex_typed_topk": (C.c_int, [_p, _i64, _i64, _p, _i64, _i32, _p, _i64, _i32, _p, _p, _p, _i64, _p, _i64,
+                                           _p, _p, _p, _i64, _p, _p, _i32, _p, _i64, _p, _p, _p]),
     "mrgcn_distmult_group_supported": (_i32, [_p, _i64, _p, _i64, _i32, _i64, _i64, _i64, _i32]),
     "mrgcn_distmult_group_fwd_workspace": (C.c_int64, []),
     "mrgcn_distmult_group_fwd_f32": (C.c_int, [_p, _i64, _p, _i64, _i32, _p, _i64, _i32, _i32, C.c_float, _p, _p, _p, _p,

@@ -98,6 +98,48 @@ def fact_keys(known, num_nodes: int, num_relations: int):
     return np.sort((k[:, 0] * np.uint64(R) + k[:, 1]) * np.uint64(N) + k[:, 2])
 
 
+def typed_candidates(known, num_nodes: int, num_relations: int):
+    """The observed type constraints of `known` ([m, 3] facts) as a CSR over 2 * num_relations slots (Krompass, Baier,
+    Tresp, ISWC 2015): slot 2 p holds range(p) = {o : (., p, o) in known}, slot 2 p + 1 holds domain(p) =
+    {s : (s, p, .) in known}, every list ascending and duplicate free.  Returns (ptr int64 [2 R + 1], idx int32)."""
+    import numpy as np
+    N, R = int(num_nodes), int(num_relations)
+    k = np.asarray(known, dtype=np.int64).reshape(-1, 3)
+    if N < 1 or R < 1 or N >= 1 << 31:
+        raise ValueError("typed_candidates: 1 <= num_nodes < 2^31 and num_relations >= 1")
+    if len(k) and (k.min() < 0 or k[:, [0, 2]].max() >= N or k[:, 1].max() >= R):
+        raise ValueError("typed_candidates: node ids must lie in [0, num_nodes), relations in [0, num_relations)")
+    # (slot, node) pairs as one key each; the distinct keys, sorted, ARE the lists slot by slot
+    keys = np.unique(np.concatenate([(2 * k[:, 1]) * N + k[:, 2], (2 * k[:, 1] + 1) * N + k[:, 0]]))
+    ptr = np.zeros(2 * R + 1, np.int64)
+    np.cumsum(np.bincount(keys // N, minlength=2 * R), out=ptr[1:])
+    return ptr, (keys % N).astype(np.int32)
+
+
+def check_typed_candidates(ptr, idx, num_nodes: int, num_relations: int):
+    """Validates declared lists: `ptr` int64-like [2 R + 1] rising from 0 to len(idx), ids in [0, num_nodes), every
+    list ascending and duplicate free.  Returns (ptr int64, idx int32) as contiguous arrays; raises ValueError."""
+    import numpy as np
+    N, R = int(num_nodes), int(num_relations)
+    ptr = np.ascontiguousarray(np.asarray(ptr, dtype=np.int64).reshape(-1))
+    idx64 = np.asarray(idx, dtype=np.int64).reshape(-1)
+    if N < 1 or R < 1 or N >= 1 << 31:
+        raise ValueError("TypedCandidates: 1 <= num_nodes < 2^31 and num_relations >= 1")
+    if ptr.shape[0] != 2 * R + 1 or ptr[0] != 0 or ptr[-1] != len(idx64):
+        raise ValueError("TypedCandidates: ptr must be [2 * num_relations + 1], from 0 to len(idx)")
+    if np.any(np.diff(ptr) < 0):
+        raise ValueError("TypedCandidates: ptr is not monotone")
+    if len(idx64) and (idx64.min() < 0 or idx64.max() >= N):
+        raise ValueError(f"TypedCandidates: node ids must lie in [0, {N})")
+    if len(idx64) > 1:
+        inner = np.ones(len(idx64) - 1, bool)          # pairs (i, i + 1) inside one list
+        starts = ptr[1:-1]
+        inner[starts[(starts > 0) & (starts < len(idx64))] - 1] = False
+        if np.any(inner & (np.diff(idx64) <= 0)):
+            raise ValueError("TypedCandidates: every list must be ascending and duplicate free")
+    return ptr, np.ascontiguousarray(idx64.astype(np.int32))
+
+
 def _mul_hi64(h, n: int):
     """(h * n) >> 64 for uint64 `h` and 1 <= n < 2^63."""
     import numpy as np
@@ -108,17 +150,28 @@ def _mul_hi64(h, n: int):
 
 
 def negatives_draw(facts, rate, n_cand, num_nodes, num_relations, known_keys, seed, position, side=0, cand=None,
-                   to_global=None):
+                   to_global=None, typed=None):
     """`mrgcn_negatives_draw_i64` in numpy: (out int64 [n * rate, 3], unresolved uint8 [n * rate]) for the state
     (seed, position).  Negative k = i * rate + j of fact i: attempt a < NEG_MAX_ATTEMPTS takes the Philox block of
     counter (k lo, (k >> 32) | (a << 24), position lo, position hi) under key (seed lo, seed hi ^ NEG_KEY_TAG), picks
     candidate ((x << 32 | y) * n_cand) >> 64 (through `cand` when given) and is refused when the pick is the end it
     replaces or the corrupted triple's key — on global ids, through `to_global` when given — is in `known_keys` (sorted;
-    None or False: no such check).  `side`: 0 = bit 0 of word z of attempt 0 (set: the head), 1 = tails, 2 = heads."""
+    None or False: no such check).  `side`: 0 = bit 0 of word z of attempt 0 (set: the head), 1 = tails, 2 = heads.
+    `typed=(ptr, idx)`: `mrgcn_negatives_draw_typed_i64` — the candidates are slot 2 p (tails) / 2 p + 1 (heads) of the
+    CSR (`typed_candidates`), the pick idx[ptr[slot] + ((x << 32 | y) * len) >> 64] with len the slot's length;
+    `n_cand`, `cand` and `to_global` must then be left out (n_cand is not read).  An empty slot leaves the fact's end
+    and flags the negative."""
     import numpy as np
     facts = np.asarray(facts, dtype=np.int64).reshape(-1, 3)
     n, rate, n_cand, N, R = facts.shape[0], int(rate), int(n_cand), int(num_nodes), int(num_relations)
     side = NEG_SIDES.get(side, side)
+    if typed is not None:
+        if cand is not None or to_global is not None:
+            raise ValueError("negatives_draw: typed lists hold global ids and replace cand / to_global")
+        t_ptr, t_idx = np.asarray(typed[0], dtype=np.int64), np.asarray(typed[1], dtype=np.int64)
+        if t_ptr.shape[0] != 2 * R + 1 or len(t_idx) >= 1 << 32:
+            raise ValueError("negatives_draw: typed=(ptr [2 R + 1], idx)")
+        n_cand = max(n_cand, 1)
     if rate < 1 or n_cand < 1 or n * rate >= 1 << 56 or side not in (0, 1, 2):
         raise ValueError("negatives_draw: rate >= 1, n_cand >= 1, n * rate < 2^56, side 0 / 1 / 2")
     seed, position = int(seed) & 0xFFFFFFFFFFFFFFFF, int(position) & 0xFFFFFFFFFFFFFFFF
@@ -143,10 +196,18 @@ def negatives_draw(facts, rate, n_cand, num_nodes, num_relations, known_keys, se
                                     position & 0xFFFFFFFF, position >> 32), key)
         if a == 0 and side == 0:
             head = (z & np.uint64(1)) != 0
-        c = _mul_hi64((x << np.uint64(32)) | y, n_cand).astype(np.int64)
-        pk = c if cand is None else cand[c]
-        pick[pending] = pk
         hd, ss, pp, oo = head[pending], s[pending], p[pending], o[pending]
+        if typed is not None:
+            slot = 2 * pp + hd
+            begin, ln = t_ptr[slot], (t_ptr[slot + 1] - t_ptr[slot]).astype(np.uint64)
+            # (x << 32 | y) * len >> 64 with len < 2^32: both partial products stay below 2^64
+            c = ((x * ln + ((y * ln) >> np.uint64(32))) >> np.uint64(32)).astype(np.int64)
+            empty = ln == 0
+            pk = np.where(empty, np.where(hd, ss, oo), t_idx[np.where(empty, 0, begin + c)] if len(t_idx) else 0)
+        else:
+            c = _mul_hi64((x << np.uint64(32)) | y, n_cand).astype(np.int64)
+            pk = c if cand is None else cand[c]
+        pick[pending] = pk
         refused = pk == np.where(hd, ss, oo)
         if keys is not None:
             gp, gs, go = G(pk).astype(np.uint64), G(ss).astype(np.uint64), G(oo).astype(np.uint64)
@@ -191,6 +252,78 @@ def complex_candidate_scores(E, Rel, anchors, rels, side):
     for h in range(H):
         acc = acc + q[:, h:h + 1] * E[None, :, h]
     return acc
+
+
+def distmult_candidate_scores(E, Rel, anchors, rels, side):
+    """The DistMult candidate scores of the rank and top-k kernels (csrc/lp_score.hpp: lp_score_tile), restated in
+    numpy with exactly their float32 operations: float32 [nq, N], row i the scores of all N nodes as the missing end of
+    pair i = (anchors[i], rels[i]).  side "tail": sum_h (E[s, h] Rel[p, h]) E[c, h]; side "head":
+    sum_h (E[c, h] Rel[p, h]) E[o, h] — that association, every product rounded to float32, added sequentially over
+    h = 0 .. H - 1."""
+    import numpy as np
+    if side not in ("tail", "head"):
+        raise ValueError(f"side must be 'tail' or 'head', not {side!r}")
+    E = np.ascontiguousarray(E, dtype=np.float32)
+    Rel = np.ascontiguousarray(Rel, dtype=np.float32)
+    if Rel.shape[1] != E.shape[1]:
+        raise ValueError("distmult_candidate_scores: rows of equal width")
+    x, r = E[np.asarray(anchors, dtype=np.int64)], Rel[np.asarray(rels, dtype=np.int64)]
+    acc = np.zeros((x.shape[0], E.shape[0]), dtype=np.float32)
+    for h in range(E.shape[1]):
+        if side == "tail":
+            acc = acc + (x[:, h] * r[:, h])[:, None] * E[None, :, h]
+        else:
+            acc = acc + (E[None, :, h] * r[:, h:h + 1]) * x[:, h:h + 1]
+    assert acc.dtype == np.float32
+    return acc
+
+
+def rank_of(greater, ties):
+    """rank = #greater + round_half_even((#ties - 1) / 2) + 1 (link_prediction.py:633-641; csrc/lp_score.hpp:
+    lp_rank_of) on integer arrays."""
+    import numpy as np
+    m = np.asarray(ties, dtype=np.int64) - 1
+    half = m >> 1
+    half = half + ((m & 1) & (half & 1))
+    return np.asarray(greater, dtype=np.int64) + half + 1
+
+
+def typed_ranks(facts, typed, E, Rel, known=None, filtered=True, scorer="distmult"):
+    """`mrgcn_distmult_typed_ranks` / `mrgcn_complex_typed_ranks` in numpy: (raw, flt), int64 [2 nf] each — tail ranks,
+    then head ranks, in the facts' order; `flt` is None without `filtered`.  `typed=(ptr, idx)`: the candidate lists
+    (`typed_candidates`).  A fact's tail is ranked among slot 2 p, its head among slot 2 p + 1: `rank_of` over the
+    candidates' scores against the fact's own (`distmult_candidate_scores` / `complex_candidate_scores`: the kernels'
+    float32 operations).  Filtered: the other nodes that complete (s, p, .) / (., p, o) to a row of `known` (None: of
+    `facts`) are left out.  Every fact is scored.  Raises ValueError when a fact's own answer is not in its slot."""
+    import numpy as np
+    t = np.asarray(facts, dtype=np.int64).reshape(-1, 3)
+    ptr, idx = np.asarray(typed[0], dtype=np.int64), np.asarray(typed[1], dtype=np.int64)
+    cand_scores = {"distmult": distmult_candidate_scores, "complex": complex_candidate_scores}[scorer]
+    nf = len(t)
+    raw = np.zeros(2 * nf, np.int64)
+    flt = np.zeros(2 * nf, np.int64) if filtered else None
+    kn = t if known is None else np.asarray(known, dtype=np.int64).reshape(-1, 3)
+    tails, heads = {}, {}
+    if filtered:
+        for s, p, o in kn.tolist():
+            tails.setdefault((s, p), set()).add(o)
+            heads.setdefault((p, o), set()).add(s)
+    for head in (0, 1):
+        anchors, answers = (t[:, 2], t[:, 0]) if head else (t[:, 0], t[:, 2])
+        sc = cand_scores(E, Rel, anchors, t[:, 1], "head" if head else "tail") if nf else None
+        for f in range(nf):
+            s, p, o = t[f].tolist()
+            cand = idx[ptr[2 * p + head]:ptr[2 * p + head + 1]]
+            if answers[f] not in cand:
+                raise ValueError(f"typed_ranks: fact {f}'s own answer is not among its relation's candidates")
+            mine, truth = sc[f, cand], sc[f, answers[f]]
+            gt, eq = mine > truth, mine == truth
+            raw[head * nf + f] = rank_of(gt.sum(), eq.sum())
+            if filtered:
+                others = (heads.get((p, o), set()) if head else tails.get((s, p), set())) - {int(answers[f])}
+                keep = ~np.isin(cand, np.fromiter(others, np.int64, len(others)))
+                flt[head * nf + f] = rank_of((gt & keep).sum(), (eq & keep).sum())
+    return raw, flt
 
 
 def complex_scores64(triples, E, Rel):

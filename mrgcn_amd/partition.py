@@ -473,7 +473,9 @@ class GraphedPartitionedStep:
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize()
         self.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph, stream=side, capture_error_mode="thread_local"):
+        from .train import capture_without_gc
+        with capture_without_gc(), \
+                torch.cuda.graph(self.graph, stream=side, capture_error_mode="thread_local"):
             self.loss = partitioned_train_step(*args)
         self.warmup_steps = max(warmup, 1)
 

@@ -30,6 +30,9 @@ def stats() -> dict:
     device; a call inside a stream capture counts once, its replays do not), `lp.decoder.grouped` (calls of
     `tasks.link_prediction.group_loss`, counted the same way) / `lp.decoder.grouped.fallback` (those of them that scored
     the flat triples and took torch's loss: rows the group kernels do not take, or the deterministic flag).
+    `lp.negatives.typed` (calls of a `NegativeSampler` over `TypedCandidates`: the type-constrained draw; such a call
+    does not count under `lp.negatives.keyed`), `lp.rank.typed` (calls of `tasks.link_prediction.rank_typed`) and
+    `lp.topk.typed` (type-constrained `predict_topk` calls), all counted like `lp.negatives.keyed`.
     `layer.block` (feature terms with block-diagonal weights served by csrc/block_xform.hip) / `layer.block.fallback`
     (those outside its limits: the literal formula on `layers.graph.block_weight_dense`).
     Under `torch.use_deterministic_algorithms(True)`: `deterministic.distmult_bwd` (DistMult backwards on the owner

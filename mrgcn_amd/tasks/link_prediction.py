@@ -857,6 +857,92 @@ def _fact_keys_device(triples: torch.Tensor, num_nodes: int, num_relations: int,
     return torch.sort((s_ * int(num_relations) + p_) * int(num_nodes) + o_).values.contiguous()
 
 
+class TypedCandidates:
+    """Type constraints for link prediction (Krompass, Baier, Tresp: "Type-Constrained Representation Learning in
+    Knowledge Graphs", ISWC 2015): per relation the nodes that may stand at its tail (its range) and at its head (its
+    domain), as a CSR over 2 * num_relations slots — slot 2 p the TAIL candidates of relation p, slot 2 p + 1 its HEAD
+    candidates.  `ptr` (int64 [2 R + 1]) and `idx` (int32, every list ascending and duplicate free) are device tensors;
+    `ptr_host` / `idx_host` are their numpy copies, which every host-side check reads.  `TypedCandidates(ptr, idx,
+    num_nodes, num_relations)` takes DECLARED lists and validates them on the host (ValueError: `ptr` not monotone, an
+    id outside [0, num_nodes), a list not sorted or with duplicates); `from_facts` builds the OBSERVED sets;
+    `full` makes every list 0 .. N - 1 (the typed kernels then compute what the untyped ones do).  Accepted by
+    `NegativeSampler(candidates=)`, `TypedFacts` / `rank_typed` / `evaluate_typed` and `predict_topk(candidates=)`."""
+
+    def __init__(self, ptr, idx, num_nodes, num_relations, device=None):
+        from ..host import check_typed_candidates
+        as_np = lambda a: a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)   # noqa: E731
+        self.ptr_host, self.idx_host = check_typed_candidates(as_np(ptr), as_np(idx), num_nodes, num_relations)
+        self.num_nodes, self.num_relations = int(num_nodes), int(num_relations)
+        if device is None:
+            device = ptr.device if torch.is_tensor(ptr) and ptr.is_cuda else (
+                "cuda" if torch.cuda.is_available() else "cpu")
+        self.ptr = torch.from_numpy(self.ptr_host).to(device)
+        # (an empty tensor has no address; the lists are empty either way)
+        self.idx = torch.from_numpy(self.idx_host if len(self.idx_host) else np.zeros(1, np.int32)).to(device)
+        self.lengths_host = np.diff(self.ptr_host)
+        self._keys = None
+
+    @classmethod
+    def from_facts(cls, known, num_nodes, num_relations, device=None):
+        """range(p) = {o : (., p, o) in known} in slot 2 p, domain(p) = {s : (s, p, .) in known} in slot 2 p + 1
+        (`mrgcn_amd.host.typed_candidates`)."""
+        from ..host import typed_candidates
+        kn = known.detach().cpu().numpy() if torch.is_tensor(known) else np.asarray(known)
+        return cls(*typed_candidates(kn, num_nodes, num_relations), num_nodes, num_relations, device=device)
+
+    @classmethod
+    def full(cls, num_nodes, num_relations, device=None):
+        N, R = int(num_nodes), int(num_relations)
+        return cls(np.arange(2 * R + 1, dtype=np.int64) * N, np.tile(np.arange(N, dtype=np.int32), 2 * R), N, R,
+                   device=device)
+
+    def to(self, device):
+        """The same lists on `device` (the host copies are shared)."""
+        d = torch.device(device)
+        if d.type == self.ptr.device.type and (d.index is None or d.index == self.ptr.device.index):
+            return self
+        return TypedCandidates(self.ptr_host, self.idx_host, self.num_nodes, self.num_relations, device=device)
+
+    def slot(self, relation: int, side="tail"):
+        """The numpy list of `relation`'s tail ("tail") or head ("head") candidates."""
+        s = 2 * int(relation) + _side(side)
+        return self.idx_host[self.ptr_host[s]:self.ptr_host[s + 1]]
+
+    def contains(self, slots, nodes):
+        """Per (slot, node) pair: is the node in the slot's list?  (host arrays)"""
+        if self._keys is None:   # the lists as one rising key array
+            self._keys = (np.repeat(np.arange(2 * self.num_relations, dtype=np.int64), self.lengths_host)
+                          * self.num_nodes + self.idx_host)
+        k = np.asarray(slots, dtype=np.int64) * self.num_nodes + np.asarray(nodes, dtype=np.int64)
+        if len(self._keys) == 0:
+            return np.zeros(k.shape, bool)
+        return self._keys[np.minimum(np.searchsorted(self._keys, k), len(self._keys) - 1)] == k
+
+
+def _relation_tiles(rel, what: str):
+    """Groups items by relation for the typed kernels: `order` (int64: the items' indices relation by relation, stable),
+    `tile_ptr` (int64 [ntiles + 1]) over that sequence — tiles of at most 8 (csrc/lp_score.hpp: kLpFB) items of ONE
+    relation — and `tile_rel` (int32 [ntiles])."""
+    rel = np.asarray(rel, dtype=np.int64)
+    order = np.argsort(rel, kind="stable")
+    rs = rel[order]
+    starts = np.flatnonzero(np.r_[True, rs[1:] != rs[:-1]]) if len(rs) else np.zeros(0, np.int64)
+    ends = np.r_[starts[1:], len(rs)] if len(rs) else np.zeros(0, np.int64)
+    per_run = (ends - starts + 7) // 8                                   # tiles of each relation's run
+    run_of_tile = np.repeat(np.arange(len(starts)), per_run)
+    first = np.cumsum(per_run) - per_run                                 # a run's first tile
+    begin = starts[run_of_tile] + 8 * (np.arange(len(run_of_tile)) - first[run_of_tile])
+    tile_ptr = np.r_[begin, len(rs)].astype(np.int64)
+    tile_rel = rs[begin].astype(np.int32) if len(begin) else np.zeros(0, np.int32)
+    assert np.all(np.diff(tile_ptr) >= 1) and np.all(np.diff(tile_ptr) <= 8), what
+    return order.astype(np.int64), tile_ptr, tile_rel
+
+
+def _dev_or_dummy(a: np.ndarray, device) -> torch.Tensor:
+    """A host array on the device; an empty one as one zero (an empty tensor has no address)."""
+    return torch.from_numpy(np.ascontiguousarray(a) if a.size else np.zeros(1, a.dtype)).to(device)
+
+
 class NegativeSampler:
     """`rate` negatives per fact, corrupted against `candidates` (None: every node 0 .. num_nodes - 1) and refused when
     they are known facts — what the reference's sampler (link_prediction.py:247-264: 20 % of the facts, nodes of the
@@ -871,7 +957,16 @@ class NegativeSampler:
     the graph the keys speak of.  `side`: "both" (a random bit per negative), "tail" or "head".  `seed` (None:
     `torch.initial_seed()`) and the position live in `.state`, two int64 on the device; `reseed` rewrites them in place,
     also under a captured graph.  `.unresolved` flags the negatives whose MRGCN_NEG_MAX_ATTEMPTS draws were all refused
-    (the last draw stands: it may be a known fact with label 0); `num_unresolved()` reads the count back."""
+    (the last draw stands: it may be a known fact with label 0); `num_unresolved()` reads the count back.
+
+    `candidates` may be a `TypedCandidates`: the type-constrained draw (mrgcn_negatives_draw_typed_i64) — the new tail
+    of a fact of relation p comes from the relation's tail candidates, the new head from its head candidates; the same
+    Philox counter, side bit and refusals, so with `TypedCandidates.full` the buffer equals the untyped sampler's bit
+    for bit.  A fact whose relation has an EMPTY list on a side the sampler may draw raises ValueError here (host,
+    once); a list whose only node is the end it replaces is refused at every attempt and flagged in `.unresolved`.
+    Typed lists hold global ids: together with `to_global` they raise `MrgcnError`.  Everything else — the tensors, the
+    two launches, the capture, `train_step`, `fit`, both flat and grouped decoders — is unchanged;
+    `stats()["lp.negatives.typed"]` counts these calls."""
 
     def __init__(self, facts, num_nodes, num_relations, rate=1, known=None, candidates=None, to_global=None,
                  side="both", seed=None):
@@ -880,6 +975,24 @@ class NegativeSampler:
         facts = torch.as_tensor(np.asarray(facts) if not torch.is_tensor(facts) else facts).long()
         if facts.dim() != 2 or facts.shape[1] != 3:
             raise ValueError("NegativeSampler: facts must be [n, 3]")
+        if isinstance(candidates, TypedCandidates):   # (host checks first: they answer without a device)
+            if to_global is not None:
+                raise _lib.MrgcnError("NegativeSampler: typed candidates hold global ids; batch-local ids "
+                                      "(to_global) are not supported with them")
+            if side not in NEG_SIDES:
+                raise ValueError(f"NegativeSampler: side is one of {sorted(NEG_SIDES)}, not {side!r}")
+            if candidates.num_nodes != int(num_nodes) or candidates.num_relations != int(num_relations):
+                raise ValueError("NegativeSampler: the typed candidates were built for another num_nodes / "
+                                 "num_relations")
+            rel = facts[:, 1].cpu().numpy()
+            if len(rel) and (rel.min() < 0 or rel.max() >= candidates.num_relations):
+                raise ValueError(f"NegativeSampler: relation ids must lie in [0, {candidates.num_relations})")
+            for sd, name in ((0, "tail"), (1, "head")):
+                if NEG_SIDES[side] in (0, 1 + sd):
+                    empty = candidates.lengths_host[2 * rel + sd] == 0
+                    if empty.any():
+                        raise ValueError(f"NegativeSampler: relation {int(rel[empty][0])} has no {name} candidates, "
+                                         f"but the sampler may draw that side")
         if not facts.is_cuda:
             facts = facts.cuda()
         dev = facts.device
@@ -897,7 +1010,11 @@ class NegativeSampler:
         self.labels[n:] = 0
         self.unresolved = torch.zeros(n * rate, dtype=torch.uint8, device=dev)
         self.to_global = None if to_global is None else torch.as_tensor(to_global).long().to(dev).contiguous()
-        if candidates is None:
+        self.typed = None
+        if isinstance(candidates, TypedCandidates):
+            self.typed = candidates.to(dev)
+            self.candidates, self.n_cand = None, N
+        elif candidates is None:
             self.candidates, self.n_cand = None, (N if self.to_global is None else int(self.to_global.numel()))
         else:
             self.candidates = torch.as_tensor(candidates).long().to(dev).contiguous()
@@ -923,6 +1040,15 @@ class NegativeSampler:
         return int(self.unresolved.sum())
 
     def __call__(self):
+        if self.typed is not None:
+            with torch.cuda.device(self.buf.device):
+                _lib.check(_lib.load().mrgcn_negatives_draw_typed_i64(
+                    _ptr(self.buf), self.n, self.rate, _ptr(self.typed.ptr), _ptr(self.typed.idx), _ptr(self.keys),
+                    int(self.keys.numel()) if self.keys is not None else 0, self.num_nodes, self.num_relations,
+                    self.side, _ptr(self.state), C.c_void_p(self.buf.data_ptr() + 24 * self.n), _ptr(self.unresolved),
+                    _stream()), "negatives_draw_typed")
+            bump("lp.negatives.typed")
+            return self.buf, self.labels
         with torch.cuda.device(self.buf.device):
             _lib.check(_lib.load().mrgcn_negatives_draw_i64(
                 _ptr(self.buf), self.n, self.rate, _ptr(self.candidates), self.n_cand, _ptr(self.to_global),
@@ -1363,7 +1489,92 @@ def _check_ids(queries, num_nodes: int, num_relations: int):
                          f"found {lo_r} .. {hi_r}")
 
 
-def predict_topk(queries, node_embeddings, edge_embeddings, k, side="tail", known=None, scorer="distmult"):
+class TypedQueries:
+    """The queries of a type-constrained `predict_topk`, grouped by relation on the host: `queries` [nq, 2] rows (anchor
+    node, relation) — a device tensor is read back once, as `known_lists` needs them on the host anyway —, `types` a
+    `TypedCandidates`, `side` "tail" / "head", `known` as `predict_topk`'s (None, an [m, 3] array of facts, or a ready
+    (ptr, idx) pair of device tensors indexed by the caller's query order).  Holds the device tensors of the call:
+    `q`, `order` / `tile_ptr` / `tile_rel` (tiles of at most 8 queries of ONE relation), `work` (one row {tile,
+    candidate tile} per block), `q_tiles` (candidate tiles per query), the exclusion lists, and `max_slot`, the
+    longest candidate list among the queries' — what the workspace is sized by.  Build it beforehand and pass it as
+    `queries` to capture the call in a graph."""
+
+    def __init__(self, queries, types: TypedCandidates, side="tail", known=None, device=None):
+        if not isinstance(types, TypedCandidates):
+            raise TypeError("TypedQueries: types must be a TypedCandidates")
+        self.side, self.head = side, _side(side)
+        if device is None:
+            device = queries.device if torch.is_tensor(queries) and queries.is_cuda else types.ptr.device
+        q_host = (queries.detach().cpu().numpy() if torch.is_tensor(queries) else np.asarray(queries)).astype(
+            np.int64).reshape(-1, 2)
+        _check_ids(q_host, types.num_nodes, types.num_relations)
+        self.types = types.to(device)
+        self.nq = nq = len(q_host)
+        order, tile_ptr, tile_rel = _relation_tiles(q_host[:, 1], "TypedQueries")
+        lens = types.lengths_host[2 * q_host[:, 1] + self.head] if nq else np.zeros(0, np.int64)
+        self.max_slot = int(lens.max()) if nq else 0
+        q_tiles = (lens + 255) // 256
+        ctiles = q_tiles[order[tile_ptr[:-1]]] if len(tile_rel) else np.zeros(0, np.int64)
+        work = np.stack([np.repeat(np.arange(len(tile_rel), dtype=np.int64), ctiles),
+                         np.arange(int(ctiles.sum())) - np.repeat(np.cumsum(ctiles) - ctiles, ctiles)], 1)
+        if len(work) >= 1 << 31:
+            raise ValueError("TypedQueries: too many (query tile, candidate tile) pairs for one grid")
+        self.ntiles, self.nwork = len(tile_rel), len(work)
+        self.scores_computed = int(lens.sum())
+        self.q_host = q_host
+        self.q = torch.from_numpy(np.ascontiguousarray(q_host)).to(device)
+        self.order = _dev_or_dummy(order, device)
+        self.tile_ptr = torch.from_numpy(tile_ptr).to(device)
+        self.tile_rel = _dev_or_dummy(tile_rel, device)
+        self.work = _dev_or_dummy(work.astype(np.int32), device)
+        self.q_tiles = _dev_or_dummy(q_tiles.astype(np.int32), device)
+        self.excl = None
+        if known is not None:
+            if isinstance(known, (tuple, list)) and len(known) == 2 and all(torch.is_tensor(a) for a in known):
+                ptr, idx = known
+                if not (ptr.dtype == torch.int64 and idx.dtype == torch.int32 and ptr.numel() == nq + 1):
+                    raise ValueError("predict_topk: known=(ptr, idx) must be tensors, int64 [nq + 1] and int32")
+                ptr, idx = ptr.to(device).contiguous(), idx.to(device).contiguous()
+            elif isinstance(known, (tuple, list)) and len(known) == 2 and any(
+                    a is None or torch.is_tensor(a) for a in known):
+                raise _lib.MrgcnError("predict_topk: exclusion lists need both tensors of the (ptr, idx) pair")
+            else:
+                kn = known.cpu().numpy() if torch.is_tensor(known) else np.asarray(known)
+                ptr, idx = (torch.from_numpy(a).to(device) for a in known_lists(q_host, kn, side))
+            if idx.numel() == 0:
+                idx = torch.zeros(1, dtype=torch.int32, device=device)
+            self.excl = (ptr, idx)
+
+
+def _predict_topk_typed(tq: TypedQueries, E, Rel, k: int, cx: bool):
+    dev, N, H = E.device, int(E.shape[0]), int(E.shape[1])
+    types = tq.types
+    if N != types.num_nodes or int(Rel.shape[0]) < types.num_relations or tq.q.device != dev:
+        raise _lib.MrgcnError("predict_topk: the embeddings do not match the typed queries (nodes, relations or device)")
+    nq = tq.nq
+    out_idx = torch.empty((nq, k), dtype=torch.int64, device=dev)
+    out_score = torch.empty((nq, k), dtype=torch.float32, device=dev)
+    if nq == 0:
+        return out_idx, out_score
+    lib = _lib.load()
+    ws_bytes = int((lib.mrgcn_complex_typed_topk_workspace if cx else lib.mrgcn_distmult_typed_topk_workspace)(
+        N, H, nq, k, tq.max_slot))
+    if ws_bytes < 0:
+        raise _lib.MrgcnError("predict_topk: sizes outside mrgcn_distmult_typed_topk's limits")
+    ws = torch.empty((ws_bytes + 7) // 8, dtype=torch.int64, device=dev)
+    ptr, idx = tq.excl if tq.excl is not None else (None, None)
+    with torch.cuda.device(dev):
+        _lib.check((lib.mrgcn_complex_typed_topk if cx else lib.mrgcn_distmult_typed_topk)(
+            _ptr(E), E.stride(0), N, _ptr(Rel), Rel.stride(0), H, _ptr(tq.q), nq, tq.head, _ptr(tq.order),
+            _ptr(tq.tile_ptr), _ptr(tq.tile_rel), tq.ntiles, _ptr(tq.work), tq.nwork, _ptr(tq.q_tiles),
+            _ptr(types.ptr), _ptr(types.idx), tq.max_slot, _ptr(ptr), _ptr(idx), k, _ptr(ws), ws_bytes,
+            _ptr(out_idx), _ptr(out_score), _stream()), "complex_typed_topk" if cx else "distmult_typed_topk")
+    bump("lp.topk.typed")
+    return out_idx, out_score
+
+
+def predict_topk(queries, node_embeddings, edge_embeddings, k, side="tail", known=None, scorer="distmult",
+                 candidates=None):
     """The k best completions of every query: `queries` [nq, 2] rows (anchor node, relation) — numpy or a tensor —,
     side="tail" ranks the nodes c of (anchor, relation, c), side="head" those of (c, relation, anchor).  Returns
     (idx int64 [nq, k], scores float32 [nq, k]) on the embeddings' device: score descending, equal scores (-0 == +0) by
@@ -1374,7 +1585,27 @@ def predict_topk(queries, node_embeddings, edge_embeddings, k, side="tail", know
     device tensors (int64 [nq + 1], int32) — with it and `queries` as a device tensor a call builds nothing on the host
     and can be captured in a graph (ids are then checked outside captures only).  1 <= k <= 256.  Embeddings must be
     finite; results with NaN are undefined.  `scorer="complex"`: ComplEx scores — those of the ComplEx ranks, bit for
-    bit, and of `mrgcn_amd.host.complex_candidate_scores` (mrgcn_complex_topk); an odd width raises `MrgcnError`."""
+    bit, and of `mrgcn_amd.host.complex_candidate_scores` (mrgcn_complex_topk); an odd width raises `MrgcnError`.
+    `candidates` (a `TypedCandidates`): the k best nodes OF THE QUERY RELATION'S LIST on the asked side (its tail
+    candidates for side="tail", its head candidates for side="head") instead of all nodes — the same order, ties,
+    exclusions and (-1, -inf) tails, scores bit-equal to the untyped call's for the same (query, node) pairs
+    (mrgcn_distmult_typed_topk).  The queries are grouped by relation on the host at call time (a device tensor is read
+    back once) and the rows come back in the caller's order; a `TypedQueries` built beforehand and passed as `queries`
+    makes the call host-free and capturable.  It carries its own side, lists and exclusions: `side` must then name the
+    side it was built for, `known` must be left out and `candidates`, when given, must hold the lists it was built
+    with — anything else raises ValueError instead of answering another question than the one asked."""
+    if isinstance(queries, TypedQueries):
+        if side != queries.side:
+            raise ValueError(f"predict_topk: the TypedQueries were built for side={queries.side!r}, not {side!r}; "
+                             f"pass side={queries.side!r}")
+        if known is not None:
+            raise ValueError("predict_topk: a TypedQueries carries its own exclusions (TypedQueries(known=...)); "
+                             "leave `known` out")
+        if candidates is not None and not (
+                isinstance(candidates, TypedCandidates) and candidates.num_nodes == queries.types.num_nodes
+                and np.array_equal(candidates.ptr_host, queries.types.ptr_host)
+                and np.array_equal(candidates.idx_host, queries.types.idx_host)):
+            raise ValueError("predict_topk: the TypedQueries were built with other candidate lists")
     head = _side(side)
     cx = _scorer(scorer, "predict_topk")
     if cx:
@@ -1390,6 +1621,12 @@ def predict_topk(queries, node_embeddings, edge_embeddings, k, side="tail", know
         raise ValueError("predict_topk: node and edge embeddings differ in width")
     if N == 0:
         raise ValueError("predict_topk: no nodes")
+    if candidates is not None or isinstance(queries, TypedQueries):
+        if not isinstance(queries, TypedQueries):
+            if not isinstance(candidates, TypedCandidates):
+                raise TypeError("predict_topk: candidates must be a TypedCandidates")
+            queries = TypedQueries(queries, candidates, side=side, known=known, device=dev)
+        return _predict_topk_typed(queries, E, Rel, k, cx)
     on_device = torch.is_tensor(queries) and queries.is_cuda
     q_host = None
     if on_device:
@@ -1434,19 +1671,21 @@ def predict_topk(queries, node_embeddings, edge_embeddings, k, side="tail", know
     return out_idx, out_score
 
 
-def predict_links(model, batch, queries, k, side="tail", known=None, scorer="distmult"):
+def predict_links(model, batch, queries, k, side="tail", known=None, scorer="distmult", candidates=None):
     """`predict_topk` on a model's own embeddings: `model.eval()`, then — without gradients — the batch's node
     embeddings (`_embed`: an MRGCN's forward, or a bare RGCN on the batch structure) against the model's relation
     embeddings.  `batch`: a FullBatch or a masked / sliced MiniBatch.  With a mini-batch the node ids of `queries`,
     `known` and the result are the BATCH-LOCAL ones (positions in `batch.node_index`, as in the facts `mkbatches`
     returns); map results back with `batch.node_index[idx]`.  The model is left in eval mode.  `scorer`: see
+    `predict_topk`.  `candidates` (a `TypedCandidates` over the ids of the embeddings, so full-batch): see
     `predict_topk`."""
     _side(side)
     _scorer(scorer, "predict_links")
     model.eval()
     with torch.no_grad():
         E = _embed(model, batch)
-        return predict_topk(queries, E, _relations(model), k, side=side, known=known, scorer=scorer)
+        return predict_topk(queries, E, _relations(model), k, side=side, known=known, scorer=scorer,
+                            candidates=candidates)
 
 
 # ---- the reference's full-batch run loop on the device (link_prediction.py:191-422; csrc/lp_eval.hip) ---------------
@@ -1615,6 +1854,141 @@ def evaluate_facts(node_embeddings, edge_embeddings, parts: FactParts, want_rank
     return (out, raw, flt) if want_ranks else out
 
 
+# ---- type-constrained ranks (csrc/lp_typed.hip) -----------------------------------------------------------------------
+class TypedFacts:
+    """The facts of a type-constrained evaluation, grouped for `rank_typed` — built once on the host, like `FactParts`.
+    `types`: a `TypedCandidates`.  Every fact's tail must be among its relation's tail candidates and its head among
+    the head candidates (ValueError otherwise: the rank rule counts the fact's own answer among the candidates).  The
+    facts are ordered by relation and cut into tiles of at most 8 facts of ONE relation (`order`, `tile_ptr`,
+    `tile_rel`; `work`: one row {2 tile + side, candidate tile} per block of the scoring grid).  `lists`: the filter
+    lists in `filter_lists`' CSR form, indexed by the fact's ORIGINAL position — with `known=None` from the facts
+    themselves (truedicts' semantics over the whole fact set), with `known` ([m, 3]) from those triples; None when not
+    `filtered`.  `part_ptr` (with `mrr_batchsize`: the parts of `FactParts`, else one part) serves `rank_metrics` only:
+    the ranks do not depend on it.  `scores_computed`: candidate scores one `rank_typed` call forms."""
+
+    def __init__(self, facts, types: TypedCandidates, known=None, filtered=True, mrr_batchsize=None, device=None):
+        if not isinstance(types, TypedCandidates):
+            raise TypeError("TypedFacts: types must be a TypedCandidates")
+        if device is None:
+            device = facts.device if torch.is_tensor(facts) and facts.is_cuda else types.ptr.device
+        data = (facts.detach().cpu().numpy() if torch.is_tensor(facts) else np.asarray(facts)).astype(np.int64)
+        if data.ndim != 2 or data.shape[1] != 3 or len(data) == 0:
+            raise ValueError("TypedFacts: facts must be a non-empty [n, 3] array")
+        n, N, R = len(data), types.num_nodes, types.num_relations
+        if data.min() < 0 or data[:, [0, 2]].max() >= N or data[:, 1].max() >= R:
+            raise ValueError(f"TypedFacts: node ids must lie in [0, {N}), relation ids in [0, {R})")
+        ok_t = types.contains(2 * data[:, 1], data[:, 2])
+        ok_h = types.contains(2 * data[:, 1] + 1, data[:, 0])
+        if not (ok_t.all() and ok_h.all()):
+            f = int(np.flatnonzero(~(ok_t & ok_h))[0])
+            raise ValueError(f"TypedFacts: fact {f} {tuple(int(v) for v in data[f])} has its "
+                             f"{'tail' if not ok_t[f] else 'head'} outside its relation's candidates")
+        self.n, self.filtered, self.types = n, bool(filtered), types.to(device)
+        order, tile_ptr, tile_rel = _relation_tiles(data[:, 1], "TypedFacts")
+        lens = types.lengths_host
+        both = np.repeat(2 * np.arange(len(tile_rel), dtype=np.int64), 2) + np.tile([0, 1], len(tile_rel))
+        ctiles = (lens[2 * tile_rel[both >> 1].astype(np.int64) + (both & 1)] + 255) // 256
+        work = np.stack([np.repeat(both, ctiles),
+                         np.arange(int(ctiles.sum())) - np.repeat(np.cumsum(ctiles) - ctiles, ctiles)], 1)
+        if len(work) >= 1 << 31 or len(tile_rel) >= 1 << 30:
+            raise ValueError("TypedFacts: too many (fact tile, candidate tile) pairs for one grid")
+        self.ntiles, self.nwork = len(tile_rel), len(work)
+        self.tile_fill = n / (8.0 * max(len(tile_rel), 1))
+        self.scores_computed = int((lens[2 * data[:, 1]] + lens[2 * data[:, 1] + 1]).sum())
+        self.order_host, self.tile_ptr_host, self.tile_rel_host = order, tile_ptr, tile_rel
+        self.facts = torch.from_numpy(np.ascontiguousarray(data)).to(device)
+        self.order = torch.from_numpy(order).to(device)
+        self.tile_ptr = torch.from_numpy(tile_ptr).to(device)
+        self.tile_rel = _dev_or_dummy(tile_rel, device)
+        self.work = _dev_or_dummy(work.astype(np.int32), device)
+        if mrr_batchsize is None or mrr_batchsize <= 0:
+            mrr_batchsize = n
+        sizes = [len(s) for s in np.array_split(np.arange(n), max(n // int(mrr_batchsize), 1))]
+        self.part_ptr_host = np.zeros(len(sizes) + 1, np.int64)
+        np.cumsum(sizes, out=self.part_ptr_host[1:])
+        self.nparts = len(sizes)
+        self.part_ptr = torch.from_numpy(self.part_ptr_host).to(device)
+        self.lists = None
+        if filtered:
+            kn = data if known is None else (known.detach().cpu().numpy() if torch.is_tensor(known)
+                                             else np.asarray(known)).astype(np.int64).reshape(-1, 3)
+            cat = []
+            for side, a, ans in (("tail", 0, 2), ("head", 2, 0)):
+                ptr, idx = known_lists(data[:, [a, 1]], kn, side)     # what is known per (anchor, relation) ...
+                owner = np.repeat(np.arange(n), np.diff(ptr))
+                keep = idx != data[owner, ans]                        # ... but the fact's own answer
+                kept = np.zeros(n + 1, np.int64)
+                np.cumsum(np.bincount(owner[keep], minlength=n), out=kept[1:])
+                cat += [kept, idx[keep].astype(np.int32)]
+            self.lists = tuple(_dev_or_dummy(a, device) for a in cat)
+        self._bufs: dict = {}
+
+
+def rank_typed(tfacts: TypedFacts, node_embeddings, edge_embeddings, scorer="distmult"):
+    """Type-constrained raw and filtered ranks (mrgcn_distmult_typed_ranks / mrgcn_complex_typed_ranks): `(raw, flt)`,
+    int64 [2 * nf] device tensors — tail ranks, then head ranks, in the ORIGINAL fact order, so `rank_metrics` applies
+    unchanged; `flt` is None when `tfacts` carries no lists.  A fact's tail is ranked among its relation's tail
+    candidates and its head among the head candidates: rank = #greater + round_half_even((#ties - 1) / 2) + 1 over
+    those candidates, for `flt` without the fact's filter list.  A candidate's score is `compute_ranks_fast`'s, bit for
+    bit (the same float32 operations in the same order), so with `TypedCandidates.full` the ranks equal `rank_both`'s.
+    EVERY fact is scored: the reference's rule that facts at positions >= num_nodes of a call stay unscored is
+    `compute_ranks_fast`'s contract and is NOT carried over.  The workspace and both results are allocated at the first
+    call for a shape and kept on `tfacts`: later calls return the same tensors, allocate nothing and do not
+    synchronise — capturable.  `scorer="complex"`: ComplEx scores; an odd width raises `MrgcnError`."""
+    cx = _scorer(scorer, "rank_typed")
+    if cx:
+        _complex_width(node_embeddings.shape[-1], "rank_typed")
+    if not isinstance(tfacts, TypedFacts):
+        raise TypeError("rank_typed: facts must be a TypedFacts (it holds the grouping by relation)")
+    E = _f32_rows(node_embeddings.detach(), "node_embeddings")
+    Rel = _f32_rows(edge_embeddings.detach(), "edge_embeddings")
+    dev, nf, N, H = E.device, tfacts.n, int(E.shape[0]), int(E.shape[1])
+    types = tfacts.types
+    if Rel.shape[1] != H:
+        raise ValueError("rank_typed: node and edge embeddings differ in width")
+    if N != types.num_nodes or int(Rel.shape[0]) < types.num_relations or tfacts.facts.device != dev:
+        raise _lib.MrgcnError("rank_typed: the embeddings do not match the typed facts (nodes, relations or device)")
+    lib = _lib.load()
+    key = (N, H, cx)
+    if key not in tfacts._bufs:
+        ws_bytes = int((lib.mrgcn_complex_typed_ranks_workspace if cx else lib.mrgcn_distmult_typed_ranks_workspace)(
+            N, H, nf))
+        if ws_bytes < 0:
+            raise _lib.MrgcnError("rank_typed: sizes outside the typed rank kernels' limits")
+        tfacts._bufs[key] = (torch.empty((ws_bytes + 3) // 4, dtype=torch.int32, device=dev), ws_bytes,
+                             torch.empty(2 * nf, dtype=torch.int64, device=dev),
+                             torch.empty(2 * nf, dtype=torch.int64, device=dev) if tfacts.lists is not None else None)
+    ws, ws_bytes, raw, flt = tfacts._bufs[key]
+    ls = tfacts.lists if tfacts.lists is not None else [None] * 4
+    with torch.cuda.device(dev):
+        _lib.check((lib.mrgcn_complex_typed_ranks if cx else lib.mrgcn_distmult_typed_ranks)(
+            _ptr(E), E.stride(0), N, _ptr(Rel), Rel.stride(0), H, _ptr(tfacts.facts), nf, _ptr(tfacts.order),
+            _ptr(tfacts.tile_ptr), _ptr(tfacts.tile_rel), tfacts.ntiles, _ptr(tfacts.work), tfacts.nwork,
+            _ptr(types.ptr), _ptr(types.idx), _ptr(ls[0]), _ptr(ls[1]), _ptr(ls[2]), _ptr(ls[3]), _ptr(ws), ws_bytes,
+            _ptr(raw), _ptr(flt), _stream()), "complex_typed_ranks" if cx else "distmult_typed_ranks")
+    bump("lp.rank.typed")
+    return raw, flt
+
+
+def evaluate_typed(node_embeddings, edge_embeddings, tfacts: TypedFacts, out=None, score=None, want_ranks=False,
+                   scorer="distmult"):
+    """`evaluate_facts` over type-constrained ranks: `rank_typed` and one `rank_metrics` per rank type over the parts of
+    `tfacts`.  Returns the float32 `[8]` device vector raw mrr, hits@1, hits@3, hits@10, then the same filtered (-1
+    each without lists) — `out`, when given — and with `want_ranks` also `(raw, flt)`.  `score` (a float32 device
+    scalar) receives `1 - raw mrr`.  No synchronisation; capturable (with `out` given, nothing is allocated after the
+    first call).  The tuples `fit` yields keep the reference's shape: call this beside it."""
+    _scorer(scorer, "evaluate_typed")
+    raw, flt = rank_typed(tfacts, node_embeddings, edge_embeddings, scorer=scorer)
+    if out is None:
+        out = torch.empty(8, dtype=torch.float32, device=raw.device)
+    rank_metrics(raw, tfacts.part_ptr, out[:4], score)
+    if flt is not None:
+        rank_metrics(flt, tfacts.part_ptr, out[4:])
+    else:
+        out[4:].fill_(-1.0)
+    return (out, raw, flt) if want_ranks else out
+
+
 def eval_schedule(nepoch, eval_interval, has_valid):
     """Which epochs of train_model evaluate what: `[(epoch, eval_train, eval_valid, records)]` for epochs 1 .. nepoch.
     The training facts are evaluated when `epoch % eval_interval == 0 or epoch == nepoch` (:336); the validation
@@ -1731,7 +2105,9 @@ class FitEpochs:
         for fn in (self._train_epoch, self._eval_epoch):
             g = torch.cuda.CUDAGraph()
             Fn.take_captured_pair_sums()
-            with torch.cuda.graph(g, stream=side, capture_error_mode="thread_local"):
+            from ..train import capture_without_gc
+            with capture_without_gc(), \
+                    torch.cuda.graph(g, stream=side, capture_error_mode="thread_local"):
                 fn()
             self._pair_sums.append(Fn.take_captured_pair_sums())
             self._graphs.append(g)
@@ -2113,7 +2489,9 @@ class BatchFitEpochs:
         for fn in (self._train_epoch, self._eval_epoch):
             g = torch.cuda.CUDAGraph()
             Fn.take_captured_pair_sums()
-            with torch.cuda.graph(g, stream=side, capture_error_mode="thread_local"):
+            from ..train import capture_without_gc
+            with capture_without_gc(), \
+                    torch.cuda.graph(g, stream=side, capture_error_mode="thread_local"):
                 fn()
             self._pair_sums.append(Fn.take_captured_pair_sums())
             self._graphs.append(g)

@@ -412,7 +412,9 @@ class GraphedBatchEpoch(BatchEpoch):
         torch.cuda.synchronize()
         self.graph = torch.cuda.CUDAGraph()
         Fn.take_captured_pair_sums()
-        with torch.cuda.graph(self.graph, stream=side, capture_error_mode="thread_local"):
+        from ..train import capture_without_gc
+        with capture_without_gc(), \
+                torch.cuda.graph(self.graph, stream=side, capture_error_mode="thread_local"):
             self._run()
         self._pair_sums = Fn.take_captured_pair_sums()
         self.warmup_steps = max(warmup, 1)

@@ -10,6 +10,8 @@ from __future__ import annotations
 
 import ctypes as C
 
+from contextlib import contextmanager
+
 import torch
 
 from . import _lib as L
@@ -216,6 +218,24 @@ def _reg_tables(model, params):
     return tables or None
 
 
+@contextmanager
+def capture_without_gc():
+    """Around a stream capture: collect dead cycles first, then keep the cyclic collector off until the capture ends.
+    torch no longer collects in front of a capture, and a collection that starts in the middle of one — in whichever
+    thread allocates the object that crosses the threshold, the autograd worker included — runs the destructors of
+    whatever dead cycle holds device objects (an earlier run's captured graphs and their pools) while the capture is
+    open."""
+    import gc
+    gc.collect()
+    was = gc.isenabled()
+    gc.disable()
+    try:
+        yield
+    finally:
+        if was:
+            gc.enable()
+
+
 class GraphedStep:
     """Any allocation-stable, synchronisation-free step `fn()` (returning a device scalar) captured into a hipGraph and
     replayed — e.g. one full-batch link-prediction epoch: negatives drawn on the device from torch's default generator
@@ -233,7 +253,8 @@ class GraphedStep:
         torch.cuda.synchronize()
         self.graph = torch.cuda.CUDAGraph()
         Fn.take_captured_pair_sums()
-        with torch.cuda.graph(self.graph, stream=side, capture_error_mode="thread_local"):
+        with capture_without_gc(), \
+                torch.cuda.graph(self.graph, stream=side, capture_error_mode="thread_local"):
             self.out = fn()
         self._pair_sums = Fn.take_captured_pair_sums()
         self.warmup_steps = max(warmup, 1)
@@ -277,7 +298,8 @@ class GraphedTrainStep:
         # watchdog in a multi-rank job) do not invalidate the capture.  Captured on the stream the warm-up steps ran
         # on: whatever keeps scratch per stream (a plan's product scratch) has met this stream already.
         Fn.take_captured_pair_sums()
-        with torch.cuda.graph(self.graph, stream=side, capture_error_mode="thread_local"):
+        with capture_without_gc(), \
+                torch.cuda.graph(self.graph, stream=side, capture_error_mode="thread_local"):
             self.loss = train_step(*args)
         # the pair-sum tables of a constant layer input that the graph reads (built by the warm-up steps): a replay
         # cannot see an in-place change of X, so their keys are compared again on the host in front of every replay
@@ -671,7 +693,8 @@ class GraphedTrainEvalStep:
         torch.cuda.synchronize()
         self.graph = torch.cuda.CUDAGraph()
         Fn.take_captured_pair_sums()
-        with torch.cuda.graph(self.graph, stream=side, capture_error_mode="thread_local"):
+        with capture_without_gc(), \
+                torch.cuda.graph(self.graph, stream=side, capture_error_mode="thread_local"):
             self.values = train_eval_step(*args, **kw)
         self._pair_sums = Fn.take_captured_pair_sums()
         self.loss = self.values[0]
