@@ -163,6 +163,15 @@ int mrgcn_plan_create_csr_hinted(mrgcn_plan_t **plan, int64_t num_rows, int64_t 
                                  const int32_t *indices, const float *data, int32_t boundary_cast_i8,
                                  uint32_t flags, const int32_t *operand_row_bytes, int32_t n_row_bytes,
                                  void *stream);
+/* A VALUE OVERLAY of `parent`: a second plan that BORROWS every index array, descriptor and order of the parent and OWNS
+ * fresh copies of the values (VAL, MVAL, CVAL; one array on a lean plan, aliased as the parent's is) and its own product
+ * scratch.  Every entry point that takes a plan runs unchanged on it and reads its values; the parent's arrays are never
+ * written.  mrgcn_edge_dropout_draw_f32 rewrites the overlay's values.  The parent must outlive the overlay; destroying
+ * the overlay (mrgcn_plan_destroy / _destroy_after) frees only what it owns.  Not inside a stream capture (it allocates,
+ * and the first overlay of a plan builds the per-entry coordinates the draw reads).  Refused: an overlay of an overlay,
+ * a plan with operand replicas; mrgcn_support_create* refuse an overlay (a support copies values out of its plan). */
+int mrgcn_plan_create_overlay(const mrgcn_plan_t *parent, mrgcn_plan_t **child, void *stream);
+int mrgcn_plan_is_overlay(const mrgcn_plan_t *plan);
 int mrgcn_plan_destroy(mrgcn_plan_t *plan);
 /* mrgcn_plan_destroy waits for ALL work in flight on the plan's device.  _destroy_after waits only for `event` (a
  * hipEvent_t the caller recorded behind the last work that uses the plan, on whichever stream; NULL: nothing used it)
@@ -1204,6 +1213,20 @@ int mrgcn_row_scale_f32(float *Y, int64_t ld, int64_t rows, int32_t F, const flo
  * row makes cheaper (a gradient whose consumer goes by the same flags).  out may be dY. */
 int mrgcn_row_scale_live_f32(const float *dY, int64_t ld_dY, int64_t rows, int32_t F, const float *m,
                              const uint8_t *row_flags, int32_t zero_dead, float *out, int64_t ld_out, void *stream);
+
+/* ---- edge dropout on the device (csrc/edge_dropout.hip; Schlichtkrull et al. 2018, §5) --------------------------
+ * Rewrites the three value arrays of the overlay `child` from its parent's.  Entry (row i, source node j, relation r)
+ * takes word x of the Philox4x32-10 block of counter (i, j, r | layer << 24, position lo) under key (seed lo,
+ * seed hi ^ position hi ^ 0x45444745): below floor(rates[r] * 2^32) the entry is dropped and holds 0.0f, otherwise it
+ * holds a * keep_r in one fp32 multiply, keep_r = 1.0f / (1.0f - rates[r]) (`rescale` = 0: keep_r = 1).  `rates`: num_relations
+ * floats in DEVICE memory, each in [0, 1) (rate 0 leaves the parent's bits).  `state_dev`: the int64 pair {seed, position}
+ * in device memory; with `advance` the one-thread launch of node dropout moves the position behind the draw (the last
+ * layer's draw of a step).  The result depends on (seed, position, layer, i, j, r, rates[r]) only — never on the grid or
+ * on which of the three orders an entry is met in.  Stream ordered, allocation free, capturable.  Refused: a plan that
+ * is no overlay, num_relations >= 2^24, layer outside 0 .. 255.  (mrgcn_amd/host.py: edge_dropout_values is the host
+ * mirror.) */
+int mrgcn_edge_dropout_draw_f32(mrgcn_plan_t *child, const float *rates, int32_t rescale, int64_t *state_dev,
+                                int32_t layer, int32_t advance, void *stream);
 
 /* ---- keyed, filtered negatives for the link-prediction decoder (csrc/lp_negatives.hip) ----------------------------
  * The reference corrupts 20 % of a batch's facts with nodes of the batch and never checks a draw against the known

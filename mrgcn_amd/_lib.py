@@ -100,6 +100,9 @@ SIGNATURES = {
     "mrgcn_plan_create_hinted": (C.c_int, [C.POINTER(_p), _i64, _i64, _i32, _i64, _p, _p, _p, _i32, _u32, _p, _i32, _p]),
     "mrgcn_plan_create_csr_hinted": (C.c_int, [C.POINTER(_p), _i64, _i64, _i32, _i64, _p, _p, _p, _i32, _u32, _p, _i32,
                                                _p]),
+    "mrgcn_plan_create_overlay": (C.c_int, [_p, C.POINTER(_p), _p]),
+    "mrgcn_plan_is_overlay": (C.c_int, [_p]),
+    "mrgcn_edge_dropout_draw_f32": (C.c_int, [_p, _p, _i32, _p, _i32, _i32, _p]),
     "mrgcn_plan_destroy": (C.c_int, [_p]),
     "mrgcn_plan_destroy_after": (C.c_int, [_p, _p]),
     "mrgcn_plan_info": (C.c_int, [_p, C.POINTER(PlanInfo)]),

@@ -192,13 +192,17 @@ int plan_scratch(const mrgcn_plan *p, hipStream_t s, float **partials, int32_t *
 bool plan_literal_cols(const mrgcn_plan *p, hipStream_t s);
 // the compact column of every CSC entry (mrgcn_plan::ecol), built by the first call outside a capture
 bool plan_entry_cols(const mrgcn_plan *p, hipStream_t s);
+// the one-thread launch that moves the position of a device {seed, position} pair on by one (node_dropout.hip)
+int philox_state_advance(int64_t *state_dev, hipStream_t s);
 // entries a wave of the entry-sliced transposed product owns; records it leaves: 2 per wave x (1 + 16) floats
 constexpr int kSegWaveEntries = 256;
 inline int64_t seg_waves(int64_t nnz) { return (nnz + kSegWaveEntries - 1) / kSegWaveEntries; }
 inline int64_t seg_scratch_floats(int64_t nnz) { return 2 * seg_waves(nnz) * 17; }
 }  // namespace mrgcn
 
-struct mrgcn_plan {
+// Everything of a plan that a plain copy may share: sizes and device arrays.  A VALUE OVERLAY (mrgcn_plan_create_overlay,
+// plan.hip) starts as a copy of its parent's and replaces the value arrays and the product scratch by its own.
+struct mrgcn_plan_arrays {
   int64_t num_rows = 0, num_nodes = 0, num_relations = 0, nnz = 0, ncols = 0;
   int64_t max_row_nnz = 0, max_col_nnz = 0;
   int64_t device_bytes = 0;
@@ -288,12 +292,6 @@ struct mrgcn_plan {
           *r3s_chunk_row = nullptr;
   int32_t r3s_n_chunks = 0;
   float *partials = nullptr;  // [max(r_n_chunks, c_n_chunks) * kWsFeatures]
-  // `partials` and `r3_ticket` are SCRATCH of the products, written by every launch: one set per stream that runs
-  // products on the plan, so that products on different streams never share it (mrgcn::plan_scratch).  The set above
-  // serves the first stream that asks; another stream gets its own at its first product on the plan.
-  struct StreamScratch { hipStream_t stream; float *partials; int32_t *ticket; };
-  mutable std::vector<StreamScratch> stream_scratch;
-  mutable std::mutex scratch_mu;
   // LITERAL products of narrow layers on the COMPACT view's row classes: the literal column r*N + j of every entry in
   // the compact view's entry order (built by the first such product outside a capture; plan.hip: plan_literal_cols)
   mutable int32_t *mlcol = nullptr;  // [nnz]
@@ -320,6 +318,22 @@ struct mrgcn_plan {
     }
     return v;
   }
+};
+
+struct mrgcn_plan : mrgcn_plan_arrays {
+  // `partials` and `r3_ticket` are SCRATCH of the products, written by every launch: one set per stream that runs
+  // products on the plan, so that products on different streams never share it (mrgcn::plan_scratch).  The set above
+  // serves the first stream that asks; another stream gets its own at its first product on the plan.
+  struct StreamScratch { hipStream_t stream; float *partials; int32_t *ticket; };
+  mutable std::vector<StreamScratch> stream_scratch;
+  mutable std::mutex scratch_mu;
+  // A value overlay (mrgcn_plan_create_overlay): `parent` set — every index array, descriptor and order above is the
+  // parent's, borrowed; val / mval / cval (one array on a lean plan), partials, r3_ticket, work_tickets and the
+  // per-stream scratch sets are its own.  The parent outlives its overlays (the caller's duty; plan.py keeps it alive).
+  const mrgcn_plan *parent = nullptr;
+  // what the edge-dropout draw (edge_dropout.hip) reads beside mlcol / ecol, built on the PARENT when its first overlay
+  // is created: the output row of every entry of the COMPACT view
+  mutable int32_t *mrow = nullptr;  // [nnz]
 };
 
 // The GRADIENT SUPPORT of a set of output rows on a plan (plan.hip builds it, support.hip computes on it): in a

@@ -153,6 +153,12 @@ int row_scale(const float *src, int64_t lds, int64_t rows, int32_t F, const floa
 }
 
 }  // namespace
+
+int philox_state_advance(int64_t *state_dev, hipStream_t s) {
+  k_node_dropout_advance<<<dim3(1), dim3(1), 0, s>>>(state_dev);
+  MRGCN_HIP_TRY(hipGetLastError());
+  return MRGCN_OK;
+}
 }  // namespace mrgcn
 
 extern "C" {

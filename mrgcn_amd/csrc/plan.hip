@@ -1096,6 +1096,16 @@ int create_impl(mrgcn_plan *p, int64_t nnz_in, const int64_t *rows, const int64_
 // hands every array of the plan back to its device's pool (`ep`: a wait that covers all users of the plan has completed:
 // pool_free's covered_epoch) and deletes the descriptor
 void release_plan(mrgcn_plan *q, uint64_t ep) {
+  if (q->parent) {  // a value overlay: its values and its scratch are all it owns
+    void *own[] = {q->val, q->lean ? nullptr : q->mval, q->cval, q->partials, q->r3_ticket, q->work_tickets};
+    for (void *a : own) pool_free(a, q->build_stream, ep);
+    for (size_t i = 1; i < q->stream_scratch.size(); ++i) {
+      pool_free(q->stream_scratch[i].partials, q->build_stream, ep);
+      pool_free(q->stream_scratch[i].ticket, q->build_stream, ep);
+    }
+    delete q;
+    return;
+  }
   if (q->lean) {  // aliases of rowptr / ccol / val / r_*: one owner each
     q->ptr3 = nullptr; q->mcol = nullptr; q->mval = nullptr;
     q->q_long_row = q->q_long_cptr = q->q_chunk_beg = q->q_chunk_end = q->q_chunk_row = nullptr;
@@ -1110,7 +1120,7 @@ void release_plan(mrgcn_plan *q, uint64_t ep) {
                   q->r3s_long_row, q->r3s_long_cptr, q->r3s_chunk_beg, q->r3s_chunk_end, q->r3s_chunk_row,
                   q->n_rperm, q->n_relptr, q->n_rnode, q->n_rmpos, q->n_relchunk_rel, q->n_relchunk_beg,
                   q->n_relchunk_end, q->n_relchunk_ptr, q->n_relchunk_ids, q->op_node, q->op_rel, q->mlcol,
-                  q->work_tickets, q->ecol};
+                  q->work_tickets, q->ecol, q->mrow};
   // (after the wait any stream may take the blocks; the plan's own build stream is where the next build of a
   // similar slice will ask for them again: the pool hands them back without a driver call)
   for (void *a : ptrs) pool_free(a, q->build_stream, ep);
@@ -1343,6 +1353,111 @@ int plan_scratch(const mrgcn_plan *p, hipStream_t s, float **partials, int32_t *
   p->stream_scratch.push_back({s, pa, ti});
   *partials = pa;
   *ticket = ti;
+  return MRGCN_OK;
+}
+
+namespace {
+// mrow[e] = output row of entry e of the COMPACT view (rank k holds row rowmap[k]): one wave per rank
+__global__ void k_entry_rows(const int32_t *__restrict__ ptr3, const int32_t *__restrict__ rowmap, int64_t rows,
+                             int32_t *__restrict__ mrow) {
+  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int64_t k = t >> 6;
+  if (k >= rows) return;
+  const int32_t row = rowmap[k], end = ptr3[k + 1];
+  for (int32_t e = ptr3[k] + (int32_t)(t & 63); e < end; e += 64) mrow[e] = row;
+}
+
+// The coordinates (row, literal column) of every entry in the COMPACT and the CSC order, kept on the PARENT for all its
+// overlays: mlcol + mrow (compact order; a lean plan's compact view is its CSR) and ecol (CSC order).  Built when the
+// first overlay is created, never inside a capture.
+int plan_entry_coords(const mrgcn_plan *p, hipStream_t s) {
+  if (p->nnz == 0) return MRGCN_OK;
+  if (!p->lean && !plan_literal_cols(p, s)) {
+    set_error("overlay: the literal columns of the compact view could not be built (a stream capture is under way?)");
+    return MRGCN_ERR_INVALID;
+  }
+  std::lock_guard<std::mutex> lock(p->scratch_mu);
+  if ((p->lean || p->mrow) && p->ecol) return MRGCN_OK;
+  int32_t *rows = nullptr, *cols = nullptr;
+  if (!p->lean && !p->mrow) {
+    MRGCN_HIP_TRY(pool_alloc((void **)&rows, (size_t)p->nnz * sizeof(int32_t), s));
+    k_entry_rows<<<dim3((unsigned)((p->num_rows * 64 + 255) / 256)), dim3(256), 0, s>>>(p->ptr3, p->rowmap, p->num_rows,
+                                                                                       rows);
+  }
+  if (!p->ecol) {
+    if (pool_alloc((void **)&cols, (size_t)p->nnz * sizeof(int32_t), s) != hipSuccess) {
+      pool_free(rows, s);
+      set_error("overlay: out of device memory for the entry columns");
+      return MRGCN_ERR_HIP;
+    }
+    k_entry_cols<<<dim3((unsigned)std::min<int64_t>((p->ncols + 255) / 256, 65535)), dim3(256), 0, s>>>(p->cptr, p->ncols,
+                                                                                                     cols);
+  }
+  if (hipGetLastError() != hipSuccess || hipStreamSynchronize(s) != hipSuccess) {
+    pool_free(rows, s);
+    pool_free(cols, s);
+    set_error("overlay: building the entry coordinates failed");
+    return MRGCN_ERR_HIP;
+  }
+  if (rows) p->mrow = rows;
+  if (cols) p->ecol = cols;
+  return MRGCN_OK;
+}
+}  // namespace
+
+// A second plan over the parent's structure with values of its own (include/mrgcn_hip.h: mrgcn_plan_create_overlay).
+int create_overlay(const mrgcn_plan *parent, mrgcn_plan **out, hipStream_t s) {
+  hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
+  MRGCN_REQUIRE(hipStreamIsCapturing(s, &st) == hipSuccess && st == hipStreamCaptureStatusNone,
+                "an overlay is created outside a stream capture (it allocates and waits)");
+  int dev = 0;
+  MRGCN_HIP_TRY(hipGetDevice(&dev));
+  MRGCN_REQUIRE(dev == parent->device, "overlay: the parent plan lives on another device");
+  MRGCN_REQUIRE(!parent->parent, "overlay: the parent is an overlay itself (take another overlay of ITS parent)");
+  MRGCN_REQUIRE(parent->n_rep == 0, "overlay: a plan with operand replicas keeps no (node, relation) for its replica rows");
+  MRGCN_REQUIRE(parent->lean || parent->nnz == 0 || parent->op_node, "overlay: the plan has no operand ids");
+  if (parent->build_stream != s) MRGCN_HIP_TRY(hipStreamSynchronize(parent->build_stream));
+  int rc = plan_entry_coords(parent, s);
+  if (rc != MRGCN_OK) return rc;
+  mrgcn_plan *c = new mrgcn_plan();
+  static_cast<mrgcn_plan_arrays &>(*c) = *parent;   // every array borrowed ...
+  c->parent = parent;
+  c->build_stream = s;
+  c->device_bytes = 0;
+  c->val = c->mval = c->cval = c->partials = nullptr;   // ... but these, which the overlay owns
+  c->r3_ticket = nullptr;
+  c->work_tickets = nullptr;
+  const int64_t nnz = parent->nnz;
+  const size_t vb = (size_t)nnz * sizeof(float);
+  auto fail = [&](hipError_t e) {
+    set_error(std::string("overlay: ") + hipGetErrorString(e));
+    free_plan(c);
+    return MRGCN_ERR_HIP;
+  };
+  hipError_t e;
+  if ((e = plan_alloc(c, &c->val, nnz)) != hipSuccess) return fail(e);
+  if (c->lean) c->mval = c->val;
+  else if ((e = plan_alloc(c, &c->mval, nnz)) != hipSuccess) return fail(e);
+  if ((e = plan_alloc(c, &c->cval, nnz)) != hipSuccess) return fail(e);
+  if ((e = plan_alloc(c, &c->partials, c->partials_floats)) != hipSuccess) return fail(e);
+  if (parent->r3_ticket) {
+    if ((e = plan_alloc(c, &c->r3_ticket, c->ticket_ints)) != hipSuccess) return fail(e);
+    if ((e = hipMemsetAsync(c->r3_ticket, 0, (size_t)std::max<int64_t>(c->ticket_ints, 1) * sizeof(int32_t), s)) != hipSuccess)
+      return fail(e);
+  }
+  if (parent->work_tickets) {
+    if ((e = plan_alloc(c, &c->work_tickets, (int64_t)kWorkTickets * kWorkTicketStride)) != hipSuccess) return fail(e);
+    if ((e = hipMemsetAsync(c->work_tickets, 0, (size_t)kWorkTickets * kWorkTicketStride * sizeof(unsigned long long), s)) !=
+        hipSuccess)
+      return fail(e);
+  }
+  if (nnz > 0) {
+    if ((e = hipMemcpyAsync(c->val, parent->val, vb, hipMemcpyDeviceToDevice, s)) != hipSuccess) return fail(e);
+    if (!c->lean && (e = hipMemcpyAsync(c->mval, parent->mval, vb, hipMemcpyDeviceToDevice, s)) != hipSuccess)
+      return fail(e);
+    if ((e = hipMemcpyAsync(c->cval, parent->cval, vb, hipMemcpyDeviceToDevice, s)) != hipSuccess) return fail(e);
+  }
+  *out = c;
   return MRGCN_OK;
 }
 
@@ -2104,6 +2219,8 @@ int mrgcn_support_create_ex(mrgcn_support_t **out, const mrgcn_plan_t *plan, con
   MRGCN_REQUIRE(out && plan && row_flags, "NULL");
   MRGCN_REQUIRE((flags & ~MRGCN_SUPPORT_FORWARD) == 0, "flags");
   MRGCN_REQUIRE(!plan->lean, "a lean plan (mini-batch slice) keeps no transposed view to build a support on");
+  MRGCN_REQUIRE(!plan->parent, "a value overlay (edge dropout) takes no gradient support: its copy of the values would "
+                               "go stale at the next draw");
   return mrgcn_support_create_chain(out, 1, plan, row_flags, flags, stream);
 }
 
@@ -2113,6 +2230,8 @@ int mrgcn_support_create_chain(mrgcn_support_t **out, int32_t n, const mrgcn_pla
   MRGCN_REQUIRE(out && plan && row_flags && n >= 1 && n <= 64, "NULL / n");
   MRGCN_REQUIRE((flags & ~MRGCN_SUPPORT_FORWARD) == 0, "flags");
   MRGCN_REQUIRE(!plan->lean, "a lean plan (mini-batch slice) keeps no transposed view to build a support on");
+  MRGCN_REQUIRE(!plan->parent, "a value overlay (edge dropout) takes no gradient support: its copy of the values would "
+                               "go stale at the next draw");
   MRGCN_REQUIRE(n == 1 || plan->num_rows == plan->num_nodes, "a chain needs rows = nodes (the stacked adjacency)");
   std::vector<mrgcn_support *> qs(n);
   for (int i = 0; i < n; ++i) {
@@ -2292,6 +2411,14 @@ int mrgcn_plan_create_csr(mrgcn_plan_t **plan, int64_t num_rows, int64_t num_nod
   return mrgcn_plan_create_csr_hinted(plan, num_rows, num_nodes, num_relations, nnz, indptr, indices, data,
                                       boundary_cast_i8, flags, nullptr, 0, stream);
 }
+
+int mrgcn_plan_create_overlay(const mrgcn_plan_t *parent, mrgcn_plan_t **child, void *stream) {
+  MRGCN_REQUIRE(parent && child, "NULL");
+  *child = nullptr;
+  return mrgcn::create_overlay(parent, child, (hipStream_t)stream);
+}
+
+int mrgcn_plan_is_overlay(const mrgcn_plan_t *plan) { return plan && plan->parent ? 1 : 0; }
 
 int mrgcn_plan_destroy(mrgcn_plan_t *plan) {
   if (plan) mrgcn::free_plan(plan);

@@ -484,7 +484,9 @@ class _SpmmLiteral(torch.autograd.Function):
             F = dY.shape[1]
             param = ctx.param
             rows = getattr(param, "_mrgcn_rows", None) if param is not None else None
-            if rows is not None and rows.get("kind") == "index" and rows.get("plan") is not plan:
+            # (a value overlay — edge dropout — has its parent's columns: the entry is keyed by the structure)
+            base = plan.parent if getattr(plan, "is_overlay", False) else plan
+            if rows is not None and rows.get("kind") == "index" and rows.get("plan") is not base:
                 # another adjacency (mini-batches, a second graph): other compact columns — rows outside THIS set may
                 # hold moments that must keep decaying: dense gradients for this parameter from now on
                 rows["dense_only"] = True
@@ -498,10 +500,10 @@ class _SpmmLiteral(torch.autograd.Function):
                 # (ClipAdam: mrgcn_adam_step_index_rows_f32) updates those rows only.  `.grad` stays None.
                 _check_consumed(rows)
                 if rows is None or rows.get("kind") != "index":
-                    if torch.cuda.is_current_stream_capturing() and getattr(plan, "_ulcol_long", None) is None:
+                    if torch.cuda.is_current_stream_capturing() and getattr(base, "_ulcol_long", None) is None:
                         raise L.MrgcnError("the literal column list of this plan is built on first use: run one "
                                            "backward of the layer before capturing it")
-                    rows = _index_rows_entry(param, plan)
+                    rows = _index_rows_entry(param, base)
                 g = torch.empty((plan.ncols, F), dtype=torch.float32, device=dY.device)
                 plan.spmm(L.VIEW_TRANSPOSED, dY, out=g)
                 rows["g"], rows["fresh"] = g, True
@@ -715,6 +717,11 @@ class _RgcnLayer(torch.autograd.Function):
             if not (meta and meta.get("structural")):
                 row_flags = None   # (a structural row set stays a valid superset under the mask; a scanned one is stale)
         sparse_rows = bool(meta and meta.get("sparse_rows"))
+        overlay = bool(getattr(plan, "is_overlay", False))
+        if sparse_rows and overlay:
+            raise L.MrgcnError("edge dropout: an output gradient with unwritten rows (train.train_step's loss) needs the "
+                               "backward on a gradient support, which a value overlay of the plan does not take; use a "
+                               "loss with a dense gradient, or set_edge_dropout(0.0)")
         if sparse_rows and row_flags is None:
             raise L.MrgcnError("internal: an output gradient with unwritten rows arrived without its row flags")
         m = getattr(ctx, "row_scale", None)
@@ -790,7 +797,8 @@ class _RgcnLayer(torch.autograd.Function):
         if _POISON_DEAD:
             dM.fill_(float("nan"))
         live = node_live = None
-        gauge = _live_gauge(plan, F, ctx.relu, dev) if _LIVE_COLS else None
+        # (an overlay — edge dropout — takes the general transposed product on its own CVAL)
+        gauge = _live_gauge(plan, F, ctx.relu, dev) if (_LIVE_COLS and not overlay) else None
         if sparse_rows and (gauge is None or F > 16):
             raise L.MrgcnError("internal: an output gradient with unwritten rows needs the live-row backward")
         # (unwritten rows outside the flags: only the live-row form may read this gradient, whatever the gauge says)
@@ -936,6 +944,8 @@ def _discovered_rows(owner, plan, dY, F, dev):
     if (owner is None or torch.cuda.is_current_stream_capturing() or dY.shape[0] != plan.num_rows
             or getattr(plan, "lean", False)):   # (a lean plan is a one-step mini-batch slice: its row set never comes back)
         return None
+    if getattr(plan, "is_overlay", False):   # (no support on a value overlay: nothing to look the rows up for)
+        return None
     if dY.dim() != 2 or dY.stride(1) != 1 or dY.dtype != torch.float32:
         return None
     if owner.__dict__.get("_mrgcn_found_rows_dense"):
@@ -964,7 +974,7 @@ def _discovered_rows(owner, plan, dY, F, dev):
 
 def _support_of(plan, meta, F, dev):
     """The gradient support for an output gradient whose live rows are known structurally, or None."""
-    if not meta or not meta.get("structural") or F > 16:
+    if not meta or not meta.get("structural") or F > 16 or getattr(plan, "is_overlay", False):
         return None
     rf = meta["row_live"]
     if rf is None or rf.numel() != plan.num_rows or rf.device != dev or rf.dtype != torch.uint8:

@@ -84,6 +84,39 @@ def node_dropout_mask(n: int, p: float, seed: int, position: int, layer: int):
 # ---- keyed, filtered negatives: the host mirror of mrgcn_negatives_draw_i64 (csrc/lp_negatives.hip) -------------------
 NEG_MAX_ATTEMPTS = 8     # include/mrgcn_hip.h: MRGCN_NEG_MAX_ATTEMPTS
 NEG_KEY_TAG = 0x4E454753  # xor-ed into the key's high word: another stream than node dropout's under the same seed
+EDGE_KEY_TAG = 0x45444745  # the same for edge dropout (csrc/edge_dropout.hip: kEdgeTag)
+
+
+# ---- edge dropout: the host mirror of mrgcn_edge_dropout_draw_f32 (csrc/edge_dropout.hip) -----------------------------
+def edge_dropout_values(rows, nodes, rels, vals, rates, seed, position, layer, rescale=True):
+    """The fp32 values the device leaves for the entries (row i, source node j, relation r) = (rows, nodes, rels) with
+    stored values `vals`: entry (i, j, r) takes word x of the Philox block with counter (i, j, r | layer << 24,
+    position lo) and key (seed lo, seed hi ^ position hi ^ EDGE_KEY_TAG); below floor(p_r * 2^32) it is dropped (0.0),
+    otherwise it holds vals * keep_r in one fp32 multiply, keep_r = fp32 1 / fp32 (1 - p_r) (`rescale=False`: 1).
+    `rates`: one probability per relation (taken as fp32, as the device reads them).  Rate 0 returns the stored bits."""
+    import numpy as np
+    rows, nodes, rels = (np.asarray(a, dtype=np.int64).reshape(-1) for a in (rows, nodes, rels))
+    vals = np.asarray(vals, dtype=np.float32).reshape(-1)
+    rates = np.asarray(rates, dtype=np.float32).reshape(-1)
+    layer = int(layer)
+    if not (rows.shape == nodes.shape == rels.shape == vals.shape):
+        raise ValueError("rows, nodes, rels and vals have one value per entry")
+    if rates.shape[0] >= 1 << 24 or not 0 <= layer < 256:
+        raise ValueError("edge dropout: fewer than 2^24 relations and a layer in 0 .. 255 (the counter packs r | layer << 24)")
+    if rels.size and (rels.min() < 0 or rels.max() >= rates.shape[0]):
+        raise ValueError("a relation outside the rate vector")
+    if np.any(~(rates >= 0)) or np.any(rates >= 1):
+        raise ValueError("edge dropout rates lie in [0, 1)")
+    seed, position = int(seed) & 0xFFFFFFFFFFFFFFFF, int(position) & 0xFFFFFFFFFFFFFFFF
+    words = philox4x32_10((rows.astype(np.uint64), nodes.astype(np.uint64),
+                           rels.astype(np.uint64) | np.uint64(layer << 24), position & 0xFFFFFFFF),
+                          (seed & 0xFFFFFFFF, (seed >> 32) ^ (position >> 32) ^ EDGE_KEY_TAG))
+    thr = np.array([node_dropout_threshold(float(p)) for p in rates], dtype=np.uint64)
+    keep = np.array([node_dropout_keep_value(float(p)) if rescale else np.float32(1.0) for p in rates], dtype=np.float32)
+    p_e = rates[rels]
+    kept = (vals * keep[rels]).astype(np.float32)
+    out = np.where(words[0][:rows.size] < thr[rels], np.float32(0.0), kept).astype(np.float32)
+    return np.where(p_e > 0, out, vals).astype(np.float32)   # (rate 0: the stored bits, -0.0 and NaNs included)
 NEG_SIDES = {"both": 0, "tail": 1, "head": 2}
 
 

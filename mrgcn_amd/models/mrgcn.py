@@ -160,6 +160,18 @@ class MRGCN(nn.Module):
         self.rgcn.set_node_dropout(mode, seed)
         return self
 
+    def set_edge_dropout(self, p: float = 0.0, self_loop=None, rates=None, rescale: bool = True, seed=None):
+        """Edge dropout of the R-GCN's training forwards, drawn on the GPU per layer and per relation —
+        `RGCN.set_edge_dropout`."""
+        self.rgcn.set_edge_dropout(p, self_loop, rates, rescale, seed)
+        return self
+
+    edge_dropout_seed = property(lambda self: self.rgcn.edge_dropout_seed,
+                                 lambda self, v: setattr(self.rgcn, "edge_dropout_seed", v))
+    edge_dropout_position = property(lambda self: self.rgcn.edge_dropout_position,
+                                     lambda self, v: setattr(self.rgcn, "edge_dropout_position", v))
+    last_edge_plans = property(lambda self: self.rgcn.last_edge_plans)
+
     def set_compute_dtype(self, dtype: str):
         """"f32" (the reference's arithmetic: the parity default) or "bf16" — BASELINE config 3's pipeline: the R-GCN
         layers store their activations in bf16 (`RGCN.set_operand_dtype`), the encoders' products (MLP / TCNN / heads)

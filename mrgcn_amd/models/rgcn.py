@@ -12,6 +12,58 @@ from ..layers.graph import GraphConvolution
 from ..plan import build_plans_parallel, plan_of
 
 
+class _DrawState:
+    """{seed, position} of a device draw with node dropout's semantics: host words until the first forward makes the
+    int64 pair in device memory, then that pair — written in place, so a captured step keeps reading the same words."""
+
+    def __init__(self, what: str):
+        self.what, self.seed, self.position, self.state = what, None, 0, None
+
+    def device_state(self, device):
+        from .. import _lib
+        from .. import functional as Fn
+        st = self.state
+        if st is None or st.device != device:
+            if st is not None:
+                self.seed, self.position = self.word(0), self.word(1)
+            if torch.cuda.is_current_stream_capturing():
+                raise _lib.MrgcnError(f"{self.what}: the device state is made by the first forward; run one step "
+                                      "before capturing")
+            if self.seed is None:
+                self.seed = torch.initial_seed()
+            st = self.state = Fn.node_dropout_state(self.seed, self.position, device)
+        return st
+
+    def word(self, i):
+        if self.state is None:
+            v = (self.seed, self.position)[i]
+            return (torch.initial_seed() if v is None else int(v)) & 0xFFFFFFFFFFFFFFFF
+        return int(self.state[i].item()) & 0xFFFFFFFFFFFFFFFF   # (a read-back: not for the inside of a step)
+
+    def set_word(self, i, value):
+        from .. import functional as Fn
+        value = int(value) & 0xFFFFFFFFFFFFFFFF
+        other = self.word(1 - i)
+        if i == 0:
+            self.seed = value
+        else:
+            self.position = value
+        if self.state is not None:   # in place: a captured step keeps reading the same words
+            pair = (value, other) if i == 0 else (other, value)
+            self.state.copy_(Fn.node_dropout_state(pair[0], pair[1], self.state.device))
+
+
+def refuse_edge_dropout(model, what: str):
+    """Raises when `model` (or a module inside it) would draw edge dropout in its next forward: for the steps whose
+    backward cannot run on a value overlay."""
+    from .. import _lib
+    for m in model.modules():
+        if isinstance(m, RGCN) and m._edge_dropout_active():
+            raise _lib.MrgcnError(f"edge dropout: {what} is outside what runs on a value overlay of the plan (full-batch "
+                                  "forward, dense output gradient: tasks.link_prediction.train_step / fit / GraphedStep, "
+                                  "or a plain loss.backward()); set_edge_dropout(0.0) for this step")
+
+
 class RGCN(nn.Module):
     def __init__(self, modules, num_relations, num_nodes, num_bases, p_dropout, featureless, bias,
                  link_prediction, num_blocks=-1):
@@ -45,6 +97,15 @@ class RGCN(nn.Module):
         self.last_node_masks = []        # the masks of the last device-mode forward (references, not copies)
         self._node_dropout_seed, self._node_dropout_position = None, 0   # until the device state exists
         self._node_dropout_state = None  # int64 {seed, position} in device memory
+
+        # edge dropout (set_edge_dropout): per-relation rates, a device state of its own, one value overlay of the
+        # adjacency's plan per layer.  None of this is a parameter or a buffer either.
+        self._edge_rates = None          # R host floats, or None: off
+        self._edge_rescale = True
+        self._edge_state = _DrawState("edge dropout")
+        self._edge_rates_dev = {}        # device -> fp32 [R]
+        self._edge_plans = {}            # id(plan) -> (plan, [overlay per layer])
+        self.last_edge_plans = []        # the overlays of the last training forward (references)
 
         if link_prediction:
             # DistMult diagonal relation embeddings (rgcn.py:55-61)
@@ -130,6 +191,92 @@ class RGCN(nn.Module):
                                      doc="stream position of the device draw: the number of device-mode forwards so "
                                          "far (each one takes the masks of one position)")
 
+    # -- edge dropout ----------------------------------------------------------------------------------------------
+    def set_edge_dropout(self, p: float = 0.0, self_loop=None, rates=None, rescale: bool = True, seed=None):
+        """Edge dropout on the device (Schlichtkrull et al. 2018, §5: 0.4 on ordinary edges, 0.2 on self-loops): in
+        `train()` mode every full-batch forward draws, per graph-convolution layer, which entries of the adjacency are
+        dropped — Philox4x32-10 keyed by (seed, position, layer, row, source node, relation), csrc/edge_dropout.hip —
+        into a value overlay of the plan (`GraphPlan.overlay()`), and the layer computes on that overlay, forward and
+        backward.  `p`: the rate of every relation but the last; `self_loop`: the rate of the last relation, the
+        identity block (None: `p`); `rates`: one rate per relation instead of both.  Each rate in [0, 1).  `rescale`:
+        kept entries are multiplied by 1 / (1 - rate).  `eval()` forwards use the plan itself and draw nothing.  With
+        every rate zero the model runs exactly as without the call.  Fused engine, full-batch plans only.  `seed`: None
+        keeps the current one (at first torch's initial seed)."""
+        R = int(self.layers["layer_0"].num_relations)
+        if rates is None:
+            rates = [float(p)] * (R - 1) + [float(p if self_loop is None else self_loop)]
+        else:
+            rates = [float(r) for r in rates]
+            if len(rates) != R:
+                raise ValueError(f"edge dropout: {len(rates)} rates for {R} relations")
+        for r in rates:
+            if not 0.0 <= r < 1.0:
+                raise ValueError(f"edge dropout rates lie in [0, 1), but got {r}")
+        if any(r > 0.0 for r in rates):
+            self._check_edge_dropout_engine()
+            self._edge_rates = rates
+        else:
+            self._edge_rates = None
+        self._edge_rescale = bool(rescale)
+        for t in self._edge_rates_dev.values():   # in place: a captured step keeps reading the same vector
+            t.copy_(torch.tensor(rates, dtype=torch.float32))
+        if seed is not None:
+            self.edge_dropout_seed = seed
+        return self
+
+    def _check_edge_dropout_engine(self):
+        from .. import _lib
+        bad = [k for k, layer in self.layers.items() if layer.engine != "fused"]
+        if bad:
+            raise _lib.MrgcnError(f"edge dropout runs on the fused engine; {', '.join(bad)} use the "
+                                  f"'{self.layers[bad[0]].engine}' engine (set_engine('fused'), or set_edge_dropout(0.0))")
+
+    def _edge_dropout_active(self) -> bool:
+        return self.training and self._edge_rates is not None
+
+    edge_dropout_seed = property(lambda self: self._edge_state.word(0), lambda self, v: self._edge_state.set_word(0, v),
+                                 doc="seed of the edge-dropout draw (64 bits); a state of its own, in no state_dict")
+    edge_dropout_position = property(lambda self: self._edge_state.word(1),
+                                     lambda self, v: self._edge_state.set_word(1, v),
+                                     doc="stream position of the edge-dropout draw: the number of training forwards "
+                                         "with edge dropout so far")
+
+    def __getstate__(self):
+        # (copies and pickles of the model take no plan handles along: the overlays are made again on first use)
+        state = dict(self.__dict__)
+        state["_edge_plans"], state["last_edge_plans"], state["_edge_rates_dev"] = {}, [], {}
+        return state
+
+    def _edge_overlays(self, plan):
+        """The overlays of `plan`, one per layer, drawn for this forward (all of them before the first layer runs: the
+        backward of layer l then reads the values its forward read)."""
+        from .. import _lib
+        self._check_edge_dropout_engine()
+        if getattr(plan, "is_overlay", False) or plan.lean:
+            raise _lib.MrgcnError("edge dropout draws into overlays of a full-batch plan")
+        ent = self._edge_plans.get(id(plan))
+        if ent is None or ent[0] is not plan or any(o._h is None for o in ent[1]):
+            if torch.cuda.is_current_stream_capturing():
+                raise _lib.MrgcnError("edge dropout: the overlays of a plan are made by the first training forward; run "
+                                      "one step before capturing")
+            while len(self._edge_plans) >= 4:   # (a handful of graphs per model)
+                for o in self._edge_plans.pop(next(iter(self._edge_plans)))[1]:
+                    o.close()
+            ent = self._edge_plans[id(plan)] = (plan, [plan.overlay() for _ in range(self.num_layers)])
+        overlays = ent[1]
+        dev = plan.device
+        st = self._edge_state.device_state(dev)
+        rates = self._edge_rates_dev.get(dev)
+        if rates is None:
+            if torch.cuda.is_current_stream_capturing():
+                raise _lib.MrgcnError("edge dropout: the rate vector is made by the first training forward; run one "
+                                      "step before capturing")
+            rates = self._edge_rates_dev[dev] = torch.tensor(self._edge_rates, dtype=torch.float32).to(dev)
+        for l, o in enumerate(overlays):
+            o.draw(rates, st, l, rescale=self._edge_rescale, advance=l == len(overlays) - 1)
+        self.last_edge_plans = overlays
+        return overlays
+
     def _device_masks(self, rows, device):
         """The node masks of one forward in device mode, `rows[l]` values for layer l: the explicit
         `node_dropout_masks` when set, else one draw per distinct run of equal sizes, the last one moving the position."""
@@ -168,6 +315,11 @@ class RGCN(nn.Module):
         """rgcn.py:91-128: layer l computes the embeddings of the nodes (L-1-l) hops from the batch
         nodes out of those one hop further, on the matching row slice of A."""
         from ..data.batch import A_BatchMasked, getAdjacencyNodeColumnIdx
+        if self._edge_dropout_active():
+            from .. import _lib
+            raise _lib.MrgcnError("edge dropout: masked and slice mini-batches are outside what runs on a value overlay "
+                                  "(a masked batch's supports copy the plan's values; a value refresh for them is "
+                                  "future work): full-batch forwards only, or set_edge_dropout(0.0)")
         if isinstance(A, A_BatchMasked):
             return self._forward_masked(X, A)
         if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
@@ -260,7 +412,25 @@ class RGCN(nn.Module):
 
     def _forward_full_batch(self, X, A):
         # the plan all layers share is built (on first use) for every layer's operand layout
-        plan_of(A, self.num_nodes, self.layers["layer_0"].num_relations, operand_row_bytes=self.operand_row_bytes())
+        plan = plan_of(A, self.num_nodes, self.layers["layer_0"].num_relations,
+                       operand_row_bytes=self.operand_row_bytes())
+        if self._edge_dropout_active():
+            # edge dropout: layer l computes on overlay l of the plan, whose values this forward has just drawn
+            overlays = self._edge_overlays(plan)
+            masks = None
+            if self._device_dropout():
+                masks = self._device_masks([self.num_nodes] * self.num_layers, X.device if X is not None else A.device)
+            for l, (key, layer) in enumerate(self.layers.items()):
+                f_activation = self.activations[key] if key in self.activations else None
+                fuse_relu = isinstance(f_activation, nn.ReLU) and (masks is not None or self.p_dropout <= 0.0)
+                X = layer._forward_fused(X, overlays[l], relu=fuse_relu,
+                                         row_scale=masks[l] if masks is not None else None)
+                if masks is None and self.p_dropout > 0.0:   # (the host draw, as below)
+                    ones = dropout(torch.ones(self.num_nodes), p=self.p_dropout).to(X.device)
+                    X = X * ones.unsqueeze(1)
+                if f_activation is not None and not fuse_relu:
+                    X = f_activation(X)
+            return X
         if self._device_dropout():
             # node dropout on the device: the masks of all layers in one draw, each applied inside its layer's function
             # (the ReLU stays in the product's epilogue: relu(m z) = m relu(z) for m >= 0)

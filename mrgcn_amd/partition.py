@@ -278,6 +278,14 @@ class PartitionedRGCN(nn.Module):
                                   "(the single-GPU RGCN on the fused engine draws on the device)")
         return self
 
+    def set_edge_dropout(self, p: float = 0.0, self_loop=None, rates=None, rescale: bool = True, seed=None):
+        """The partitioned engines have no edge dropout (models/rgcn.py: RGCN.set_edge_dropout)."""
+        if any(float(r) != 0.0 for r in (rates if rates is not None else (p, self_loop or 0.0))):
+            raise Fn.L.MrgcnError(f"{type(self).__name__}: edge dropout is outside the partitioned engines (their "
+                                  "backward runs on gradient supports, which copy the plan's values; the single-GPU "
+                                  "RGCN on the fused engine draws into value overlays)")
+        return self
+
     def sharded_parameters(self):
         return [l.weight_I for l in self.layers.values() if l.weight_I is not None]
 

@@ -167,6 +167,30 @@ class GraphPlan:
         A._mrgcn_plan = self
         return A
 
+    # -- value overlay (include/mrgcn_hip.h: mrgcn_plan_create_overlay) -------------------------------
+    is_overlay = False
+
+    def overlay(self) -> "GraphPlan":
+        """A second plan over this plan's structure with VALUES of its own (edge dropout draws into them): it borrows
+        every index array and order, owns copies of VAL / MVAL / CVAL and its own product scratch, and runs every
+        product this plan runs.  This plan's arrays are never written.  The overlay keeps this plan alive; closing it
+        frees only what it owns.  Not inside a stream capture."""
+        if self.is_overlay:
+            raise L.MrgcnError("an overlay of an overlay: take another overlay of its parent")
+        handle = C.c_void_p()
+        with torch.cuda.device(self.device):
+            L.check(L.load().mrgcn_plan_create_overlay(self.handle, C.byref(handle), _stream_ptr(self.device)),
+                    "mrgcn_plan_create_overlay")
+        child = OverlayPlan.__new__(OverlayPlan)
+        child.parent = self
+        child.device = self.device
+        child.num_rows, child.num_nodes, child.num_relations = self.num_rows, self.num_nodes, self.num_relations
+        child.lean, child.operand_row_bytes = self.lean, self.operand_row_bytes
+        child._adopt(handle)
+        import weakref
+        self.__dict__.setdefault("_overlays", weakref.WeakSet()).add(child)   # (closed with this plan, before it)
+        return child
+
     # -- lifetime -------------------------------------------------------------------
     def close(self, after_event=None):
         """Releases the plan's device memory.  Default: after a wait for everything in flight on the device.
@@ -175,6 +199,8 @@ class GraphPlan:
         if getattr(self, "_h", None) is not None and self._h:
             for sup in self.__dict__.pop("_supports", {}).values():  # (they read the plan's arrays: first)
                 sup.close()
+            for ov in list(self.__dict__.pop("_overlays", ())):       # (value overlays borrow them: first as well)
+                ov.close()
             _release("plan", self._h, after_event)
             self._h = None
 
@@ -365,6 +391,67 @@ class GraphPlan:
                 + self.ncols * F * elem_bytes + self.num_rows * F * elem_bytes)
 
 
+class OverlayPlan(GraphPlan):
+    """A value overlay of a plan (`GraphPlan.overlay()`): the parent's structure, values of its own.  Holds on to its
+    parent.  What is structure only — the units of the wide-layer backward, the literal column lists — is the parent's
+    own cache; what would COPY values out of the plan (a gradient support) is refused: the copy would go stale at the
+    next edge-dropout draw."""
+    is_overlay = True
+
+    def __init__(self, *a, **k):
+        raise L.MrgcnError("an overlay is made by GraphPlan.overlay()")
+
+    def close(self, after_event=None):
+        if getattr(self, "_h", None) is not None and self._h:
+            _release("plan", self._h, after_event)   # (the library frees what the overlay owns, nothing of the parent's)
+            self._h = None
+
+    def draw(self, rates: torch.Tensor, state: torch.Tensor, layer: int, rescale: bool = True, advance: bool = False):
+        """Rewrites this overlay's values from the parent's (mrgcn_edge_dropout_draw_f32): `rates` fp32 [num_relations]
+        and `state` int64 {seed, position}, both in device memory."""
+        if (rates.dtype != torch.float32 or rates.numel() != self.num_relations or not rates.is_contiguous()
+                or rates.device != self.device):
+            raise L.MrgcnError(f"edge dropout: `rates` is a contiguous fp32 vector of {self.num_relations} values on "
+                               f"{self.device}")
+        if state.dtype != torch.int64 or state.numel() != 2 or state.device != self.device:
+            raise L.MrgcnError("edge dropout: the state is an int64 pair {seed, position} in device memory")
+        with torch.cuda.device(self.device):
+            L.check(L.load().mrgcn_edge_dropout_draw_f32(self.handle, rates.data_ptr(), int(bool(rescale)),
+                                                         state.data_ptr(), int(layer), int(bool(advance)),
+                                                         _stream_ptr(self.device)), "mrgcn_edge_dropout_draw_f32")
+        from .stats import bump
+        bump("edge_dropout.device")
+        return self
+
+    # structure only: the parent's caches
+    def ulcol_long(self):
+        t = getattr(self, "_ulcol_long", None)
+        if t is None:
+            t = self._ulcol_long = self.parent.ulcol_long()
+        return t
+
+    def ulcol_sorted(self):
+        ent = self.__dict__.get("_ulcol_sorted")
+        if ent is None:
+            ent = self.__dict__["_ulcol_sorted"] = self.parent.ulcol_sorted()
+        return ent
+
+    def wide_units(self, unit_entries: int = 256):
+        ent = self.__dict__.get("_wide_units")
+        if ent is None:
+            ent = self.__dict__["_wide_units"] = self.parent.wide_units(unit_entries)
+        return ent
+
+    def wide_units_det(self, unit_entries: int = 64):
+        ent = self.__dict__.get("_wide_units_det")
+        if ent is None:
+            ent = self.__dict__["_wide_units_det"] = self.parent.wide_units_det(unit_entries)
+        return ent
+
+    def support_for(self, row_flags):
+        _refuse_overlay(self)
+
+
 class GraphSupport:
     """Host handle of a gradient support (mrgcn_support_t): the live columns / entries / nodes of a plan for a fixed
     set of output rows that can carry gradient.  Holds on to the flags tensor it was built from (its identity is the
@@ -375,6 +462,7 @@ class GraphSupport:
         masked pass over the plan, csrc/masked.hip).  (`_handle`: adopt a support that exists — GraphSupport.chain.)"""
         import weakref
         lib = L.load()
+        _refuse_overlay(plan)
         if _handle is None and (row_flags.dtype != torch.uint8 or row_flags.numel() != plan.num_rows
                                 or not row_flags.is_contiguous()):
             raise L.MrgcnError(f"row_flags must be a contiguous uint8 tensor of {plan.num_rows} rows")
@@ -409,6 +497,7 @@ class GraphSupport:
         """`n` supports in one build (one host wait): the first on `row_flags`, each next one on the NODE_FLAGS of the
         one before — the samples of the n layers of a mini-batch (mrgcn_support_create_chain)."""
         lib = L.load()
+        _refuse_overlay(plan)
         if row_flags.dtype != torch.uint8 or row_flags.numel() != plan.num_rows or not row_flags.is_contiguous():
             raise L.MrgcnError(f"row_flags must be a contiguous uint8 tensor of {plan.num_rows} rows")
         hs = (C.c_void_p * n)()
@@ -558,6 +647,12 @@ class GraphSupport:
             t = torch.empty((max(int(numel), 2),), dtype=torch.float32, device=self.device)
             self._ws[key] = t
         return t
+
+
+def _refuse_overlay(plan):
+    if getattr(plan, "is_overlay", False):
+        raise L.MrgcnError("a gradient support copies values out of its plan and would go stale at the next "
+                           "edge-dropout draw: not on an overlay (a value refresh for supports is future work)")
 
 
 def _device_array(ptr: int, n: int, dtype, device) -> torch.Tensor:

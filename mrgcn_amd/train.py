@@ -164,6 +164,10 @@ def train_step(model, forward_fn, idx, targets, optimizer, l1_lambda: float = 0.
     Adam kernel.  `loss_fn(logits, idx, targets)`: another loss of the same contract in place of
     `categorical_crossentropy(..., sole_consumer=True)` (tasks.node_classification: the batch's loss with its accuracy
     out of the same launch)."""
+    if isinstance(model, torch.nn.Module):
+        from .models.rgcn import refuse_edge_dropout
+        refuse_edge_dropout(model, "train.train_step (its loss hands down row-sparse gradients, whose backward runs on "
+                                   "gradient supports)")
     params = [p for g in optimizer.param_groups for p in g["params"]]
     clear_row_grads(params)
     logits = forward_fn()

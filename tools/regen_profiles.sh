@@ -123,6 +123,9 @@ python3 tools/lp_all_probe.py --out $o/lp_all_probe.json > $o/lp_all_probe.txt 2
 # (10o) a block-diagonal hidden layer (200 -> 200, 40 blocks) at the FB15k-237 shape: its five passes alone, the layer on
 # the fused engine against the literal engine on the dense expansion (with peak memory), the replayed two-layer fit epoch
 python3 tools/block_layer_probe.py --out $o/block_layer_probe.json > $o/block_layer_probe.txt 2> $o/block_layer_probe.err
+# (10p) edge dropout: one layer's draw alone and the replayed fit epoch with it on and off, FB15k-237 and AM shapes
+# (run the same script in a checkout of the parent commit for profiles/edge_dropout_probe_parent.json)
+python3 tools/edge_dropout_probe.py --out $o/edge_dropout_probe.json > $o/edge_dropout_probe.txt 2> $o/edge_dropout_probe.err
 hipcc -O3 --offload-arch=gfx950 -std=c++17 tools/lab/copy_lab.hip -o /tmp/copy_lab 2>/dev/null && /tmp/copy_lab > $o/copy_lab.txt 2>&1
 python3 tools/lab/spmm_hot_lab.py > $o/spmm_hot_lab.txt 2>&1
 # the CPU suite last: the tree these artefacts describe is green
