@@ -1338,6 +1338,44 @@ int mrgcn_lp_all_bwd_f32(const float *Q, int64_t ldQ, int64_t m, const float *E,
                          const int64_t *target, const float *lse, const float *gl, float *dQ, int64_t lddQ, float *dE,
                          int64_t lddE, void *workspace, int64_t workspace_bytes, void *stream);
 
+/* ---- KvsAll decoder: multi-hot BCE against all candidates, label smoothed (csrc/lp_kvsall.hip) ---------------------
+ * Every DISTINCT query vector Q[q] scored against ALL rows of the candidate table E under a binary cross-entropy whose
+ * target marks all known answers of the query: x[q][c] = Q[q] . E[c], Y'[q][c] = (1 - eps) [c in ans(q)] + eps / N,
+ * loss = the mean over the m N scores of bce_with_logits(x, Y') — the "1-N scoring" of Dettmers, Minervini, Stenetorp,
+ * Riedel ("Convolutional 2D Knowledge Graph Embeddings", AAAI 2018) with the label smoothing of Szegedy et al.
+ * ("Rethinking the Inception Architecture for Computer Vision", CVPR 2016); the reference has the sampled BCE only
+ * (mrgcn/tasks/link_prediction.py:645-665, :550-554), so the papers stand where a reference call site would.  The unit
+ * does not know the scorer (tasks/link_prediction.py: pair_vectors builds Q).  The [m, N] scores are never stored and
+ * no label enters the dense kernels (the 64 x 64 MFMA tiles of csrc/lp_all.hip):
+ *   sum_c bce = sum_c softplus(x) - (eps / N) sum_c x - (1 - eps) sum_{c in ans(q)} x,
+ *   d / dx    = sigmoid(x) - eps / N - (1 - eps) [c in ans(q)],
+ * the last term of each taken along the lists of the nnz (query, answer) pairs.  Q [m, H] and E [N, H] are float32 with row
+ * strides ldQ / ldE.  ans_ptr int64 [m + 1] / ans_idx int32 [nnz]: the answers of query q are
+ * ans_idx[ans_ptr[q] .. ans_ptr[q + 1]), ascending, 0 <= answer < N (not checked here); an empty list is legal.
+ * cand_ptr int64 [N + 1] / cand_qry int32 [nnz]: the transposed lists — the queries that have candidate c as an answer,
+ * ascending.
+ * _supported: mrgcn_lp_all_supported's rule; _workspace: the bytes _fwd needs (-1 for sizes it does not take); _bwd
+ *   needs none.
+ * _fwd: per_query [m] (may be NULL) = sum_c bce of the query, *loss WRITTEN: the per-query sums added as float64 in a
+ *   fixed order, divided by m N and rounded once.  The softplus is max(x, 0) + log1p(exp(-|x|)).
+ * _bwd: with G[q][c] = (sigmoid(x[q][c]) - eps / N) * *gl / (m N) (gl: a float in DEVICE memory, no host read),
+ *   less (1 - eps) * *gl / (m N) on the listed pairs (in the gradient tile itself, as eps (1 - 1 / N) - sigmoid(-x):
+ *   along ans_* for dQ, along cand_* for dE), dQ = G . E and dE = G^T . Q are WRITTEN (every output row has one owning block;
+ *   nothing is added).  dQ / dE may be NULL (skipped; cand_* may then be NULL with dE, ans_* with dQ); lddQ / lddE
+ *   >= H.
+ * label_smoothing outside [0, 1) is an argument error.  No float atomics: equal inputs give equal bits.  Stream
+ * ordered, no allocation, capturable. */
+int32_t mrgcn_lp_kvsall_supported(const float *Q, int64_t ldQ, int64_t m, const float *E, int64_t ldE, int64_t N,
+                                  int32_t H);
+int64_t mrgcn_lp_kvsall_workspace(int64_t m, int64_t N, int32_t H);
+int mrgcn_lp_kvsall_fwd_f32(const float *Q, int64_t ldQ, int64_t m, const float *E, int64_t ldE, int64_t N, int32_t H,
+                            const int64_t *ans_ptr, const int32_t *ans_idx, double label_smoothing, float *per_query,
+                            float *loss, void *workspace, int64_t workspace_bytes, void *stream);
+int mrgcn_lp_kvsall_bwd_f32(const float *Q, int64_t ldQ, int64_t m, const float *E, int64_t ldE, int64_t N, int32_t H,
+                            const int64_t *ans_ptr, const int32_t *ans_idx, const int64_t *cand_ptr,
+                            const int32_t *cand_qry, double label_smoothing, const float *gl, float *dQ, int64_t lddQ,
+                            float *dE, int64_t lddE, void *workspace, int64_t workspace_bytes, void *stream);
+
 /* ---- block-diagonal relation transform (csrc/block_xform.hip) ------------------------------------------------------
  * Schlichtkrull et al. 2018, "Modeling Relational Data with Graph Convolutional Networks", eq. 4:
  * W_r = blockdiag(Q_r[0], ..., Q_r[NB-1]), NB blocks of ki x fo = (K / NB) x (F / NB); input columns b ki .. b ki + ki - 1

@@ -447,6 +447,93 @@ def all_lse32(Q, E, target):
     return lse, x[np.arange(Q.shape[0]), tg]
 
 
+# ---- the KvsAll decoder (csrc/lp_kvsall.hip; tasks/link_prediction.py: KvsAllQueries, kvsall_loss) -----------------
+def _kvsall_side(t, key, ans):
+    """The distinct keys of the (duplicate-free) facts `t` by rising key -> (one fact per key — its first answer's —,
+    ptr, the answers ascending within a key)."""
+    import numpy as np
+    order = np.lexsort((ans, key))
+    key, ans = key[order], ans[order]
+    first = np.flatnonzero(np.concatenate([[True], key[1:] != key[:-1]])) if len(key) else np.zeros(0, np.int64)
+    ptr = np.concatenate([first, [len(key)]]).astype(np.int64)
+    return t[order[first]], ptr, ans
+
+
+def kvsall_queries(facts, num_nodes, num_relations, side="both"):
+    """The queries of the KvsAll objective (Dettmers et al. 2018, "1-N scoring") over `facts` [n, 3] ->
+    (reps [m, 3], m_tail, ptr int64 [m + 1], idx int32 [nnz], cptr int64 [num_nodes + 1], cqry int32 [nnz]).  Tail
+    queries are the distinct (s, p) by rising s R + p, their answers all o with (s, p, o) a fact; head queries the
+    distinct (p, o) by rising p N + o, their answers all s.  `side="both"`: the tail queries, then the head queries;
+    "tail" / "head": those alone (m_tail = m / 0).  Answers ascend within a query and a duplicate fact counts once.
+    `reps[q]` is one fact of query q (the one with its smallest answer): what `pair_vectors` builds the query's vector
+    from.  cptr / cqry are the transposed lists: the queries that have node c as an answer, ascending."""
+    import numpy as np
+    if side not in ALL_SIDES:
+        raise ValueError(f"side is one of {ALL_SIDES}, not {side!r}")
+    N, R = int(num_nodes), int(num_relations)
+    t = np.asarray(facts, dtype=np.int64).reshape(-1, 3)
+    if len(t) and (t.min() < 0 or max(t[:, 0].max(), t[:, 2].max()) >= N or t[:, 1].max() >= R):
+        raise ValueError("kvsall_queries: an id of the facts is outside num_nodes / num_relations")
+    t = np.unique(t, axis=0)
+    reps, ptrs, idxs, m_tail = [], [], [], 0
+    if side in ("both", "tail"):
+        r, p, a = _kvsall_side(t, t[:, 0] * R + t[:, 1], t[:, 2])
+        reps.append(r), ptrs.append(p), idxs.append(a)
+        m_tail = len(r)
+    if side in ("both", "head"):
+        r, p, a = _kvsall_side(t, t[:, 1] * N + t[:, 2], t[:, 0])
+        reps.append(r), idxs.append(a)
+        ptrs.append(p if not ptrs else p[1:] + ptrs[0][-1])
+    reps, ptr, idx = np.concatenate(reps, axis=0), np.concatenate(ptrs), np.concatenate(idxs)
+    qry = np.repeat(np.arange(len(reps), dtype=np.int64), np.diff(ptr))
+    order = np.argsort(idx, kind="stable")     # (the pairs are query-major: a stable sort keeps the queries ascending)
+    cptr = np.concatenate([[0], np.cumsum(np.bincount(idx, minlength=N))]).astype(np.int64)
+    return reps, m_tail, ptr, idx.astype(np.int32), cptr, qry[order].astype(np.int32)
+
+
+def _kvsall_dense_labels(m, N, ptr, idx, eps, dtype):
+    import numpy as np
+    Y = np.zeros((m, N), dtype=dtype)
+    Y[np.repeat(np.arange(m), np.diff(np.asarray(ptr, dtype=np.int64))), np.asarray(idx, dtype=np.int64)] = 1
+    return Y, (dtype(1) - dtype(eps)) * Y + dtype(eps / N)
+
+
+def kvsall_loss64(Q, E, ptr, idx, label_smoothing=0.0, upstream=1.0):
+    """The KvsAll loss in numpy float64: `binary_cross_entropy_with_logits(Q E^T, Y', reduction="mean")` with
+    Y' = (1 - eps) Y + eps / N, Y[q][c] = 1 iff c is in idx[ptr[q] .. ptr[q + 1]) -> (loss, per_query [m] — the sum of
+    the query's N terms —, dQ [m, H], dE [N, H]), the gradients for the upstream scalar `upstream`.  The softplus is
+    max(x, 0) + log1p(exp(-|x|)) and the sigmoid exp(min(x, 0)) / (1 + exp(-|x|)): nothing overflows."""
+    import numpy as np
+    Q, E = np.asarray(Q, dtype=np.float64), np.asarray(E, dtype=np.float64)
+    eps = float(label_smoothing)
+    if not 0.0 <= eps < 1.0:
+        raise ValueError("kvsall_loss64: label_smoothing in [0, 1)")
+    m, N = Q.shape[0], E.shape[0]
+    _, Ys = _kvsall_dense_labels(m, N, ptr, idx, eps, np.float64)
+    x = Q @ E.T
+    e = np.exp(-np.abs(x))
+    per_query = (np.maximum(x, 0.0) + np.log1p(e) - Ys * x).sum(axis=1)
+    G = (np.exp(np.minimum(x, 0.0)) / (1.0 + e) - Ys) * (float(upstream) / (m * N))
+    return float(per_query.sum() / (m * N)), per_query, G @ E, G.T @ Q
+
+
+def kvsall_loss32(Q, E, ptr, idx, label_smoothing=0.0):
+    """`kvsall_loss64`'s forward restated in float32, in the kernels' split — a float32 matmul, a float32 softplus,
+    float32 sums: per_query = sum softplus(x) - (eps / N) sum x - (1 - eps) sum of the answers' x -> (loss, per_query
+    [m]) as float32: what the kernels differ from in summation order and in the last ulp of exp / log1p."""
+    import numpy as np
+    f = np.float32
+    Q, E = np.ascontiguousarray(Q, dtype=f), np.ascontiguousarray(E, dtype=f)
+    eps = float(label_smoothing)
+    m, N = Q.shape[0], E.shape[0]
+    Y, _ = _kvsall_dense_labels(m, N, ptr, idx, eps, f)
+    x = Q @ E.T
+    S = (np.maximum(x, f(0)) + np.log1p(np.exp(-np.abs(x)))).sum(axis=1, dtype=f)
+    per_query = S - f(eps / N) * x.sum(axis=1, dtype=f) - f(1.0 - eps) * (Y * x).sum(axis=1, dtype=f)
+    assert per_query.dtype == f
+    return f(per_query.sum(dtype=f) / f(float(m) * float(N))), per_query
+
+
 # ---- block-diagonal relation transform (csrc/block_xform.hip; Schlichtkrull et al. 2018, eq. 4) ----------------------
 # W: (R, NB, ki, fo), W_r = blockdiag(W[r, 0], ..., W[r, NB-1]); a compact column c is the pair (node[c], rel[c]).
 def block_weight_dense64(W):

@@ -691,22 +691,181 @@ def all_loss(facts, node_embeddings, edge_embeddings, side="both", scorer="distm
     return all_pairs_loss(Q, E, target)
 
 
-def _all_facts(sampler, fallback, who):
-    """The facts of the 1-vs-all decoder: `sampler.facts` (both device samplers have it; the sampler is NOT called, no
-    negatives are drawn), else `fallback`."""
+def _all_facts(sampler, fallback, who, decoder="all"):
+    """The facts of the 1-vs-all and KvsAll decoders: `sampler.facts` (both device samplers have it; the sampler is NOT
+    called, no negatives are drawn), else `fallback`."""
     if sampler is None:
         return fallback
     facts = getattr(sampler, "facts", None)
     if facts is None:
-        raise _lib.MrgcnError(f"{who}: decoder='all' reads the facts from `sampler.facts` (DeviceNegativeSampler and "
-                              f"NegativeSampler have it), which {type(sampler).__name__} lacks")
+        raise _lib.MrgcnError(f"{who}: decoder={decoder!r} reads the facts from `sampler.facts` (DeviceNegativeSampler "
+                              f"and NegativeSampler have it), which {type(sampler).__name__} lacks")
     return facts
 
 
-def _decoder_args(decoder, loss, pos_weight, samplers, who, scorer="distmult"):
-    """The run loops' `decoder` / `loss` / `pos_weight` / `scorer` keywords, checked before any kernel is touched ->
-    (grouped?, loss, pos_weight as a host float or None)."""
+# ---- the KvsAll decoder (csrc/lp_kvsall.hip) ------------------------------------------------------------------------
+# Dettmers et al. 2018's "1-N scoring": every DISTINCT (s, p, ?) and (?, p, o) query of the facts scored once against
+# all nodes under a binary cross-entropy whose target marks ALL known answers of the query, with label smoothing
+# (Szegedy et al. 2016) — what Ruffinelli et al. 2020 found, with 1-vs-all, to train DistMult and ComplEx best.  The
+# 1-vs-all softmax keeps a query's other true answers in its denominator; here they are positives.
+def _smoothing(label_smoothing, who) -> float:
+    eps = float(label_smoothing)
+    if not 0.0 <= eps < 1.0:
+        raise _lib.MrgcnError(f"{who}: label_smoothing is in [0, 1), not {label_smoothing!r}")
+    return eps
+
+
+class KvsAllQueries:
+    """The queries of the KvsAll objective over a fixed fact set, built once on the host (`host.kvsall_queries`: the
+    order of queries and answers is defined there) and kept on `device` (None: the facts' device for a tensor, else the
+    current GPU; "cpu" works without one): `reps` int64 [m, 3] — one fact per query, tail queries first —, `ptr` int64
+    [m + 1] / `idx` int32 [nnz] the answers of every query, `cptr` int64 [num_nodes + 1] / `cqry` int32 [nnz] the
+    queries of every node, `rows` int64 [nnz] the query of every (query, answer) pair; `m`, `m_tail`, `nnz` as host
+    ints.  Reads the facts on the host: not inside a stream capture."""
+
+    def __init__(self, facts, num_nodes, num_relations, side="both", device=None):
+        from .. import host
+        _all_side(side, "KvsAllQueries")
+        if torch.is_tensor(facts):
+            if facts.is_cuda and torch.cuda.is_current_stream_capturing():
+                raise _lib.MrgcnError("KvsAllQueries: the kvsall queries are built on the host, outside a stream capture")
+            if device is None:
+                device = facts.device
+            facts = facts.detach().cpu().numpy()
+        t = np.asarray(facts)
+        if t.ndim != 2 or t.shape[1] != 3 or t.shape[0] < 1 or t.dtype.kind not in "iu":
+            raise _lib.MrgcnError("KvsAllQueries: the kvsall facts are integer [n, 3] with n >= 1")
+        try:
+            reps, m_tail, ptr, idx, cptr, cqry = host.kvsall_queries(t, num_nodes, num_relations, side)
+        except ValueError as e:
+            raise _lib.MrgcnError(f"KvsAllQueries: {e}") from None
+        device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        self.side, self.num_nodes, self.num_relations = side, int(num_nodes), int(num_relations)
+        self.m, self.m_tail, self.nnz = int(len(reps)), int(m_tail), int(len(idx))
+        rows = np.repeat(np.arange(self.m, dtype=np.int64), np.diff(ptr))
+        self.reps, self.ptr, self.idx, self.cptr, self.cqry, self.rows = (
+            torch.from_numpy(np.ascontiguousarray(a)).to(device) for a in (reps, ptr, idx, cptr, cqry, rows))
+        self.device = self.reps.device
+
+
+def _kvsall_supported(lib, Q, E) -> bool:
+    return bool(Q.shape[0] >= 1 and E.shape[0] >= 1 and lib.mrgcn_lp_kvsall_supported(
+        _ptr(Q), Q.stride(0), Q.shape[0], _ptr(E), E.stride(0), E.shape[0], E.shape[1]))
+
+
+class _KvsAllLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, Q, E, kq, eps):
+        lib = _lib.load()
+        m, N, H = Q.shape[0], E.shape[0], E.shape[1]
+        loss = torch.empty((), dtype=torch.float32, device=E.device)
+        ws = _det_scratch(E.device, "lp_kvsall", int(lib.mrgcn_lp_kvsall_workspace(m, N, H)))
+        _lib.check(lib.mrgcn_lp_kvsall_fwd_f32(_ptr(Q), Q.stride(0), m, _ptr(E), E.stride(0), N, H, _ptr(kq.ptr),
+                                               _ptr(kq.idx), eps, None, _ptr(loss), _ptr(ws), ws.numel(), _stream()),
+                   "lp_kvsall_fwd")
+        ctx.save_for_backward(Q, E)
+        ctx.kvsall = (kq, eps)
+        return loss
+
+    @staticmethod
+    def backward(ctx, gl):
+        Q, E = ctx.saved_tensors
+        kq, eps = ctx.kvsall
+        gl = gl.contiguous().float()
+        dQ = torch.empty(Q.shape, dtype=torch.float32, device=Q.device) if ctx.needs_input_grad[0] else None
+        dE = torch.empty(E.shape, dtype=torch.float32, device=E.device) if ctx.needs_input_grad[1] else None
+        _lib.check(_lib.load().mrgcn_lp_kvsall_bwd_f32(
+            _ptr(Q), Q.stride(0), Q.shape[0], _ptr(E), E.stride(0), E.shape[0], E.shape[1], _ptr(kq.ptr), _ptr(kq.idx),
+            _ptr(kq.cptr), _ptr(kq.cqry), eps, _ptr(gl), _ptr(dQ), Q.shape[1], _ptr(dE), E.shape[1], None, 0,
+            _stream()), "lp_kvsall_bwd")
+        return dQ, dE, None, None
+
+
+def kvsall_pairs_loss(Q, E, queries, label_smoothing=0.0):
+    """The mean binary cross-entropy of the scores Q E^T (float32 [m, H] and [N, H] on the device) against the
+    label-smoothed multi-hot target of `queries` (a `KvsAllQueries` with m queries over N nodes, on the same device):
+    `F.binary_cross_entropy_with_logits(Q @ E.T, (1 - eps) Y + eps / N)` as a float32 device scalar carrying autograd
+    to Q and E, without the [m, N] matrices (csrc/lp_kvsall.hip); never synchronises.  Shapes the kernels do not take —
+    H % 4 != 0, H > 256, rows not 16-byte aligned — materialise both (`stats()["lp.decoder.kvsall.fallback"]`)."""
+    import torch.nn.functional as F
+    eps = _smoothing(label_smoothing, "kvsall_pairs_loss")
+    Q, E = _f32_rows(Q, "Q"), _f32_rows(E, "E")
+    if not isinstance(queries, KvsAllQueries):
+        raise _lib.MrgcnError("kvsall_pairs_loss: queries is a KvsAllQueries")
+    if Q.shape[1] != E.shape[1] or Q.shape[0] != queries.m or E.shape[0] != queries.num_nodes \
+            or queries.device != E.device:
+        raise _lib.MrgcnError("kvsall_pairs_loss: Q [m, H], E [N, H] and the kvsall queries' m, num_nodes and device")
+    if not _kvsall_supported(_lib.load(), Q, E):
+        bump("lp.decoder.kvsall.fallback")
+        N = E.shape[0]
+        Y = torch.full((queries.m, N), eps / N, dtype=torch.float32, device=E.device)
+        Y[queries.rows, queries.idx.long()] = (1.0 - eps) + eps / N
+        # (the m N terms added in float64 and rounded once, as the kernels' loss is)
+        terms = F.binary_cross_entropy_with_logits(Q @ E.t(), Y, reduction="none")
+        return (terms.sum(dtype=torch.float64) / (float(queries.m) * float(N))).float()
+    return _KvsAllLoss.apply(Q, E, queries, eps)
+
+
+def kvsall_loss(queries, node_embeddings, edge_embeddings, label_smoothing=0.0, scorer="distmult"):
+    """The KvsAll loss of a fact set's `KvsAllQueries`: every distinct (s, p, ?) query — and (?, p, o) query, by the
+    queries' side — scored against ALL rows of `node_embeddings`, all known answers of the query positives, the target
+    smoothed to (1 - label_smoothing) Y + label_smoothing / N, the binary cross-entropy averaged over all m N scores
+    (`kvsall_pairs_loss`).  A float32 device scalar carrying autograd to both embedding tensors; never synchronises, so
+    a hipGraph captures it.  `scorer`: "distmult" or "complex" — the query vectors are `pair_vectors` of the queries'
+    representative facts, the tail queries' then the head queries'; the kernels do not know the scorer."""
+    _scorer(scorer, "kvsall_loss")
+    eps = _smoothing(label_smoothing, "kvsall_loss")
+    if not isinstance(queries, KvsAllQueries):
+        raise _lib.MrgcnError("kvsall_loss: queries is a KvsAllQueries (the kvsall decoder scores distinct queries, not "
+                              "facts)")
+    E = _f32_rows(node_embeddings, "node_embeddings")
+    Rel = _f32_rows(edge_embeddings, "edge_embeddings")
+    if queries.num_nodes != E.shape[0] or queries.num_relations > Rel.shape[0]:
+        raise _lib.MrgcnError("kvsall_loss: the kvsall queries were built for other num_nodes / num_relations")
+    bump("lp.decoder.kvsall")
+    mt, q = queries.m_tail, []
+    if mt:
+        q.append(pair_vectors(queries.reps[:mt], E, Rel, "tail", scorer)[0])
+    if mt < queries.m:
+        q.append(pair_vectors(queries.reps[mt:], E, Rel, "head", scorer)[0])
+    return kvsall_pairs_loss(q[0] if len(q) == 1 else torch.cat(q, 0), E, queries, eps)
+
+
+def _kvsall_queries_of(holder, facts, num_nodes, num_relations, device):
+    """The `KvsAllQueries` of the loops' facts, built on first use outside a stream capture and kept on `holder` — the
+    sampler of a full-batch loop (beside `_static`), a batch's device state in the mini-batch loops."""
+    get = holder.get if isinstance(holder, dict) else lambda k: getattr(holder, k, None)
+    kept = get("_kvsall")
+    if kept is not None and kept[0] is facts and (kept[1].num_nodes, kept[1].num_relations) == (num_nodes, num_relations):
+        return kept[1]
+    if torch.cuda.is_current_stream_capturing():
+        raise _lib.MrgcnError("decoder='kvsall': the facts' queries are built on first use, outside a stream capture")
+    kept = (facts, KvsAllQueries(facts, num_nodes, num_relations, "both", device=device))
+    if isinstance(holder, dict):
+        holder["_kvsall"] = kept
+    else:
+        holder._kvsall = kept
+    return kept[1]
+
+
+def _decoder_args(decoder, loss, pos_weight, samplers, who, scorer="distmult", label_smoothing=0.0):
+    """The run loops' `decoder` / `loss` / `pos_weight` / `scorer` / `label_smoothing` keywords, checked before any
+    kernel is touched -> (grouped?, loss, pos_weight as a host float or None)."""
     cx = _scorer(scorer, who)
+    eps = _smoothing(label_smoothing, who)
+    if decoder == "kvsall":
+        if loss == "softmax":
+            raise _lib.MrgcnError(f"{who}: decoder='kvsall' is the multi-hot binary cross-entropy: it takes loss='bce' "
+                                  "(a KL / softmax form of kvsall is not built)")
+        if loss != "bce":
+            raise _lib.MrgcnError(f"{who}: decoder='kvsall' takes loss='bce', not {loss!r}")
+        if pos_weight is not None:
+            raise _lib.MrgcnError(f"{who}: pos_weight is not built for decoder='kvsall'")
+        for smp in samplers:
+            _all_facts(smp, None, who, "kvsall")
+        return False, "bce", None
+    if eps != 0.0:
+        raise _lib.MrgcnError(f"{who}: label_smoothing belongs to decoder='kvsall', not to decoder={decoder!r}")
     if decoder not in ("triples", "grouped", "all"):
         raise _lib.MrgcnError(f"{who}: decoder is 'triples', 'grouped' or 'all', not {decoder!r}")
     if decoder == "all":
@@ -748,13 +907,18 @@ def _sampler_static(sampler, num_nodes, num_relations):
 
 
 def _decoder_loss(triples, labels, E, Rel, static, sampler=None, decoder="triples", loss="bce", pos_weight=None,
-                  scorer="distmult"):
+                  scorer="distmult", label_smoothing=0.0, holder=None):
     """The decoder line of every step and run loop: the flat BCE of `score_distmult_bc` (`scorer="complex"`: of
     `score_complex_bc`), or the grouped loss over `sampler`'s groups (`static` None: the sampler's own stored
     orders), or — `decoder="all"`, `triples` then the facts alone — the 1-vs-all softmax cross-entropy on both sides
-    (`all_loss`)."""
+    (`all_loss`), or — `decoder="kvsall"`, `triples` again the facts — the KvsAll loss of their distinct queries
+    (`kvsall_loss`; the queries are kept on `holder`, None: on the sampler)."""
     if decoder == "all":
         return all_loss(triples, E, Rel, side="both", scorer=scorer)
+    if decoder == "kvsall":
+        kq = _kvsall_queries_of(sampler if holder is None else holder, triples, int(E.shape[0]), int(Rel.shape[0]),
+                                E.device)
+        return kvsall_loss(kq, E, Rel, label_smoothing, scorer)
     if decoder != "grouped":
         score = score_complex_bc if scorer == "complex" else score_distmult_bc
         return binary_crossentropy(score(triples, E, Rel, static=static), labels)
@@ -1283,7 +1447,8 @@ def _penalised_backward_and_step(model, optimizer, loss, clip, l1_lambda, l2_lam
 
 
 def train_batch_step(model, batch, facts, optimizer, negatives=None, clip=1.0, slot=None, sampler=None,
-                     l1_lambda=0.0, l2_lambda=0.0, decoder="triples", loss="bce", pos_weight=None, scorer="distmult"):
+                     l1_lambda=0.0, l2_lambda=0.0, decoder="triples", loss="bce", pos_weight=None, scorer="distmult",
+                     label_smoothing=0.0):
     """One batch of train_model (link_prediction.py:226-331): 20 % of the batch's facts corrupted inside the batch
     (half the heads, half the tails replaced by batch nodes, :239-263) — drawn on the device, or `negatives` (an
     [n // 5, 3] array of batch-local triples, e.g. the reference's draws) —, DistMult scores of facts + negatives, BCE,
@@ -1301,10 +1466,14 @@ def train_batch_step(model, batch, facts, optimizer, negatives=None, clip=1.0, s
     place of the flat scores and BCE — `loss` "bce" (with `pos_weight`) or "softmax"; everything else unchanged.
     `scorer="complex"`: ComplEx scores (`score_complex_bc`) under the flat BCE; not with the grouped decoder.
     `decoder="all"` with `loss="softmax"`: the 1-vs-all softmax cross-entropy (`all_loss`) of the batch's facts —
-    `sampler.facts` when there is a sampler, which is not called — against the batch's own nodes, on both sides."""
+    `sampler.facts` when there is a sampler, which is not called — against the batch's own nodes, on both sides.
+    `decoder="kvsall"` (with `loss="bce"`, the default) and `label_smoothing`: the KvsAll loss (`kvsall_loss`) of the
+    distinct queries of those same facts, in batch-local ids, against the batch's own nodes; the `KvsAllQueries` are
+    built on the first step, outside a stream capture, and kept with the batch's device state."""
     from ..optim import clip_grad_norm_
     from ..train import ClipAdam
-    grouped, group_kind, pos_weight = _decoder_args(decoder, loss, pos_weight, [sampler], "train_batch_step", scorer)
+    grouped, group_kind, pos_weight = _decoder_args(decoder, loss, pos_weight, [sampler], "train_batch_step", scorer,
+                                                    label_smoothing)
     E = _embed(model, batch)
     st = _batch_state(batch, facts, E.device)
     if slot is not None and not (torch.is_tensor(slot) and slot.is_cuda and slot.dtype == torch.float32
@@ -1316,6 +1485,11 @@ def train_batch_step(model, batch, facts, optimizer, negatives=None, clip=1.0, s
         if negatives is not None:
             raise _lib.MrgcnError("train_batch_step: decoder='all' scores every node of the batch: it takes no negatives")
         triples, labels = _all_facts(sampler, st["facts"], "train_batch_step"), None
+    elif decoder == "kvsall":
+        if negatives is not None:
+            raise _lib.MrgcnError("train_batch_step: decoder='kvsall' scores every node of the batch: it takes no "
+                                  "negatives")
+        triples, labels = _all_facts(sampler, st["facts"], "train_batch_step", "kvsall"), None
     elif sampler is not None:
         triples, labels = sampler()
     elif negatives is None:
@@ -1327,7 +1501,7 @@ def train_batch_step(model, batch, facts, optimizer, negatives=None, clip=1.0, s
         labels[st["facts"].shape[0]:] = 0
     optimizer.zero_grad()
     loss = _decoder_loss(triples, labels, E, _relations(model), None, sampler, decoder, group_kind, pos_weight,
-                         scorer)
+                         scorer, label_smoothing, st)
     if l1_lambda > 0 or l2_lambda > 0:
         loss = _penalised_backward_and_step(model, optimizer, loss, clip, l1_lambda, l2_lambda)
     else:
@@ -1349,19 +1523,21 @@ def prepare_batches(batches, device):
 
 
 def train_epoch(batches, model, optimizer, clip=1.0, l1_lambda=0.0, l2_lambda=0.0, samplers=None, decoder="triples",
-                loss="bce", pos_weight=None, scorer="distmult"):
+                loss="bce", pos_weight=None, scorer="distmult", label_smoothing=0.0):
     """One epoch of train_model (:226-331): every batch once, in the fixed order of `mkbatches`; the mean of the batch
     losses (:326-331), read back once after the last step.  `l1_lambda` / `l2_lambda`: see `train_batch_step`.
     `samplers`: one sampler per batch (None: each batch's own `DeviceNegativeSampler`); `decoder` / `loss` /
-    `pos_weight` / `scorer`: see `train_batch_step` — the grouped decoder needs `NegativeSampler`s."""
+    `pos_weight` / `scorer` / `label_smoothing`: see `train_batch_step` — the grouped decoder needs
+    `NegativeSampler`s."""
     batches = list(batches)
     smps = list(samplers) if samplers is not None else [None] * len(batches)
     if len(smps) != len(batches):
         raise _lib.MrgcnError("train_epoch: one sampler per batch")
-    _decoder_args(decoder, loss, pos_weight, smps, "train_epoch", scorer)
+    _decoder_args(decoder, loss, pos_weight, smps, "train_epoch", scorer, label_smoothing)
     model.train()
     losses = [train_batch_step(model, batch, facts, optimizer, clip=clip, l1_lambda=l1_lambda, l2_lambda=l2_lambda,
-                               sampler=smp, decoder=decoder, loss=loss, pos_weight=pos_weight, scorer=scorer)
+                               sampler=smp, decoder=decoder, loss=loss, pos_weight=pos_weight, scorer=scorer,
+                               label_smoothing=label_smoothing)
               for (batch, facts), smp in zip(batches, smps)]
     return float(np.mean([float(x) for x in torch.stack(losses).cpu().numpy()])) if losses else float("nan")
 
@@ -2003,7 +2179,7 @@ def eval_schedule(nepoch, eval_interval, has_valid):
 
 
 def train_step(model, forward_fn, sampler, optimizer, static=None, clip=1.0, l1_lambda=0.0, l2_lambda=0.0,
-               decoder="triples", loss="bce", pos_weight=None, scorer="distmult"):
+               decoder="triples", loss="bce", pos_weight=None, scorer="distmult", label_smoothing=0.0):
     """One full-batch epoch of train_model (:231-326): `triples, labels = sampler()` (a `DeviceNegativeSampler`, or any
     callable that returns the facts followed by their corrupted copies and the 1 / 0 labels on the device without
     synchronising), `forward_fn()` for the node embeddings (e.g. `lambda: model(None, A)`), DistMult scores, BCE,
@@ -2016,19 +2192,27 @@ def train_step(model, forward_fn, sampler, optimizer, static=None, clip=1.0, l1_
     on first use outside a capture.  `scorer="complex"`: ComplEx scores (`score_complex_bc`) under the flat BCE; not
     with the grouped decoder.  `decoder="all"` with `loss="softmax"`: the 1-vs-all softmax cross-entropy (`all_loss`)
     of `sampler.facts` against every row of the embeddings, on both sides, with either scorer; the sampler is not
-    called and no negatives are drawn."""
+    called and no negatives are drawn.  `decoder="kvsall"` (with `loss="bce"`, the default) and `label_smoothing`: the
+    KvsAll loss (`kvsall_loss`) of the distinct (s, p, ?) and (?, p, o) queries of `sampler.facts`, all known answers
+    of a query positives, with either scorer; the sampler is not called, and the `KvsAllQueries` are built on the
+    first step, outside a stream capture, and kept on the sampler."""
     from ..optim import clip_grad_norm_
     from ..train import ClipAdam
-    _, group_kind, pos_weight = _decoder_args(decoder, loss, pos_weight, [sampler], "train_step", scorer)
+    _, group_kind, pos_weight = _decoder_args(decoder, loss, pos_weight, [sampler], "train_step", scorer,
+                                              label_smoothing)
     if decoder == "all":   # (the sampler is not called: no negatives are drawn)
         if sampler is None:
             raise _lib.MrgcnError("train_step: decoder='all' reads the facts from `sampler.facts`: pass a sampler")
         triples, labels = _all_facts(sampler, None, "train_step"), None
+    elif decoder == "kvsall":
+        if sampler is None:
+            raise _lib.MrgcnError("train_step: decoder='kvsall' reads the facts from `sampler.facts`: pass a sampler")
+        triples, labels = _all_facts(sampler, None, "train_step", "kvsall"), None
     else:
         triples, labels = sampler()
     emb = forward_fn()
     loss = _decoder_loss(triples, labels, emb, _relations(model), static, sampler, decoder, group_kind, pos_weight,
-                         scorer)
+                         scorer, label_smoothing)
     optimizer.zero_grad(set_to_none=True)
     if l1_lambda > 0 or l2_lambda > 0:
         return _penalised_backward_and_step(model, optimizer, loss, clip, l1_lambda, l2_lambda)
@@ -2056,11 +2240,12 @@ class FitEpochs:
 
     def __init__(self, model, forward_fn, tparts, vparts, optimizer, stopper=None, poll=8, graphed=True, sampler=None,
                  static=None, warmup=3, l1_lambda=0.0, l2_lambda=0.0, decoder="triples", loss="bce", pos_weight=None,
-                 scorer="distmult"):
+                 scorer="distmult", label_smoothing=0.0):
         from .. import functional as Fn
         from ..train import _COUNT_ONLY, _StopState
-        _, loss, pos_weight = _decoder_args(decoder, loss, pos_weight, [sampler], "fit", scorer)
-        self.decoder = dict(decoder=decoder, loss=loss, pos_weight=pos_weight, scorer=scorer)
+        _, loss, pos_weight = _decoder_args(decoder, loss, pos_weight, [sampler], "fit", scorer, label_smoothing)
+        self.decoder = dict(decoder=decoder, loss=loss, pos_weight=pos_weight, scorer=scorer,
+                            label_smoothing=float(label_smoothing))
         self.scorer = scorer
         dev = tparts.facts.device
         if stopper is not None and vparts is None:
@@ -2069,7 +2254,7 @@ class FitEpochs:
             raise _lib.MrgcnError("fit(graphed=True) needs ClipAdam(..., capturable=True)")
         if sampler is None:
             sampler = DeviceNegativeSampler(tparts.facts)
-            if static is None and decoder != "all":   # (the 1-vs-all decoder has no stored orders to walk)
+            if static is None and decoder not in ("all", "kvsall"):   # (those have no stored orders to walk)
                 was = model.training
                 model.eval()
                 with torch.no_grad():
@@ -2204,7 +2389,8 @@ def _run_schedule(run, sched, nepoch, poll, stopper):
 
 def fit(model, forward_fn, train_facts, valid_facts, optimizer, nepoch, eval_interval=1, mrr_batchsize=100,
         filter_ranks=True, early_stop=None, poll=8, graphed=True, sampler=None, warmup=3, static=None,
-        l1_lambda=0.0, l2_lambda=0.0, decoder="triples", loss="bce", pos_weight=None, scorer="distmult"):
+        l1_lambda=0.0, l2_lambda=0.0, decoder="triples", loss="bce", pos_weight=None, scorer="distmult",
+        label_smoothing=0.0):
     """The reference's full-batch link-prediction loop (train_model, link_prediction.py:191-373, with test_model
     :375-422) as a generator over its tuples `(epoch, loss, train_mrr, train_hits_at_k, valid_mrr, valid_hits_at_k)`
     — epochs from 1, `loss` a float, an mrr `{"raw", "flt"}`, hits `{"raw": [h@1, h@3, h@10], "flt": [...]}`, None
@@ -2220,6 +2406,8 @@ def fit(model, forward_fn, train_facts, valid_facts, optimizer, nepoch, eval_int
     ComplEx in place of DistMult, in the steps' flat BCE (eager and captured) and in both evaluations of an evaluating
     epoch; not with the grouped decoder.  `decoder="all"` with `loss="softmax"`: the 1-vs-all softmax cross-entropy
     (`all_loss`) of the training facts against all nodes in every step, with either scorer; no negatives are drawn.
+    `decoder="kvsall"` with `label_smoothing`: the KvsAll loss (`kvsall_loss`) of the training facts' distinct queries
+    in every step, with either scorer; the warm-up epochs of a capture build the `KvsAllQueries`.
 
     An epoch is one of two step functions, chosen on the host from the epoch number (no device read):
     a training epoch — `train_step`, its loss into a device ring — and an evaluating epoch — the same, then ONE
@@ -2241,14 +2429,14 @@ def fit(model, forward_fn, train_facts, valid_facts, optimizer, nepoch, eval_int
     Under `torch.use_deterministic_algorithms(True)` the step takes the deterministic decoder kernels; what is added
     here (ranks: integer counts; metrics: a fixed-order float64 sum; records) has no float atomics."""
     from ..train import _as_device_stopper
-    _decoder_args(decoder, loss, pos_weight, [sampler], "fit", scorer)
+    _decoder_args(decoder, loss, pos_weight, [sampler], "fit", scorer, label_smoothing)
     dev = next(model.parameters()).device
     nepoch, poll = int(nepoch), max(int(poll), 1)
     tparts = FactParts(train_facts, mrr_batchsize, filter_ranks, device=dev)
     vparts = FactParts(valid_facts, mrr_batchsize, filter_ranks, device=dev) if valid_facts is not None else None
     stopper = _as_device_stopper(early_stop, model, optimizer)
     run = FitEpochs(model, forward_fn, tparts, vparts, optimizer, stopper, poll, graphed, sampler, static, warmup,
-                    l1_lambda, l2_lambda, decoder, loss, pos_weight, scorer)
+                    l1_lambda, l2_lambda, decoder, loss, pos_weight, scorer, label_smoothing)
     sched = eval_schedule(nepoch, eval_interval, vparts is not None)
     yield from _run_schedule(run, sched, nepoch, poll, stopper)
 
@@ -2435,11 +2623,12 @@ class BatchFitEpochs:
 
     def __init__(self, model, train_batches, valid_batches, optimizer, stopper=None, poll=8, graphed=True,
                  filter_ranks=True, samplers=None, warmup=3, clip=1.0, l1_lambda=0.0, l2_lambda=0.0,
-                 decoder="triples", loss="bce", pos_weight=None, scorer="distmult"):
+                 decoder="triples", loss="bce", pos_weight=None, scorer="distmult", label_smoothing=0.0):
         from .. import functional as Fn
         from ..train import _COUNT_ONLY, _StopState
         _no_complex(scorer, "BatchFitEpochs")
-        _decoder_args(decoder, loss, pos_weight, [None] if samplers is None else [], "fit_batches")
+        _decoder_args(decoder, loss, pos_weight, [None] if samplers is None else [], "fit_batches",
+                      label_smoothing=label_smoothing)
         train_batches, valid_batches = list(train_batches), list(valid_batches or [])
         if not train_batches:
             raise _lib.MrgcnError("fit_batches: no training batches")
@@ -2456,8 +2645,9 @@ class BatchFitEpochs:
         self.filter_ranks, self.clip = bool(filter_ranks), clip
         self.l1_lambda, self.l2_lambda = float(l1_lambda), float(l2_lambda)
         self.samplers = [samplers(i, b, f) if samplers is not None else None for i, (b, f) in enumerate(train_batches)]
-        _, loss, pos_weight = _decoder_args(decoder, loss, pos_weight, self.samplers, "fit_batches")
-        self.decoder = dict(decoder=decoder, loss=loss, pos_weight=pos_weight)
+        _, loss, pos_weight = _decoder_args(decoder, loss, pos_weight, self.samplers, "fit_batches",
+                                            label_smoothing=label_smoothing)
+        self.decoder = dict(decoder=decoder, loss=loss, pos_weight=pos_weight, label_smoothing=float(label_smoothing))
         nt, nv = len(train_batches), len(valid_batches)
         self.loss_ctr = _StopState(dev, 1, 0.0, _COUNT_ONLY)   # counts every epoch
         self.eval_ctr = stopper.state if stopper is not None else _StopState(dev, 1, 0.0, _COUNT_ONLY)
@@ -2559,7 +2749,8 @@ class BatchFitEpochs:
 
 def fit_batches(model, train_batches, valid_batches, optimizer, nepoch, eval_interval=1, filter_ranks=True,
                 early_stop=None, poll=8, graphed=True, max_graph_batches=None, warmup=3, samplers=None,
-                l1_lambda=0.0, l2_lambda=0.0, decoder="triples", loss="bce", pos_weight=None, scorer="distmult"):
+                l1_lambda=0.0, l2_lambda=0.0, decoder="triples", loss="bce", pos_weight=None, scorer="distmult",
+                label_smoothing=0.0):
     """The reference's mini-batch link-prediction loop (train_model with gcn_batchsize > 0, link_prediction.py:224-373,
     with test_model :375-422) as a generator over its tuples `(epoch, loss, train_mrr, train_hits_at_k, valid_mrr,
     valid_hits_at_k)`, with `fit`'s contract row for row: the schedule (`eval_schedule`), the loss ring and the eval
@@ -2587,13 +2778,16 @@ def fit_batches(model, train_batches, valid_batches, optimizer, nepoch, eval_int
     e.g. `batch_negative_samplers`), `loss`, `pos_weight`: the grouped loss in every batch step (`group_loss`).
     `decoder="all"` with `loss="softmax"`: the 1-vs-all softmax cross-entropy (`all_loss`) of every batch's facts
     against that batch's own nodes; `samplers` may stay None, and a sampler that is given is not called.
+    `decoder="kvsall"` with `label_smoothing`: the KvsAll loss (`kvsall_loss`) of every batch's distinct queries against
+    that batch's own nodes, the `KvsAllQueries` built by the warm-up epochs (or the first eager epoch) per batch.
 
     Out of scope: literal-encoder batches inside a capture, the partitioned engines, and `scorer="complex"` (raises
     `MrgcnError`: the fused batch evaluation scores DistMult only)."""
     from ..train import _as_device_stopper
     from .node_classification import MAX_GRAPH_BATCHES, _is_fixed_structure
     _no_complex(scorer, "fit_batches")
-    _decoder_args(decoder, loss, pos_weight, [None] if samplers is None else [], "fit_batches")
+    _decoder_args(decoder, loss, pos_weight, [None] if samplers is None else [], "fit_batches",
+                  label_smoothing=label_smoothing)
     train_batches, valid_batches = list(train_batches), list(valid_batches or [])
     nepoch, poll = int(nepoch), max(int(poll), 1)
     if early_stop is not None and not valid_batches:
@@ -2606,6 +2800,6 @@ def fit_batches(model, train_batches, valid_batches, optimizer, nepoch, eval_int
     stopper = _as_device_stopper(early_stop, model, optimizer)
     run = BatchFitEpochs(model, train_batches, valid_batches, optimizer, stopper, poll, capture, filter_ranks, samplers,
                          warmup, l1_lambda=l1_lambda, l2_lambda=l2_lambda, decoder=decoder, loss=loss,
-                         pos_weight=pos_weight)
+                         pos_weight=pos_weight, label_smoothing=label_smoothing)
     sched = eval_schedule(nepoch, eval_interval, bool(valid_batches))
     yield from _run_schedule(run, sched, nepoch, poll, stopper)

@@ -120,6 +120,14 @@ python3 tools/lp_complex_probe.py --out $o/lp_complex_probe.json > $o/lp_complex
 # that fits, the replayed training epoch of fit with decoder="all" against decoder="grouped" at 10 negatives, the median
 # mini-batch's step; every leg in a child process under its own time limit
 python3 tools/lp_all_probe.py --out $o/lp_all_probe.json > $o/lp_all_probe.txt 2> $o/lp_all_probe.err
+# (10n') the KvsAll decoder at the FB15k-237 shape beside the 1-vs-all one in the same run (`all_loss` first and last):
+# kvsall_loss forward and backward with the queries' m, nnz and m / 2n, the kernels alone with their per-query ratio to
+# lp_all's, torch's materialised BCE where it fits with both peak memories, the replayed fit epoch with
+# decoder="kvsall" (label_smoothing 0 and 0.1) beside the untouched decoders, the median mini-batch's step.  The
+# untouched decoders' band is the PARENT commit's on the same box: check the parent out beside this tree, build it, copy
+# tools/lp_kvsall_probe.py into it and run `python3 tools/lp_kvsall_probe.py --legs epoch_untouched
+# batch_step_untouched --out <this tree>/profiles/lp_kvsall_probe_parent.json` there.
+python3 tools/lp_kvsall_probe.py --out $o/lp_kvsall_probe.json > $o/lp_kvsall_probe.txt 2> $o/lp_kvsall_probe.err
 # (10o) a block-diagonal hidden layer (200 -> 200, 40 blocks) at the FB15k-237 shape: its five passes alone, the layer on
 # the fused engine against the literal engine on the dense expansion (with peak memory), the replayed two-layer fit epoch
 python3 tools/block_layer_probe.py --out $o/block_layer_probe.json > $o/block_layer_probe.txt 2> $o/block_layer_probe.err
