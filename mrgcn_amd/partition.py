@@ -25,6 +25,7 @@ import os
 from . import functional as Fn
 from .layers.graph import GraphConvolution
 from .plan import GraphPlan
+from .train import _CapturedStep
 
 # MRGCN_PART_COMPACT_GATHER=0: the backward all-gather moves every row of the output gradient (A/B)
 _COMPACT_GATHER = os.environ.get("MRGCN_PART_COMPACT_GATHER", "1") != "0"
@@ -459,12 +460,14 @@ def partitioned_train_step(model: PartitionedRGCN, X_local, idx_global, targets,
     return total
 
 
-class GraphedPartitionedStep:
+class GraphedPartitionedStep(_CapturedStep):
     """`partitioned_train_step` captured into a hipGraph — local kernels AND the RCCL collectives between them — and
     replayed: at 8 ranks every rank's share of an AM-sized graph is launch-latency territory (AM/8 on one rank:
     1.85 ms eager, 1.58 ms replayed).  Needs the nccl backend (gloo's CPU-staged collectives cannot be captured),
     `ClipAdam(capturable=True)` and static shapes; the warm-up steps are real optimizer steps, as in
-    `train.GraphedTrainStep`.  Every rank must construct it (the capture runs the collectives' bookkeeping on all
+    `train.GraphedTrainStep`.  Captured and replayed through `train.Captured`, and so, like every other graphed step, a
+    replay raises `MrgcnError` when the optimizer's state was loaded after the capture and re-checks the pair-sum table
+    of a wide constant `X_local` that layer 0's dW reads.  Every rank must construct it (the capture runs the collectives' bookkeeping on all
     ranks alike).  Exercised with one rank over RCCL on the test box; never run on more than one GPU so far."""
 
     def __init__(self, model: PartitionedRGCN, X_local, idx_global, targets, optimizer, warmup: int = 3, row_sparse=None):
@@ -472,24 +475,10 @@ class GraphedPartitionedStep:
             raise RuntimeError("GraphedPartitionedStep needs ClipAdam(..., capturable=True)")
         if dist.is_initialized() and dist.get_backend(model.group) != "nccl":
             raise RuntimeError("GraphedPartitionedStep needs the nccl (RCCL) backend")
-        args = (model, X_local, idx_global, targets, optimizer, row_sparse)
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            for _ in range(max(warmup, 1)):
-                partitioned_train_step(*args)
-        torch.cuda.current_stream().wait_stream(side)
-        torch.cuda.synchronize()
-        self.graph = torch.cuda.CUDAGraph()
-        from .train import capture_without_gc
-        with capture_without_gc(), \
-                torch.cuda.graph(self.graph, stream=side, capture_error_mode="thread_local"):
-            self.loss = partitioned_train_step(*args)
-        self.warmup_steps = max(warmup, 1)
 
-    def __call__(self):
-        self.graph.replay()
-        return self.loss
+        def step():
+            return partitioned_train_step(model, X_local, idx_global, targets, optimizer, row_sparse)
+        self.loss = self._capture(step, warmup, optimizer)
 
 
 def partitioned_lp_step(model: PartitionedRGCN, X_local, triples, labels, optimizer):

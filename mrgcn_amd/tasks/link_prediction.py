@@ -10,6 +10,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+from typing import NamedTuple
 
 import numpy as np
 import torch
@@ -850,7 +851,10 @@ def _kvsall_queries_of(holder, facts, num_nodes, num_relations, device):
 
 def _decoder_args(decoder, loss, pos_weight, samplers, who, scorer="distmult", label_smoothing=0.0):
     """The run loops' `decoder` / `loss` / `pos_weight` / `scorer` / `label_smoothing` keywords, checked before any
-    kernel is touched -> (grouped?, loss, pos_weight as a host float or None)."""
+    kernel is touched -> the `_Decoder` they resolve to.  A `_Decoder` as `decoder` (a loop handing its record to the
+    epochs it builds) is taken as it is; the samplers are checked either way."""
+    if isinstance(decoder, _Decoder):
+        return decoder.checked(samplers, who)
     cx = _scorer(scorer, who)
     eps = _smoothing(label_smoothing, who)
     if decoder == "kvsall":
@@ -861,9 +865,7 @@ def _decoder_args(decoder, loss, pos_weight, samplers, who, scorer="distmult", l
             raise _lib.MrgcnError(f"{who}: decoder='kvsall' takes loss='bce', not {loss!r}")
         if pos_weight is not None:
             raise _lib.MrgcnError(f"{who}: pos_weight is not built for decoder='kvsall'")
-        for smp in samplers:
-            _all_facts(smp, None, who, "kvsall")
-        return False, "bce", None
+        return _Decoder("kvsall", "bce", None, scorer, eps).checked(samplers, who)
     if eps != 0.0:
         raise _lib.MrgcnError(f"{who}: label_smoothing belongs to decoder='kvsall', not to decoder={decoder!r}")
     if decoder not in ("triples", "grouped", "all"):
@@ -877,9 +879,7 @@ def _decoder_args(decoder, loss, pos_weight, samplers, who, scorer="distmult", l
         if pos_weight is not None:
             raise _lib.MrgcnError(f"{who}: pos_weight belongs to loss='bce' (the 1-vs-all softmax has no labels to "
                                   "weigh)")
-        for smp in samplers:
-            _all_facts(smp, None, who)
-        return False, "softmax", None
+        return _Decoder("all", "softmax", None, scorer, 0.0).checked(samplers, who)
     if cx and decoder == "grouped":
         raise _lib.MrgcnError(f"{who}: decoder='grouped' scores DistMult only: scorer='complex' takes the flat "
                               "decoder (decoder='triples')")
@@ -887,13 +887,9 @@ def _decoder_args(decoder, loss, pos_weight, samplers, who, scorer="distmult", l
         if loss != "bce" or pos_weight is not None:
             raise _lib.MrgcnError(f"{who}: loss={loss!r} / pos_weight need decoder='grouped' (the flat decoder has the "
                                   "plain BCE only)")
-        return False, "bce", None
+        return _Decoder("triples", "bce", None, scorer, 0.0).checked(samplers, who)
     _, w = _group_args(loss, pos_weight, who)
-    for smp in samplers:
-        if not isinstance(smp, NegativeSampler):
-            raise _lib.MrgcnError(f"{who}: decoder='grouped' takes NegativeSampler's layout (rate negatives behind "
-                                  f"every fact): pass NegativeSampler(s), not {type(smp).__name__}")
-    return True, loss, (None if pos_weight is None else w)
+    return _Decoder("grouped", loss, None if pos_weight is None else w, scorer, 0.0).checked(samplers, who)
 
 
 def _sampler_static(sampler, num_nodes, num_relations):
@@ -906,25 +902,67 @@ def _sampler_static(sampler, num_nodes, num_relations):
     return st
 
 
-def _decoder_loss(triples, labels, E, Rel, static, sampler=None, decoder="triples", loss="bce", pos_weight=None,
-                  scorer="distmult", label_smoothing=0.0, holder=None):
-    """The decoder line of every step and run loop: the flat BCE of `score_distmult_bc` (`scorer="complex"`: of
-    `score_complex_bc`), or the grouped loss over `sampler`'s groups (`static` None: the sampler's own stored
-    orders), or — `decoder="all"`, `triples` then the facts alone — the 1-vs-all softmax cross-entropy on both sides
-    (`all_loss`), or — `decoder="kvsall"`, `triples` again the facts — the KvsAll loss of their distinct queries
-    (`kvsall_loss`; the queries are kept on `holder`, None: on the sampler)."""
-    if decoder == "all":
-        return all_loss(triples, E, Rel, side="both", scorer=scorer)
-    if decoder == "kvsall":
-        kq = _kvsall_queries_of(sampler if holder is None else holder, triples, int(E.shape[0]), int(Rel.shape[0]),
-                                E.device)
-        return kvsall_loss(kq, E, Rel, label_smoothing, scorer)
-    if decoder != "grouped":
-        score = score_complex_bc if scorer == "complex" else score_distmult_bc
-        return binary_crossentropy(score(triples, E, Rel, static=static), labels)
-    if static is None:
-        static = _sampler_static(sampler, int(E.shape[0]), int(Rel.shape[0]))
-    return group_loss(triples, E, Rel, sampler.n, sampler.rate, loss=loss, pos_weight=pos_weight, static=static)
+class _Decoder(NamedTuple):
+    """The steps' and run loops' decoder keywords, resolved once by `_decoder_args`: `kind` ("triples", "grouped",
+    "all", "kvsall"), `loss` ("bce" / "softmax"), `pos_weight` (a host float or None), `scorer`, `label_smoothing`."""
+    kind: str
+    loss: str
+    pos_weight: "float | None"
+    scorer: str
+    label_smoothing: float
+
+    def checked(self, samplers, who):
+        """-> self, after what the decoder asks of the samplers it is given (None: a batch's own facts and draws)."""
+        for smp in samplers:
+            if self.kind in ("all", "kvsall"):
+                _all_facts(smp, None, who, self.kind)
+            elif self.kind == "grouped" and not isinstance(smp, NegativeSampler):
+                raise _lib.MrgcnError(f"{who}: decoder='grouped' takes NegativeSampler's layout (rate negatives behind "
+                                      f"every fact): pass NegativeSampler(s), not {type(smp).__name__}")
+        return self
+
+    def scored(self, sampler, who, st=None, negatives=None):
+        """What a step scores -> (triples, labels).  The `all` and `kvsall` decoders read the facts — `sampler.facts`,
+        else those of the batch's device state `st` — and do not call the sampler: no negatives are drawn, labels are
+        None.  The others call `sampler`, else the batch's own sampler, else append the caller's `negatives`."""
+        if self.kind in ("all", "kvsall"):
+            if negatives is not None:
+                raise _lib.MrgcnError(f"{who}: decoder={self.kind!r} scores every node of the batch: it takes no "
+                                      "negatives")
+            if sampler is None and st is None:
+                raise _lib.MrgcnError(f"{who}: decoder={self.kind!r} reads the facts from `sampler.facts`: pass a "
+                                      "sampler")
+            return _all_facts(sampler, None if st is None else st["facts"], who, self.kind), None
+        if sampler is not None or st is None:
+            return sampler()
+        if negatives is None:
+            return st["sampler"]()
+        facts = st["facts"]
+        neg = torch.as_tensor(np.asarray(negatives), dtype=torch.int64).to(facts.device)
+        triples = torch.cat([facts, neg.reshape(-1, 3)])
+        labels = torch.ones(triples.shape[0], dtype=torch.float32, device=facts.device)
+        labels[facts.shape[0]:] = 0
+        return triples, labels
+
+    def loss_of(self, triples, labels, E, Rel, static, sampler, holder=None):
+        """The decoder line of every step and run loop: the flat BCE of `score_distmult_bc` (`scorer="complex"`: of
+        `score_complex_bc`), or the grouped loss over `sampler`'s groups (`static` None: the sampler's own stored
+        orders), or — `all`, `triples` then the facts alone — the 1-vs-all softmax cross-entropy on both sides
+        (`all_loss`), or — `kvsall`, `triples` again the facts — the KvsAll loss of their distinct queries
+        (`kvsall_loss`; the queries are kept on `holder`, None: on the sampler)."""
+        if self.kind == "all":
+            return all_loss(triples, E, Rel, side="both", scorer=self.scorer)
+        if self.kind == "kvsall":
+            kq = _kvsall_queries_of(sampler if holder is None else holder, triples, int(E.shape[0]), int(Rel.shape[0]),
+                                    E.device)
+            return kvsall_loss(kq, E, Rel, self.label_smoothing, self.scorer)
+        if self.kind != "grouped":
+            score = score_complex_bc if self.scorer == "complex" else score_distmult_bc
+            return binary_crossentropy(score(triples, E, Rel, static=static), labels)
+        if static is None:
+            static = _sampler_static(sampler, int(E.shape[0]), int(Rel.shape[0]))
+        return group_loss(triples, E, Rel, sampler.n, sampler.rate, loss=self.loss, pos_weight=self.pos_weight,
+                          static=static)
 
 
 def sample_negatives(batch_data: np.ndarray, rng=np.random):
@@ -1446,6 +1484,20 @@ def _penalised_backward_and_step(model, optimizer, loss, clip, l1_lambda, l2_lam
     return loss.detach() if optimizer.reg_loss is None else loss.detach() + optimizer.reg_loss
 
 
+def _backward_and_step(model, optimizer, loss, clip, l1_lambda, l2_lambda):
+    """The tail of every step: backward, the gradient clipped at `clip` (inside the step of a `ClipAdam` that has a
+    `max_norm`, by `clip_grad_norm_` otherwise), the optimizer step -> the loss (with its penalty) as a device scalar."""
+    from ..optim import clip_grad_norm_
+    from ..train import ClipAdam
+    if l1_lambda > 0 or l2_lambda > 0:
+        return _penalised_backward_and_step(model, optimizer, loss, clip, l1_lambda, l2_lambda)
+    loss.backward()
+    if not (isinstance(optimizer, ClipAdam) and optimizer.max_norm is not None):
+        clip_grad_norm_(model.parameters(), clip)
+    optimizer.step()
+    return loss.detach()
+
+
 def train_batch_step(model, batch, facts, optimizer, negatives=None, clip=1.0, slot=None, sampler=None,
                      l1_lambda=0.0, l2_lambda=0.0, decoder="triples", loss="bce", pos_weight=None, scorer="distmult",
                      label_smoothing=0.0):
@@ -1470,46 +1522,24 @@ def train_batch_step(model, batch, facts, optimizer, negatives=None, clip=1.0, s
     `decoder="kvsall"` (with `loss="bce"`, the default) and `label_smoothing`: the KvsAll loss (`kvsall_loss`) of the
     distinct queries of those same facts, in batch-local ids, against the batch's own nodes; the `KvsAllQueries` are
     built on the first step, outside a stream capture, and kept with the batch's device state."""
-    from ..optim import clip_grad_norm_
-    from ..train import ClipAdam
-    grouped, group_kind, pos_weight = _decoder_args(decoder, loss, pos_weight, [sampler], "train_batch_step", scorer,
-                                                    label_smoothing)
+    dec = _decoder_args(decoder, loss, pos_weight, [sampler], "train_batch_step", scorer, label_smoothing)
+    return _train_batch_step(model, batch, facts, optimizer, negatives, clip, slot, sampler, l1_lambda, l2_lambda, dec)
+
+
+def _train_batch_step(model, batch, facts, optimizer, negatives, clip, slot, sampler, l1_lambda, l2_lambda, dec):
+    """`train_batch_step` behind its keyword checks, on the resolved `_Decoder`."""
+    who = "train_batch_step"
     E = _embed(model, batch)
     st = _batch_state(batch, facts, E.device)
     if slot is not None and not (torch.is_tensor(slot) and slot.is_cuda and slot.dtype == torch.float32
                                  and slot.numel() == 1):
-        raise _lib.MrgcnError("train_batch_step: slot is one float32 on the device")
+        raise _lib.MrgcnError(f"{who}: slot is one float32 on the device")
     if negatives is not None and sampler is not None:
-        raise _lib.MrgcnError("train_batch_step: negatives or a sampler, not both")
-    if decoder == "all":
-        if negatives is not None:
-            raise _lib.MrgcnError("train_batch_step: decoder='all' scores every node of the batch: it takes no negatives")
-        triples, labels = _all_facts(sampler, st["facts"], "train_batch_step"), None
-    elif decoder == "kvsall":
-        if negatives is not None:
-            raise _lib.MrgcnError("train_batch_step: decoder='kvsall' scores every node of the batch: it takes no "
-                                  "negatives")
-        triples, labels = _all_facts(sampler, st["facts"], "train_batch_step", "kvsall"), None
-    elif sampler is not None:
-        triples, labels = sampler()
-    elif negatives is None:
-        triples, labels = st["sampler"]()
-    else:
-        neg = torch.as_tensor(np.asarray(negatives), dtype=torch.int64).to(E.device)
-        triples = torch.cat([st["facts"], neg.reshape(-1, 3)])
-        labels = torch.ones(triples.shape[0], dtype=torch.float32, device=E.device)
-        labels[st["facts"].shape[0]:] = 0
+        raise _lib.MrgcnError(f"{who}: negatives or a sampler, not both")
+    triples, labels = dec.scored(sampler, who, st, negatives)
     optimizer.zero_grad()
-    loss = _decoder_loss(triples, labels, E, _relations(model), None, sampler, decoder, group_kind, pos_weight,
-                         scorer, label_smoothing, st)
-    if l1_lambda > 0 or l2_lambda > 0:
-        loss = _penalised_backward_and_step(model, optimizer, loss, clip, l1_lambda, l2_lambda)
-    else:
-        loss.backward()
-        if not (isinstance(optimizer, ClipAdam) and optimizer.max_norm is not None):
-            clip_grad_norm_(model.parameters(), clip)
-        optimizer.step()
-        loss = loss.detach()
+    loss = dec.loss_of(triples, labels, E, _relations(model), None, sampler, st)
+    loss = _backward_and_step(model, optimizer, loss, clip, l1_lambda, l2_lambda)
     if slot is not None:
         slot.view(1).copy_(loss.view(1))
     return loss
@@ -1533,11 +1563,9 @@ def train_epoch(batches, model, optimizer, clip=1.0, l1_lambda=0.0, l2_lambda=0.
     smps = list(samplers) if samplers is not None else [None] * len(batches)
     if len(smps) != len(batches):
         raise _lib.MrgcnError("train_epoch: one sampler per batch")
-    _decoder_args(decoder, loss, pos_weight, smps, "train_epoch", scorer, label_smoothing)
+    dec = _decoder_args(decoder, loss, pos_weight, smps, "train_epoch", scorer, label_smoothing)
     model.train()
-    losses = [train_batch_step(model, batch, facts, optimizer, clip=clip, l1_lambda=l1_lambda, l2_lambda=l2_lambda,
-                               sampler=smp, decoder=decoder, loss=loss, pos_weight=pos_weight, scorer=scorer,
-                               label_smoothing=label_smoothing)
+    losses = [_train_batch_step(model, batch, facts, optimizer, None, clip, None, smp, l1_lambda, l2_lambda, dec)
               for (batch, facts), smp in zip(batches, smps)]
     return float(np.mean([float(x) for x in torch.stack(losses).cpu().numpy()])) if losses else float("nan")
 
@@ -2196,31 +2224,17 @@ def train_step(model, forward_fn, sampler, optimizer, static=None, clip=1.0, l1_
     KvsAll loss (`kvsall_loss`) of the distinct (s, p, ?) and (?, p, o) queries of `sampler.facts`, all known answers
     of a query positives, with either scorer; the sampler is not called, and the `KvsAllQueries` are built on the
     first step, outside a stream capture, and kept on the sampler."""
-    from ..optim import clip_grad_norm_
-    from ..train import ClipAdam
-    _, group_kind, pos_weight = _decoder_args(decoder, loss, pos_weight, [sampler], "train_step", scorer,
-                                              label_smoothing)
-    if decoder == "all":   # (the sampler is not called: no negatives are drawn)
-        if sampler is None:
-            raise _lib.MrgcnError("train_step: decoder='all' reads the facts from `sampler.facts`: pass a sampler")
-        triples, labels = _all_facts(sampler, None, "train_step"), None
-    elif decoder == "kvsall":
-        if sampler is None:
-            raise _lib.MrgcnError("train_step: decoder='kvsall' reads the facts from `sampler.facts`: pass a sampler")
-        triples, labels = _all_facts(sampler, None, "train_step", "kvsall"), None
-    else:
-        triples, labels = sampler()
+    dec = _decoder_args(decoder, loss, pos_weight, [sampler], "train_step", scorer, label_smoothing)
+    return _train_step(model, forward_fn, sampler, optimizer, static, clip, l1_lambda, l2_lambda, dec)
+
+
+def _train_step(model, forward_fn, sampler, optimizer, static, clip, l1_lambda, l2_lambda, dec):
+    """`train_step` behind its keyword checks, on the resolved `_Decoder`."""
+    triples, labels = dec.scored(sampler, "train_step")
     emb = forward_fn()
-    loss = _decoder_loss(triples, labels, emb, _relations(model), static, sampler, decoder, group_kind, pos_weight,
-                         scorer, label_smoothing)
+    loss = dec.loss_of(triples, labels, emb, _relations(model), static, sampler)
     optimizer.zero_grad(set_to_none=True)
-    if l1_lambda > 0 or l2_lambda > 0:
-        return _penalised_backward_and_step(model, optimizer, loss, clip, l1_lambda, l2_lambda)
-    loss.backward()
-    if not (isinstance(optimizer, ClipAdam) and optimizer.max_norm is not None):
-        clip_grad_norm_(model.parameters(), clip)
-    optimizer.step()
-    return loss.detach()
+    return _backward_and_step(model, optimizer, loss, clip, l1_lambda, l2_lambda)
 
 
 def _unpack(vec):
@@ -2229,32 +2243,78 @@ def _unpack(vec):
     return {"raw": v[0], "flt": v[4]}, {"raw": v[1:4], "flt": v[5:8]}
 
 
-class FitEpochs:
+class _Epochs:
+    """What `FitEpochs` and `BatchFitEpochs` share: the counters (`loss_ctr` counts every epoch, `eval_ctr` the
+    records), the rings of `poll` rows, `row` and `score`, `reset()`, and `train_epoch()` / `eval_epoch()`, which run
+    the subclass's `_train_epoch` / `_eval_epoch` — eagerly, or as a replay of the one captured hipGraph each is
+    (`train.Captured`, the discipline of DESIGN §13: the `warmup` epochs of the capture are real optimizer steps, the
+    last of them an evaluating epoch, after which the counters and rings are reset).  Subclasses also supply
+    `last_epoch`."""
+    _stats = None   # the stats() keys of a training and an evaluating epoch, counted as `.graphed` or `.eager`
+
+    def _tables(self, dev, stopper, poll):
+        from ..train import _COUNT_ONLY, _StopState
+        self.loss_ctr = _StopState(dev, 1, 0.0, _COUNT_ONLY)   # counts every epoch
+        self.eval_ctr = stopper.state if stopper is not None else _StopState(dev, 1, 0.0, _COUNT_ONLY)
+        self.loss_ring = torch.zeros((poll, 4), dtype=torch.float32, device=dev)
+        self.eval_ring = torch.zeros((poll, EVAL_ROW), dtype=torch.float32, device=dev)
+        self.row = torch.zeros(EVAL_ROW, dtype=torch.float32, device=dev)
+        self.score = torch.zeros((), dtype=torch.float32, device=dev)
+
+    def _start(self, graphed, warmup, optimizer, who):
+        from ..train import Captured
+        self.graphed = bool(graphed)
+        if not graphed:
+            self.reset()
+            return
+        nw = self.warmup_steps = max(int(warmup), 1)
+
+        def warm():
+            for _ in range(nw - 1):
+                self._train_epoch()
+            self._eval_epoch()
+            self.reset()
+        self._captured = Captured((self._train_epoch, self._eval_epoch), warm, optimizer, who)
+
+    def reset(self):
+        self.loss_ctr.reset()
+        self.eval_ctr.reset()
+        self.loss_ring.zero_()
+        self.eval_ring.zero_()
+
+    def _epoch(self, i):
+        out = self._captured.replay(i) if self.graphed else (self._train_epoch, self._eval_epoch)[i]()
+        if self._stats is not None:
+            bump(f"{self._stats[i]}.{'graphed' if self.graphed else 'eager'}")
+        return out
+
+    def train_epoch(self):
+        return self._epoch(0)
+
+    def eval_epoch(self):
+        return self._epoch(1)
+
+
+class FitEpochs(_Epochs):
     """The two epochs `fit` is made of, as callables on one set of device rings (see `fit` for what they do):
     `train_epoch()` — `train_step`, its loss into row `epochs % poll` of `loss_ring` — and `eval_epoch()` — the same,
     then one `eval()` forward, `evaluate_facts` of the training and the validation parts, the `EVAL_ROW` values into row
     `records % poll` of `eval_ring` by the early-stop record, the snapshot behind its flag — and `last_epoch()`:
     a training epoch, then the training metrics into `last`, eagerly.  `graphed=True`: the first two are one captured
-    hipGraph each, a single chain on the capture stream; the `warmup` epochs of the capture are real optimizer steps
-    (the last of them an evaluating epoch), after which the counters and rings are reset."""
+    hipGraph each (`_Epochs`)."""
 
     def __init__(self, model, forward_fn, tparts, vparts, optimizer, stopper=None, poll=8, graphed=True, sampler=None,
                  static=None, warmup=3, l1_lambda=0.0, l2_lambda=0.0, decoder="triples", loss="bce", pos_weight=None,
                  scorer="distmult", label_smoothing=0.0):
-        from .. import functional as Fn
-        from ..train import _COUNT_ONLY, _StopState
-        _, loss, pos_weight = _decoder_args(decoder, loss, pos_weight, [sampler], "fit", scorer, label_smoothing)
-        self.decoder = dict(decoder=decoder, loss=loss, pos_weight=pos_weight, scorer=scorer,
-                            label_smoothing=float(label_smoothing))
-        self.scorer = scorer
-        dev = tparts.facts.device
+        self.dec = dec = _decoder_args(decoder, loss, pos_weight, [sampler], "fit", scorer, label_smoothing)
         if stopper is not None and vparts is None:
             raise _lib.MrgcnError("fit: early stopping scores the validation MRR: pass valid_facts")
         if graphed and not getattr(optimizer, "capturable", False):
             raise _lib.MrgcnError("fit(graphed=True) needs ClipAdam(..., capturable=True)")
+        dev = tparts.facts.device
         if sampler is None:
             sampler = DeviceNegativeSampler(tparts.facts)
-            if static is None and decoder not in ("all", "kvsall"):   # (those have no stored orders to walk)
+            if static is None and dec.kind not in ("all", "kvsall"):   # (those have no stored orders to walk)
                 was = model.training
                 model.eval()
                 with torch.no_grad():
@@ -2264,59 +2324,14 @@ class FitEpochs:
         self.model, self.forward_fn, self.tparts, self.vparts = model, forward_fn, tparts, vparts
         self.optimizer, self.stopper, self.sampler, self.static, self.poll = optimizer, stopper, sampler, static, poll
         self.l1_lambda, self.l2_lambda = float(l1_lambda), float(l2_lambda)
-        self.loss_ctr = _StopState(dev, 1, 0.0, _COUNT_ONLY)   # counts every epoch
-        self.eval_ctr = stopper.state if stopper is not None else _StopState(dev, 1, 0.0, _COUNT_ONLY)
-        self.loss_ring = torch.zeros((poll, 4), dtype=torch.float32, device=dev)
-        self.eval_ring = torch.zeros((poll, EVAL_ROW), dtype=torch.float32, device=dev)
-        self.row = torch.zeros(EVAL_ROW, dtype=torch.float32, device=dev)
-        self.score = torch.zeros((), dtype=torch.float32, device=dev)
+        self._tables(dev, stopper, poll)
         self.last = torch.zeros(8, dtype=torch.float32, device=dev)
-        self.train_epoch, self.eval_epoch = self._train_epoch, self._eval_epoch
-        if not graphed:
-            self.reset()
-            return
-        nw = max(int(warmup), 1)
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            for _ in range(nw - 1):
-                self._train_epoch()
-            self._eval_epoch()
-            self.reset()
-        torch.cuda.current_stream().wait_stream(side)
-        torch.cuda.synchronize()
-        self.warmup_steps = nw
-        self._graphs, self._pair_sums = [], []
-        for fn in (self._train_epoch, self._eval_epoch):
-            g = torch.cuda.CUDAGraph()
-            Fn.take_captured_pair_sums()
-            from ..train import capture_without_gc
-            with capture_without_gc(), \
-                    torch.cuda.graph(g, stream=side, capture_error_mode="thread_local"):
-                fn()
-            self._pair_sums.append(Fn.take_captured_pair_sums())
-            self._graphs.append(g)
-        self._state_gen = optimizer._state_gen
-        self.train_epoch, self.eval_epoch = (lambda: self._replay(0)), (lambda: self._replay(1))
-
-    def reset(self):
-        self.loss_ctr.reset()
-        self.eval_ctr.reset()
-        self.loss_ring.zero_()
-        self.eval_ring.zero_()
-
-    def _replay(self, i):
-        if self.optimizer._state_gen != self._state_gen:
-            raise _lib.MrgcnError("fit: the optimizer's state was loaded after the capture (the captured graphs still "
-                                  "update the old moment buffers)")
-        for sup in self._pair_sums[i]:
-            sup.pair_sums_refresh()
-        self._graphs[i].replay()
+        self._start(graphed, warmup, optimizer, "fit")
 
     def _train_epoch(self):
         self.model.train()
-        loss = train_step(self.model, self.forward_fn, self.sampler, self.optimizer, self.static,
-                          l1_lambda=self.l1_lambda, l2_lambda=self.l2_lambda, **self.decoder)
+        loss = _train_step(self.model, self.forward_fn, self.sampler, self.optimizer, self.static, 1.0,
+                           self.l1_lambda, self.l2_lambda, self.dec)
         self.loss_ctr.record(loss, self.loss_ring, (loss,))
         return loss
 
@@ -2324,7 +2339,7 @@ class FitEpochs:
         self.model.eval()
         with torch.no_grad():
             E, Rel = self.forward_fn(), _relations(self.model)
-            evaluate_facts(E, Rel, self.tparts, out=out, scorer=self.scorer)
+            evaluate_facts(E, Rel, self.tparts, out=out, scorer=self.dec.scorer)
         return E, Rel
 
     def _eval_epoch(self):
@@ -2333,7 +2348,7 @@ class FitEpochs:
         try:
             E, Rel = self._evaluate_train(self.row[1:9])
             if self.vparts is not None:   # (against the same embeddings)
-                evaluate_facts(E, Rel, self.vparts, out=self.row[9:17], score=self.score, scorer=self.scorer)
+                evaluate_facts(E, Rel, self.vparts, out=self.row[9:17], score=self.score, scorer=self.dec.scorer)
         finally:
             self.model.train()
         (self.stopper if self.stopper is not None else self.eval_ctr).record_row(self.score, self.row, self.eval_ring)
@@ -2429,14 +2444,14 @@ def fit(model, forward_fn, train_facts, valid_facts, optimizer, nepoch, eval_int
     Under `torch.use_deterministic_algorithms(True)` the step takes the deterministic decoder kernels; what is added
     here (ranks: integer counts; metrics: a fixed-order float64 sum; records) has no float atomics."""
     from ..train import _as_device_stopper
-    _decoder_args(decoder, loss, pos_weight, [sampler], "fit", scorer, label_smoothing)
+    dec = _decoder_args(decoder, loss, pos_weight, [sampler], "fit", scorer, label_smoothing)
     dev = next(model.parameters()).device
     nepoch, poll = int(nepoch), max(int(poll), 1)
     tparts = FactParts(train_facts, mrr_batchsize, filter_ranks, device=dev)
     vparts = FactParts(valid_facts, mrr_batchsize, filter_ranks, device=dev) if valid_facts is not None else None
     stopper = _as_device_stopper(early_stop, model, optimizer)
     run = FitEpochs(model, forward_fn, tparts, vparts, optimizer, stopper, poll, graphed, sampler, static, warmup,
-                    l1_lambda, l2_lambda, decoder, loss, pos_weight, scorer, label_smoothing)
+                    l1_lambda, l2_lambda, dec)
     sched = eval_schedule(nepoch, eval_interval, vparts is not None)
     yield from _run_schedule(run, sched, nepoch, poll, stopper)
 
@@ -2610,25 +2625,22 @@ def rank_batches(model, batches, filtered=True, scorer="distmult"):
     return mrr, hits_at_k, rankings
 
 
-class BatchFitEpochs:
+class BatchFitEpochs(_Epochs):
     """The epochs `fit_batches` is made of, as callables on one set of device tables (see `fit_batches` for what they
     do): `train_epoch()` — every training batch in order (`train_batch_step`, its loss into slot i), the mean of the
     slots into row `epochs % poll` of `loss_ring` —, `eval_epoch()` — the same, then `eval_batches` of the training
     batches and of the validation batches, the `EVAL_ROW` means into row `records % poll` of `eval_ring` by the
     early-stop record, the snapshot behind its flag — and `last_epoch()`: a training epoch, then the training metrics
-    into `last`, eagerly.  `graphed=True`: the first two are one captured hipGraph each, under `GraphedBatchEpoch`'s
-    discipline — `warmup` real epochs on the capture stream (the last of them an evaluating one), `thread_local`
-    capture, a single chain on the one stream, counters and rings reset after the warm-up, the optimizer's
-    `_state_gen` compared and the supports' pair-sum tables refreshed in front of every replay."""
+    into `last`, eagerly.  `graphed=True`: the first two are one captured hipGraph each (`_Epochs`).  The epochs are
+    counted in `stats()` (`lp.batch_epoch.*`, `lp.batch_eval_epoch.*`)."""
+    _stats = ("lp.batch_epoch", "lp.batch_eval_epoch")
 
     def __init__(self, model, train_batches, valid_batches, optimizer, stopper=None, poll=8, graphed=True,
                  filter_ranks=True, samplers=None, warmup=3, clip=1.0, l1_lambda=0.0, l2_lambda=0.0,
                  decoder="triples", loss="bce", pos_weight=None, scorer="distmult", label_smoothing=0.0):
-        from .. import functional as Fn
-        from ..train import _COUNT_ONLY, _StopState
         _no_complex(scorer, "BatchFitEpochs")
-        _decoder_args(decoder, loss, pos_weight, [None] if samplers is None else [], "fit_batches",
-                      label_smoothing=label_smoothing)
+        dec = _decoder_args(decoder, loss, pos_weight, [None] if samplers is None else [], "fit_batches",
+                            label_smoothing=label_smoothing)
         train_batches, valid_batches = list(train_batches), list(valid_batches or [])
         if not train_batches:
             raise _lib.MrgcnError("fit_batches: no training batches")
@@ -2645,68 +2657,21 @@ class BatchFitEpochs:
         self.filter_ranks, self.clip = bool(filter_ranks), clip
         self.l1_lambda, self.l2_lambda = float(l1_lambda), float(l2_lambda)
         self.samplers = [samplers(i, b, f) if samplers is not None else None for i, (b, f) in enumerate(train_batches)]
-        _, loss, pos_weight = _decoder_args(decoder, loss, pos_weight, self.samplers, "fit_batches",
-                                            label_smoothing=label_smoothing)
-        self.decoder = dict(decoder=decoder, loss=loss, pos_weight=pos_weight, label_smoothing=float(label_smoothing))
+        self.dec = dec.checked(self.samplers, "fit_batches")
         nt, nv = len(train_batches), len(valid_batches)
-        self.loss_ctr = _StopState(dev, 1, 0.0, _COUNT_ONLY)   # counts every epoch
-        self.eval_ctr = stopper.state if stopper is not None else _StopState(dev, 1, 0.0, _COUNT_ONLY)
-        self.loss_ring = torch.zeros((poll, 4), dtype=torch.float32, device=dev)
-        self.eval_ring = torch.zeros((poll, EVAL_ROW), dtype=torch.float32, device=dev)
+        self._tables(dev, stopper, poll)
         self.loss_slots = torch.zeros(nt, dtype=torch.float32, device=dev)
         self.train_slots = torch.zeros((nt, 8), dtype=torch.float32, device=dev)
         self.valid_slots = torch.zeros((max(nv, 1), 8), dtype=torch.float32, device=dev)
-        self.row = torch.zeros(EVAL_ROW, dtype=torch.float32, device=dev)
-        self.score = torch.zeros((), dtype=torch.float32, device=dev)
         self._last_row = torch.zeros(EVAL_ROW, dtype=torch.float32, device=dev)
         self.last = self._last_row[1:9]
-        self.graphed = bool(graphed)
-        if not graphed:
-            self.reset()
-            return
-        nw = max(int(warmup), 1)
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            for _ in range(nw - 1):
-                self._train_epoch()
-            self._eval_epoch()
-            self.reset()
-        torch.cuda.current_stream().wait_stream(side)
-        torch.cuda.synchronize()
-        self.warmup_steps = nw
-        self._graphs, self._pair_sums = [], []
-        for fn in (self._train_epoch, self._eval_epoch):
-            g = torch.cuda.CUDAGraph()
-            Fn.take_captured_pair_sums()
-            from ..train import capture_without_gc
-            with capture_without_gc(), \
-                    torch.cuda.graph(g, stream=side, capture_error_mode="thread_local"):
-                fn()
-            self._pair_sums.append(Fn.take_captured_pair_sums())
-            self._graphs.append(g)
-        self._state_gen = optimizer._state_gen
-
-    def reset(self):
-        self.loss_ctr.reset()
-        self.eval_ctr.reset()
-        self.loss_ring.zero_()
-        self.eval_ring.zero_()
-
-    def _replay(self, i):
-        if self.optimizer._state_gen != self._state_gen:
-            raise _lib.MrgcnError("fit_batches: the optimizer's state was loaded after the capture (the captured "
-                                  "graphs still update the old moment buffers)")
-        for sup in self._pair_sums[i]:
-            sup.pair_sums_refresh()
-        self._graphs[i].replay()
+        self._start(graphed, warmup, optimizer, "fit_batches")
 
     def _train_epoch(self):
         self.model.train()   # (:232)
         for i, (batch, facts) in enumerate(self.train_batches):
-            train_batch_step(self.model, batch, facts, self.optimizer, clip=self.clip, slot=self.loss_slots[i:i + 1],
-                             sampler=self.samplers[i], l1_lambda=self.l1_lambda, l2_lambda=self.l2_lambda,
-                             **self.decoder)
+            _train_batch_step(self.model, batch, facts, self.optimizer, None, self.clip, self.loss_slots[i:i + 1],
+                              self.samplers[i], self.l1_lambda, self.l2_lambda, self.dec)
         _lp_batch_means(self.loss_slots, len(self.train_batches), None, 0, None, 0, self.row)
         self.loss_ctr.record(self.row[0:1], self.loss_ring, (self.row[0:1],))
 
@@ -2721,22 +2686,6 @@ class BatchFitEpochs:
         finally:
             self.model.train()
         (self.stopper if self.stopper is not None else self.eval_ctr).record_row(self.score, self.row, self.eval_ring)
-
-    def train_epoch(self):
-        if self.graphed:
-            self._replay(0)
-            bump("lp.batch_epoch.graphed")
-        else:
-            self._train_epoch()
-            bump("lp.batch_epoch.eager")
-
-    def eval_epoch(self):
-        if self.graphed:
-            self._replay(1)
-            bump("lp.batch_eval_epoch.graphed")
-        else:
-            self._eval_epoch()
-            bump("lp.batch_eval_epoch.eager")
 
     def last_epoch(self):
         self.train_epoch()
@@ -2786,8 +2735,8 @@ def fit_batches(model, train_batches, valid_batches, optimizer, nepoch, eval_int
     from ..train import _as_device_stopper
     from .node_classification import MAX_GRAPH_BATCHES, _is_fixed_structure
     _no_complex(scorer, "fit_batches")
-    _decoder_args(decoder, loss, pos_weight, [None] if samplers is None else [], "fit_batches",
-                  label_smoothing=label_smoothing)
+    dec = _decoder_args(decoder, loss, pos_weight, [None] if samplers is None else [], "fit_batches",
+                        label_smoothing=label_smoothing)
     train_batches, valid_batches = list(train_batches), list(valid_batches or [])
     nepoch, poll = int(nepoch), max(int(poll), 1)
     if early_stop is not None and not valid_batches:
@@ -2799,7 +2748,6 @@ def fit_batches(model, train_batches, valid_batches, optimizer, nepoch, eval_int
                    and all(_is_fixed_structure(b) for b, _ in train_batches + valid_batches))
     stopper = _as_device_stopper(early_stop, model, optimizer)
     run = BatchFitEpochs(model, train_batches, valid_batches, optimizer, stopper, poll, capture, filter_ranks, samplers,
-                         warmup, l1_lambda=l1_lambda, l2_lambda=l2_lambda, decoder=decoder, loss=loss,
-                         pos_weight=pos_weight, label_smoothing=label_smoothing)
+                         warmup, l1_lambda=l1_lambda, l2_lambda=l2_lambda, decoder=dec)
     sched = eval_schedule(nepoch, eval_interval, bool(valid_batches))
     yield from _run_schedule(run, sched, nepoch, poll, stopper)

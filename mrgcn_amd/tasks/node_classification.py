@@ -15,7 +15,6 @@ import numpy as np
 import torch
 
 from .. import _lib as L
-from .. import functional as Fn
 from .. import train as T
 from ..stats import bump
 
@@ -384,13 +383,11 @@ def train_epoch(model, train_batches, valid_batches, optimizer, early_stop=None,
                       l2_lambda=l2_lambda)()
 
 
-class GraphedBatchEpoch(BatchEpoch):
-    """`BatchEpoch` captured into ONE hipGraph and replayed, with `train.GraphedTrainEvalStep`'s discipline: `warmup`
-    real epochs on the capture stream (plans, per-stream scratch and the loss's row flags exist afterwards),
-    `thread_local` capture, a single chain on the one stream (no parallel branches), the counter and the ring reset
-    after the warm-up so that the first replay is record 1, the optimizer's `_state_gen` compared and the pair-sum
-    tables of the supports refreshed in front of every replay.  Needs `ClipAdam(capturable=True)`; the batches are
-    masked batches (`mkbatches(..., plan=...)`) or full batches — slice batches cut their slices per forward: run
+class GraphedBatchEpoch(BatchEpoch, T._CapturedStep):
+    """`BatchEpoch` captured into ONE hipGraph and replayed through `train.Captured`: `warmup` real
+    epochs on the capture stream (plans, per-stream scratch and the loss's row flags exist afterwards), then the
+    counter and the ring reset, so that the first replay is record 1.  Needs `ClipAdam(capturable=True)`; the batches
+    are masked batches (`mkbatches(..., plan=...)`) or full batches — slice batches cut their slices per forward: run
     them through `BatchEpoch`."""
 
     def __init__(self, model, train_batches, valid_batches, optimizer, early_stop=None, ring=None, poll=8,
@@ -402,31 +399,10 @@ class GraphedBatchEpoch(BatchEpoch):
             if not _is_fixed_structure(b):
                 raise L.MrgcnError("GraphedBatchEpoch: slice batches are not captured; build the batches on the full "
                                    "graph's plan (mkbatches(..., plan=plan): the masked path) or use BatchEpoch")
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            for _ in range(max(warmup, 1)):
-                self._run()
-            self.reset()
-        torch.cuda.current_stream().wait_stream(side)
-        torch.cuda.synchronize()
-        self.graph = torch.cuda.CUDAGraph()
-        Fn.take_captured_pair_sums()
-        from ..train import capture_without_gc
-        with capture_without_gc(), \
-                torch.cuda.graph(self.graph, stream=side, capture_error_mode="thread_local"):
-            self._run()
-        self._pair_sums = Fn.take_captured_pair_sums()
-        self.warmup_steps = max(warmup, 1)
-        self._state_gen = optimizer._state_gen
+        self._capture(self._run, warmup, optimizer, self.reset)
 
     def __call__(self):
-        if self.optimizer._state_gen != self._state_gen:
-            raise L.MrgcnError("GraphedBatchEpoch: the optimizer's state was loaded after the capture; build a new "
-                               "GraphedBatchEpoch (the captured graph still updates the old moment buffers)")
-        for sup in self._pair_sums:
-            sup.pair_sums_refresh()
-        self.graph.replay()
+        T._CapturedStep.__call__(self)
         bump("nc.batch_epoch.graphed")
         return self.row
 
@@ -457,19 +433,4 @@ def fit(model, train_batches, valid_batches, optimizer, nepoch, early_stop=None,
     else:
         run = BatchEpoch(*args)
         run.reset()
-    counter, ring, stopper = run.counter, run.ring, run.stopper
-    done = 0
-    epoch = 0
-    while epoch < nepoch:
-        for _ in range(min(poll, nepoch - epoch)):
-            run()
-            epoch += 1
-        st = counter.read()
-        rows = ring.cpu()
-        for r in range(done, int(st.records)):
-            row = rows[r % poll]
-            yield (r + 1, float(row[0]), float(row[1]), float(row[2]), float(row[3]))
-        done = int(st.records)
-        if st.stop:
-            stopper.restore_()
-            return
+    yield from T._poll_records(run, run.counter, run.ring, nepoch, poll, run.stopper)

@@ -240,40 +240,87 @@ def capture_without_gc():
             gc.enable()
 
 
-class GraphedStep:
-    """Any allocation-stable, synchronisation-free step `fn()` (returning a device scalar) captured into a hipGraph and
-    replayed — e.g. one full-batch link-prediction epoch: negatives drawn on the device from torch's default generator
-    (whose state torch advances per replay), encoder, DistMult scores, BCE, backward, `ClipAdam(capturable=True)`.
-    `warmup` real calls run first, on the stream the capture then uses (plans and their per-stream scratch exist, lazily
-    built caches are filled)."""
+class Captured:
+    """The capture discipline of every graphed step and run loop, once.  `warmup()` runs on a side stream
+    (the real steps that build plans, per-stream scratch and lazily filled caches, then whatever counter and ring
+    resets the caller wants in front of record 1); then each zero-argument callable of `fns` is captured into a
+    hipGraph of its own on that same stream — a single chain per graph, no parallel branches, `thread_local` (calls
+    other threads make meanwhile, e.g. a process group's watchdog, do not invalidate the capture), the cyclic
+    collector held off (`capture_without_gc`).  Capturing executes nothing on the device.
 
-    def __init__(self, fn, warmup: int = 3):
+    `graphs`, `outs` (what each `fn` returned under capture) and `pair_sums` (per graph, the pair-sum tables of a
+    constant layer input that the graph reads) are lists in the order of `fns`.  `replay(i)` compares `optimizer`'s
+    `_state_gen` with the captured one (`load_state_dict` replaces the moment tensors and the device step counter a
+    graph was captured on) and raises `MrgcnError` under the name `who`, refreshes graph i's pair-sum tables (a replay
+    cannot see an in-place change of X: integer compares on the host, a rebuild in place on a mismatch), replays and
+    returns `outs[i]`."""
+
+    def __init__(self, fns, warmup, optimizer=None, who=""):
+        # the captured launches name the addresses of whatever the callables close over (a sampler's buffers, stored
+        # orders): they live as long as the graphs do, also when the caller keeps nothing but this object
+        self._fns, self._who = tuple(fns), who
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):
-            for _ in range(max(warmup, 1)):
-                fn()
+            warmup()
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize()
-        self.graph = torch.cuda.CUDAGraph()
-        Fn.take_captured_pair_sums()
-        with capture_without_gc(), \
-                torch.cuda.graph(self.graph, stream=side, capture_error_mode="thread_local"):
-            self.out = fn()
-        self._pair_sums = Fn.take_captured_pair_sums()
+        self.graphs, self.outs, self.pair_sums = [], [], []
+        for fn in self._fns:
+            g = torch.cuda.CUDAGraph()
+            Fn.take_captured_pair_sums()
+            # (on the stream the warm-up ran on: whatever keeps scratch per stream has met it already)
+            with capture_without_gc(), torch.cuda.graph(g, stream=side, capture_error_mode="thread_local"):
+                self.outs.append(fn())
+            self.pair_sums.append(Fn.take_captured_pair_sums())
+            self.graphs.append(g)
+        self._optimizer, self._state_gen = optimizer, (optimizer._state_gen if optimizer is not None else None)
+
+    def replay(self, i=0):
+        if self._optimizer is not None and self._optimizer._state_gen != self._state_gen:
+            if len(self.graphs) == 1:
+                raise L.MrgcnError(f"{self._who}: the optimizer's state was loaded after the capture; build a new "
+                                   f"{self._who} (the captured graph still updates the old moment buffers)")
+            raise L.MrgcnError(f"{self._who}: the optimizer's state was loaded after the capture (the captured graphs "
+                               "still update the old moment buffers)")
+        for sup in self.pair_sums[i]:
+            sup.pair_sums_refresh()
+        self.graphs[i].replay()
+        return self.outs[i]
+
+
+class _CapturedStep:
+    """One step captured once (`Captured`) after `warmup` real calls of it (at least one) and replayed by calling the
+    object."""
+
+    def _capture(self, step, warmup, optimizer=None, then=None):
+        """-> what `step()` returned under capture; `then()` closes the warm-up (counter and ring resets)."""
         self.warmup_steps = max(warmup, 1)
-        # the captured launches name the addresses of whatever `fn` closes over (a sampler's buffers, stored orders):
-        # they live as long as the graph does, also when the caller keeps nothing but this object
-        self._fn = fn
+
+        def warm():
+            for _ in range(self.warmup_steps):
+                step()
+            if then is not None:
+                then()
+        self._captured = Captured([step], warm, optimizer, type(self).__name__)
+        self.graph = self._captured.graphs[0]
+        return self._captured.outs[0]
 
     def __call__(self):
-        for sup in self._pair_sums:   # (tables of a constant input the graph reads: rebuilt in place if X was changed)
-            sup.pair_sums_refresh()
-        self.graph.replay()
-        return self.out
+        return self._captured.replay()
 
 
-class GraphedTrainStep:
+class GraphedStep(_CapturedStep):
+    """Any allocation-stable, synchronisation-free step `fn()` (returning a device scalar) captured into a hipGraph and
+    replayed — e.g. one full-batch link-prediction epoch: negatives drawn on the device from torch's default generator
+    (whose state torch advances per replay), encoder, DistMult scores, BCE, backward, `ClipAdam(capturable=True)`.
+    `warmup` real calls run first, on the stream the capture then uses (`Captured`)."""
+
+    def __init__(self, fn, warmup: int = 3):
+        self.out = self._capture(fn, warmup)
+
+
+class GraphedTrainStep(_CapturedStep):
     """One full-batch epoch captured into a hipGraph (torch.cuda.CUDAGraph) and replayed: the ~40
     kernel launches of a step become one graph launch, which is what bounds the small shapes
     (AIFB / MUTAG epochs are launch-latency territory).  Everything in the step is stream-ordered
@@ -283,45 +330,19 @@ class GraphedTrainStep:
         step = GraphedTrainStep(model, lambda: model(X, A), idx, targets, optimizer)
         loss = step()          # device scalar, no host sync
 
-    The graph plans must exist before capture (the warm-up steps build them); shapes are static."""
+    The graph plans must exist before capture (the warm-up steps build them); shapes are static.  Capturing executes
+    nothing on the device: `warmup` optimizer steps have been taken when the constructor returns (the optimizer's
+    device counter says the same; ClipAdam.state_dict() reads it back)."""
 
     def __init__(self, model, forward_fn, idx, targets, optimizer, warmup: int = 3,
                  l1_lambda: float = 0.0, l2_lambda: float = 0.0, row_sparse=None):
         if not getattr(optimizer, "capturable", False):
             raise L.MrgcnError("GraphedTrainStep needs ClipAdam(..., capturable=True)")
-        args = (model, forward_fn, idx, targets, optimizer, l1_lambda, l2_lambda, row_sparse)
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            for _ in range(max(warmup, 1)):
-                train_step(*args)
-        torch.cuda.current_stream().wait_stream(side)
-        torch.cuda.synchronize()
-        self.graph = torch.cuda.CUDAGraph()
-        # thread_local: calls other threads make while this one captures (e.g. the process group's
-        # watchdog in a multi-rank job) do not invalidate the capture.  Captured on the stream the warm-up steps ran
-        # on: whatever keeps scratch per stream (a plan's product scratch) has met this stream already.
-        Fn.take_captured_pair_sums()
-        with capture_without_gc(), \
-                torch.cuda.graph(self.graph, stream=side, capture_error_mode="thread_local"):
-            self.loss = train_step(*args)
-        # the pair-sum tables of a constant layer input that the graph reads (built by the warm-up steps): a replay
-        # cannot see an in-place change of X, so their keys are compared again on the host in front of every replay
-        self._pair_sums = Fn.take_captured_pair_sums()
-        # capturing executes nothing on the device: `warmup` optimizer steps have been taken so far (the
-        # optimizer's device counter says the same; ClipAdam.state_dict() reads it back)
-        self.warmup_steps = max(warmup, 1)
-        self._optimizer, self._state_gen = optimizer, optimizer._state_gen
 
-    def __call__(self):
-        if self._optimizer._state_gen != self._state_gen:
-            # load_state_dict replaced the moment tensors and the device step counter the graph was captured on
-            raise L.MrgcnError("GraphedTrainStep: the optimizer's state was loaded after the capture; build a new "
-                               "GraphedTrainStep (the captured graph still updates the old moment buffers)")
-        for sup in self._pair_sums:
-            sup.pair_sums_refresh()   # (integer compares; on a mismatch the table is rebuilt in place on this stream)
-        self.graph.replay()
-        return self.loss
+        def step():
+            return train_step(model, forward_fn, idx, targets, optimizer, l1_lambda, l2_lambda, row_sparse)
+        self.loss = self._capture(step, warmup, optimizer)
+        self._pair_sums = self._captured.pair_sums[0]
 
 
 # ---- validation and early stopping inside the epoch (csrc/early_stop.hip) -------------------------------------------
@@ -660,7 +681,7 @@ def _as_device_stopper(early_stop, model, optimizer):
     return DeviceEarlyStop(model, optimizer, early_stop.full_patience, early_stop.tolerance, early_stop.delay)
 
 
-class GraphedTrainEvalStep:
+class GraphedTrainEvalStep(_CapturedStep):
     """`train_eval_step` captured into one hipGraph and replayed: the training step, the evaluation of both label
     sets, the metrics row, the early-stop record and the conditional snapshot of the best state, on the one capture
     stream (a single chain, no parallel branches), with no host synchronisation.
@@ -670,11 +691,10 @@ class GraphedTrainEvalStep:
                                     early_stop=EarlyStop(7, 0.01), metrics=ring)
         step(); ...; step.early_stop.poll()
 
-    The capture discipline is GraphedTrainStep's: `warmup` real epochs on the capture stream, `thread_local` capture,
-    pair-sum tables re-checked in front of every replay, the optimizer's `_state_gen` compared.  `warmup` optimizer
-    steps have been taken when the constructor returns (capturing executes nothing), but they leave no trace in the
-    bookkeeping: the early-stop state and the ring are reset after the warm-up, just before the capture, so the first
-    replay is record 1.  `early_stop`: a DeviceEarlyStop, or a host EarlyStop as its configuration."""
+    Captured and replayed through `Captured`.  `warmup` optimizer steps have been taken when the constructor returns
+    (capturing executes nothing), but they leave no trace in the bookkeeping: the early-stop state and the ring are
+    reset after the warm-up, just before the capture, so the first replay is record 1.  `early_stop`: a
+    DeviceEarlyStop, or a host EarlyStop as its configuration."""
 
     def __init__(self, model, forward_fn, idx, targets, optimizer, valid=None, early_stop=None, metrics=None,
                  warmup: int = 3, l1_lambda: float = 0.0, l2_lambda: float = 0.0, row_sparse=None):
@@ -685,36 +705,17 @@ class GraphedTrainEvalStep:
         self.counter = early_stop.state if early_stop is not None else _StopState(idx.device, 1, 0.0, _COUNT_ONLY)
         kw = dict(l1_lambda=l1_lambda, l2_lambda=l2_lambda, row_sparse=row_sparse, valid=valid, early_stop=early_stop,
                   metrics=self.metrics, counter=self.counter)
-        args = (model, forward_fn, idx, targets, optimizer)
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            for _ in range(max(warmup, 1)):
-                train_eval_step(*args, **kw)
+
+        def step():
+            return train_eval_step(model, forward_fn, idx, targets, optimizer, **kw)
+
+        def reset():
             self.counter.reset()
             self.metrics.zero_()
-        torch.cuda.current_stream().wait_stream(side)
-        torch.cuda.synchronize()
-        self.graph = torch.cuda.CUDAGraph()
-        Fn.take_captured_pair_sums()
-        with capture_without_gc(), \
-                torch.cuda.graph(self.graph, stream=side, capture_error_mode="thread_local"):
-            self.values = train_eval_step(*args, **kw)
-        self._pair_sums = Fn.take_captured_pair_sums()
+        self.values = self._capture(step, warmup, optimizer, reset)
         self.loss = self.values[0]
-        self.warmup_steps = max(warmup, 1)
-        self._optimizer, self._state_gen = optimizer, optimizer._state_gen
 
-    def __call__(self):
-        if self._optimizer._state_gen != self._state_gen:
-            raise L.MrgcnError("GraphedTrainEvalStep: the optimizer's state was loaded after the capture; build a new "
-                               "GraphedTrainEvalStep (the captured graph still updates the old moment buffers)")
-        for sup in self._pair_sums:
-            sup.pair_sums_refresh()
-        self.graph.replay()
-        return self.values
-
-    step = __call__
+    step = _CapturedStep.__call__
 
 
 def fit(model, forward_fn, train, valid, optimizer, nepoch, early_stop=None, poll=8, graphed=True,
@@ -758,6 +759,13 @@ def fit(model, forward_fn, train, valid, optimizer, nepoch, early_stop=None, pol
         def run():
             return train_eval_step(model, forward_fn, idx, targets, optimizer, l1_lambda, l2_lambda, row_sparse,
                                    valid=valid, early_stop=stopper, metrics=ring, counter=counter)
+    yield from _poll_records(run, counter, ring, nepoch, poll, stopper)
+
+
+def _poll_records(run, counter, ring, nepoch, poll, stopper):
+    """The host side of this `fit` and of `node_classification.fit`: `run()` for `nepoch` epochs in windows of `poll`,
+    one look at the device per window (`counter.read()`, the ring of `poll` rows), the rows of the records made since
+    the last look as `(epoch, train_loss, train_acc, val_loss, val_acc)`, `stopper.restore_()` after a latched stop."""
     done = 0
     epoch = 0
     while epoch < nepoch:

@@ -20,15 +20,15 @@ def _free_port():
     return p
 
 
-def _problem():
+def _problem(K=6):
     from mrgcn_amd import synth
     g = synth.make_graph("aifb", seed=9, scale=0.5)
     rng = np.random.default_rng(9)
     N = g.num_nodes
-    X = rng.standard_normal((N, 6)).astype(np.float32)
+    X = rng.standard_normal((N, K)).astype(np.float32)
     idx = np.sort(rng.choice(N, 120, replace=False)).astype(np.int64)
     y = rng.integers(0, 4, 120).astype(np.int64)
-    mods = [(6, 8, "mrgcn", torch.nn.ReLU()), (8, 4, "mrgcn", None)]
+    mods = [(K, 8, "mrgcn", torch.nn.ReLU()), (8, 4, "mrgcn", None)]
     return g, X, idx, y, mods
 
 
@@ -160,19 +160,78 @@ def _graphed_worker(rank, world, port, state, out):
                 partitioned_train_step(model, Xl, idx, y, opt)
             losses = [float(partitioned_train_step(model, Xl, idx, y, opt)) for _ in range(3)]
         res.append((losses, model.layers["layer_1"].weight_F.detach().cpu().numpy()))
-    out[rank] = res
+    # the optimizer's state loaded after the capture: the captured graph would go on updating the old moments
+    kept = (dict(opt.state), dict(opt._dev_step))
+    opt.load_state_dict(opt.state_dict())
+    try:
+        step()
+        refused = None
+    except Exception as e:  # noqa: BLE001  (its type and text are the parent's to judge)
+        refused = (type(e).__name__, str(e))
+    del kept
+    out[rank] = res, refused, _replays_after_x_changed(part, dev)
     dist.destroy_process_group()
+
+
+def _replays_after_x_changed(part, dev):
+    """24 input columns (> 16) into 8 features: layer 0's dW runs on the pair-sum table of the constant X
+    (`functional._dw_pair_sums_table`), which a captured step reads at a fixed address.  Two warm-up steps and one more,
+    then X doubled IN PLACE, then two steps — eagerly, and as replays of the step captured before the change."""
+    import mrgcn_amd
+    import mrgcn_amd.functional as Fn
+    from mrgcn_amd.partition import GraphedPartitionedStep, PartitionedRGCN, partitioned_train_step
+    from mrgcn_amd.train import ClipAdam
+    Fn._DW_PAIR_SUMS_CAP = 1 << 30   # (this worker's own process; more pairs than nodes here: past the default cap)
+    g, X, idx, y, mods = _problem(K=24)
+    res = {}
+    for graphed in (False, True):
+        torch.manual_seed(5)
+        model = PartitionedRGCN(mods, g.num_relations, g.num_nodes, 5, False, True, part).to(dev)
+        model.build_plan(g.rows, g.cols, g.vals, dev)
+        Xl = part.shard_rows(torch.from_numpy(X)).to(dev)
+        opt = ClipAdam(model.parameters(), lr=0.01, max_norm=1.0, capturable=graphed)
+        opt.set_distributed(None, model.sharded_parameters())
+
+        def count(key):
+            return mrgcn_amd.stats().get(key, 0)
+        if graphed:
+            took = count("backward.dw_pair_sums")
+            step = GraphedPartitionedStep(model, Xl, idx, y, opt, warmup=2)
+            res["route_taken_in_warmup"] = count("backward.dw_pair_sums") - took
+            res["tables_of_the_graph"] = len(step._captured.pair_sums[0])
+        else:
+            def step():
+                return partitioned_train_step(model, Xl, idx, y, opt)
+            step(), step()
+        step()
+        Xl.mul_(2.0)
+        builds = count("dw_pair_sums.build")
+        losses = [float(step()) for _ in range(2)]
+        res[graphed] = (losses, model.layers["layer_0"].weight_F.detach().cpu().numpy(),
+                        count("dw_pair_sums.build") - builds)
+    return res
 
 
 @pytest.mark.timeout(600)
 def test_graphed_partitioned_step_over_rccl_with_one_rank():
     """GraphedPartitionedStep: the partitioned step with its RCCL collectives captured into a hipGraph and replayed
-    gives the eager steps' losses and weights (one rank over the nccl backend: what this box can run)."""
+    gives the eager steps' losses and weights (one rank over the nccl backend: what this box can run); a replay
+    refuses an optimizer state loaded after the capture, and sees an in-place change of a wide constant X."""
     state, _, _, _ = _single()
     mgr = mp.Manager()
     out = mgr.dict()
     mp.spawn(_graphed_worker, args=(1, _free_port(), state, out), nprocs=1, join=True)
-    (l_e, w_e), (l_g, w_g) = out[0]
+    ((l_e, w_e), (l_g, w_g)), refused, changed = out[0]
+    np.testing.assert_allclose(l_g, l_e, rtol=2e-4, atol=2e-5)
+    np.testing.assert_allclose(w_g, w_e, rtol=1e-3, atol=2e-5)
+    # through the capture helper the step compares the optimizer's generation in front of a replay ...
+    assert refused is not None and refused[0] == "MrgcnError", refused
+    assert "GraphedPartitionedStep: the optimizer's state was loaded after the capture" in refused[1]
+    # ... and re-checks the pair-sum table its layer-0 dW reads: the replay after X changed in place rebuilds it (once)
+    # and steps as the eager step does — the loss AFTER that step and layer 0's weights carry the dW
+    assert changed["route_taken_in_warmup"] >= 2 and changed["tables_of_the_graph"] == 1, changed
+    (l_e, w_e, builds_e), (l_g, w_g, builds_g) = changed[False], changed[True]
+    assert builds_g == 1 and builds_e == 1, (builds_g, builds_e)
     np.testing.assert_allclose(l_g, l_e, rtol=2e-4, atol=2e-5)
     np.testing.assert_allclose(w_g, w_e, rtol=1e-3, atol=2e-5)
 
