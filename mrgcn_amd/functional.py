@@ -3,6 +3,7 @@ or CPU fallback."""
 from __future__ import annotations
 
 import os
+from typing import NamedTuple
 
 import torch
 
@@ -602,6 +603,74 @@ def _dcomp_ordered(plan, dM, F, live, wI, comp):
     return out
 
 
+class _LayerView(NamedTuple):
+    """What a backward reads about a layer: built by each autograd `backward` from its own context (`_RgcnLayer`, the
+    halo engine's `_HaloLayerFn`), which alone knows its argument order."""
+    plan: GraphPlan   # the plan whose compact columns the operand has (the halo engine: P_col)
+    F: int
+    weight_I: object
+    comp_I: object
+    X: object         # the layer input as the forward's kernels read it (fp32 rows), or None
+    W_F: object
+    need_dX: bool
+    need_dW: bool
+    owner: object     # the layer module: its `weight_I` parameter carries the row-sparse gradient entry
+    x_is_relu_out: bool
+    Xb: object        # the input's bf16 rows (the bf16 pipeline), or None
+    x_src: object     # the caller's tensor behind X when it is data (the key of the pair-sum table), or None
+
+
+def _operand_forward(plan: GraphPlan, F: int, weight_I, comp_I, Xc, Xb, Wc, bf16: bool = False) -> torch.Tensor:
+    """The compact operand of `plan`'s columns in operand order (ld = _ld_for(F), bf16: _ld_for_bf16(F)):
+    M[c] = comp_I[r_c] . V_I[j_c] (or weight_I[r_c*N + j_c]) + X[j_c] . W_F[r_c] — the transform, then the mix or the
+    gather.  The caller prepares the input: `Xc` its rows with unit column stride, `Xb` their bf16 copy when the
+    transform is to read that (the bf16 pipeline), `Wc` contiguous."""
+    lib = L.load()
+    dev = plan.device
+    ld = _ld_for_bf16(F) if bf16 else _ld_for(F)
+    M = torch.empty((plan.nop, ld), dtype=torch.bfloat16 if bf16 else torch.float32, device=dev)
+    sfx = "bf16" if bf16 else "f32"
+    s = _stream(dev)
+    with torch.cuda.device(dev):
+        addend, ldA, addend_bf16 = 0, 0, False
+        if Xc is not None:
+            K = Xc.shape[1]
+            if weight_I is not None:
+                # feature term in plain compact order (sequential writes); the input-term
+                # pass below adds it while it emits the final rows in operand order
+                addend_bf16 = (Xb is not None and comp_I is not None and comp_I.shape[1] <= 64
+                               and (comp_I.shape[1] * F) % 4 == 0)
+                ldA = 16 if addend_bf16 else (F + 3) // 4 * 4
+                out = torch.empty((plan.ncols, ldA), dtype=torch.bfloat16 if addend_bf16 else torch.float32, device=dev)
+                ldo, order, addend = ldA, 0, out.data_ptr()
+            else:
+                out, ldo, order = M, ld, 1
+            if Xb is not None:
+                bump("bf16.xform_xbf16")
+                L.check(lib.mrgcn_rel_transform_fwd_xbf16(plan.handle, Xb.data_ptr(), Xb.stride(0), K, Wc.data_ptr(), F,
+                                                          out.data_ptr(), ldo, order, int(out.dtype == torch.bfloat16),
+                                                          s), "mrgcn_rel_transform_fwd_xbf16")
+            else:
+                fwd = getattr(lib, "mrgcn_rel_transform_fwd_" + sfx) if out is M else lib.mrgcn_rel_transform_fwd_f32
+                L.check(fwd(plan.handle, Xc.data_ptr(), Xc.stride(0), K, Wc.data_ptr(), F, out.data_ptr(), ldo, order,
+                            s), "mrgcn_rel_transform_fwd_" + sfx)   # (the addend stays fp32)
+        if weight_I is not None:
+            wI = weight_I.contiguous()
+            if comp_I is None:
+                L.check(getattr(lib, "mrgcn_gather_rows_" + sfx)(plan.handle, wI.data_ptr(), F, addend, ldA, M.data_ptr(),
+                                                                 ld, s), "mrgcn_gather_rows_" + sfx)
+            elif addend_bf16:
+                cI = comp_I.contiguous()
+                L.check(lib.mrgcn_basis_mix_fwd_abf16(plan.handle, wI.data_ptr(), cI.data_ptr(), cI.shape[1], F, addend,
+                                                      ldA, M.data_ptr(), ld, 1, s), "mrgcn_basis_mix_fwd_abf16")
+            else:
+                cI = comp_I.contiguous()
+                L.check(getattr(lib, "mrgcn_basis_mix_fwd_" + sfx)(plan.handle, wI.data_ptr(), cI.data_ptr(), cI.shape[1],
+                                                                   F, addend, ldA, M.data_ptr(), ld, s),
+                        "mrgcn_basis_mix_fwd_" + sfx)
+    return M
+
+
 class _RgcnLayer(torch.autograd.Function):
     """Y = relu?( A' . M + b ),  M[c] = comp_I[r_c] . V_I[j_c, :, :]  (or weight_I[r_c*N + j_c])
                                        + X[j_c] . W_F[r_c]
@@ -611,69 +680,23 @@ class _RgcnLayer(torch.autograd.Function):
     @staticmethod
     def forward(ctx, plan: GraphPlan, F: int, weight_I, comp_I, X, W_F, bias, relu: bool, bf16: bool = False,
                 owner=None, row_scale=None):
-        lib = L.load()
-        dev = plan.device
         # bf16: the compact operand M is stored in bf16 (one rounding at its store); a WIDE input (K > 16) is read as
         # bf16 rows by the transform on v_mfma_f32_16x16x32_bf16 and the feature term's rows travel in bf16 too (the
         # bf16 pipeline, `bf16_rows`); parameters, every accumulation, Y and the backward's sums stay fp32
-        ld = _ld_for_bf16(F) if bf16 else _ld_for(F)
-        M = torch.empty((plan.nop, ld), dtype=torch.bfloat16 if bf16 else torch.float32, device=dev)
-        sfx = "bf16" if bf16 else "f32"
-        xform_fwd = getattr(lib, "mrgcn_rel_transform_fwd_" + sfx)
-        mix_fwd = getattr(lib, "mrgcn_basis_mix_fwd_" + sfx)
-        gather_rows = getattr(lib, "mrgcn_gather_rows_" + sfx)
-        s = _stream(dev)
         Xc = Wc = Xb = None
-        with torch.cuda.device(dev):
-            addend, ldA, addend_bf16 = 0, 0, False
-            if X is not None:
-                K = X.shape[1]
-                Wc = W_F.contiguous()
-                if bf16 and (K > 16 or X.dtype == torch.bfloat16) and _BF16_PIPELINE:
-                    ldo = 16 if weight_I is not None else ld
-                    if lib.mrgcn_rel_transform_xbf16_supported(plan.handle, K, F, (K + 7) // 8 * 8, ldo):
-                        Xb = bf16_rows(X)
-                if Xb is None and X.dtype != torch.float32:
-                    raise L.MrgcnError("a bf16 layer input needs operand_dtype 'bf16' and a shape the bf16 transform takes")
-                Xc = X if (X.dim() == 2 and X.stride(1) == 1) else X.contiguous()  # row-strided X is taken as it is
-                if Xb is None:
-                    Xc = line_aligned_rows(Xc)   # (a constant feature matrix: rows of whole 128-byte lines, copied once)
-                if weight_I is not None:
-                    # feature term in plain compact order (sequential writes); the input-term
-                    # pass below adds it while it emits the final rows in operand order
-                    addend_bf16 = (Xb is not None and comp_I is not None and comp_I.shape[1] <= 64
-                                   and (comp_I.shape[1] * F) % 4 == 0)
-                    ldA = 16 if addend_bf16 else (F + 3) // 4 * 4
-                    M2 = torch.empty((plan.ncols, ldA), dtype=torch.bfloat16 if addend_bf16 else torch.float32,
-                                     device=dev)
-                    out, ldo, order = M2, ldA, 0
-                    addend = M2.data_ptr()
-                else:
-                    out, ldo, order = M, ld, 1
-                if Xb is not None:
-                    bump("bf16.xform_xbf16")
-                    L.check(lib.mrgcn_rel_transform_fwd_xbf16(plan.handle, Xb.data_ptr(), Xb.stride(0), K, Wc.data_ptr(), F,
-                                                              out.data_ptr(), ldo, order,
-                                                              int(out.dtype == torch.bfloat16), s),
-                            "mrgcn_rel_transform_fwd_xbf16")
-                else:
-                    fwd = xform_fwd if out is M else lib.mrgcn_rel_transform_fwd_f32  # M2 stays fp32
-                    L.check(fwd(plan.handle, Xc.data_ptr(), Xc.stride(0), Xc.shape[1], Wc.data_ptr(), F,
-                                out.data_ptr(), ldo, order, s), "mrgcn_rel_transform_fwd_" + sfx)
-            if weight_I is not None:
-                wI = weight_I.contiguous()
-                if comp_I is not None:
-                    cI = comp_I.contiguous()
-                    if addend_bf16:
-                        L.check(lib.mrgcn_basis_mix_fwd_abf16(plan.handle, wI.data_ptr(), cI.data_ptr(), cI.shape[1], F,
-                                                              addend, ldA, M.data_ptr(), ld, 1, s),
-                                "mrgcn_basis_mix_fwd_abf16")
-                    else:
-                        L.check(mix_fwd(plan.handle, wI.data_ptr(), cI.data_ptr(), cI.shape[1], F, addend, ldA,
-                                        M.data_ptr(), ld, s), "mrgcn_basis_mix_fwd_" + sfx)
-                else:
-                    L.check(gather_rows(plan.handle, wI.data_ptr(), F, addend, ldA, M.data_ptr(), ld, s),
-                            "mrgcn_gather_rows_" + sfx)
+        if X is not None:
+            K = X.shape[1]
+            Wc = W_F.contiguous()
+            if bf16 and (K > 16 or X.dtype == torch.bfloat16) and _BF16_PIPELINE:
+                ldo = 16 if weight_I is not None else _ld_for_bf16(F)
+                if L.load().mrgcn_rel_transform_xbf16_supported(plan.handle, K, F, (K + 7) // 8 * 8, ldo):
+                    Xb = bf16_rows(X)
+            if Xb is None and X.dtype != torch.float32:
+                raise L.MrgcnError("a bf16 layer input needs operand_dtype 'bf16' and a shape the bf16 transform takes")
+            Xc = X if (X.dim() == 2 and X.stride(1) == 1) else X.contiguous()  # row-strided X is taken as it is
+            if Xb is None:
+                Xc = line_aligned_rows(Xc)   # (a constant feature matrix: rows of whole 128-byte lines, copied once)
+        M = _operand_forward(plan, F, weight_I, comp_I, Xc, Xb, Wc, bf16)
         plan.replicate(M)  # (plans with operand replicas only)
         # a hidden layer's output stays in rows padded to whole 16-byte pieces (the product stores whole pieces: -5 %);
         # an output the caller sees is dense like the reference's
@@ -684,14 +707,13 @@ class _RgcnLayer(torch.autograd.Function):
         ctx.row_scale = _check_row_scale(row_scale, Y.shape[0], Y.device)
         if ctx.row_scale is not None:
             row_scale_(Y, ctx.row_scale)
-        ctx.plan, ctx.F, ctx.ld, ctx.relu, ctx.owner = plan, F, ld, relu, owner
+        ctx.plan, ctx.F, ctx.relu, ctx.owner, ctx.has_bias = plan, F, relu, owner, bias is not None
         ctx.Xb = Xb   # the input's bf16 rows (the bf16 pipeline): what the backward's dW gathers
         # the caller's tensor behind Xc when it is data: the key of what is cached per constant input (pair sums)
         ctx.x_src = X if (X is not None and not X.requires_grad) else None
         # the layer's input is the output of a fused ReLU (marked by the layer that made it): its own sign is that
         # ReLU's mask, so this layer's backward can hand its input gradient on already masked
         ctx.x_is_relu_out = X is not None and bool(getattr(X, "_mrgcn_relu_out", False))
-        ctx.has = (weight_I is not None, comp_I is not None, X is not None, bias is not None)
         ctx.save_for_backward(weight_I, comp_I, Xc, Wc, Y if relu else None)
         return Y
 
@@ -701,233 +723,280 @@ class _RgcnLayer(torch.autograd.Function):
 
     @staticmethod
     def _backward(ctx, dY):
-        lib = L.load()
-        plan, F = ctx.plan, ctx.F
+        """The chooser: the incoming gradient is prepared once, then the first route that takes it runs — on a gradient
+        support, the wide featureless layer straight from dY, or through dM in plain compact order."""
         weight_I, comp_I, X, W_F, Y = ctx.saved_tensors
-        has_I, has_comp, has_X, has_bias = ctx.has
-        dev = plan.device
-        s = _stream(dev)
-        dY = dY.contiguous()
-        # what the layer above knows about this gradient (see `_grad_meta`): its ReLU mask is applied already, and
-        # which of its rows hold anything
-        meta = _grad_meta(dY)
-        row_flags = meta["row_live"] if meta else None
-        if ctx.relu and not (meta and meta["relu_applied"]):
-            dY = relu_bwd(dY, Y)
-            if not (meta and meta.get("structural")):
-                row_flags = None   # (a structural row set stays a valid superset under the mask; a scanned one is stale)
-        sparse_rows = bool(meta and meta.get("sparse_rows"))
-        overlay = bool(getattr(plan, "is_overlay", False))
-        if sparse_rows and overlay:
-            raise L.MrgcnError("edge dropout: an output gradient with unwritten rows (train.train_step's loss) needs the "
-                               "backward on a gradient support, which a value overlay of the plan does not take; use a "
-                               "loss with a dense gradient, or set_edge_dropout(0.0)")
-        if sparse_rows and row_flags is None:
-            raise L.MrgcnError("internal: an output gradient with unwritten rows arrived without its row flags")
-        m = getattr(ctx, "row_scale", None)
-        looked = False
-        if m is not None:
-            # node dropout: dz_i = m_i . relu_bwd(y_i, dy_i), over the rows that hold anything.  A plain dense gradient's
-            # rows are looked up BEFORE the scale: the label set is the same every epoch, the dropped rows are not
-            if meta is None and _SUPPORT and _LIVE_COLS and _DISCOVER and F <= 16:
-                meta, looked = _discovered_rows(ctx.owner, plan, dY, F, dev), True
-                if meta:
-                    bump("discovered_rows")
-                row_flags = meta["row_live"] if meta else row_flags
-            dY = row_scale_live(dY, m, row_flags, zero_dead=not sparse_rows)
-        # (rows outside the flags are zeros — or, with `sparse_rows`, unwritten: the flagged rows are all there is to add)
-        dbias = _bias_grad(dY, row_flags) if has_bias else None
-        if meta is None and not looked and _SUPPORT and _LIVE_COLS and _DISCOVER and F <= 16:
-            # a plain dense gradient (the reference's own loss: CrossEntropyLoss on Y_hat[idx] leaves zeros + the
-            # labelled rows): which rows hold anything is looked up, and while that set equals last epoch's the
-            # backward runs on the support built for it
-            meta = _discovered_rows(ctx.owner, plan, dY, F, dev)
-            if meta:
-                bump("discovered_rows")
-            row_flags = meta["row_live"] if meta else row_flags
-        sup = _support_of(plan, meta, F, dev) if (_SUPPORT and _LIVE_COLS) else None
+        has_X = X is not None
+        lay = _LayerView(ctx.plan, ctx.F, weight_I, comp_I, X, W_F, has_X and ctx.needs_input_grad[4],
+                         has_X and ctx.needs_input_grad[5], ctx.owner, ctx.x_is_relu_out, ctx.Xb, ctx.x_src)
+        dY, meta, row_flags, sparse_rows, dbias = _incoming_gradient(lay, dY, Y, ctx.relu, ctx.row_scale, ctx.has_bias)
+        grads = None
+        sup = _support_of(lay.plan, meta, lay.F, lay.plan.device) if (_SUPPORT and _LIVE_COLS) else None
         if sup is not None:
-            out = _RgcnLayer._backward_on_support(ctx, sup, dY, dbias)
-            if out is not None:
+            grads = _RgcnLayer._backward_on_support(lay, sup, dY)
+            if grads is not None:
                 bump("backward.support")
-                return out
-        # (the units of the wide-layer backward are built on first use, with host round trips: not inside a capture)
-        if (has_I and has_comp and not has_X and not sparse_rows and weight_I.dim() == 3 and not plan.lean
-                and dY.stride(0) % 4 == 0
-                and (("_wide_units_det" if (_WIDE_DET or torch.are_deterministic_algorithms_enabled())
-                      else "_wide_units") in plan.__dict__
-                     or not torch.cuda.is_current_stream_capturing())):
-            Bn = weight_I.shape[1]
-            param = getattr(ctx.owner, "weight_I", None)
-            if (lib.mrgcn_wide_input_bwd_supported(plan.handle, Bn, F)
-                    and not (param is not None and _row_sparse_for(param) and _LIVE_COLS)):
-                # a wide featureless layer with few bases (the link-prediction encoder): dV and dcomp straight from
-                # dY over the plan's entries — the 4 F-byte rows of dM are never written (csrc/wide_input.hip)
-                wI = weight_I.contiguous()
-                d_wI, d_comp = torch.empty_like(wI), torch.empty_like(comp_I)
-                flag = torch.are_deterministic_algorithms_enabled()
-                if flag:
-                    bump("deterministic.wide_input")
-                if _WIDE_DET or flag:
-                    # units of 64 entries, no float atomics: bitwise reproducible (plan.wide_units_det)
-                    u = plan.wide_units_det(_WIDE_UNIT)
-                    nws = int(lib.mrgcn_wide_input_bwd_det_workspace(plan.handle, u["n_slots"], Bn, F))
-                    ws = u["ws"].get((Bn, F))
-                    if ws is None or ws.numel() < nws:
-                        ws = u["ws"][(Bn, F)] = torch.empty((max(nws, 4),), dtype=torch.float32, device=dev)
-                    with torch.cuda.device(dev):
-                        L.check(lib.mrgcn_wide_input_bwd_det_f32(
-                            plan.handle, u["erel"].data_ptr(), u["node"].data_ptr(), u["beg"].data_ptr(),
-                            u["end"].data_ptr(), u["slot"].data_ptr(), u["n_units"], u["hub_node"].data_ptr(),
-                            u["hub_ptr"].data_ptr(), u["n_hubs"], u["n_slots"], dY.data_ptr(), dY.stride(0), wI.data_ptr(),
-                            comp_I.contiguous().data_ptr(), Bn, F, d_wI.data_ptr(), d_comp.data_ptr(), ws.data_ptr(),
-                            ws.numel(), s), "mrgcn_wide_input_bwd_det_f32")
-                else:
-                    erel, un, ub, ue, um, nu = plan.wide_units()
-                    with torch.cuda.device(dev):
-                        L.check(lib.mrgcn_wide_input_bwd_f32(
-                            plan.handle, erel.data_ptr(), un.data_ptr(), ub.data_ptr(), ue.data_ptr(), um.data_ptr(), nu,
-                            dY.data_ptr(), dY.stride(0), wI.data_ptr(), comp_I.contiguous().data_ptr(), Bn, F,
-                            d_wI.data_ptr(), d_comp.data_ptr(), s), "mrgcn_wide_input_bwd_f32")
-                bump("backward.wide_input")
-                return None, None, d_wI, d_comp, None, None, dbias, None, None, None
-        # dM = A'^T dY over touched columns only, plain compact order (its consumers are node-major)
-        ld = (F + 3) // 4 * 4
-        dM = torch.empty((plan.ncols, ld), dtype=torch.float32, device=dev)
-        if _POISON_DEAD:
-            dM.fill_(float("nan"))
-        live = node_live = None
-        # (an overlay — edge dropout — takes the general transposed product on its own CVAL)
-        gauge = _live_gauge(plan, F, ctx.relu, dev) if (_LIVE_COLS and not overlay) else None
-        if sparse_rows and (gauge is None or F > 16):
-            raise L.MrgcnError("internal: an output gradient with unwritten rows needs the live-row backward")
-        # (unwritten rows outside the flags: only the live-row form may read this gradient, whatever the gauge says)
-        if gauge is not None and (sparse_rows or (F <= 16 and gauge.sparse())):
-            # with few labelled nodes most rows of dY are zeros: gather the others only, and keep one
-            # byte per compact column: does it carry any gradient?
-            live = torch.empty((plan.ncols,), dtype=torch.uint8, device=dev)
-            # (a layer whose input wants a gradient also gets a flag per source node: its dX pass skips by it)
-            node_live = (torch.empty((plan.num_nodes,), dtype=torch.uint8, device=dev)
-                         if (has_X and ctx.needs_input_grad[4]) else None)
-            scratch = torch.empty((int(lib.mrgcn_spmm_transposed_live_scratch(plan.handle)),),
-                                  dtype=torch.uint8, device=dev)
-            # rows of dM without gradient are not even written when every consumer goes by the flags
-            # (the no-bases scatter reads dM itself)
-            write_dead = int(has_I and not has_comp)
-            if row_flags is not None and (row_flags.numel() != plan.num_rows or row_flags.device != dev):
-                row_flags = None
-            with torch.cuda.device(dev):
-                L.check(lib.mrgcn_spmm_transposed_live_flagged_f32(
-                    plan.handle, dY.data_ptr(), dY.stride(0), F, dM.data_ptr(), ld, scratch.data_ptr(),
-                    live.data_ptr(), gauge.dev.data_ptr(), write_dead,
-                    row_flags.data_ptr() if row_flags is not None else 0,
-                    node_live.data_ptr() if node_live is not None else 0, s), "mrgcn_spmm_transposed_live_flagged_f32")
-            gauge.publish()
-            bump("backward.marking")
-        else:
-            plan.spmm(L.VIEW_TRANSPOSED, dY, F=F, out=dM)
-            bump("backward.general")
-        d_wI = d_comp = dX = dW = None
-        # The consumers of dM are independent of each other and bound by different resources
-        # (dV: HBM writes, dcomp: vector-memory issue, dW/dX: matrix cores + gathers), so the
-        # input-term and feature-term backward run on two HIP streams (MRGCN_OVERLAP=0: one).
-        overlap = has_I and has_X and _OVERLAP
-        main = torch.cuda.current_stream(dev)
-        side = _side_stream(dev) if overlap else main
-        if overlap:
-            side.wait_stream(main)  # dM is ready on `main`
-        with torch.cuda.device(dev):
-            if has_I and has_comp:
-                N_, Bn, _ = weight_I.shape
-                wI = weight_I.contiguous()
-                d_comp = torch.empty_like(comp_I)
-                param = getattr(ctx.owner, "weight_I", None)
-                rows = None
-                if (live is not None and param is not None and weight_I.is_contiguous()
-                        and param.shape == weight_I.shape and _row_sparse_for(param)):
-                    rows = _node_rows_entry(param, dev)
-                    # when the shape allows it no gradient tensor exists at all: the backward keeps flags, dcomp
-                    # and ||dV||^2, and ClipAdam rebuilds each live block from dM inside the Adam pass
-                    # (mrgcn_adam_step_rows_fused_f32); otherwise the blocks of the live nodes go to rows["g"]
-                    fused = bool(lib.mrgcn_adam_rows_fused_supported(plan.handle, Bn, F))
-                    if not rows.get("cur_owned"):
-                        # (`cur` may be a gradient support's own node flags — _support_weight_I_grads — which this path
-                        # must not overwrite: the flags written below are this entry's own)
-                        rows["cur"], rows["cur_owned"] = torch.zeros(N_, dtype=torch.uint8, device=dev), True
-                    if not fused and rows["g"] is None:
-                        rows["g"] = torch.empty_like(wI)
-                if rows is not None:
-                    sq = torch.zeros((), dtype=torch.float64, device=dev)
-                    L.check(lib.mrgcn_basis_mix_bwd_f32(
-                        plan.handle, dM.data_ptr(), ld, live.data_ptr(), wI.data_ptr(), comp_I.data_ptr(), Bn, F,
-                        0 if fused else rows["g"].data_ptr(), rows["cur"].data_ptr(), d_comp.data_ptr(),
-                        sq.data_ptr(), s), "mrgcn_basis_mix_bwd_f32")
-                    rows["sumsq"], rows["fresh"] = sq, True
-                    bump("weight_I.fused_rows" if fused else "weight_I.rows")
-                    # what the fused update reads: dM and the column flags of this backward, and the coefficients
-                    # as they were (the optimizer may update weight_I_comp before weight_I)
-                    rows["fused"] = dict(plan=plan, dM=dM, ld=ld, live=live, comp=comp_I.detach().clone(), B=Bn,
-                                         F=F) if fused else None
-                    d_wI = None  # travels in param._mrgcn_rows
-                else:
-                    bump("weight_I.dense")
-                    d_wI = torch.empty_like(wI)
-                    L.check(lib.mrgcn_basis_mix_bwd_f32(
-                        plan.handle, dM.data_ptr(), ld, live.data_ptr() if live is not None else 0, wI.data_ptr(),
-                        comp_I.data_ptr(), Bn, F, d_wI.data_ptr(), 0, d_comp.data_ptr(), 0, s),
-                        "mrgcn_basis_mix_bwd_f32")
-                    if torch.are_deterministic_algorithms_enabled():
-                        # the kernel's dcomp is a float-atomic sum; under the flag it is summed again in a fixed order
-                        # (this branch only: the row-sparse one above keeps the kernel's)
-                        bump("deterministic.dcomp")
-                        d_comp = _dcomp_ordered(plan, dM, F, live, wI, comp_I)
-            elif has_I:
-                # dense (R*N) x F gradient in one pass: the touched rows from dM, zeros everywhere else
-                d_wI = torch.empty(weight_I.shape, dtype=torch.float32, device=dev)
-                if torch.cuda.is_current_stream_capturing() and "_ulcol_sorted" not in plan.__dict__:
-                    raise L.MrgcnError("the sorted column list of this plan is built on first use: run one backward "
-                                       "of the layer before capturing it")
-                srows, sperm = plan.ulcol_sorted()
-                L.check(lib.mrgcn_scatter_rows_zero_fill_f32(srows.data_ptr(), sperm.data_ptr(), srows.numel(),
-                                                             dM.data_ptr(), ld, F, d_wI.data_ptr(), d_wI.shape[0], s),
-                        "mrgcn_scatter_rows_zero_fill_f32")
-            if has_X:
-                need_dX = ctx.needs_input_grad[4]
-                need_dW = ctx.needs_input_grad[5]
-                K = X.shape[1]
-                dx_flags = None
-                with torch.cuda.stream(side):
-                    if need_dX:
-                        dX = torch.empty((X.shape[0], K), dtype=torch.float32, device=dev)
-                    if need_dW:
-                        dW = torch.empty_like(W_F)
-                    if need_dX or need_dW:
-                        ws = None
-                        nws = int(lib.mrgcn_rel_transform_bwd_workspace(plan.handle, K, F, int(need_dX),
-                                                                        int(need_dW)))
-                        if nws > 0:
-                            ws = torch.empty((nws,), dtype=torch.float32, device=dev)
-                        # the input gradient leaves finished: masked by the ReLU that produced X (when X is such an
-                        # output) and with a flag per row — the layer below then neither masks nor scans it
-                        finish = need_dX and bool(lib.mrgcn_rel_transform_bwd_masked_supported(
-                            plan.handle, K, F, ws.numel() if ws is not None else 0))
-                        dx_flags = torch.empty((X.shape[0],), dtype=torch.uint8, device=dev) if finish else None
-                        L.check(lib.mrgcn_rel_transform_bwd_masked_f32(
-                            plan.handle, dM.data_ptr(), ld, live.data_ptr() if live is not None else 0,
-                            X.data_ptr(), X.stride(0), K, W_F.data_ptr(), F,
-                            dX.data_ptr() if need_dX else 0, K, dW.data_ptr() if need_dW else 0,
-                            ws.data_ptr() if ws is not None else 0, ws.numel() if ws is not None else 0,
-                            int(finish and ctx.x_is_relu_out), dx_flags.data_ptr() if finish else 0,
-                            node_live.data_ptr() if (finish and node_live is not None and live is not None) else 0,
-                            side.cuda_stream), "mrgcn_rel_transform_bwd_masked_f32")
-                        if finish:
-                            _set_grad_meta(dX, dx_flags, finish and ctx.x_is_relu_out)
-                if overlap:
-                    main.wait_stream(side)
-                    for t in (dX, dW, ws, dM, live, dx_flags, node_live):  # allocated / used on `side`: keep the allocator honest
-                        if t is not None:
-                            t.record_stream(side if (t is dM or t is live or t is node_live) else main)
+        if grads is None:
+            grads = _backward_wide_input(lay, dY, sparse_rows)
+        if grads is None:
+            grads = _backward_compact(lay, dY, ctx.relu, row_flags, sparse_rows)
+        d_wI, d_comp, dX, dW = grads
         return None, None, d_wI, d_comp, dX, dW, dbias, None, None, None
+
+
+def _incoming_gradient(lay: _LayerView, dY, Y, relu: bool, m, has_bias: bool):
+    """The layer's output gradient made ready for a route: (dY, meta, row_flags, sparse_rows, dbias) — dY contiguous
+    with the ReLU mask and the node-dropout scale `m` applied, what is known about its rows, the bias gradient."""
+    plan, F, dev = lay.plan, lay.F, lay.plan.device
+    dY = dY.contiguous()
+    # what the layer above knows about this gradient (see `_grad_meta`): its ReLU mask is applied already, and
+    # which of its rows hold anything
+    meta = _grad_meta(dY)
+    row_flags = meta["row_live"] if meta else None
+    if relu and not (meta and meta["relu_applied"]):
+        dY = relu_bwd(dY, Y)
+        if not (meta and meta.get("structural")):
+            row_flags = None   # (a structural row set stays a valid superset under the mask; a scanned one is stale)
+    sparse_rows = bool(meta and meta.get("sparse_rows"))
+    if sparse_rows and getattr(plan, "is_overlay", False):
+        raise L.MrgcnError("edge dropout: an output gradient with unwritten rows (train.train_step's loss) needs the "
+                           "backward on a gradient support, which a value overlay of the plan does not take; use a "
+                           "loss with a dense gradient, or set_edge_dropout(0.0)")
+    if sparse_rows and row_flags is None:
+        raise L.MrgcnError("internal: an output gradient with unwritten rows arrived without its row flags")
+    # (rows outside the flags are zeros — or, with `sparse_rows`, unwritten: the flagged rows are all there is to add)
+    dbias = _bias_grad(dY, row_flags) if (has_bias and m is None) else None
+    if meta is None and _SUPPORT and _LIVE_COLS and _DISCOVER and F <= 16:
+        # a plain dense gradient (the reference's own loss: CrossEntropyLoss on Y_hat[idx] leaves zeros + the
+        # labelled rows): which rows hold anything is looked up, and while that set equals last epoch's the
+        # backward runs on the support built for it.  Behind the bias gradient (a sum over all rows, not the flagged
+        # ones), but BEFORE a node-dropout scale: the label set is the same every epoch, the dropped rows are not
+        meta = _discovered_rows(lay.owner, plan, dY, F, dev)
+        if meta:
+            bump("discovered_rows")
+            row_flags = meta["row_live"]
+    if m is not None:
+        # node dropout: dz_i = m_i . relu_bwd(y_i, dy_i), over the rows that hold anything
+        dY = row_scale_live(dY, m, row_flags, zero_dead=not sparse_rows)
+        dbias = _bias_grad(dY, row_flags) if has_bias else None
+    return dY, meta, row_flags, sparse_rows, dbias
+
+
+def _backward_wide_input(lay: _LayerView, dY, sparse_rows: bool):
+    """Route: a wide featureless layer with few bases (the link-prediction encoder) — dV and dcomp straight from dY
+    over the plan's entries, the 4 F-byte rows of dM are never written (csrc/wide_input.hip).  None: not this layer."""
+    lib = L.load()
+    plan, F, weight_I, comp_I = lay.plan, lay.F, lay.weight_I, lay.comp_I
+    det = _WIDE_DET or torch.are_deterministic_algorithms_enabled()
+    # (the units of the wide-layer backward are built on first use, with host round trips: not inside a capture)
+    if not (weight_I is not None and comp_I is not None and lay.X is None and not sparse_rows and weight_I.dim() == 3
+            and not plan.lean and dY.stride(0) % 4 == 0
+            and (("_wide_units_det" if det else "_wide_units") in plan.__dict__
+                 or not torch.cuda.is_current_stream_capturing())):
+        return None
+    Bn = weight_I.shape[1]
+    param = getattr(lay.owner, "weight_I", None)
+    if (not lib.mrgcn_wide_input_bwd_supported(plan.handle, Bn, F)
+            or (param is not None and _row_sparse_for(param) and _LIVE_COLS)):
+        return None
+    dev = plan.device
+    s = _stream(dev)
+    wI = weight_I.contiguous()
+    d_wI, d_comp = torch.empty_like(wI), torch.empty_like(comp_I)
+    if torch.are_deterministic_algorithms_enabled():
+        bump("deterministic.wide_input")
+    if det:
+        # units of 64 entries, no float atomics: bitwise reproducible (plan.wide_units_det)
+        u = plan.wide_units_det(_WIDE_UNIT)
+        nws = int(lib.mrgcn_wide_input_bwd_det_workspace(plan.handle, u["n_slots"], Bn, F))
+        ws = u["ws"].get((Bn, F))
+        if ws is None or ws.numel() < nws:
+            ws = u["ws"][(Bn, F)] = torch.empty((max(nws, 4),), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            L.check(lib.mrgcn_wide_input_bwd_det_f32(
+                plan.handle, u["erel"].data_ptr(), u["node"].data_ptr(), u["beg"].data_ptr(),
+                u["end"].data_ptr(), u["slot"].data_ptr(), u["n_units"], u["hub_node"].data_ptr(),
+                u["hub_ptr"].data_ptr(), u["n_hubs"], u["n_slots"], dY.data_ptr(), dY.stride(0), wI.data_ptr(),
+                comp_I.contiguous().data_ptr(), Bn, F, d_wI.data_ptr(), d_comp.data_ptr(), ws.data_ptr(),
+                ws.numel(), s), "mrgcn_wide_input_bwd_det_f32")
+    else:
+        erel, un, ub, ue, um, nu = plan.wide_units()
+        with torch.cuda.device(dev):
+            L.check(lib.mrgcn_wide_input_bwd_f32(
+                plan.handle, erel.data_ptr(), un.data_ptr(), ub.data_ptr(), ue.data_ptr(), um.data_ptr(), nu,
+                dY.data_ptr(), dY.stride(0), wI.data_ptr(), comp_I.contiguous().data_ptr(), Bn, F,
+                d_wI.data_ptr(), d_comp.data_ptr(), s), "mrgcn_wide_input_bwd_f32")
+    bump("backward.wide_input")
+    return d_wI, d_comp, None, None
+
+
+def _backward_compact(lay: _LayerView, dY, relu: bool, row_flags, sparse_rows: bool):
+    """Route: dM = A'^T dY over touched columns only, in plain compact order (its consumers are node-major), then the
+    gradients from dM (`_grads_from_dM`)."""
+    lib = L.load()
+    plan, F = lay.plan, lay.F
+    dev = plan.device
+    s = _stream(dev)
+    ld = (F + 3) // 4 * 4
+    dM = torch.empty((plan.ncols, ld), dtype=torch.float32, device=dev)
+    if _POISON_DEAD:
+        dM.fill_(float("nan"))
+    live = node_live = None
+    # (an overlay — edge dropout — takes the general transposed product on its own CVAL)
+    gauge = _live_gauge(plan, F, relu, dev) if (_LIVE_COLS and not getattr(plan, "is_overlay", False)) else None
+    if sparse_rows and (gauge is None or F > 16):
+        raise L.MrgcnError("internal: an output gradient with unwritten rows needs the live-row backward")
+    # (unwritten rows outside the flags: only the live-row form may read this gradient, whatever the gauge says)
+    if gauge is not None and (sparse_rows or (F <= 16 and gauge.sparse())):
+        # with few labelled nodes most rows of dY are zeros: gather the others only, and keep one
+        # byte per compact column: does it carry any gradient?
+        live = torch.empty((plan.ncols,), dtype=torch.uint8, device=dev)
+        # (a layer whose input wants a gradient also gets a flag per source node: its dX pass skips by it)
+        node_live = torch.empty((plan.num_nodes,), dtype=torch.uint8, device=dev) if lay.need_dX else None
+        scratch = torch.empty((int(lib.mrgcn_spmm_transposed_live_scratch(plan.handle)),),
+                              dtype=torch.uint8, device=dev)
+        # rows of dM without gradient are not even written when every consumer goes by the flags
+        # (the no-bases scatter reads dM itself)
+        write_dead = int(lay.weight_I is not None and lay.comp_I is None)
+        if row_flags is not None and (row_flags.numel() != plan.num_rows or row_flags.device != dev):
+            row_flags = None
+        with torch.cuda.device(dev):
+            L.check(lib.mrgcn_spmm_transposed_live_flagged_f32(
+                plan.handle, dY.data_ptr(), dY.stride(0), F, dM.data_ptr(), ld, scratch.data_ptr(),
+                live.data_ptr(), gauge.dev.data_ptr(), write_dead,
+                row_flags.data_ptr() if row_flags is not None else 0,
+                node_live.data_ptr() if node_live is not None else 0, s), "mrgcn_spmm_transposed_live_flagged_f32")
+        gauge.publish()
+        bump("backward.marking")
+    else:
+        plan.spmm(L.VIEW_TRANSPOSED, dY, F=F, out=dM)
+        bump("backward.general")
+    d_wI, d_comp, dX, dW = _grads_from_dM(lay, dM, ld, live, node_live, s)
+    if d_wI is not None and lay.comp_I is not None and torch.are_deterministic_algorithms_enabled():
+        # the mix backward's dcomp is a float-atomic sum; under the flag it is summed again in a fixed order (the dense
+        # branch only: the row-sparse one keeps the kernel's; nor the halo engine, whose sums arrive through index_add_)
+        bump("deterministic.dcomp")
+        d_comp = _dcomp_ordered(plan, dM, F, live, lay.weight_I.contiguous(), lay.comp_I)
+    return d_wI, d_comp, dX, dW
+
+
+class _SideFork:
+    """The consumers of dM are independent of each other and bound by different resources (dV: HBM writes, dcomp:
+    vector-memory issue, dW/dX: matrix cores + gathers), so the input-term and feature-term backward run on two HIP
+    streams (MRGCN_OVERLAP=0: one).  Made when dM is ready on the current stream: `side` waits for it; the feature-term
+    block runs under `torch.cuda.stream(fork.side)`; `join` makes the current stream wait back."""
+
+    def __init__(self, dev, overlap: bool):
+        self.overlap = bool(overlap)
+        self.main = torch.cuda.current_stream(dev)
+        self.side = _side_stream(dev) if self.overlap else self.main
+        if self.overlap:
+            self.side.wait_stream(self.main)
+
+    def join(self, made=(), read=()):
+        """`made`: tensors allocated on `side` that `main` goes on with; `read`: tensors of `main` that `side` read —
+        each is recorded on the other stream, to keep the allocator honest."""
+        if not self.overlap:
+            return
+        self.main.wait_stream(self.side)
+        for ts, st in ((made, self.main), (read, self.side)):
+            for t in ts:
+                if t is not None:
+                    t.record_stream(st)
+
+
+def _grads_from_dM(lay: _LayerView, dM, ld: int, live, node_live, s: int, plain: bool = False):
+    """(d weight_I, d weight_I_comp, dX, dW) from dM [ncols, ld], the gradient of the operand rows in plain compact
+    order: the mix backward (row-sparse or fused-rows when the parameter's optimizer reads that form, else dense) or the
+    literal scatter, and the masked transform backward.  `live` / `node_live`: the flags of the live-marking product
+    (None: every row of dM is written).  `plain`: the halo engine's form — one stream, and dX leaves neither masked nor
+    flagged (its rows are one rank's share of a sum)."""
+    lib = L.load()
+    plan, F, weight_I, comp_I, X, W_F = lay[:6]
+    dev = plan.device
+    has_I, has_comp, has_X = weight_I is not None, comp_I is not None, X is not None
+    d_wI = d_comp = dX = dW = None
+    fork = _SideFork(dev, has_I and has_X and _OVERLAP and not plain)
+    with torch.cuda.device(dev):
+        if has_I and has_comp:
+            N_, Bn, _ = weight_I.shape
+            wI = weight_I.contiguous()
+            d_comp = torch.empty_like(comp_I)
+            param = getattr(lay.owner, "weight_I", None)
+            rows = None
+            if (live is not None and param is not None and weight_I.is_contiguous()
+                    and param.shape == weight_I.shape and _row_sparse_for(param)):
+                rows = _node_rows_entry(param, dev)
+                # when the shape allows it no gradient tensor exists at all: the backward keeps flags, dcomp
+                # and ||dV||^2, and ClipAdam rebuilds each live block from dM inside the Adam pass
+                # (mrgcn_adam_step_rows_fused_f32); otherwise the blocks of the live nodes go to rows["g"]
+                fused = bool(lib.mrgcn_adam_rows_fused_supported(plan.handle, Bn, F))
+                if not rows.get("cur_owned"):
+                    # (`cur` may be a gradient support's own node flags — _support_weight_I_grads — which this path
+                    # must not overwrite: the flags written below are this entry's own)
+                    rows["cur"], rows["cur_owned"] = torch.zeros(N_, dtype=torch.uint8, device=dev), True
+                if not fused and rows["g"] is None:
+                    rows["g"] = torch.empty_like(wI)
+            if rows is not None:
+                sq = torch.zeros((), dtype=torch.float64, device=dev)
+                L.check(lib.mrgcn_basis_mix_bwd_f32(
+                    plan.handle, dM.data_ptr(), ld, live.data_ptr(), wI.data_ptr(), comp_I.data_ptr(), Bn, F,
+                    0 if fused else rows["g"].data_ptr(), rows["cur"].data_ptr(), d_comp.data_ptr(),
+                    sq.data_ptr(), s), "mrgcn_basis_mix_bwd_f32")
+                rows["sumsq"], rows["fresh"] = sq, True
+                bump("weight_I.fused_rows" if fused else "weight_I.rows")
+                # what the fused update reads: dM and the column flags of this backward, and the coefficients
+                # as they were (the optimizer may update weight_I_comp before weight_I)
+                rows["fused"] = dict(plan=plan, dM=dM, ld=ld, live=live, comp=comp_I.detach().clone(), B=Bn,
+                                     F=F) if fused else None
+                # (d_wI travels in param._mrgcn_rows)
+            else:
+                bump("weight_I.dense")
+                d_wI = torch.empty_like(wI)
+                L.check(lib.mrgcn_basis_mix_bwd_f32(
+                    plan.handle, dM.data_ptr(), ld, live.data_ptr() if live is not None else 0, wI.data_ptr(),
+                    comp_I.contiguous().data_ptr(), Bn, F, d_wI.data_ptr(), 0, d_comp.data_ptr(), 0, s),
+                    "mrgcn_basis_mix_bwd_f32")
+        elif has_I:
+            # dense (R*N) x F gradient in one pass: the touched rows from dM, zeros everywhere else
+            d_wI = torch.empty(weight_I.shape, dtype=torch.float32, device=dev)
+            if torch.cuda.is_current_stream_capturing() and "_ulcol_sorted" not in plan.__dict__:
+                raise L.MrgcnError("the sorted column list of this plan is built on first use: run one backward "
+                                   "of the layer before capturing it")
+            srows, sperm = plan.ulcol_sorted()
+            L.check(lib.mrgcn_scatter_rows_zero_fill_f32(srows.data_ptr(), sperm.data_ptr(), srows.numel(),
+                                                         dM.data_ptr(), ld, F, d_wI.data_ptr(), d_wI.shape[0], s),
+                    "mrgcn_scatter_rows_zero_fill_f32")
+        if has_X:
+            need_dX, need_dW = lay.need_dX, lay.need_dW
+            K = X.shape[1]
+            ws = dx_flags = None
+            with torch.cuda.stream(fork.side):
+                if need_dX:
+                    dX = torch.empty((X.shape[0], K), dtype=torch.float32, device=dev)
+                if need_dW:
+                    dW = torch.empty_like(W_F)
+                if need_dX or need_dW:
+                    nws = int(lib.mrgcn_rel_transform_bwd_workspace(plan.handle, K, F, int(need_dX), int(need_dW)))
+                    if nws > 0:
+                        ws = torch.empty((nws,), dtype=torch.float32, device=dev)
+                    # the input gradient leaves finished: masked by the ReLU that produced X (when X is such an
+                    # output) and with a flag per row — the layer below then neither masks nor scans it
+                    finish = not plain and need_dX and bool(lib.mrgcn_rel_transform_bwd_masked_supported(
+                        plan.handle, K, F, ws.numel() if ws is not None else 0))
+                    dx_flags = torch.empty((X.shape[0],), dtype=torch.uint8, device=dev) if finish else None
+                    L.check(lib.mrgcn_rel_transform_bwd_masked_f32(
+                        plan.handle, dM.data_ptr(), ld, live.data_ptr() if live is not None else 0,
+                        X.data_ptr(), X.stride(0), K, W_F.data_ptr(), F,
+                        dX.data_ptr() if need_dX else 0, K, dW.data_ptr() if need_dW else 0,
+                        ws.data_ptr() if ws is not None else 0, ws.numel() if ws is not None else 0,
+                        int(finish and lay.x_is_relu_out), dx_flags.data_ptr() if finish else 0,
+                        node_live.data_ptr() if (finish and node_live is not None and live is not None) else 0,
+                        fork.side.cuda_stream), "mrgcn_rel_transform_bwd_masked_f32")
+                    if finish:
+                        _set_grad_meta(dX, dx_flags, finish and lay.x_is_relu_out)
+            fork.join(made=(dX, dW, ws, dx_flags), read=(dM, live, node_live))
+    return d_wI, d_comp, dX, dW
 
 
 _DISCOVER = os.environ.get("MRGCN_DISCOVER_ROWS", "1") != "0"
@@ -1055,96 +1124,82 @@ def _wide_bwd(sup, dY, wI, comp_I, Bn, F, dV, dense, d_comp, sq, s):
     bump("weight_I.wide_masked")
 
 
-def _support_backward_workspace(ctx, sup):
+def _support_backward_workspace(lay: _LayerView, sup):
     """floats of workspace the transform's backward on `sup` needs (0: no feature term), or None when a shape is outside
     what the support calls take (the caller then runs another path)."""
     lib = L.load()
-    weight_I, comp_I, X, W_F, Y = ctx.saved_tensors
-    has_I, has_comp, has_X, has_bias = ctx.has
-    F = ctx.F
-    if has_I and not has_comp:
+    F, weight_I, comp_I = lay.F, lay.weight_I, lay.comp_I
+    if weight_I is not None and comp_I is None:
         return None  # (the literal (R*N) x F gradient is scattered from plain compact order)
-    if has_I and (comp_I.shape[1] > 64 or F > 16):
+    if weight_I is not None and (comp_I.shape[1] > 64 or F > 16):
         return None  # (outside the support's node-major mix backward: mrgcn_support_mix_bwd_f32)
-    need_dX = has_X and ctx.needs_input_grad[4]
-    need_dW = has_X and ctx.needs_input_grad[5]
     nws = 0
-    if need_dX or need_dW:
-        nws = int(lib.mrgcn_support_rel_transform_bwd_workspace(sup.handle, X.shape[1], F, int(need_dX), int(need_dW)))
+    if lay.need_dX or lay.need_dW:
+        nws = int(lib.mrgcn_support_rel_transform_bwd_workspace(sup.handle, lay.X.shape[1], F, int(lay.need_dX),
+                                                                int(lay.need_dW)))
         if nws < 0:
             return None
     return nws
 
 
-def _backward_on_support(ctx, sup, dY, dbias):
-    """_RgcnLayer.backward on a gradient support: dM and every per-column product are [L, ld] arrays by live number;
+def _backward_on_support(lay: _LayerView, sup, dY):
+    """Route: the backward on a gradient support — dM and every per-column product are [L, ld] arrays by live number;
     no marking, no flags, no zero fills (csrc/support.hip).  None when a shape is outside what the support calls
-    take (the caller then runs the per-epoch marking path)."""
+    take (the caller then runs another route)."""
     lib = L.load()
-    nws = _support_backward_workspace(ctx, sup)
+    nws = _support_backward_workspace(lay, sup)
     if nws is None:
         return None
-    plan, F = ctx.plan, ctx.F
-    dev = plan.device
-    s = _stream(dev)
-    ld = (F + 3) // 4 * 4
+    dev = lay.plan.device
+    ld = (lay.F + 3) // 4 * 4
     dM = torch.empty((max(sup.L, 1), ld), dtype=torch.float32, device=dev)
     with torch.cuda.device(dev):
-        L.check(lib.mrgcn_support_spmm_t_f32(sup.handle, dY.data_ptr(), dY.stride(0), F, dM.data_ptr(), ld, s),
-                "mrgcn_support_spmm_t_f32")
-    return _support_backward_from_dM(ctx, sup, dM, ld, dbias, nws, dY=dY)
+        L.check(lib.mrgcn_support_spmm_t_f32(sup.handle, dY.data_ptr(), dY.stride(0), lay.F, dM.data_ptr(), ld,
+                                             _stream(dev)), "mrgcn_support_spmm_t_f32")
+    return _support_backward_from_dM(lay, sup, dM, ld, nws, dY=dY)
 
 
-def _dw_pair_sums_table(ctx, sup, X, K, F, need_dX, need_dW, dY):
+def _dw_pair_sums_table(lay: _LayerView, sup, dY):
     """The pair-sum table the layer's dW may run on (None: the gather kernel): only dW wanted, X wide fp32 data with no
     bf16 copy in use, the layer's own output gradient at hand, and a valid table or the chance to build one."""
-    if not (_DW_PAIR_SUMS and dY is not None and need_dW and not need_dX and K > 16 and F <= 16):
+    X, K = lay.X, lay.X.shape[1]
+    if not (_DW_PAIR_SUMS and dY is not None and lay.need_dW and not lay.need_dX and K > 16 and lay.F <= 16):
         return None
-    src = getattr(ctx, "x_src", None)
-    if src is None:
-        src = X
-    if (getattr(ctx, "Xb", None) is not None or X.dtype != torch.float32 or X.requires_grad or src.requires_grad
+    src = lay.x_src if lay.x_src is not None else X
+    if (lay.Xb is not None or X.dtype != torch.float32 or X.requires_grad or src.requires_grad
             or src.dtype != torch.float32 or src.dim() != 2 or dY.dtype != torch.float32 or dY.stride(1) != 1):
         return None
     cap = _DW_PAIR_SUMS_CAP if _DW_PAIR_SUMS_CAP > 0 else src.shape[0] * K * 4
     return sup.pair_sums(src, X, K, cap)
 
 
-def _support_backward_from_dM(ctx, sup, dM, ld, dbias, nws, dY=None):
-    """The layer's parameter / input gradients from dM [L, ld] (the gradient of the live columns' operand rows, by the
-    support's live numbers): mix backward, the transform's dW / dX.  `ctx`: anything with _RgcnLayer's context fields
-    (plan, F, saved_tensors, has, needs_input_grad, owner, x_is_relu_out, Xb) — the node-partitioned halo engine sums
-    the ranks' contributions into dM first and calls this on its own columns' support (partition_halo.py).  `dY`: the
-    layer's own output gradient (ReLU mask applied) when dM is this support's product with it and nothing else — the dW
-    of a constant wide input may then come from the pair-sum table (`_dw_pair_sums_table`)."""
+def _support_backward_from_dM(lay: _LayerView, sup, dM, ld: int, nws: int, dY=None):
+    """(d weight_I, d weight_I_comp, dX, dW) from dM [L, ld] (the gradient of the live columns' operand rows, by the
+    support's live numbers): mix backward, the transform's dW / dX.  The node-partitioned halo engine sums the ranks'
+    contributions into dM first and calls this on its own columns' support (partition_halo.py).  `dY`: the layer's own
+    output gradient (ReLU mask applied) when dM is this support's product with it and nothing else — the dW of a
+    constant wide input may then come from the pair-sum table (`_dw_pair_sums_table`)."""
     lib = L.load()
-    plan, F = ctx.plan, ctx.F
-    weight_I, comp_I, X, W_F, Y = ctx.saved_tensors
-    has_I, has_comp, has_X, has_bias = ctx.has
+    plan, F, weight_I, comp_I, X, W_F, need_dX, need_dW = lay[:8]
     dev = plan.device
-    need_dX = has_X and ctx.needs_input_grad[4]
-    need_dW = has_X and ctx.needs_input_grad[5]
-    K = X.shape[1] if has_X else 0
-    s = _stream(dev)
+    has_I = weight_I is not None
+    K = X.shape[1] if X is not None else 0
     d_wI = d_comp = dX = dW = None
-    overlap = has_I and has_X and _OVERLAP
-    main = torch.cuda.current_stream(dev)
-    side = _side_stream(dev) if overlap else main
-    if overlap:
-        side.wait_stream(main)
+    fork = _SideFork(dev, has_I and X is not None and _OVERLAP)
+    side = fork.side
     with torch.cuda.device(dev):
         if has_I:
-            d_wI, d_comp = _support_weight_I_grads(ctx.owner, sup, plan, dM, ld, weight_I, comp_I, F, s)
+            d_wI, d_comp = _support_weight_I_grads(lay.owner, sup, plan, dM, ld, weight_I, comp_I, F, _stream(dev))
         if need_dX or need_dW:
             with torch.cuda.stream(side):
                 if need_dX:
                     dX = torch.empty((X.shape[0], K), dtype=torch.float32, device=dev)
                 if need_dW:
                     dW = torch.empty_like(W_F)
-                S = _dw_pair_sums_table(ctx, sup, X, K, F, need_dX, need_dW, dY)
+                S = _dw_pair_sums_table(lay, sup, dY)
                 ws = sup.workspace(("xform", K, F), nws) if S is None else None
-                mask = bool(need_dX and ctx.x_is_relu_out and K <= 16)
-                Xb = getattr(ctx, "Xb", None)
+                mask = bool(need_dX and lay.x_is_relu_out and K <= 16)
+                Xb = lay.Xb
                 if S is not None:
                     # dW[r] = sum over r's (row, relation) pairs of S[p]^T . dY[row_p]: the table in order, dM not read
                     bump("backward.dw_pair_sums")
@@ -1168,13 +1223,8 @@ def _support_backward_from_dM(ctx, sup, dM, ld, dbias, nws, dY=None):
                 if need_dX:
                     # the rows that can hold anything: the nodes of this support — the row set of the layer below
                     _set_grad_meta(dX, sup.node_flags(), mask, structural=True)
-            if overlap:
-                main.wait_stream(side)
-                for t in (dX, dW):
-                    if t is not None:
-                        t.record_stream(main)
-                dM.record_stream(side)
-    return None, None, d_wI, d_comp, dX, dW, dbias, None, None, None
+            fork.join(made=(dX, dW), read=(dM,))
+    return d_wI, d_comp, dX, dW
 
 
 _RgcnLayer._backward_on_support = staticmethod(_backward_on_support)

@@ -244,9 +244,10 @@ class _AllGatherRows(torch.autograd.Function):
 
 
 # ---- the partitioned model ----------------------------------------------------------------------
-class PartitionedRGCN(nn.Module):
-    """`RGCN` (models/rgcn.py) with node-partitioned layers.  `modules` as for RGCN.  Every
-    rank constructs it with the same seed; `load_full_state` shards a reference-shaped state."""
+class _PartitionedModel(nn.Module):
+    """What the two node-partitioned engines share: `RGCN`'s constructor (models/rgcn.py; `modules` as for RGCN) with
+    local layers over this rank's S source nodes, and the sharding of the parameters.  Every rank constructs it with
+    the same seed; `load_full_state` shards a reference-shaped state."""
 
     def __init__(self, modules, num_relations, num_nodes, num_bases, featureless, bias, part: NodePartition,
                  group=None, link_prediction=False, num_blocks=-1):
@@ -270,7 +271,6 @@ class PartitionedRGCN(nn.Module):
                 featureless=featureless if first else False)
             self.relu.append(isinstance(act, nn.ReLU))
         self.num_layers = len(self.layers)
-        self.plan = None
 
     def set_node_dropout(self, mode: str, seed=None):
         """The partitioned engines have no node dropout on the device (models/rgcn.py: RGCN.set_node_dropout)."""
@@ -308,6 +308,29 @@ class PartitionedRGCN(nn.Module):
                 else:
                     p.copy_(full)
 
+    @torch.no_grad()
+    def sync_replicated(self, src: int = 0):
+        """Replicated parameters must start identical on every rank."""
+        for q in self.replicated_parameters():
+            if _staged(q, self.group):
+                buf = q.detach().cpu()
+                dist.broadcast(buf, src, group=self.group)
+                q.copy_(buf.to(q.device))
+            else:
+                dist.broadcast(q.data, src, group=self.group)
+
+    def allreduce_replicated_grads(self):
+        """Gradients of the small replicated parameters are sums over all columns of A."""
+        for p in self.replicated_parameters():
+            if p.grad is not None:
+                all_reduce_sum_(p.grad, self.group)
+
+
+class PartitionedRGCN(_PartitionedModel):
+    """`RGCN` (models/rgcn.py) with node-partitioned layers: the column partition, one reduce-scatter of partial sums
+    per layer."""
+    plan = None
+
     def build_plan(self, rows, cols, vals, device):
         lr, lc, lv = self.part.local_coo(rows, cols, vals, self.num_relations)
         A = torch.sparse_coo_tensor(torch.from_numpy(np.stack([lr, lc])), torch.from_numpy(lv),
@@ -327,23 +350,6 @@ class PartitionedRGCN(nn.Module):
                 Y = Y + layer.b
             H = _ReluRows.apply(Y) if self.relu[i] else Y
         return H
-
-    @torch.no_grad()
-    def sync_replicated(self, src: int = 0):
-        """Replicated parameters must start identical on every rank."""
-        for q in self.replicated_parameters():
-            if _staged(q, self.group):
-                buf = q.detach().cpu()
-                dist.broadcast(buf, src, group=self.group)
-                q.copy_(buf.to(q.device))
-            else:
-                dist.broadcast(q.data, src, group=self.group)
-
-    def allreduce_replicated_grads(self):
-        """Gradients of the small replicated parameters are sums over all columns of A."""
-        for p in self.replicated_parameters():
-            if p.grad is not None:
-                all_reduce_sum_(p.grad, self.group)
 
     # -- overlapped form: every replicated gradient is reduced as soon as autograd has accumulated it, on the
     #    communication stream, while the backward of the layers below it still computes (the dominant local work

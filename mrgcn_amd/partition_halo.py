@@ -26,17 +26,12 @@ from __future__ import annotations
 import numpy as np
 import torch
 import torch.distributed as dist
-import torch.nn as nn
 
 from . import _lib as L
 from . import functional as Fn
-from .layers.graph import GraphConvolution
-from .partition import NodePartition, _staged, all_reduce_sum_, partitioned_loss
+from .partition import NodePartition, _PartitionedModel, _staged, all_reduce_sum_, partitioned_loss
 from .plan import GraphPlan
 from .stats import bump
-
-import os
-_COMPOSED = os.environ.get("MRGCN_HALO_COMPOSED", "0") == "1"   # the layer as a composition of autograd pieces (round 5)
 
 
 # ---- index maps (host, pure numpy + one exchange of requests): testable without a GPU ---------------------------------
@@ -137,209 +132,10 @@ def wait_rows_exchange(pending: _Pending):
         pending.work = None
 
 
-class _SendRows(torch.autograd.Function):
-    """send = M[pos] (the operand rows the other ranks read).  Backward: the gradient rows that came back from those
-    ranks — `_ExchangedRows.backward` STARTED their exchange and handed the receive buffer on; here, after the backward
-    of the product over this rank's own columns (created later in the forward: autograd runs it first), the stream waits
-    for it and adds the rows into the operand's gradient."""
-
-    @staticmethod
-    def forward(ctx, M, pos, back: _Pending):
-        ctx.back, ctx.n = back, M.shape[0]
-        ctx.save_for_backward(pos)
-        return M.index_select(0, pos)
-
-    @staticmethod
-    def backward(ctx, g):
-        (pos,) = ctx.saved_tensors
-        wait_rows_exchange(ctx.back)
-        dM = torch.zeros((ctx.n,) + tuple(g.shape[1:]), dtype=g.dtype, device=g.device)
-        dM.index_add_(0, pos, g)
-        return dM, None, None
-
-
-class _ExchangedRows(torch.autograd.Function):
-    """The autograd node of the operand-row exchange.  Forward: the exchange itself was started earlier
-    (`start_rows_exchange`, before the product over the rank's own columns); this node waits for it and returns the
-    received rows.  It is created AFTER that product, so that in the backward it runs BEFORE the product's: the reverse
-    exchange (gradient rows back to their senders) is started here and is in flight under the own product's backward;
-    `_SendRows.backward` waits for it."""
-
-    @staticmethod
-    def forward(ctx, send, in_splits, out_splits, group, fwd: _Pending, back: _Pending):
-        ctx.in_splits, ctx.out_splits, ctx.group, ctx.back = in_splits, out_splits, group, back
-        wait_rows_exchange(fwd)
-        return fwd.buf.view_as(fwd.buf)
-
-    @staticmethod
-    def backward(ctx, g):
-        out = start_rows_exchange(g.contiguous(), ctx.out_splits, ctx.in_splits, ctx.group, ctx.back)
-        return out, None, None, None, None, None
-
-
-# ---- the two local halves of a layer as autograd functions -----------------------------------------------------------
+# ---- the whole layer as ONE autograd function: forward with the exchange under the own product, backward on gradient
+# ---- supports ------------------------------------------------------------------------------------------------------------
 def _stream(dev) -> int:
     return torch.cuda.current_stream(dev).cuda_stream
-
-
-class _OperandFn(torch.autograd.Function):
-    """M = the compact operand of graph.py:69-94 for the columns of `plan` (operand order, ld = functional._ld_for(F)):
-    M[c] = comp_I[r_c] . V_I[j_c] (or weight_I[r_c*N + j_c]) + X[j_c] . W_F[r_c].  The backward takes the gradient of
-    those rows and runs the plan-level kernels (no gradient-sparsity shortcut)."""
-
-    @staticmethod
-    def forward(ctx, plan: GraphPlan, F: int, weight_I, comp_I, X, W_F):
-        lib = L.load()
-        dev = plan.device
-        ld = Fn._ld_for(F)
-        M = torch.empty((plan.nop, ld), dtype=torch.float32, device=dev)
-        s = _stream(dev)
-        Xc = Wc = None
-        with torch.cuda.device(dev):
-            addend, ldA = 0, 0
-            if X is not None:
-                Xc = X if (X.dim() == 2 and X.stride(1) == 1) else X.contiguous()
-                Wc = W_F.contiguous()
-                if weight_I is not None:
-                    ldA = (F + 3) // 4 * 4
-                    M2 = torch.empty((plan.ncols, ldA), dtype=torch.float32, device=dev)
-                    out, ldo, order = M2, ldA, 0
-                    addend = M2.data_ptr()
-                else:
-                    out, ldo, order = M, ld, 1
-                L.check(lib.mrgcn_rel_transform_fwd_f32(plan.handle, Xc.data_ptr(), Xc.stride(0), Xc.shape[1],
-                                                        Wc.data_ptr(), F, out.data_ptr(), ldo, order, s),
-                        "mrgcn_rel_transform_fwd_f32")
-            if weight_I is not None:
-                wI = weight_I.contiguous()
-                if comp_I is not None:
-                    cI = comp_I.contiguous()
-                    L.check(lib.mrgcn_basis_mix_fwd_f32(plan.handle, wI.data_ptr(), cI.data_ptr(), cI.shape[1], F, addend,
-                                                        ldA, M.data_ptr(), ld, s), "mrgcn_basis_mix_fwd_f32")
-                else:
-                    L.check(lib.mrgcn_gather_rows_f32(plan.handle, wI.data_ptr(), F, addend, ldA, M.data_ptr(), ld, s),
-                            "mrgcn_gather_rows_f32")
-        plan.replicate(M)
-        ctx.plan, ctx.F = plan, F
-        ctx.has = (weight_I is not None, comp_I is not None, X is not None)
-        ctx.save_for_backward(weight_I, comp_I, Xc, Wc)
-        return M
-
-    @staticmethod
-    def backward(ctx, dM_op):
-        lib = L.load()
-        plan, F = ctx.plan, ctx.F
-        weight_I, comp_I, X, W_F = ctx.saved_tensors
-        has_I, has_comp, has_X = ctx.has
-        dev = plan.device
-        s = _stream(dev)
-        ld = (F + 3) // 4 * 4
-        # the gradient rows in plain compact order, as the node-major consumers read them
-        dM = torch.zeros((plan.ncols, ld), dtype=torch.float32, device=dev)
-        dM[:, :F] = dM_op.index_select(0, _mpos_long(plan))[:, :F]
-        d_wI = d_comp = dX = dW = None
-        with torch.cuda.device(dev):
-            if has_I and has_comp:
-                wI = weight_I.contiguous()
-                Bn = wI.shape[1]
-                d_wI, d_comp = torch.empty_like(wI), torch.empty_like(comp_I)
-                L.check(lib.mrgcn_basis_mix_bwd_f32(plan.handle, dM.data_ptr(), ld, 0, wI.data_ptr(),
-                                                    comp_I.contiguous().data_ptr(), Bn, F, d_wI.data_ptr(), 0,
-                                                    d_comp.data_ptr(), 0, s), "mrgcn_basis_mix_bwd_f32")
-            elif has_I:
-                d_wI = torch.zeros_like(weight_I)
-                d_wI.index_copy_(0, plan.ulcol_long(), dM[:, :F])
-            if has_X:
-                need_dX, need_dW = ctx.needs_input_grad[4], ctx.needs_input_grad[5]
-                K = X.shape[1]
-                if need_dX or need_dW:
-                    nws = int(lib.mrgcn_rel_transform_bwd_workspace(plan.handle, K, F, int(need_dX), int(need_dW)))
-                    ws = torch.empty((max(nws, 1),), dtype=torch.float32, device=dev)
-                    if need_dX:
-                        dX = torch.empty((X.shape[0], K), dtype=torch.float32, device=dev)
-                    if need_dW:
-                        dW = torch.empty_like(W_F)
-                    L.check(lib.mrgcn_rel_transform_bwd_masked_f32(
-                        plan.handle, dM.data_ptr(), ld, 0, X.data_ptr(), X.stride(0), K, W_F.data_ptr(), F,
-                        dX.data_ptr() if need_dX else 0, K, dW.data_ptr() if need_dW else 0, ws.data_ptr(), nws, 0, 0, 0,
-                        s), "mrgcn_rel_transform_bwd_masked_f32")
-        return None, None, d_wI, d_comp, dX, dW
-
-
-def _mpos_long(plan: GraphPlan) -> torch.Tensor:
-    t = plan.__dict__.get("_mpos_long")
-    if t is None:
-        t = plan.__dict__["_mpos_long"] = torch.from_numpy(plan.export(L.ARR_MPOS).astype(np.int64)).to(plan.device)
-    return t
-
-
-class _ProductFn(torch.autograd.Function):
-    """Y = relu?( A' . M + b ) on the COMPACT view of `plan` (M in operand order); backward: A'^T dY by compact column,
-    scattered back into operand order."""
-
-    @staticmethod
-    def forward(ctx, plan: GraphPlan, M, F: int, bias, relu: bool):
-        Y = plan.spmm(L.VIEW_COMPACT, M.contiguous(), F=F, bias=bias, relu=relu)
-        ctx.plan, ctx.F, ctx.relu, ctx.has_bias, ctx.shape = plan, F, relu, bias is not None, tuple(M.shape)
-        ctx.save_for_backward(Y if relu else None)
-        return Y
-
-    @staticmethod
-    def backward(ctx, dY):
-        plan, F = ctx.plan, ctx.F
-        (Y,) = ctx.saved_tensors
-        dY = dY.contiguous()
-        if ctx.relu:
-            dY = Fn.relu_bwd(dY, Y)
-        dbias = Fn._bias_grad(dY) if ctx.has_bias else None
-        ld = (F + 3) // 4 * 4
-        dMc = torch.empty((plan.ncols, ld), dtype=torch.float32, device=dY.device)
-        plan.spmm(L.VIEW_TRANSPOSED, dY, F=F, out=dMc)
-        dM = torch.zeros(ctx.shape, dtype=torch.float32, device=dY.device)
-        dM[:, :F].index_copy_(0, _mpos_long(plan), dMc[:, :F])
-        return None, dM, None, dbias, None
-
-
-# ---- the whole layer as ONE autograd function: forward with the exchange under the own product, backward on gradient
-# ---- supports (round 6) ------------------------------------------------------------------------------------------------
-def _operand_forward(plan: GraphPlan, F: int, weight_I, comp_I, X, W_F):
-    """_OperandFn.forward's kernels: the compact operand of `plan`'s columns in operand order.  Returns (M, Xc, Wc)."""
-    lib = L.load()
-    dev = plan.device
-    ld = Fn._ld_for(F)
-    M = torch.empty((plan.nop, ld), dtype=torch.float32, device=dev)
-    s = _stream(dev)
-    Xc = Wc = None
-    with torch.cuda.device(dev):
-        addend, ldA = 0, 0
-        if X is not None:
-            Xc = X if (X.dim() == 2 and X.stride(1) == 1) else X.contiguous()
-            Wc = W_F.contiguous()
-            if weight_I is not None:
-                ldA = (F + 3) // 4 * 4
-                M2 = torch.empty((plan.ncols, ldA), dtype=torch.float32, device=dev)
-                out, ldo, order = M2, ldA, 0
-                addend = M2.data_ptr()
-            else:
-                out, ldo, order = M, ld, 1
-            L.check(lib.mrgcn_rel_transform_fwd_f32(plan.handle, Xc.data_ptr(), Xc.stride(0), Xc.shape[1],
-                                                    Wc.data_ptr(), F, out.data_ptr(), ldo, order, s),
-                    "mrgcn_rel_transform_fwd_f32")
-        if weight_I is not None:
-            wI = weight_I.contiguous()
-            if comp_I is not None:
-                cI = comp_I.contiguous()
-                L.check(lib.mrgcn_basis_mix_fwd_f32(plan.handle, wI.data_ptr(), cI.data_ptr(), cI.shape[1], F, addend,
-                                                    ldA, M.data_ptr(), ld, s), "mrgcn_basis_mix_fwd_f32")
-            else:
-                L.check(lib.mrgcn_gather_rows_f32(plan.handle, wI.data_ptr(), F, addend, ldA, M.data_ptr(), ld, s),
-                        "mrgcn_gather_rows_f32")
-    return M, Xc, Wc
-
-
-class _Ctx:
-    """what functional._support_backward_from_dM reads off an autograd context"""
-    __slots__ = ("plan", "F", "saved_tensors", "has", "needs_input_grad", "owner", "x_is_relu_out", "Xb")
 
 
 class _HaloLayerFn(torch.autograd.Function):
@@ -360,7 +156,11 @@ class _HaloLayerFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, hp, group, F: int, relu: bool, weight_I, comp_I, X, W_F, bias, owner):
-        M_col, Xc, Wc = _operand_forward(hp.p_col, F, weight_I, comp_I, X, W_F)
+        # (fp32 operand; the input as it is: no bf16 rows, no line-aligned copy)
+        Xc = Wc = None
+        if X is not None:
+            Xc, Wc = X if (X.dim() == 2 and X.stride(1) == 1) else X.contiguous(), W_F.contiguous()
+        M_col = Fn._operand_forward(hp.p_col, F, weight_I, comp_I, Xc, None, Wc)
         ld = M_col.shape[1]
         pend = _Pending()
         send = M_col.index_select(0, hp.send_pos)
@@ -378,7 +178,7 @@ class _HaloLayerFn(torch.autograd.Function):
         if relu:
             Y = torch.relu_(Y)
         ctx.hp, ctx.group, ctx.F, ctx.relu, ctx.owner = hp, group, F, relu, owner
-        ctx.has = (weight_I is not None, comp_I is not None, X is not None, bias is not None)
+        ctx.has_bias = bias is not None
         ctx.x_is_relu_out = X is not None and bool(getattr(X, "_mrgcn_relu_out", False))
         ctx.save_for_backward(weight_I, comp_I, Xc, Wc, Y if relu else None)
         return Y
@@ -388,28 +188,24 @@ class _HaloLayerFn(torch.autograd.Function):
         lib = L.load()
         hp, group, F = ctx.hp, ctx.group, ctx.F
         weight_I, comp_I, X, W_F, Y = ctx.saved_tensors
-        has_I, has_comp, has_X, has_bias = ctx.has
         dev = hp.device
         meta = Fn._grad_meta(dY)
         dY = dY.contiguous()
         if ctx.relu and not (meta is not None and meta.get("relu_applied")):
             dY = Fn.relu_bwd(dY, Y)
         flags = meta["row_live"] if (meta and meta.get("structural")) else None
-        dbias = Fn._bias_grad(dY, flags) if has_bias else None
+        dbias = Fn._bias_grad(dY, flags) if ctx.has_bias else None
         ld = (F + 3) // 4 * 4
         s = _stream(dev)
-        shim = _Ctx()
-        shim.plan, shim.F, shim.has, shim.owner, shim.Xb = hp.p_col, F, ctx.has, ctx.owner, None
-        shim.saved_tensors, shim.x_is_relu_out = ctx.saved_tensors, ctx.x_is_relu_out
-        # (positions of _RgcnLayer.forward's arguments: [4] = X, [5] = W_F)
-        shim.needs_input_grad = (False, False, ctx.needs_input_grad[4], ctx.needs_input_grad[5], ctx.needs_input_grad[6],
-                                 ctx.needs_input_grad[7], False, False, False, False)
+        # (this function's own argument order: [6] = X, [7] = W_F)
+        lay = Fn._LayerView(hp.p_col, F, weight_I, comp_I, X, W_F, X is not None and ctx.needs_input_grad[6],
+                            X is not None and ctx.needs_input_grad[7], ctx.owner, ctx.x_is_relu_out, None, None)
         use_sup = (flags is not None and F <= 16 and Fn._SUPPORT and Fn._LIVE_COLS and flags.dtype == torch.uint8
                    and flags.numel() == hp.p_own.num_rows and flags.device == dev)
         live = nws = None
         if use_sup:
             live = hp.live(flags)
-            nws = Fn._support_backward_workspace(shim, live["sup_col"])
+            nws = Fn._support_backward_workspace(lay, live["sup_col"])
         if live is not None and nws is not None:
             bump("backward.support")
             bump("halo.backward.support")
@@ -433,8 +229,7 @@ class _HaloLayerFn(torch.autograd.Function):
             wait_rows_exchange(back)
             if back.buf.shape[0] > 0:
                 dM_col.index_add_(0, live["recv_to_col"], back.buf)
-            out = Fn._support_backward_from_dM(shim, sup_col, dM_col, ld, dbias, nws)
-            _, _, d_wI, d_comp, dX, dW, dbias, _, _, _ = out
+            d_wI, d_comp, dX, dW = Fn._support_backward_from_dM(lay, sup_col, dM_col, ld, nws)
             return None, None, None, None, d_wI, d_comp, dX, dW, dbias, None
         # ---- dense gradient: general transposed products, plan-level backward in P_col's compact order ----------------
         bump("halo.backward.dense")
@@ -454,32 +249,7 @@ class _HaloLayerFn(torch.autograd.Function):
         wait_rows_exchange(back)
         if back.buf.shape[0] > 0:
             dM[:, :F].index_add_(0, hp.send_cid, back.buf[:, :F])
-        d_wI = d_comp = dX = dW = None
-        with torch.cuda.device(dev):
-            if has_I and has_comp:
-                wI = weight_I.contiguous()
-                Bn = wI.shape[1]
-                d_wI, d_comp = torch.empty_like(wI), torch.empty_like(comp_I)
-                L.check(lib.mrgcn_basis_mix_bwd_f32(p_col.handle, dM.data_ptr(), ld, 0, wI.data_ptr(),
-                                                    comp_I.contiguous().data_ptr(), Bn, F, d_wI.data_ptr(), 0,
-                                                    d_comp.data_ptr(), 0, s), "mrgcn_basis_mix_bwd_f32")
-            elif has_I:
-                d_wI = torch.zeros_like(weight_I)
-                d_wI.index_copy_(0, p_col.ulcol_long(), dM[:, :F])
-            if has_X:
-                need_dX, need_dW = ctx.needs_input_grad[6], ctx.needs_input_grad[7]
-                K = X.shape[1]
-                if need_dX or need_dW:
-                    nw = int(lib.mrgcn_rel_transform_bwd_workspace(p_col.handle, K, F, int(need_dX), int(need_dW)))
-                    ws = torch.empty((max(nw, 1),), dtype=torch.float32, device=dev)
-                    if need_dX:
-                        dX = torch.empty((X.shape[0], K), dtype=torch.float32, device=dev)
-                    if need_dW:
-                        dW = torch.empty_like(W_F)
-                    L.check(lib.mrgcn_rel_transform_bwd_masked_f32(
-                        p_col.handle, dM.data_ptr(), ld, 0, X.data_ptr(), X.stride(0), K, W_F.data_ptr(), F,
-                        dX.data_ptr() if need_dX else 0, K, dW.data_ptr() if need_dW else 0, ws.data_ptr(), nw, 0, 0, 0,
-                        s), "mrgcn_rel_transform_bwd_masked_f32")
+        d_wI, d_comp, dX, dW = Fn._grads_from_dM(lay, dM, ld, None, None, s, plain=True)
         return None, None, None, None, d_wI, d_comp, dX, dW, dbias, None
 
 
@@ -632,68 +402,11 @@ class HaloPlans:
 
 
 # ---- the model -----------------------------------------------------------------------------------------------------------
-class HaloPartitionedRGCN(nn.Module):
+class HaloPartitionedRGCN(_PartitionedModel):
     """`RGCN` (models/rgcn.py) with the row partition + operand-row halo exchange.  Same constructor and sharding of the
     parameters as `partition.PartitionedRGCN`."""
 
-    def __init__(self, modules, num_relations, num_nodes, num_bases, featureless, bias, part: NodePartition, group=None,
-                 link_prediction=False, num_blocks=-1):
-        super().__init__()
-        if num_blocks is not None and num_blocks > 0:
-            raise L.MrgcnError("num_blocks: the partitioned engines have no block-diagonal feature term (models.rgcn.RGCN "
-                               "runs it on one device)")
-        if link_prediction:
-            self.relations = nn.Parameter(torch.empty((num_relations, modules[-1][1])))
-            nn.init.xavier_uniform_(self.relations)
-        self.part, self.group = part, group
-        self.num_nodes, self.num_relations, self.num_bases = num_nodes, num_relations, num_bases
-        self.layers = nn.ModuleDict()
-        self.relu = []
-        for i, (indim, outdim, _t, act) in enumerate(modules):
-            first = i == 0
-            self.layers[f"layer_{i}"] = GraphConvolution(
-                indim, outdim, num_relations, part.S, num_bases=num_bases, bias=bias, input_layer=first,
-                featureless=featureless if first else False)
-            self.relu.append(isinstance(act, nn.ReLU))
-        self.num_layers = len(self.layers)
-        self.plans = None
-
-    # (the same sharding helpers as the column-partition model)
-
-    def set_node_dropout(self, mode: str, seed=None):
-        """The partitioned engines have no node dropout on the device (models/rgcn.py: RGCN.set_node_dropout)."""
-        if mode != "host":
-            raise Fn.L.MrgcnError(f"{type(self).__name__}: node dropout mode {mode!r} is outside the partitioned engines "
-                                  "(the single-GPU RGCN on the fused engine draws on the device)")
-        return self
-
-    def set_edge_dropout(self, p: float = 0.0, self_loop=None, rates=None, rescale: bool = True, seed=None):
-        """The partitioned engines have no edge dropout (models/rgcn.py: RGCN.set_edge_dropout)."""
-        if any(float(r) != 0.0 for r in (rates if rates is not None else (p, self_loop or 0.0))):
-            raise Fn.L.MrgcnError(f"{type(self).__name__}: edge dropout is outside the partitioned engines (their "
-                                  "backward runs on gradient supports, which copy the plan's values; the single-GPU "
-                                  "RGCN on the fused engine draws into value overlays)")
-        return self
-
-    def sharded_parameters(self):
-        return [l.weight_I for l in self.layers.values() if l.weight_I is not None]
-
-    def replicated_parameters(self):
-        sh = {id(p) for p in self.sharded_parameters()}
-        return [p for p in self.parameters() if id(p) not in sh]
-
-    @torch.no_grad()
-    def load_full_state(self, state: dict):
-        if "relations" in state and hasattr(self, "relations"):
-            self.relations.copy_(state["relations"].to(self.relations.device))
-        for i, layer in enumerate(self.layers.values()):
-            for name, p in layer.named_parameters():
-                full = state[f"layers.layer_{i}.{name}"].to(p.device)
-                if name == "weight_I":
-                    S_b = self.num_bases if self.num_bases > 0 else self.num_relations
-                    p.copy_(self.part.shard_weight_I(full, S_b, node_major=layer.weight_I_node_major))
-                else:
-                    p.copy_(full)
+    plans = None
 
     def build_plan(self, rows, cols, vals, device):
         rb = sorted({l.operand_row_bytes() for l in self.layers.values()})
@@ -701,11 +414,6 @@ class HaloPartitionedRGCN(nn.Module):
         return self.plans
 
     def forward(self, X_local):
-        if not _COMPOSED:
-            return self._forward_fused(X_local)
-        return self._forward_composed(X_local)
-
-    def _forward_fused(self, X_local):
         """every layer one autograd function (`_HaloLayerFn`): backward on gradient supports"""
         hp = self.plans
         H = X_local
@@ -725,57 +433,6 @@ class HaloPartitionedRGCN(nn.Module):
                 H._mrgcn_relu_out = True
         return H
 
-    def _forward_composed(self, X_local):
-        """the round-5 form: the layer composed of autograd pieces (MRGCN_HALO_COMPOSED=1; dense backward)"""
-        hp = self.plans
-        H = X_local
-        for i, layer in enumerate(self.layers.values()):
-            F, B = layer.outdim, layer.num_bases
-            weight_I = comp_I = Xin = W_F = None
-            if layer.input_layer:
-                weight_I = layer.weight_I
-                comp_I = layer.weight_I_comp if B > 0 else None
-            if not (layer.input_layer and layer.featureless):
-                Xin, W_F = H, layer.weight_F
-                if B > 0:
-                    W_F = Fn._BasisContract.apply(layer.weight_F_comp, W_F)
-            M_col = _OperandFn.apply(hp.p_col, F, weight_I, comp_I, Xin, W_F)           # my columns' operand rows
-            # the rows the other ranks read leave first; the product over my own columns runs under the exchange — and
-            # its backward under the reverse exchange (see _ExchangedRows)
-            fwd, back = _Pending(), _Pending()
-            send = _SendRows.apply(M_col, hp.send_pos, back)
-            start_rows_exchange(send, hp.in_splits, hp.out_splits, self.group, fwd)
-            M_own = torch.zeros((hp.p_own.nop, M_col.shape[1]), dtype=torch.float32, device=M_col.device)
-            M_own = M_own.index_copy(0, hp.own_dst, M_col.index_select(0, hp.own_src))
-            b = layer.b if layer.bias else None
-            Y = _ProductFn.apply(hp.p_own, M_own, F, None, False)
-            recv = _ExchangedRows.apply(send, hp.in_splits, hp.out_splits, self.group, fwd, back)
-            if hp.halo_columns > 0:
-                M_halo = torch.zeros((hp.p_halo.nop, M_col.shape[1]), dtype=torch.float32, device=M_col.device)
-                M_halo = M_halo.index_copy(0, hp.halo_dst, recv)
-                Y = Y + _ProductFn.apply(hp.p_halo, M_halo, F, None, False)
-            else:   # (a rank that reads no remote column still takes part in the backward's exchange)
-                Y = Y + recv.sum() * 0.0
-            if b is not None:
-                Y = Y + b
-            H = torch.relu(Y) if self.relu[i] else Y
-        return H
-
-    @torch.no_grad()
-    def sync_replicated(self, src: int = 0):
-        for q in self.replicated_parameters():
-            if _staged(q, self.group):
-                buf = q.detach().cpu()
-                dist.broadcast(buf, src, group=self.group)
-                q.copy_(buf.to(q.device))
-            else:
-                dist.broadcast(q.data, src, group=self.group)
-
-    def allreduce_replicated_grads(self):
-        for p in self.replicated_parameters():
-            if p.grad is not None:
-                all_reduce_sum_(p.grad, self.group)
-
 
 def halo_train_step(model: HaloPartitionedRGCN, X_local, idx_global, targets, optimizer, row_sparse=None):
     """One full-batch epoch on the halo engine: dense gradients (`.grad` of every parameter), the replicated ones
@@ -788,7 +445,7 @@ def halo_train_step(model: HaloPartitionedRGCN, X_local, idx_global, targets, op
     optimizer.zero_grad(set_to_none=True)
     # (as partition._backward_and_step: row-sparse weight_I gradient + fused row Adam on this rank's node blocks when
     # the backward runs on gradient supports)
-    sparse_ok = (row_sparse is not False and not _COMPOSED and _ROW_SPARSE_DEFAULT and isinstance(optimizer, ClipAdam)
+    sparse_ok = (row_sparse is not False and _ROW_SPARSE_DEFAULT and isinstance(optimizer, ClipAdam)
                  and all(float(g["weight_decay"]) == 0.0 for g in optimizer.param_groups))
     prev = Fn.row_sparse_weight_grad(sparse_ok)
     try:

@@ -1008,8 +1008,8 @@ def test_a_plain_dense_gradient_finds_its_gradient_support():
     taken = []
     orig = Fn._RgcnLayer._backward_on_support
 
-    def spy(ctx, sup, dY, dbias):
-        out = orig(ctx, sup, dY, dbias)
+    def spy(lay, sup, dY):
+        out = orig(lay, sup, dY)
         taken.append(out is not None)
         return out
     for rows_ in sets:
@@ -1027,6 +1027,29 @@ def test_a_plain_dense_gradient_finds_its_gradient_support():
             torch.testing.assert_close(a, b, rtol=1e-4, atol=1e-5)   # (another summation order)
     assert taken == [True] * len(sets), taken
     assert int(layer.__dict__["_mrgcn_found_rows"].sum()) == 42   # the union of every set seen
+
+
+@pytest.mark.parametrize("F", [12, 10])
+def test_literal_gradient_from_plain_compact_dM_is_the_index_copy_bit_for_bit(F):
+    """functional._grads_from_dM for a featureless layer without bases, every row of dM written (`live=None`: the halo
+    engine's dense backward): the (R*N) x F gradient of the literal table is dM's first F columns copied to the compact
+    columns' rows over zeros — bitwise `zeros.index_copy_(0, plan.ulcol_long(), dM[:, :F])`; with F = 10 in rows of
+    ld = 12 the pad columns (here nonzero) must not leak."""
+    from mrgcn_amd import functional as Fn
+    from mrgcn_amd.plan import plan_of
+    N, R, ld = 64, 3, 12
+    rng = np.random.default_rng(F)
+    rows, cols = rng.integers(0, N, 6 * N), rng.integers(0, R * N, 6 * N)
+    At = torch.sparse_coo_tensor(torch.from_numpy(np.stack([rows, cols])), torch.ones(6 * N), (N, R * N)).coalesce().cuda()
+    plan = plan_of(At, N, R)
+    assert 0 < plan.ncols < R * N
+    weight_I = torch.randn(R * N, F, device="cuda")
+    dM = torch.randn(plan.ncols, ld, device="cuda")
+    lay = Fn._LayerView(plan, F, weight_I, None, None, None, False, False, None, False, None, None)
+    d_wI, d_comp, dX, dW = Fn._grads_from_dM(lay, dM, ld, None, None, torch.cuda.current_stream().cuda_stream, plain=True)
+    want = torch.zeros_like(weight_I).index_copy_(0, plan.ulcol_long(), dM[:, :F])
+    assert d_wI.shape == want.shape and torch.equal(d_wI, want)
+    assert d_comp is None and dX is None and dW is None
 
 
 @pytest.mark.gpu

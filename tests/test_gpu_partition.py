@@ -439,8 +439,32 @@ def _halo_worker(rank, world, port, state, out, lp_mode=False, backend="gloo", r
         opt.set_distributed(None, model.sharded_parameters())
         tr, yy = torch.from_numpy(facts).to(dev), torch.from_numpy(Y).to(dev)
         emb0 = model(None).detach().cpu().numpy()[: part.n_local]
-        losses = [float(halo_lp_step(model, None, tr, yy, opt)) for _ in range(2)]
-        out[rank] = (emb0, losses, model.relations.detach().cpu().numpy(), hp.halo_columns)
+        losses = [float(halo_lp_step(model, None, tr, yy, opt))]
+        # the second step with the exchange calls and the own product logged (the dense route: the product over this
+        # rank's own columns is a Python call)
+        from mrgcn_amd import _lib as L
+        from mrgcn_amd import partition_halo as ph
+        log = []
+        real_start, real_wait, real_spmm = ph.start_rows_exchange, ph.wait_rows_exchange, hp.p_own.spmm
+
+        def logged_start(*a):
+            log.append("exchange started")
+            return real_start(*a)
+
+        def logged_wait(p):
+            log.append("exchange awaited")
+            return real_wait(p)
+
+        def logged_spmm(view, *a, **k):
+            log.append("own transposed product" if view == L.VIEW_TRANSPOSED else "own product")
+            return real_spmm(view, *a, **k)
+        ph.start_rows_exchange, ph.wait_rows_exchange, hp.p_own.spmm = logged_start, logged_wait, logged_spmm
+        try:
+            losses.append(float(halo_lp_step(model, None, tr, yy, opt)))
+        finally:
+            ph.start_rows_exchange, ph.wait_rows_exchange = real_start, real_wait
+            del hp.p_own.spmm
+        out[rank] = (emb0, losses, model.relations.detach().cpu().numpy(), hp.halo_columns, log)
         dist.destroy_process_group()
         return
     g, X, idx, y, mods = _problem()
@@ -557,3 +581,11 @@ def test_halo_engine_link_prediction_equals_single_gpu():
         np.testing.assert_allclose(out[r][1], losses, rtol=2e-4, atol=2e-5)
         d = np.abs(out[r][2] - model.relations.detach().cpu().numpy())
         assert (d > 2e-5).mean() < 5e-3 and d.max() <= 0.05
+    # the ORDER of a step on every rank: each layer's forward sends its operand rows off before the product over its own
+    # columns, and each layer's backward STARTS the reverse exchange of gradient rows, then runs the transposed product
+    # over its own columns, and only then waits for the rows (over RCCL: in flight under that product).  The values — a
+    # row's gradient comes back from the rank that read it — are what the comparisons above check.
+    fwd = ["exchange started", "own product", "exchange awaited"]
+    bwd = ["exchange started", "own transposed product", "exchange awaited"]
+    for r in (0, 1):
+        assert out[r][4] == fwd * len(mods) + bwd * len(mods), out[r][4]
