@@ -40,6 +40,12 @@ def _ptr(t):
     return C.c_void_p(t.data_ptr()) if t is not None else None
 
 
+def _or_dummy(t: torch.Tensor) -> torch.Tensor:
+    """A filter or exclusion list as the entries take it: an empty one as one zero (an empty tensor has no address;
+    the list is empty either way)."""
+    return t if t.numel() else torch.zeros(1, dtype=t.dtype, device=t.device)
+
+
 def _f32_rows(t: torch.Tensor, what: str) -> torch.Tensor:
     if not t.is_cuda:
         raise _lib.MrgcnError(f"{what} must live on the GPU (mrgcn_amd has no CPU decoder)")
@@ -118,142 +124,28 @@ class SortedTriples:
         return True
 
 
-class _DistMultScore(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, E, Rel, triples, static=None):
-        ctx.static = static
-        lib = _lib.load()
-        n, H = triples.shape[0], E.shape[1]
-        scores = torch.empty(n, dtype=torch.float32, device=E.device)
-        _lib.check(lib.mrgcn_distmult_score_f32(_ptr(E), E.stride(0), _ptr(Rel), Rel.stride(0), H,
-                                                _ptr(triples), n, _ptr(scores), _stream()), "distmult_score")
-        ctx.save_for_backward(E, Rel, triples)
-        return scores
-
-    @staticmethod
-    def backward(ctx, g):
-        E, Rel, triples = ctx.saved_tensors
-        lib = _lib.load()
-        g = g.contiguous().float()
-        if ctx.needs_input_grad[0] and ctx.needs_input_grad[1]:
-            # (both gradients out of ONE zeroed buffer: one fill launch per step instead of two)
-            off = (E.numel() + 3) // 4 * 4   # (dR keeps the buffer's 16-byte alignment)
-            buf = torch.zeros(off + Rel.numel(), dtype=torch.float32, device=E.device)
-            dE, dR = buf[:E.numel()].view(E.shape), buf[off:].view(Rel.shape)
-        else:
-            dE = torch.zeros_like(E, memory_format=torch.contiguous_format) if ctx.needs_input_grad[0] else None
-            dR = torch.zeros_like(Rel, memory_format=torch.contiguous_format) if ctx.needs_input_grad[1] else None
-        n = triples.shape[0]
-        st = ctx.static
-        if torch.are_deterministic_algorithms_enabled():
-            bump("deterministic.distmult_bwd")
-            _distmult_bwd_det(lib, E, Rel, triples, g, dE, dR, st)
-            return dE, dR, None, None
-        if st is not None and st.covers(triples) and os.environ.get("MRGCN_LP_SORTED_BWD", "1") != "0":
-            # the fixed facts through their stored orders (runs of equal targets summed in registers), the few
-            # freshly drawn ones behind them through the scatter kernel: no sort in the epoch
-            ns = len(st)
-            _lib.check(lib.mrgcn_distmult_score_bwd_sorted_f32(
-                _ptr(E), E.stride(0), _ptr(Rel), Rel.stride(0), E.shape[1], _ptr(triples), ns, _ptr(g),
-                _ptr(st.order[0]), _ptr(st.order[1]), _ptr(st.order[2]), _ptr(dE), dE.stride(0) if dE is not None else 0,
-                _ptr(dR), dR.stride(0) if dR is not None else 0, _stream()), "distmult_score_bwd_sorted")
-            if n > ns:
-                tail, gtail, nt = C.c_void_p(triples.data_ptr() + 24 * ns), C.c_void_p(g.data_ptr() + 4 * ns), n - ns
-                if (nt >= 1024 and E.shape[0] <= (1 << 22) and Rel.shape[0] <= (1 << 22)
-                        and os.environ.get("MRGCN_LP_COUNTING", "1") != "0"):
-                    # enough of them to collide in the scatter kernel's atomics (54 k corrupted facts on 237 relation
-                    # rows: 310 us at the FB15k-237 shape): a counting sort (four launches) and the sorted passes
-                    o3 = st.tail_orders(nt, E.shape[0], Rel.shape[0])
-                    _lib.check(lib.mrgcn_distmult_orders_counting(
-                        tail, nt, E.shape[0], Rel.shape[0], _ptr(o3[0]), _ptr(o3[1]), _ptr(o3[2]), _ptr(o3[3]),
-                        o3[3].numel(), _stream()), "distmult_orders_counting")
-                    _lib.check(lib.mrgcn_distmult_score_bwd_sorted_f32(
-                        _ptr(E), E.stride(0), _ptr(Rel), Rel.stride(0), E.shape[1], tail, nt, gtail, _ptr(o3[0]),
-                        _ptr(o3[1]), _ptr(o3[2]), _ptr(dE), dE.stride(0) if dE is not None else 0, _ptr(dR),
-                        dR.stride(0) if dR is not None else 0, _stream()), "distmult_score_bwd_sorted")
-                else:
-                    _lib.check(lib.mrgcn_distmult_score_bwd_f32(
-                        _ptr(E), E.stride(0), _ptr(Rel), Rel.stride(0), E.shape[1], tail, nt, gtail, _ptr(dE),
-                        dE.stride(0) if dE is not None else 0, _ptr(dR), dR.stride(0) if dR is not None else 0,
-                        _stream()), "distmult_score_bwd")
-            return dE, dR, None, None
-        if n >= _SORTED_BWD_MIN and os.environ.get("MRGCN_LP_SORTED_BWD", "1") != "0":
-            # runs of equal subject / predicate / object are summed in registers (three passes over
-            # sorted triples) instead of one float atomic per triple and feature
-            order = [torch.empty(n, dtype=torch.int64, device=E.device) for _ in range(3)]
-            ws = torch.empty(int(lib.mrgcn_distmult_orders_workspace(n)), dtype=torch.uint8, device=E.device)
-            _lib.check(lib.mrgcn_distmult_orders(_ptr(triples), n, E.shape[0], Rel.shape[0], _ptr(order[0]),
-                                                 _ptr(order[1]), _ptr(order[2]), _ptr(ws), ws.numel(), _stream()),
-                       "distmult_orders")
-            _lib.check(lib.mrgcn_distmult_score_bwd_sorted_f32(
-                _ptr(E), E.stride(0), _ptr(Rel), Rel.stride(0), E.shape[1], _ptr(triples), n, _ptr(g),
-                _ptr(order[0]), _ptr(order[1]), _ptr(order[2]), _ptr(dE), dE.stride(0) if dE is not None else 0,
-                _ptr(dR), dR.stride(0) if dR is not None else 0, _stream()), "distmult_score_bwd_sorted")
-        else:
-            _lib.check(lib.mrgcn_distmult_score_bwd_f32(
-                _ptr(E), E.stride(0), _ptr(Rel), Rel.stride(0), E.shape[1], _ptr(triples), n,
-                _ptr(g), _ptr(dE), dE.stride(0) if dE is not None else 0, _ptr(dR),
-                dR.stride(0) if dR is not None else 0, _stream()), "distmult_score_bwd")
-        return dE, dR, None, None
-
-
-def _distmult_bwd_det(lib, E, Rel, triples, g, dE, dR, st):
-    """The backward under torch.use_deterministic_algorithms(True): every dE / dRel row summed in a fixed order by one
-    owner (mrgcn_distmult_score_bwd_det_f32).  The stored facts of `st` go through their stored (stable) orders, the
-    triples behind them — or all of them without `st` — through a stable radix sort, or none up to _DET_SMALL_N (the
-    kernel then sorts them itself in one block)."""
-    n, H, dev = triples.shape[0], E.shape[1], E.device
-    lddE, lddR = (dE.stride(0) if dE is not None else 0), (dR.stride(0) if dR is not None else 0)
-
-    def run(tr, m, gm, orders):
-        ws = _det_scratch(dev, "distmult_bwd", int(lib.mrgcn_distmult_bwd_det_workspace(m, H)))
-        _lib.check(lib.mrgcn_distmult_score_bwd_det_f32(
-            _ptr(E), E.stride(0), _ptr(Rel), Rel.stride(0), H, tr, m, gm, _ptr(orders[0]), _ptr(orders[1]),
-            _ptr(orders[2]), _ptr(dE), lddE, _ptr(dR), lddR, _ptr(ws), ws.numel(), _stream()),
-            "distmult_score_bwd_det")
-
-    def stable_orders(tr, m, bufs):
-        _lib.check(lib.mrgcn_distmult_orders(tr, m, E.shape[0], Rel.shape[0], _ptr(bufs[0]), _ptr(bufs[1]),
-                                             _ptr(bufs[2]), _ptr(bufs[3]), bufs[3].numel(), _stream()),
-                   "distmult_orders")
-        return bufs[:3]
-
-    ns = 0
-    if st is not None and st.covers(triples) and os.environ.get("MRGCN_LP_SORTED_BWD", "1") != "0":
-        ns = len(st)
-        run(_ptr(triples), ns, _ptr(g), st.order)
-    m = n - ns
-    if m == 0:
-        return
-    tr, gm = C.c_void_p(triples.data_ptr() + 24 * ns), C.c_void_p(g.data_ptr() + 4 * ns)
-    if m <= _DET_SMALL_N:
-        run(tr, m, gm, [None] * 3)
-        return
-    if ns:
-        bufs = st.tail_orders_stable(m, E.shape[0], Rel.shape[0])
-    else:
-        bufs = [torch.empty(m, dtype=torch.int64, device=dev) for _ in range(3)]
-        bufs.append(torch.empty(int(lib.mrgcn_distmult_orders_workspace(m)), dtype=torch.uint8, device=dev))
-    run(tr, m, gm, stable_orders(tr, m, bufs))
-
-
-def score_distmult_bc(data, node_embeddings, edge_embeddings, static: "SortedTriples | None" = None):
-    """link_prediction.py:645-665 for the 1-D (s, p, o) index tensors train_model passes (or an int64 [n, 3] tensor).
-    `static`: the stored orders of the facts the triples START with (SortedTriples): the backward then sorts nothing."""
-    E = _f32_rows(node_embeddings, "node_embeddings")
-    Rel = _f32_rows(edge_embeddings, "edge_embeddings")
-    return _DistMultScore.apply(E, Rel, _triples(data, E.device), static)
-
-
-# ---- the ComplEx scorer beside DistMult (Trouillon et al. 2016; csrc/complex.hip) ---------------------------------
+# ---- the two scorers: DistMult, and ComplEx beside it (Trouillon et al. 2016; csrc/complex.hip) --------------------
 SCORERS = ("distmult", "complex")
 
 
-def _scorer(scorer, who: str) -> bool:
-    """The `scorer` keyword, checked before any kernel is touched -> is it ComplEx?"""
-    if scorer not in SCORERS:
-        raise _lib.MrgcnError(f"{who}: scorer is 'distmult' or 'complex', not {scorer!r}")
-    return scorer == "complex"
+class _Entries:
+    """One scorer's entries of the library — mrgcn_{scorer}_{score_f32, ranks_both, topk, typed_ranks, typed_topk} —
+    looked up by suffix on first use and kept: `entries(suffix)` -> (the entry, its `_workspace` twin or None, the
+    label an error of the entry carries).  `complex`: is the scorer ComplEx?"""
+
+    def __init__(self, scorer):
+        self.scorer, self.complex, self._kept = scorer, scorer == "complex", {}
+
+    def __call__(self, suffix):
+        e = self._kept.get(suffix)
+        if e is None:
+            lib, name = _lib.load(), f"mrgcn_{self.scorer}_{suffix}"
+            e = self._kept[suffix] = (getattr(lib, name), getattr(lib, name + "_workspace", None),
+                                      f"{self.scorer}_{suffix}".replace("_f32", ""))
+        return e
+
+
+_ENTRIES = {s: _Entries(s) for s in SCORERS}
 
 
 def _complex_width(H: int, who: str):
@@ -261,66 +153,148 @@ def _complex_width(H: int, who: str):
         raise _lib.MrgcnError(f"{who}: scorer='complex' reads a row as H / 2 complex numbers: the width {int(H)} is odd")
 
 
+def _scorer(scorer, who: str, H=None) -> _Entries:
+    """The `scorer` keyword, checked before any kernel is touched (with `H`: ComplEx's even width too) -> its
+    `_Entries`."""
+    if scorer not in SCORERS:
+        raise _lib.MrgcnError(f"{who}: scorer is 'distmult' or 'complex', not {scorer!r}")
+    if H is not None and scorer == "complex":
+        _complex_width(H, who)
+    return _ENTRIES[scorer]
+
+
 def _no_complex(scorer, who: str):
     """The entries whose ComplEx form is not built yet (csrc/lp_batches.hip's fused batch evaluation and run loop)."""
-    if _scorer(scorer, who):
+    if _scorer(scorer, who).complex:
         raise _lib.MrgcnError(f"{who}: scorer='complex' is not available in the mini-batch run loop and its fused "
                               "batch evaluation (csrc/lp_batches.hip scores DistMult only); use train_epoch / "
                               "evaluate_batches, or the full-batch `fit`")
 
 
-class _ComplexScore(torch.autograd.Function):
+# ---- the flat score backward: a plan of segments (pure), and one walk that runs it ----------------------------------
+_COUNTING_MIN = 1024          # triples behind the stored facts from which a counting sort and the sorted passes pay
+_COUNTING_MAX_IDS = 1 << 22   # mrgcn_distmult_orders_counting's tables: nodes and relations up to this many
+
+
+def _bwd_plan(scorer, n, stored, num_nodes, num_relations, deterministic, sorted_bwd=True):
+    """The segments of the backward of `n` scored triples, without a tensor or the library: a tuple of (start, count,
+    orders, kernel), empty segments left out.  `stored`: how many triples at the front are the facts of a covering
+    `SortedTriples` (None: there is none).  `orders` — "stored": the facts' stored orders; "counting": a counting sort
+    into the SortedTriples' kept buffers; "radix": the stable radix sort, into kept buffers behind a stored segment,
+    else into fresh ones; "self": none passed, the deterministic kernel sorts inside one block; None: the scatter
+    kernel takes none.  `kernel` — "sorted" (runs of equal targets summed in registers along the orders), "scatter"
+    (one float atomic per triple and feature), "det" (every row summed in a fixed order by one owner) or "complex"
+    (ComplEx's one route: stable orders, one owner per row, with or without torch's deterministic flag).
+    `sorted_bwd=False` (MRGCN_LP_SORTED_BWD=0) takes DistMult off the stored and sorted routes; ComplEx has no
+    other.  DESIGN §8 has the table."""
+    cx = scorer == "complex"
+    use = stored is not None and (sorted_bwd or cx)
+    ns = stored if use else 0
+    m = n - ns
+    if cx:
+        head, tail = "complex", ("radix", "complex")
+    elif deterministic:
+        head, tail = "det", ("self" if m <= _DET_SMALL_N else "radix", "det")
+    elif use:
+        # the fixed facts through their stored orders, the freshly drawn ones behind them through a counting sort (four
+        # launches) and the sorted passes once there are enough to collide in the scatter kernel's atomics (54 k
+        # corrupted facts on 237 relation rows: 310 us at the FB15k-237 shape): no radix sort in the epoch
+        counting = m >= _COUNTING_MIN and num_nodes <= _COUNTING_MAX_IDS and num_relations <= _COUNTING_MAX_IDS
+        head, tail = "sorted", (("counting", "sorted") if counting else (None, "scatter"))
+    else:
+        head, tail = None, (("radix", "sorted") if n >= _SORTED_BWD_MIN and sorted_bwd else (None, "scatter"))
+    return tuple(seg for seg in ((0, ns, "stored", head), (ns, m) + tail) if seg[1] > 0)
+
+
+def _grad_buffers(E, Rel, want_E: bool, want_R: bool):
+    """(dE, dR) zeroed, None where not wanted; both out of ONE buffer when both are (one fill launch per step instead
+    of two), dR keeping the buffer's 16-byte alignment."""
+    if want_E and want_R:
+        off = (E.numel() + 3) // 4 * 4
+        buf = torch.zeros(off + Rel.numel(), dtype=torch.float32, device=E.device)
+        return buf[:E.numel()].view(E.shape), buf[off:].view(Rel.shape)
+    return (torch.zeros_like(E, memory_format=torch.contiguous_format) if want_E else None,
+            torch.zeros_like(Rel, memory_format=torch.contiguous_format) if want_R else None)
+
+
+def _run_bwd_plan(plan, E, Rel, triples, g, dE, dR, static):
+    """Runs the segments of `_bwd_plan` on rows [start, start + count) of `triples` and `g`, adding into dE / dR."""
+    lib = _lib.load()
+    N, R, H, dev = E.shape[0], Rel.shape[0], E.shape[1], E.device
+    emb = (_ptr(E), E.stride(0), _ptr(Rel), Rel.stride(0), H)
+    out = (_ptr(dE), dE.stride(0) if dE is not None else 0, _ptr(dR), dR.stride(0) if dR is not None else 0)
+    for a, c, orders, kernel in plan:
+        tr, gs = (triples, g) if c == triples.shape[0] else (triples[a:a + c], g[a:a + c])
+        if orders == "stored":
+            o = static.order
+        elif orders == "counting":
+            o = static.tail_orders(c, N, R)
+            _lib.check(lib.mrgcn_distmult_orders_counting(_ptr(tr), c, N, R, _ptr(o[0]), _ptr(o[1]), _ptr(o[2]),
+                                                          _ptr(o[3]), o[3].numel(), _stream()), "distmult_orders_counting")
+        elif orders == "radix":
+            if a:
+                o = static.tail_orders_stable(c, N, R)
+            else:
+                o = [torch.empty(c, dtype=torch.int64, device=dev) for _ in range(3)]
+                o.append(torch.empty(int(lib.mrgcn_distmult_orders_workspace(c)), dtype=torch.uint8, device=dev))
+            _lib.check(lib.mrgcn_distmult_orders(_ptr(tr), c, N, R, _ptr(o[0]), _ptr(o[1]), _ptr(o[2]), _ptr(o[3]),
+                                                 o[3].numel(), _stream()), "distmult_orders")
+        else:
+            o = (None, None, None)
+        seg = emb + (_ptr(tr), c, _ptr(gs), _ptr(o[0]), _ptr(o[1]), _ptr(o[2])) + out
+        if kernel == "scatter":
+            _lib.check(lib.mrgcn_distmult_score_bwd_f32(*emb, _ptr(tr), c, _ptr(gs), *out, _stream()),
+                       "distmult_score_bwd")
+        elif kernel == "sorted":
+            _lib.check(lib.mrgcn_distmult_score_bwd_sorted_f32(*seg, _stream()), "distmult_score_bwd_sorted")
+        elif kernel == "det":
+            ws = _det_scratch(dev, "distmult_bwd", int(lib.mrgcn_distmult_bwd_det_workspace(c, H)))
+            _lib.check(lib.mrgcn_distmult_score_bwd_det_f32(*seg, _ptr(ws), ws.numel(), _stream()),
+                       "distmult_score_bwd_det")
+        else:
+            ws = _det_scratch(dev, "complex_bwd", int(lib.mrgcn_complex_bwd_workspace(c, H)))
+            _lib.check(lib.mrgcn_complex_score_bwd_f32(*seg, _ptr(ws), ws.numel(), _stream()), "complex_score_bwd")
+
+
+class _Score(torch.autograd.Function):
+    """The flat scores of either scorer; the backward is `_bwd_plan`'s, run by `_run_bwd_plan`."""
+
     @staticmethod
-    def forward(ctx, E, Rel, triples, static=None):
-        ctx.static = static
-        lib = _lib.load()
-        n, H = triples.shape[0], E.shape[1]
+    def forward(ctx, E, Rel, triples, static, scorer):
+        ctx.static, ctx.scorer = static, scorer
+        score, _, what = _ENTRIES[scorer]("score_f32")
+        n = triples.shape[0]
         scores = torch.empty(n, dtype=torch.float32, device=E.device)
-        _lib.check(lib.mrgcn_complex_score_f32(_ptr(E), E.stride(0), _ptr(Rel), Rel.stride(0), H, _ptr(triples), n,
-                                               _ptr(scores), _stream()), "complex_score")
+        _lib.check(score(_ptr(E), E.stride(0), _ptr(Rel), Rel.stride(0), E.shape[1], _ptr(triples), n, _ptr(scores),
+                         _stream()), what)
         ctx.save_for_backward(E, Rel, triples)
         return scores
 
     @staticmethod
     def backward(ctx, g):
-        # ONE route (DESIGN: "ComplEx"): runs of equal targets summed in registers along STABLE orders, every row by
-        # one owner — the stored facts of `static` through their stored orders, the triples behind them (or all of
-        # them) through the stable radix sort.  No float atomics with or without torch's deterministic flag.
         E, Rel, triples = ctx.saved_tensors
-        lib = _lib.load()
+        want_E, want_R = ctx.needs_input_grad[:2]
+        if not (want_E or want_R):
+            return None, None, None, None, None
         g = g.contiguous().float()
-        dE = torch.zeros_like(E, memory_format=torch.contiguous_format) if ctx.needs_input_grad[0] else None
-        dR = torch.zeros_like(Rel, memory_format=torch.contiguous_format) if ctx.needs_input_grad[1] else None
-        if dE is None and dR is None:
-            return None, None, None, None
-        if torch.are_deterministic_algorithms_enabled():
-            bump("deterministic.complex_bwd")
-        n, H, dev, st = triples.shape[0], E.shape[1], E.device, ctx.static
-        lddE, lddR = (dE.stride(0) if dE is not None else 0), (dR.stride(0) if dR is not None else 0)
+        dE, dR = _grad_buffers(E, Rel, want_E, want_R)
+        det = torch.are_deterministic_algorithms_enabled()
+        if det:
+            bump(f"deterministic.{ctx.scorer}_bwd")
+        st = ctx.static
+        stored = len(st) if st is not None and st.covers(triples) else None
+        plan = _bwd_plan(ctx.scorer, triples.shape[0], stored, E.shape[0], Rel.shape[0], det,
+                         os.environ.get("MRGCN_LP_SORTED_BWD", "1") != "0")
+        _run_bwd_plan(plan, E, Rel, triples, g, dE, dR, st)
+        return dE, dR, None, None, None
 
-        def run(tr, m, gm, orders):
-            ws = _det_scratch(dev, "complex_bwd", int(lib.mrgcn_complex_bwd_workspace(m, H)))
-            _lib.check(lib.mrgcn_complex_score_bwd_f32(
-                _ptr(E), E.stride(0), _ptr(Rel), Rel.stride(0), H, tr, m, gm, _ptr(orders[0]), _ptr(orders[1]),
-                _ptr(orders[2]), _ptr(dE), lddE, _ptr(dR), lddR, _ptr(ws), ws.numel(), _stream()), "complex_score_bwd")
 
-        ns = 0
-        if st is not None and st.covers(triples):
-            ns = len(st)
-            run(_ptr(triples), ns, _ptr(g), st.order)
-        m = n - ns
-        if m > 0:
-            tr, gm = C.c_void_p(triples.data_ptr() + 24 * ns), C.c_void_p(g.data_ptr() + 4 * ns)
-            if ns:
-                bufs = st.tail_orders_stable(m, E.shape[0], Rel.shape[0])
-            else:
-                bufs = [torch.empty(m, dtype=torch.int64, device=dev) for _ in range(3)]
-                bufs.append(torch.empty(int(lib.mrgcn_distmult_orders_workspace(m)), dtype=torch.uint8, device=dev))
-            _lib.check(lib.mrgcn_distmult_orders(tr, m, E.shape[0], Rel.shape[0], _ptr(bufs[0]), _ptr(bufs[1]),
-                                                 _ptr(bufs[2]), _ptr(bufs[3]), bufs[3].numel(), _stream()),
-                       "distmult_orders")
-            run(tr, m, gm, bufs[:3])
-        return dE, dR, None, None
+def score_distmult_bc(data, node_embeddings, edge_embeddings, static: "SortedTriples | None" = None):
+    """link_prediction.py:645-665 for the 1-D (s, p, o) index tensors train_model passes (or an int64 [n, 3] tensor).
+    `static`: the stored orders of the facts the triples START with (SortedTriples): the backward then sorts nothing."""
+    E = _f32_rows(node_embeddings, "node_embeddings")
+    Rel = _f32_rows(edge_embeddings, "edge_embeddings")
+    return _Score.apply(E, Rel, _triples(data, E.device), static, "distmult")
 
 
 def score_complex_bc(data, node_embeddings, edge_embeddings, static: "SortedTriples | None" = None):
@@ -329,12 +303,12 @@ def score_complex_bc(data, node_embeddings, edge_embeddings, static: "SortedTrip
     of the facts the triples START with; the triples behind them — freshly drawn negatives — are sorted anew by the
     stable radix sort).  An odd width raises `MrgcnError`."""
     H = int(node_embeddings.shape[-1])
-    _complex_width(H, "score_complex_bc")
+    _scorer("complex", "score_complex_bc", H)
     E = _f32_rows(node_embeddings, "node_embeddings")
     Rel = _f32_rows(edge_embeddings, "edge_embeddings")
     if Rel.shape[1] != H:
         raise ValueError("score_complex_bc: node and edge embeddings differ in width")
-    return _ComplexScore.apply(E, Rel, _triples(data, E.device), static)
+    return _Score.apply(E, Rel, _triples(data, E.device), static, "complex")
 
 
 class _BceLogits(torch.autograd.Function):
@@ -570,7 +544,7 @@ def pair_vectors(facts, E, Rel, side="both", scorer="distmult"):
     q = E[s] * Rel[p], target o; head q = Rel[p] * E[o], target s.  ComplEx: csrc/lp_score.hpp's pair vectors, real
     parts first — tail (xr rr - xi ri | xi rr + xr ri), head (rr xr + ri xi | rr xi - ri xr).  `side="both"`: the tail
     queries, then the head queries (m = 2 n).  `host.pair_vectors64` is the float64 mirror."""
-    cx = _scorer(scorer, "pair_vectors")
+    cx = _scorer(scorer, "pair_vectors").complex
     _all_side(side, "pair_vectors")
     H = int(E.shape[1])
     if cx:
@@ -855,7 +829,7 @@ def _decoder_args(decoder, loss, pos_weight, samplers, who, scorer="distmult", l
     epochs it builds) is taken as it is; the samplers are checked either way."""
     if isinstance(decoder, _Decoder):
         return decoder.checked(samplers, who)
-    cx = _scorer(scorer, who)
+    cx = _scorer(scorer, who).complex
     eps = _smoothing(label_smoothing, who)
     if decoder == "kvsall":
         if loss == "softmax":
@@ -1079,8 +1053,7 @@ class TypedCandidates:
             device = ptr.device if torch.is_tensor(ptr) and ptr.is_cuda else (
                 "cuda" if torch.cuda.is_available() else "cpu")
         self.ptr = torch.from_numpy(self.ptr_host).to(device)
-        # (an empty tensor has no address; the lists are empty either way)
-        self.idx = torch.from_numpy(self.idx_host if len(self.idx_host) else np.zeros(1, np.int32)).to(device)
+        self.idx = _dev_or_dummy(self.idx_host, device)
         self.lengths_host = np.diff(self.ptr_host)
         self._keys = None
 
@@ -1141,8 +1114,8 @@ def _relation_tiles(rel, what: str):
 
 
 def _dev_or_dummy(a: np.ndarray, device) -> torch.Tensor:
-    """A host array on the device; an empty one as one zero (an empty tensor has no address)."""
-    return torch.from_numpy(np.ascontiguousarray(a) if a.size else np.zeros(1, a.dtype)).to(device)
+    """A host array on the device, under `_or_dummy`'s rule."""
+    return _or_dummy(torch.from_numpy(np.ascontiguousarray(a)).to(device))
 
 
 class NegativeSampler:
@@ -1332,40 +1305,66 @@ def filter_lists(data: np.ndarray):
     return tp, ti, hp, hi
 
 
+def _rank_inputs(scorer, who, node_embeddings, edge_embeddings):
+    """What every rank and top-k entry starts with: the scorer keyword and ComplEx's even width checked first, then
+    the detached float32 tables of equal width -> (E, Rel, N, H, the scorer's `_Entries`)."""
+    entries = _scorer(scorer, who, node_embeddings.shape[-1])
+    E = _f32_rows(node_embeddings.detach(), "node_embeddings")
+    Rel = _f32_rows(edge_embeddings.detach(), "edge_embeddings")
+    N, H = int(E.shape[0]), int(E.shape[1])
+    if Rel.shape[1] != H:
+        raise ValueError(f"{who}: node and edge embeddings differ in width")
+    return E, Rel, N, H, entries
+
+
+def _check_lists(lists, nf, who):
+    ls = list(lists)
+    if len(ls) != 4 or not all(torch.is_tensor(a) and a.is_cuda for a in ls):
+        raise _lib.MrgcnError(f"{who}: lists are the four device tensors of filter_lists")
+    if not (ls[0].dtype == ls[2].dtype == torch.int64 and ls[1].dtype == ls[3].dtype == torch.int32
+            and ls[0].numel() == ls[2].numel() == nf + 1):
+        raise _lib.MrgcnError(f"{who}: lists are (int64 [n + 1], int32, int64 [n + 1], int32)")
+    return [_or_dummy(a.contiguous()) for a in ls]
+
+
+def _device_filter_lists(facts, device):
+    """`filter_lists(facts)` as the four device tensors the rank entries take."""
+    return [_or_dummy(torch.from_numpy(a).to(device)) for a in filter_lists(np.asarray(facts))]
+
+
+def _rank_one_side(E, Rel, tr, lists=None):
+    """mrgcn_distmult_ranks: the int64 [2 * nf] ranks of the device triples `tr` (tail corruption, then head
+    corruption) in one rank type — filtered by `lists` (`_device_filter_lists`), raw without."""
+    nf, N, H, dev = int(tr.shape[0]), E.shape[0], E.shape[1], E.device
+    ranks = torch.empty(2 * nf, dtype=torch.int64, device=dev)
+    if nf == 0:
+        return ranks
+    lib = _lib.load()
+    ls = lists if lists is not None else [None] * 4
+    ws_bytes = lib.mrgcn_distmult_ranks_workspace(N, H, nf)
+    ws = torch.empty((ws_bytes + 3) // 4, dtype=torch.int32, device=dev)
+    _lib.check(lib.mrgcn_distmult_ranks(_ptr(E), E.stride(0), N, _ptr(Rel), Rel.stride(0), H, _ptr(tr), nf,
+                                        _ptr(ls[0]), _ptr(ls[1]), _ptr(ls[2]), _ptr(ls[3]), _ptr(ws), ws_bytes,
+                                        _ptr(ranks), _stream()), "distmult_ranks")
+    return ranks
+
+
 def compute_ranks_fast(data, node_embeddings, edge_embeddings, batch_size=100, filtered=False, scorer="distmult"):
     """link_prediction.py:593-643.  Returns the int64 [2 * num_facts] ranks (tail corruption
     then head corruption) on the embeddings' device.  `batch_size` (the reference's
     mrr_batchsize, a memory knob for its [facts, nodes] score matrix) is accepted and unused:
     scores are never materialised here.  `scorer="complex"`: ComplEx scores (`rank_both` over one part; an odd width
     raises `MrgcnError`)."""
-    if _scorer(scorer, "compute_ranks_fast"):
-        _complex_width(node_embeddings.shape[-1], "compute_ranks_fast")
-    E = _f32_rows(node_embeddings.detach(), "node_embeddings")
-    Rel = _f32_rows(edge_embeddings.detach(), "edge_embeddings")
-    lib = _lib.load()
-    dev = E.device
+    E, Rel, _, _, entries = _rank_inputs(scorer, "compute_ranks_fast", node_embeddings, edge_embeddings)
     facts_np = data.cpu().numpy() if torch.is_tensor(data) else np.asarray(data)
-    if scorer == "complex":
-        if len(facts_np) == 0:
-            return torch.empty(0, dtype=torch.int64, device=dev)
-        lists = [torch.from_numpy(a).to(dev) for a in filter_lists(facts_np)] if filtered else None
-        raw, flt = rank_both(facts_np, E, Rel, lists=lists, scorer=scorer)
-        return flt if filtered else raw
-    tr = _triples(facts_np, dev)
-    nf, N, H = tr.shape[0], E.shape[0], E.shape[1]
-    ranks = torch.empty(2 * nf, dtype=torch.int64, device=dev)
-    if nf == 0:
-        return ranks
-    ws_bytes = lib.mrgcn_distmult_ranks_workspace(N, H, nf)
-    ws = torch.empty((ws_bytes + 3) // 4, dtype=torch.int32, device=dev)
-    lists = [None] * 4
-    if filtered:
-        lists = [torch.from_numpy(a).to(dev) for a in filter_lists(facts_np)]
-        lists = [a if a.numel() else torch.zeros(1, dtype=a.dtype, device=dev) for a in lists]
-    _lib.check(lib.mrgcn_distmult_ranks(_ptr(E), E.stride(0), N, _ptr(Rel), Rel.stride(0), H, _ptr(tr), nf,
-                                        _ptr(lists[0]), _ptr(lists[1]), _ptr(lists[2]), _ptr(lists[3]),
-                                        _ptr(ws), ws_bytes, _ptr(ranks), _stream()), "distmult_ranks")
-    return ranks
+    if not entries.complex:   # (`_triples` checks the shape, of an empty array too)
+        tr = _triples(facts_np, E.device)
+        return _rank_one_side(E, Rel, tr, _device_filter_lists(facts_np, E.device) if filtered and len(tr) else None)
+    if len(facts_np) == 0:
+        return torch.empty(0, dtype=torch.int64, device=E.device)
+    lists = _device_filter_lists(facts_np, E.device) if filtered else None
+    raw, flt = rank_both(facts_np, E, Rel, lists=lists, scorer=scorer)
+    return flt if filtered else raw
 
 
 def mrr_hits(ranks, K=(1, 3, 10)):
@@ -1576,8 +1575,7 @@ def evaluate_batches(batches, model, filtered=True, scorer="distmult"):
     computed once per batch and kept).  Returns (mrr, hits_at_k, rankings) as test_model does: {"raw", "flt"} means
     over the batches of the batches' MRR and hits@{1, 3, 10} (-1 for "flt" when not `filtered`), and the ranks of all
     batches flattened.  `scorer="complex"`: ComplEx scores (`rank_both` per batch)."""
-    cx = _scorer(scorer, "evaluate_batches")
-    lib = _lib.load()
+    _scorer(scorer, "evaluate_batches")
     model.eval()
     K = [1, 3, 10]
     hits_at_k = {"flt": [[] for _ in K], "raw": [[] for _ in K]}
@@ -1585,11 +1583,9 @@ def evaluate_batches(batches, model, filtered=True, scorer="distmult"):
     rankings = {"flt": [], "raw": []}
     with torch.no_grad():
         for batch, facts in batches:
-            E = _f32_rows(_embed(model, batch).detach(), "node_embeddings")
-            Rel = _f32_rows(_relations(model).detach(), "edge_embeddings")
+            E, Rel, _, _, entries = _rank_inputs(scorer, "evaluate_batches", _embed(model, batch), _relations(model))
             st = _batch_state(batch, facts, E.device)
-            dev = E.device
-            tr, nf, N, H = st["facts"], int(st["facts"].shape[0]), E.shape[0], E.shape[1]
+            tr = st["facts"]
             for flt in (False, True):
                 rank_type = "flt" if flt else "raw"
                 if flt and not filtered:
@@ -1598,23 +1594,11 @@ def evaluate_batches(batches, model, filtered=True, scorer="distmult"):
                         hits_at_k[rank_type][i].append(-1)
                     rankings[rank_type].append(-1)
                     continue
-                lists = [None] * 4
-                if flt:
-                    if st["lists"] is None:
-                        ls = [torch.from_numpy(a).to(dev) for a in filter_lists(np.asarray(facts))]
-                        st["lists"] = [a if a.numel() else torch.zeros(1, dtype=a.dtype, device=dev) for a in ls]
-                    lists = st["lists"]
-                ranks = torch.empty(2 * nf, dtype=torch.int64, device=dev)
-                if nf and cx:
-                    _complex_width(H, "evaluate_batches")
-                    ranks = rank_both(tr, E, Rel, lists=lists if flt else None, scorer=scorer)[1 if flt else 0]
-                elif nf:
-                    ws_bytes = lib.mrgcn_distmult_ranks_workspace(N, H, nf)
-                    ws = torch.empty((ws_bytes + 3) // 4, dtype=torch.int32, device=dev)
-                    _lib.check(lib.mrgcn_distmult_ranks(_ptr(E), E.stride(0), N, _ptr(Rel), Rel.stride(0), H, _ptr(tr),
-                                                        nf, _ptr(lists[0]), _ptr(lists[1]), _ptr(lists[2]),
-                                                        _ptr(lists[3]), _ptr(ws), ws_bytes, _ptr(ranks), _stream()),
-                               "distmult_ranks")
+                lists = _batch_lists(st, facts) if flt else None
+                if entries.complex and tr.shape[0]:
+                    ranks = rank_both(tr, E, Rel, lists=lists, scorer=scorer)[1 if flt else 0]
+                else:
+                    ranks = _rank_one_side(E, Rel, tr, lists)
                 mrr[rank_type].append(torch.mean(1.0 / ranks.float()).item())
                 for i, k in enumerate(K):
                     hits_at_k[rank_type][i].append(float(torch.mean((ranks <= k).float())))
@@ -1745,12 +1729,10 @@ class TypedQueries:
             else:
                 kn = known.cpu().numpy() if torch.is_tensor(known) else np.asarray(known)
                 ptr, idx = (torch.from_numpy(a).to(device) for a in known_lists(q_host, kn, side))
-            if idx.numel() == 0:
-                idx = torch.zeros(1, dtype=torch.int32, device=device)
-            self.excl = (ptr, idx)
+            self.excl = (ptr, _or_dummy(idx))
 
 
-def _predict_topk_typed(tq: TypedQueries, E, Rel, k: int, cx: bool):
+def _predict_topk_typed(tq: TypedQueries, E, Rel, k: int, entries: _Entries):
     dev, N, H = E.device, int(E.shape[0]), int(E.shape[1])
     types = tq.types
     if N != types.num_nodes or int(Rel.shape[0]) < types.num_relations or tq.q.device != dev:
@@ -1760,19 +1742,18 @@ def _predict_topk_typed(tq: TypedQueries, E, Rel, k: int, cx: bool):
     out_score = torch.empty((nq, k), dtype=torch.float32, device=dev)
     if nq == 0:
         return out_idx, out_score
-    lib = _lib.load()
-    ws_bytes = int((lib.mrgcn_complex_typed_topk_workspace if cx else lib.mrgcn_distmult_typed_topk_workspace)(
-        N, H, nq, k, tq.max_slot))
+    topk, workspace, what = entries("typed_topk")
+    ws_bytes = int(workspace(N, H, nq, k, tq.max_slot))
     if ws_bytes < 0:
         raise _lib.MrgcnError("predict_topk: sizes outside mrgcn_distmult_typed_topk's limits")
     ws = torch.empty((ws_bytes + 7) // 8, dtype=torch.int64, device=dev)
     ptr, idx = tq.excl if tq.excl is not None else (None, None)
     with torch.cuda.device(dev):
-        _lib.check((lib.mrgcn_complex_typed_topk if cx else lib.mrgcn_distmult_typed_topk)(
+        _lib.check(topk(
             _ptr(E), E.stride(0), N, _ptr(Rel), Rel.stride(0), H, _ptr(tq.q), nq, tq.head, _ptr(tq.order),
             _ptr(tq.tile_ptr), _ptr(tq.tile_rel), tq.ntiles, _ptr(tq.work), tq.nwork, _ptr(tq.q_tiles),
             _ptr(types.ptr), _ptr(types.idx), tq.max_slot, _ptr(ptr), _ptr(idx), k, _ptr(ws), ws_bytes,
-            _ptr(out_idx), _ptr(out_score), _stream()), "complex_typed_topk" if cx else "distmult_typed_topk")
+            _ptr(out_idx), _ptr(out_score), _stream()), what)
     bump("lp.topk.typed")
     return out_idx, out_score
 
@@ -1811,18 +1792,12 @@ def predict_topk(queries, node_embeddings, edge_embeddings, k, side="tail", know
                 and np.array_equal(candidates.idx_host, queries.types.idx_host)):
             raise ValueError("predict_topk: the TypedQueries were built with other candidate lists")
     head = _side(side)
-    cx = _scorer(scorer, "predict_topk")
-    if cx:
-        _complex_width(node_embeddings.shape[-1], "predict_topk")
+    _scorer(scorer, "predict_topk")   # (the keywords before `k`, `k` before the embeddings are looked at)
     if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= TOPK_MAX:
         raise ValueError(f"predict_topk: k must be an integer in [1, {TOPK_MAX}], not {k!r}")
     k = int(k)
-    E = _f32_rows(node_embeddings.detach(), "node_embeddings")
-    Rel = _f32_rows(edge_embeddings.detach(), "edge_embeddings")
+    E, Rel, N, H, entries = _rank_inputs(scorer, "predict_topk", node_embeddings, edge_embeddings)
     dev = E.device
-    N, H = int(E.shape[0]), int(E.shape[1])
-    if Rel.shape[1] != H:
-        raise ValueError("predict_topk: node and edge embeddings differ in width")
     if N == 0:
         raise ValueError("predict_topk: no nodes")
     if candidates is not None or isinstance(queries, TypedQueries):
@@ -1830,7 +1805,7 @@ def predict_topk(queries, node_embeddings, edge_embeddings, k, side="tail", know
             if not isinstance(candidates, TypedCandidates):
                 raise TypeError("predict_topk: candidates must be a TypedCandidates")
             queries = TypedQueries(queries, candidates, side=side, known=known, device=dev)
-        return _predict_topk_typed(queries, E, Rel, k, cx)
+        return _predict_topk_typed(queries, E, Rel, k, entries)
     on_device = torch.is_tensor(queries) and queries.is_cuda
     q_host = None
     if on_device:
@@ -1857,21 +1832,19 @@ def predict_topk(queries, node_embeddings, edge_embeddings, k, side="tail", know
                 q_host = q.cpu().numpy()
             kn = known.cpu().numpy() if torch.is_tensor(known) else np.asarray(known)
             ptr, idx = (torch.from_numpy(a).to(dev) for a in known_lists(q_host, kn, side))
-        if idx.numel() == 0:   # (an empty tensor has no address; the lists are empty either way)
-            idx = torch.zeros(1, dtype=torch.int32, device=dev)
+        idx = _or_dummy(idx)
     out_idx = torch.empty((nq, k), dtype=torch.int64, device=dev)
     out_score = torch.empty((nq, k), dtype=torch.float32, device=dev)
     if nq == 0:
         return out_idx, out_score
-    lib = _lib.load()
-    ws_bytes = int((lib.mrgcn_complex_topk_workspace if cx else lib.mrgcn_distmult_topk_workspace)(N, H, nq, k))
+    topk, workspace, what = entries("topk")
+    ws_bytes = int(workspace(N, H, nq, k))
     if ws_bytes < 0:
         raise _lib.MrgcnError("predict_topk: sizes outside mrgcn_distmult_topk's limits")
     ws = torch.empty((ws_bytes + 7) // 8, dtype=torch.int64, device=dev)
     with torch.cuda.device(dev):
-        _lib.check((lib.mrgcn_complex_topk if cx else lib.mrgcn_distmult_topk)(_ptr(E), E.stride(0), N, _ptr(Rel), Rel.stride(0), H, _ptr(q), nq, head,
-                                           _ptr(ptr), _ptr(idx), k, _ptr(ws), ws_bytes, _ptr(out_idx),
-                                           _ptr(out_score), _stream()), "complex_topk" if cx else "distmult_topk")
+        _lib.check(topk(_ptr(E), E.stride(0), N, _ptr(Rel), Rel.stride(0), H, _ptr(q), nq, head, _ptr(ptr), _ptr(idx),
+                        k, _ptr(ws), ws_bytes, _ptr(out_idx), _ptr(out_score), _stream()), what)
     return out_idx, out_score
 
 
@@ -1954,15 +1927,11 @@ def rank_both(facts, node_embeddings, edge_embeddings, lists=None, part_ptr=None
     grid (0: `rank_both_slice()`).  With device tensors nothing is copied from or to the host, nothing synchronises and
     a graph captures the call.  `scorer="complex"`: ComplEx scores (mrgcn_complex_ranks_both: the same contract, the
     fact's own score kept per side, because the two sides round differently); an odd width raises `MrgcnError`."""
-    cx = _scorer(scorer, "rank_both")
-    if cx:
-        _complex_width(node_embeddings.shape[-1], "rank_both")
+    E, Rel, N, H, entries = _rank_inputs(scorer, "rank_both", node_embeddings, edge_embeddings)
     if isinstance(facts, FactParts):
         lists = facts.lists if lists is None else lists
         part_ptr = facts.part_ptr if part_ptr is None else part_ptr
         facts = facts.facts
-    E = _f32_rows(node_embeddings.detach(), "node_embeddings")
-    Rel = _f32_rows(edge_embeddings.detach(), "edge_embeddings")
     dev = E.device
     if torch.is_tensor(facts) and facts.is_cuda and facts.dtype == torch.int64 and facts.is_contiguous():
         tr = facts
@@ -1970,36 +1939,24 @@ def rank_both(facts, node_embeddings, edge_embeddings, lists=None, part_ptr=None
             raise ValueError("facts must be [n, 3]")
     else:
         tr = _triples(facts, dev)
-    nf, N, H = int(tr.shape[0]), int(E.shape[0]), int(E.shape[1])
-    if Rel.shape[1] != H:
-        raise ValueError("rank_both: node and edge embeddings differ in width")
+    nf = int(tr.shape[0])
     raw = torch.empty(2 * nf, dtype=torch.int64, device=dev)
     flt = torch.empty(2 * nf, dtype=torch.int64, device=dev) if lists is not None else None
     if nf == 0:
         return raw, flt
-    ls = [None] * 4
-    if lists is not None:
-        ls = list(lists)
-        if len(ls) != 4 or not all(torch.is_tensor(a) and a.is_cuda for a in ls):
-            raise _lib.MrgcnError("rank_both: lists are the four device tensors of filter_lists")
-        if not (ls[0].dtype == ls[2].dtype == torch.int64 and ls[1].dtype == ls[3].dtype == torch.int32
-                and ls[0].numel() == ls[2].numel() == nf + 1):
-            raise _lib.MrgcnError("rank_both: lists are (int64 [n + 1], int32, int64 [n + 1], int32)")
-        # (an empty tensor has no address; the lists are empty either way)
-        ls = [a.contiguous() if a.numel() else torch.zeros(1, dtype=a.dtype, device=dev) for a in ls]
+    ls = _check_lists(lists, nf, "rank_both") if lists is not None else [None] * 4
     nparts = 0
     if part_ptr is not None:
         if not (part_ptr.is_cuda and part_ptr.dtype == torch.int64 and part_ptr.dim() == 1 and part_ptr.numel() >= 2):
             raise _lib.MrgcnError("rank_both: part_ptr is a device int64 [nparts + 1] tensor")
         part_ptr, nparts = part_ptr.contiguous(), int(part_ptr.numel()) - 1
-    lib = _lib.load()
-    ws_bytes = int((lib.mrgcn_complex_ranks_both_workspace if cx else lib.mrgcn_distmult_ranks_both_workspace)(N, H, nf))
+    ranks_both, workspace, what = entries("ranks_both")
+    ws_bytes = int(workspace(N, H, nf))
     ws = torch.empty((ws_bytes + 3) // 4, dtype=torch.int32, device=dev)
     with torch.cuda.device(dev):
-        _lib.check((lib.mrgcn_complex_ranks_both if cx else lib.mrgcn_distmult_ranks_both)(_ptr(E), E.stride(0), N, _ptr(Rel), Rel.stride(0), H, _ptr(tr), nf,
-                                                 _ptr(ls[0]), _ptr(ls[1]), _ptr(ls[2]), _ptr(ls[3]), _ptr(part_ptr),
-                                                 nparts, int(slice_facts), _ptr(ws), ws_bytes, _ptr(raw), _ptr(flt),
-                                                 _stream()), "complex_ranks_both" if cx else "distmult_ranks_both")
+        _lib.check(ranks_both(_ptr(E), E.stride(0), N, _ptr(Rel), Rel.stride(0), H, _ptr(tr), nf, _ptr(ls[0]),
+                              _ptr(ls[1]), _ptr(ls[2]), _ptr(ls[3]), _ptr(part_ptr), nparts, int(slice_facts),
+                              _ptr(ws), ws_bytes, _ptr(raw), _ptr(flt), _stream()), what)
     return raw, flt
 
 
@@ -2048,11 +2005,17 @@ def evaluate_facts(node_embeddings, edge_embeddings, parts: FactParts, want_rank
             and parts.part_ptr.numel() == len(ptr)):
         raise _lib.MrgcnError("evaluate_facts: part_ptr must rise from 0 to the number of facts, no part empty")
     raw, flt = rank_both(parts, node_embeddings, edge_embeddings, slice_facts=slice_facts, scorer=scorer)
+    return _metrics_of_ranks(raw, flt, parts.part_ptr, out, score, want_ranks)
+
+
+def _metrics_of_ranks(raw, flt, part_ptr, out, score, want_ranks):
+    """The end of `evaluate_facts` and `evaluate_typed`: one `rank_metrics` per rank type into the float32 [8] `out`
+    (None: a new one; -1 in the filtered four without `flt`), `1 - raw mrr` into `score`."""
     if out is None:
         out = torch.empty(8, dtype=torch.float32, device=raw.device)
-    rank_metrics(raw, parts.part_ptr, out[:4], score)
+    rank_metrics(raw, part_ptr, out[:4], score)
     if flt is not None:
-        rank_metrics(flt, parts.part_ptr, out[4:])
+        rank_metrics(flt, part_ptr, out[4:])
     else:
         out[4:].fill_(-1.0)
     return (out, raw, flt) if want_ranks else out
@@ -2139,24 +2102,17 @@ def rank_typed(tfacts: TypedFacts, node_embeddings, edge_embeddings, scorer="dis
     `compute_ranks_fast`'s contract and is NOT carried over.  The workspace and both results are allocated at the first
     call for a shape and kept on `tfacts`: later calls return the same tensors, allocate nothing and do not
     synchronise — capturable.  `scorer="complex"`: ComplEx scores; an odd width raises `MrgcnError`."""
-    cx = _scorer(scorer, "rank_typed")
-    if cx:
-        _complex_width(node_embeddings.shape[-1], "rank_typed")
+    _scorer(scorer, "rank_typed", node_embeddings.shape[-1])
     if not isinstance(tfacts, TypedFacts):
         raise TypeError("rank_typed: facts must be a TypedFacts (it holds the grouping by relation)")
-    E = _f32_rows(node_embeddings.detach(), "node_embeddings")
-    Rel = _f32_rows(edge_embeddings.detach(), "edge_embeddings")
-    dev, nf, N, H = E.device, tfacts.n, int(E.shape[0]), int(E.shape[1])
-    types = tfacts.types
-    if Rel.shape[1] != H:
-        raise ValueError("rank_typed: node and edge embeddings differ in width")
+    E, Rel, N, H, entries = _rank_inputs(scorer, "rank_typed", node_embeddings, edge_embeddings)
+    dev, nf, types = E.device, tfacts.n, tfacts.types
     if N != types.num_nodes or int(Rel.shape[0]) < types.num_relations or tfacts.facts.device != dev:
         raise _lib.MrgcnError("rank_typed: the embeddings do not match the typed facts (nodes, relations or device)")
-    lib = _lib.load()
-    key = (N, H, cx)
+    typed_ranks, workspace, what = entries("typed_ranks")
+    key = (N, H, entries.complex)
     if key not in tfacts._bufs:
-        ws_bytes = int((lib.mrgcn_complex_typed_ranks_workspace if cx else lib.mrgcn_distmult_typed_ranks_workspace)(
-            N, H, nf))
+        ws_bytes = int(workspace(N, H, nf))
         if ws_bytes < 0:
             raise _lib.MrgcnError("rank_typed: sizes outside the typed rank kernels' limits")
         tfacts._bufs[key] = (torch.empty((ws_bytes + 3) // 4, dtype=torch.int32, device=dev), ws_bytes,
@@ -2165,11 +2121,11 @@ def rank_typed(tfacts: TypedFacts, node_embeddings, edge_embeddings, scorer="dis
     ws, ws_bytes, raw, flt = tfacts._bufs[key]
     ls = tfacts.lists if tfacts.lists is not None else [None] * 4
     with torch.cuda.device(dev):
-        _lib.check((lib.mrgcn_complex_typed_ranks if cx else lib.mrgcn_distmult_typed_ranks)(
+        _lib.check(typed_ranks(
             _ptr(E), E.stride(0), N, _ptr(Rel), Rel.stride(0), H, _ptr(tfacts.facts), nf, _ptr(tfacts.order),
             _ptr(tfacts.tile_ptr), _ptr(tfacts.tile_rel), tfacts.ntiles, _ptr(tfacts.work), tfacts.nwork,
             _ptr(types.ptr), _ptr(types.idx), _ptr(ls[0]), _ptr(ls[1]), _ptr(ls[2]), _ptr(ls[3]), _ptr(ws), ws_bytes,
-            _ptr(raw), _ptr(flt), _stream()), "complex_typed_ranks" if cx else "distmult_typed_ranks")
+            _ptr(raw), _ptr(flt), _stream()), what)
     bump("lp.rank.typed")
     return raw, flt
 
@@ -2183,14 +2139,7 @@ def evaluate_typed(node_embeddings, edge_embeddings, tfacts: TypedFacts, out=Non
     first call).  The tuples `fit` yields keep the reference's shape: call this beside it."""
     _scorer(scorer, "evaluate_typed")
     raw, flt = rank_typed(tfacts, node_embeddings, edge_embeddings, scorer=scorer)
-    if out is None:
-        out = torch.empty(8, dtype=torch.float32, device=raw.device)
-    rank_metrics(raw, tfacts.part_ptr, out[:4], score)
-    if flt is not None:
-        rank_metrics(flt, tfacts.part_ptr, out[4:])
-    else:
-        out[4:].fill_(-1.0)
-    return (out, raw, flt) if want_ranks else out
+    return _metrics_of_ranks(raw, flt, tfacts.part_ptr, out, score, want_ranks)
 
 
 def eval_schedule(nepoch, eval_interval, has_valid):
@@ -2457,17 +2406,6 @@ def fit(model, forward_fn, train_facts, valid_facts, optimizer, nepoch, eval_int
 
 
 # ---- the reference's mini-batch run loop on the device (link_prediction.py:224-422; csrc/lp_batches.hip) -----------
-def _check_lists(lists, nf, dev, who):
-    ls = list(lists)
-    if len(ls) != 4 or not all(torch.is_tensor(a) and a.is_cuda for a in ls):
-        raise _lib.MrgcnError(f"{who}: lists are the four device tensors of filter_lists")
-    if not (ls[0].dtype == ls[2].dtype == torch.int64 and ls[1].dtype == ls[3].dtype == torch.int32
-            and ls[0].numel() == ls[2].numel() == nf + 1):
-        raise _lib.MrgcnError(f"{who}: lists are (int64 [n + 1], int32, int64 [n + 1], int32)")
-    # (an empty tensor has no address; the lists are empty either way)
-    return [a.contiguous() if a.numel() else torch.zeros(1, dtype=a.dtype, device=dev) for a in ls]
-
-
 def batch_eval_workspace(num_nodes, H, num_facts, device):
     """The workspace one `batch_eval` of that shape needs, as an int64 device tensor (kept by the caller)."""
     nbytes = int(_lib.load().mrgcn_distmult_batch_eval_workspace(int(num_nodes), int(H), int(num_facts)))
@@ -2500,7 +2438,7 @@ def batch_eval(node_embeddings, edge_embeddings, facts, lists=None, slot=None, r
         raise ValueError("batch_eval: node and edge embeddings differ in width")
     if N == 0:
         raise ValueError("batch_eval: no nodes")
-    ls = _check_lists(lists, nf, dev, "batch_eval") if lists is not None else [None] * 4
+    ls = _check_lists(lists, nf, "batch_eval") if lists is not None else [None] * 4
     if slot is None:
         slot = torch.empty(8, dtype=torch.float32, device=dev)
     elif not (torch.is_tensor(slot) and slot.is_cuda and slot.dtype == torch.float32 and tuple(slot.shape) == (8,)
@@ -2537,9 +2475,7 @@ def _lp_batch_means(loss_slots, n_loss, train_slots, n_train, valid_slots, n_val
 def _batch_lists(st, facts):
     """The batch's filter lists on the device, built once (shared with `evaluate_batches`)."""
     if st["lists"] is None:
-        dev = st["device"]
-        ls = [torch.from_numpy(a).to(dev) for a in filter_lists(np.asarray(facts))]
-        st["lists"] = [a if a.numel() else torch.zeros(1, dtype=a.dtype, device=dev) for a in ls]
+        st["lists"] = _device_filter_lists(facts, st["device"])
     return st["lists"]
 
 
