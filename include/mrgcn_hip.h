@@ -1376,6 +1376,38 @@ int mrgcn_lp_kvsall_bwd_f32(const float *Q, int64_t ldQ, int64_t m, const float 
                             const int32_t *cand_qry, double label_smoothing, const float *gl, float *dQ, int64_t lddQ,
                             float *dE, int64_t lddE, void *workspace, int64_t workspace_bytes, void *stream);
 
+/* ---- bf16 matrix-core arithmetic for the two all-candidates decoders (csrc/lp_tile.hpp: the bf16 tile) -------------
+ * The _bf16 entries are the _f32 entries above with the scores and the second product on v_mfma_f32_16x16x32_bf16.
+ * With ~ = rounded to bf16, nearest even:  x[q][c] = Q~[q] . E~[c], the products (exact in fp32) summed in fp32;
+ * everything after the scores — the online (max, sum), lse and its remainder, softplus, the float64 merges, the loss —
+ * is the _f32 entries' code, unchanged; the gradient tile G is formed in fp32 as there and rounded to bf16 ONCE, as it
+ * becomes the operand of dQ = G~ . E~ and dE = G~^T . Q~ (fp32 sums, fp32 outputs): the gradient of the loss as
+ * computed, the operands' rounding passed straight through.
+ * Q [m, H] and E [N, H] are bf16 TABLES (raw uint16_t rows; mrgcn_cast_rows_bf16 with ldDst = Hp makes them, once per
+ * forward): row strides ldQ / ldE in elements with ld % 32 == 0 and ld >= Hp = 32 ceil(H / 32), 16-byte aligned bases,
+ * ZEROS in [H, Hp) (not checked: what stands there enters every score).  H % 4 == 0, 4 <= H <= 256, 1 <= m, N < 2^31;
+ * outputs are float with lddQ / lddE >= H.  _supported_bf16 is that rule (1 / 0).  The workspaces are those of the
+ * _f32 entries (mrgcn_lp_all_workspace, mrgcn_lp_kvsall_workspace), lse / xt / per_query / loss / gl as there.  One
+ * owning block per output row, no float atomics: equal inputs give equal bits.  Stream ordered, no allocation,
+ * capturable. */
+int32_t mrgcn_lp_all_supported_bf16(const uint16_t *Q, int64_t ldQ, int64_t m, const uint16_t *E, int64_t ldE,
+                                    int64_t N, int32_t H);
+int mrgcn_lp_all_fwd_bf16(const uint16_t *Q, int64_t ldQ, int64_t m, const uint16_t *E, int64_t ldE, int64_t N,
+                          int32_t H, const int64_t *target, float *lse, float *xt, float *loss, void *workspace,
+                          int64_t workspace_bytes, void *stream);
+int mrgcn_lp_all_bwd_bf16(const uint16_t *Q, int64_t ldQ, int64_t m, const uint16_t *E, int64_t ldE, int64_t N,
+                          int32_t H, const int64_t *target, const float *lse, const float *gl, float *dQ, int64_t lddQ,
+                          float *dE, int64_t lddE, void *workspace, int64_t workspace_bytes, void *stream);
+int32_t mrgcn_lp_kvsall_supported_bf16(const uint16_t *Q, int64_t ldQ, int64_t m, const uint16_t *E, int64_t ldE,
+                                       int64_t N, int32_t H);
+int mrgcn_lp_kvsall_fwd_bf16(const uint16_t *Q, int64_t ldQ, int64_t m, const uint16_t *E, int64_t ldE, int64_t N,
+                             int32_t H, const int64_t *ans_ptr, const int32_t *ans_idx, double label_smoothing,
+                             float *per_query, float *loss, void *workspace, int64_t workspace_bytes, void *stream);
+int mrgcn_lp_kvsall_bwd_bf16(const uint16_t *Q, int64_t ldQ, int64_t m, const uint16_t *E, int64_t ldE, int64_t N,
+                             int32_t H, const int64_t *ans_ptr, const int32_t *ans_idx, const int64_t *cand_ptr,
+                             const int32_t *cand_qry, double label_smoothing, const float *gl, float *dQ, int64_t lddQ,
+                             float *dE, int64_t lddE, void *workspace, int64_t workspace_bytes, void *stream);
+
 /* ---- block-diagonal relation transform (csrc/block_xform.hip) ------------------------------------------------------
  * Schlichtkrull et al. 2018, "Modeling Relational Data with Graph Convolutional Networks", eq. 4:
  * W_r = blockdiag(Q_r[0], ..., Q_r[NB-1]), NB blocks of ki x fo = (K / NB) x (F / NB); input columns b ki .. b ki + ki - 1

@@ -326,6 +326,15 @@ SIGNATURES = {
                                           _p]),
     "mrgcn_lp_kvsall_bwd_f32": (C.c_int, [_p, _i64, _i64, _p, _i64, _i64, _i32, _p, _p, _p, _p, C.c_double, _p, _p, _i64,
                                           _p, _i64, _p, _i64, _p]),
+    "mrgcn_lp_all_supported_bf16": (_i32, [_p, _i64, _i64, _p, _i64, _i64, _i32]),
+    "mrgcn_lp_all_fwd_bf16": (C.c_int, [_p, _i64, _i64, _p, _i64, _i64, _i32, _p, _p, _p, _p, _p, _i64, _p]),
+    "mrgcn_lp_all_bwd_bf16": (C.c_int, [_p, _i64, _i64, _p, _i64, _i64, _i32, _p, _p, _p, _p, _i64, _p, _i64, _p,
+                                        _i64, _p]),
+    "mrgcn_lp_kvsall_supported_bf16": (_i32, [_p, _i64, _i64, _p, _i64, _i64, _i32]),
+    "mrgcn_lp_kvsall_fwd_bf16": (C.c_int, [_p, _i64, _i64, _p, _i64, _i64, _i32, _p, _p, C.c_double, _p, _p, _p, _i64,
+                                           _p]),
+    "mrgcn_lp_kvsall_bwd_bf16": (C.c_int, [_p, _i64, _i64, _p, _i64, _i64, _i32, _p, _p, _p, _p, C.c_double, _p, _p,
+                                           _i64, _p, _i64, _p, _i64, _p]),
     "mrgcn_block_transform_supported": (_i32, [_p, _i32, _i32, _i32]),
     "mrgcn_block_transform_fwd_f32": (C.c_int, [_p, _p, _i64, _i32, _p, _i32, _i32, _p, _i64, _i32, _p]),
     "mrgcn_block_transform_bwd_workspace": (C.c_int64, [_p, _i32, _i32, _i32, _i32, _i32]),

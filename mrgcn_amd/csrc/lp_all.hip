@@ -257,6 +257,174 @@ int launch_bwd(const float *R, int64_t ldR, int64_t nR, const float *S, int64_t 
   return MRGCN_OK;
 }
 
+// ---- the bf16 forms (lp_tile.hpp: the bf16 tile) ---------------------------------------------------------------------
+// The same three kernels on bf16 TABLES of Q and E (mrgcn_cast_rows_bf16, once per forward): x[q][c] = Q~[q] . E~[c]
+// with fp32 sums on v_mfma_f32_16x16x32_bf16; everything after the scores — the online (max, sum), the target's score,
+// the exponentials of the gradient tile, expm1f at the target — is the f32 kernels' code, in fp32.  G is rounded to
+// bf16 once, as it is stored for the second product, dQ = G~ . E~ and dE = G~^T . Q~ with fp32 sums and fp32 outputs: the
+// gradient of the loss as computed, the operands' rounding passed straight through.  The second product's stream
+// operand is read from the score product's own LDS image by the transposed read (second_product_bf16).
+template <int NK>
+__global__ __launch_bounds__(256) void k_lp_all_fwd_bf16(const uint16_t *__restrict__ Q, int64_t ldQ, int64_t m,
+                                                         const uint16_t *__restrict__ E, int64_t ldE, int64_t N, int H,
+                                                         const int64_t *__restrict__ target, int64_t chunk,
+                                                         float *__restrict__ pairs, float *__restrict__ xt) {
+  extern __shared__ __align__(16) uint16_t lp_all_lds16[];
+  uint16_t *Es = lp_all_lds16;
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, lm = lane & 15, kq = lane >> 4;
+  const int hq = hp32(H) / 8;
+  const int64_t q0 = (int64_t)blockIdx.x * kAT + 16 * wv;
+  const int64_t cbeg = (int64_t)blockIdx.y * chunk, cend = cbeg + chunk < N ? cbeg + chunk : N;
+  const int64_t ntiles = (cend - cbeg + kAT - 1) / kAT;
+  bf16x8a a[NK], nxt[NK];
+  load_rows_bf16<NK>(Q, ldQ, q0, m, H, lm, kq, a);
+  load_tile_bf16<NK>(E, ldE, cbeg, N, H, hq, nxt);
+  int64_t tg[4];
+  float mx[4], sm[4], xv[4];
+#pragma unroll
+  for (int reg = 0; reg < 4; ++reg) {
+    const int64_t q = q0 + 4 * kq + reg;
+    tg[reg] = target[q < m ? q : m - 1];
+    mx[reg] = -INFINITY;
+    sm[reg] = 0.f;
+    xv[reg] = 0.f;
+  }
+  for (int64_t t = 0; t < ntiles; ++t) {
+    const int64_t c0 = cbeg + t * kAT;
+    store_tile_bf16<NK>(Es, H, hq, nxt);
+    __syncthreads();
+    load_tile_bf16<NK>(E, ldE, t + 1 < ntiles ? c0 + kAT : c0, N, H, hq, nxt);  // (the last tile once more: no branch)
+    f32x4a acc[4];
+    score_tile_bf16<NK>(a, Es, H, lm, kq, acc);
+    __syncthreads();
+#pragma unroll
+    for (int reg = 0; reg < 4; ++reg) {
+      float x[4];
+      float tmax = -INFINITY;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int64_t c = c0 + 16 * j + lm;
+        x[j] = c < cend ? acc[j][reg] : -INFINITY;
+        tmax = fmaxf(tmax, x[j]);
+        if (c < cend && c == tg[reg]) xv[reg] = acc[j][reg];
+      }
+      const float mn = fmaxf(mx[reg], row_max(tmax));  // (k_lp_all_fwd's order: max, tile, one scaling of the sum)
+      float p = 0.f;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) p += expf(x[j] - mn);
+      sm[reg] = sm[reg] * expf(mx[reg] - mn) + row_sum(p);
+      mx[reg] = mn;
+    }
+  }
+#pragma unroll
+  for (int reg = 0; reg < 4; ++reg) {
+    const float v = row_sum(xv[reg]);  // one lane of the row holds it, the others 0
+    const int64_t q = q0 + 4 * kq + reg;
+    if (lm == 0 && q < m) {
+      float *p = pairs + ((int64_t)blockIdx.y * m + q) * 2;
+      p[0] = mx[reg];
+      p[1] = sm[reg];
+      if (tg[reg] >= cbeg && tg[reg] < cend) xt[q] = v;
+    }
+  }
+}
+
+// TRANS as k_lp_all_bwd: false = dQ (rows Q, stream E), true = dE (rows E, stream Q); out is fp32
+template <int NK, bool TRANS>
+__global__ __launch_bounds__(256) void k_lp_all_bwd_bf16(const uint16_t *__restrict__ R, int64_t ldR, int64_t nR,
+                                                         const uint16_t *__restrict__ S, int64_t ldS, int64_t nS, int H,
+                                                         const int64_t *__restrict__ target,
+                                                         const float *__restrict__ lse, const float *__restrict__ gl,
+                                                         int64_t m, float *__restrict__ out, int64_t ldo) {
+  extern __shared__ __align__(16) uint16_t lp_all_lds16[];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, lm = lane & 15, kq = lane >> 4;
+  const int hq = hp32(H) / 8;
+  uint16_t *Ss = lp_all_lds16;
+  uint16_t *Gs = lp_all_lds16 + kAT * tile_ld<NK>() + 16 * wv * kBGP;  // the wave's own 16 rows of the G tile
+  const int64_t r0 = (int64_t)blockIdx.x * kAT + 16 * wv;
+  const int64_t ntiles = (nS + kAT - 1) / kAT;
+  const float sc = gl[0] / (float)m;
+  bf16x8a a[NK], nxt[NK];
+  f32x4a acc2[2 * NK];
+  load_rows_bf16<NK>(R, ldR, r0, nR, H, lm, kq, a);
+  load_tile_bf16<NK>(S, ldS, 0, nS, H, hq, nxt);
+#pragma unroll
+  for (int nt = 0; nt < 2 * NK; ++nt) acc2[nt] = f32x4a{0.f, 0.f, 0.f, 0.f};
+  int64_t tgr[4];
+  float lser[4], lorr[4];
+#pragma unroll
+  for (int reg = 0; reg < 4; ++reg) {
+    const int64_t r = r0 + 4 * kq + reg;
+    tgr[reg] = TRANS ? r : target[r < nR ? r : nR - 1];
+    lser[reg] = TRANS ? 0.f : lse[r < nR ? r : nR - 1];
+    lorr[reg] = TRANS ? 0.f : lse[m + (r < nR ? r : nR - 1)];
+  }
+  for (int64_t t = 0; t < ntiles; ++t) {
+    const int64_t s0 = t * kAT;
+    store_tile_bf16<NK>(Ss, H, hq, nxt);
+    __syncthreads();
+    load_tile_bf16<NK>(S, ldS, t + 1 < ntiles ? s0 + kAT : s0, nS, H, hq, nxt);
+    int64_t tgc[4];
+    float lsec[4], lorc[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int64_t s = s0 + 16 * j + lm;
+      tgc[j] = TRANS ? target[s < nS ? s : nS - 1] : s;
+      lsec[j] = TRANS ? lse[s < nS ? s : nS - 1] : 0.f;
+      lorc[j] = TRANS ? lse[m + (s < nS ? s : nS - 1)] : 0.f;
+    }
+    f32x4a acc[4];
+    score_tile_bf16<NK>(a, Ss, H, lm, kq, acc);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const bool live = s0 + 16 * j + lm < nS;
+#pragma unroll
+      for (int reg = 0; reg < 4; ++reg) {
+        const float d = (acc[j][reg] - (TRANS ? lsec[j] : lser[reg])) - (TRANS ? lorc[j] : lorr[reg]);
+        float e = expf(d);
+        if (tgr[reg] == tgc[j]) e = expm1f(d);  // the target's p - 1 without the cancellation (one lane of a row)
+        store_g_bf16(Gs, lm, kq, j, reg, live ? e * sc : 0.f);
+      }
+    }
+    wave_lds_fence();
+    second_product_bf16<NK>(Gs, Ss, H, lm, kq, acc2);
+    wave_lds_fence();
+    __syncthreads();
+  }
+  // D: lane (lm, kq) holds rows 4 kq + reg, column 16 nt + lm
+#pragma unroll
+  for (int nt = 0; nt < 2 * NK; ++nt)
+#pragma unroll
+    for (int reg = 0; reg < 4; ++reg) {
+      const int64_t r = r0 + 4 * kq + reg;
+      const int n = 16 * nt + lm;
+      if (r < nR && n < H) out[r * ldo + n] = acc2[nt][reg];
+    }
+}
+
+template <int NK>
+int launch_fwd_bf16(const uint16_t *Q, int64_t ldQ, int64_t m, const uint16_t *E, int64_t ldE, int64_t N, int H,
+                    const int64_t *target, float *pairs, float *xt, hipStream_t s) {
+  const size_t lds = stream_lds_bf16<NK>();
+  MRGCN_HIP_TRY(raise_lds_limit((const void *)k_lp_all_fwd_bf16<NK>, lds));
+  const dim3 grid((unsigned)((m + kAT - 1) / kAT), (unsigned)chunks_of(m, N));
+  k_lp_all_fwd_bf16<NK><<<grid, dim3(256), lds, s>>>(Q, ldQ, m, E, ldE, N, H, target, chunk_of(m, N), pairs, xt);
+  MRGCN_HIP_TRY(hipGetLastError());
+  return MRGCN_OK;
+}
+
+template <int NK, bool TRANS>
+int launch_bwd_bf16(const uint16_t *R, int64_t ldR, int64_t nR, const uint16_t *S, int64_t ldS, int64_t nS, int H,
+                    const int64_t *target, const float *lse, const float *gl, int64_t m, float *out, int64_t ldo,
+                    hipStream_t s) {
+  const size_t lds = stream_lds_bf16<NK>() + g_lds_bf16();
+  MRGCN_HIP_TRY(raise_lds_limit((const void *)k_lp_all_bwd_bf16<NK, TRANS>, lds));
+  const dim3 grid((unsigned)((nR + kAT - 1) / kAT));
+  k_lp_all_bwd_bf16<NK, TRANS><<<grid, dim3(256), lds, s>>>(R, ldR, nR, S, ldS, nS, H, target, lse, gl, m, out, ldo);
+  MRGCN_HIP_TRY(hipGetLastError());
+  return MRGCN_OK;
+}
+
 }  // namespace
 }  // namespace mrgcn
 
@@ -320,6 +488,61 @@ int mrgcn_lp_all_bwd_f32(const float *Q, int64_t ldQ, int64_t m, const float *E,
 #define LP_ALL_DE(NT) launch_bwd<NT, true>(E, ldE, N, Q, ldQ, m, H, target, lse, gl, m, dE, lddE, s)
     const int rc = LP_ALL_BY_WIDTH(H, LP_ALL_DE);
 #undef LP_ALL_DE
+    if (rc != MRGCN_OK) return rc;
+  }
+  return MRGCN_OK;
+}
+
+int32_t mrgcn_lp_all_supported_bf16(const uint16_t *Q, int64_t ldQ, int64_t m, const uint16_t *E, int64_t ldE,
+                                    int64_t N, int32_t H) {
+  return Q && E && shape_ok_bf16(Q, ldQ, m, E, ldE, N, H) ? 1 : 0;
+}
+
+int mrgcn_lp_all_fwd_bf16(const uint16_t *Q, int64_t ldQ, int64_t m, const uint16_t *E, int64_t ldE, int64_t N,
+                          int32_t H, const int64_t *target, float *lse, float *xt, float *loss, void *workspace,
+                          int64_t workspace_bytes, void *stream) {
+  MRGCN_REQUIRE(Q && E && target && lse && xt && loss, "lp_all_fwd_bf16: NULL");
+  MRGCN_REQUIRE(shape_ok_bf16(Q, ldQ, m, E, ldE, N, H),
+                "lp_all_fwd_bf16: shape (H % 4 == 0, 4 <= H <= 256, 1 <= m, N < 2^31, bf16 rows of ld % 32 == 0, ld >= "
+                "32 ceil(H / 32), 16-byte aligned)");
+  MRGCN_REQUIRE(workspace && ((uintptr_t)workspace & 15) == 0 && workspace_bytes >= mrgcn_lp_all_workspace(m, N, H),
+                "lp_all_fwd_bf16: workspace (mrgcn_lp_all_workspace bytes, 16-byte aligned)");
+  hipStream_t s = (hipStream_t)stream;
+  const int64_t nchunks = chunks_of(m, N), nparts = (m + kMergeTB - 1) / kMergeTB;
+  float *pairs = (float *)workspace;
+  double *parts = (double *)((char *)workspace + align256(nchunks * m * 2 * 4));
+#define LP_ALL_FWD16(NK) launch_fwd_bf16<NK>(Q, ldQ, m, E, ldE, N, H, target, pairs, xt, s)
+  const int rc = LP_BF16_BY_WIDTH(H, LP_ALL_FWD16);
+#undef LP_ALL_FWD16
+  if (rc != MRGCN_OK) return rc;
+  k_lp_all_merge<<<dim3((unsigned)nparts), dim3(kMergeTB), 0, s>>>(pairs, nchunks, m, xt, lse, parts);
+  MRGCN_HIP_TRY(hipGetLastError());
+  k_lp_all_loss<<<dim3(1), dim3(kMergeTB), 0, s>>>(parts, nparts, m, loss);
+  MRGCN_HIP_TRY(hipGetLastError());
+  return MRGCN_OK;
+}
+
+int mrgcn_lp_all_bwd_bf16(const uint16_t *Q, int64_t ldQ, int64_t m, const uint16_t *E, int64_t ldE, int64_t N,
+                          int32_t H, const int64_t *target, const float *lse, const float *gl, float *dQ, int64_t lddQ,
+                          float *dE, int64_t lddE, void *workspace, int64_t workspace_bytes, void *stream) {
+  (void)workspace;
+  (void)workspace_bytes;  // the backward keeps nothing between its launches
+  MRGCN_REQUIRE(Q && E && target && lse && gl, "lp_all_bwd_bf16: NULL");
+  MRGCN_REQUIRE(shape_ok_bf16(Q, ldQ, m, E, ldE, N, H),
+                "lp_all_bwd_bf16: shape (H % 4 == 0, 4 <= H <= 256, 1 <= m, N < 2^31, bf16 rows of ld % 32 == 0, ld >= "
+                "32 ceil(H / 32), 16-byte aligned)");
+  MRGCN_REQUIRE((!dQ || lddQ >= H) && (!dE || lddE >= H), "lp_all_bwd_bf16: lddQ, lddE >= H");
+  hipStream_t s = (hipStream_t)stream;
+  if (dQ) {
+#define LP_ALL_DQ16(NK) launch_bwd_bf16<NK, false>(Q, ldQ, m, E, ldE, N, H, target, lse, gl, m, dQ, lddQ, s)
+    const int rc = LP_BF16_BY_WIDTH(H, LP_ALL_DQ16);
+#undef LP_ALL_DQ16
+    if (rc != MRGCN_OK) return rc;
+  }
+  if (dE) {
+#define LP_ALL_DE16(NK) launch_bwd_bf16<NK, true>(E, ldE, N, Q, ldQ, m, H, target, lse, gl, m, dE, lddE, s)
+    const int rc = LP_BF16_BY_WIDTH(H, LP_ALL_DE16);
+#undef LP_ALL_DE16
     if (rc != MRGCN_OK) return rc;
   }
   return MRGCN_OK;

@@ -280,6 +280,189 @@ int launch_bwd(const float *R, int64_t ldR, int64_t nR, const float *S, int64_t 
   return MRGCN_OK;
 }
 
+// ---- the bf16 forms (lp_tile.hpp: the bf16 tile; lp_all.hip: what is rounded where) ----------------------------------
+// The dense kernels on bf16 TABLES of Q and E: scores Q~ . E~ with fp32 sums, the softplus, the sigmoids and the list
+// masks in fp32 as above, G rounded to bf16 once as it is stored, out = G~ . S~ in fp32.
+template <int NK>
+__global__ __launch_bounds__(256) void k_kv_fwd_bf16(const uint16_t *__restrict__ Q, int64_t ldQ, int64_t m,
+                                                     const uint16_t *__restrict__ E, int64_t ldE, int64_t N, int H,
+                                                     int64_t chunk, float *__restrict__ pairs) {
+  extern __shared__ __align__(16) uint16_t lp_kv_lds16[];
+  uint16_t *Es = lp_kv_lds16;
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, lm = lane & 15, kq = lane >> 4;
+  const int hq = hp32(H) / 8;
+  const int64_t q0 = (int64_t)blockIdx.x * kAT + 16 * wv;
+  const int64_t cbeg = (int64_t)blockIdx.y * chunk, cend = cbeg + chunk < N ? cbeg + chunk : N;
+  const int64_t ntiles = (cend - cbeg + kAT - 1) / kAT;
+  bf16x8a a[NK], nxt[NK];
+  load_rows_bf16<NK>(Q, ldQ, q0, m, H, lm, kq, a);
+  load_tile_bf16<NK>(E, ldE, cbeg, N, H, hq, nxt);
+  float sp[4] = {0.f, 0.f, 0.f, 0.f}, sx[4] = {0.f, 0.f, 0.f, 0.f};
+  for (int64_t t = 0; t < ntiles; ++t) {
+    const int64_t c0 = cbeg + t * kAT;
+    store_tile_bf16<NK>(Es, H, hq, nxt);
+    __syncthreads();
+    load_tile_bf16<NK>(E, ldE, t + 1 < ntiles ? c0 + kAT : c0, N, H, hq, nxt);  // (the last tile once more: no branch)
+    f32x4a acc[4];
+    score_tile_bf16<NK>(a, Es, H, lm, kq, acc);
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const bool live = c0 + 16 * j + lm < cend;
+#pragma unroll
+      for (int reg = 0; reg < 4; ++reg) {
+        const float x = acc[j][reg];
+        sp[reg] += live ? softplus(x) : 0.f;
+        sx[reg] += live ? x : 0.f;
+      }
+    }
+  }
+#pragma unroll
+  for (int reg = 0; reg < 4; ++reg) {
+    const float s = row_sum(sp[reg]), x = row_sum(sx[reg]);
+    const int64_t q = q0 + 4 * kq + reg;
+    if (lm == 0 && q < m) {
+      float *p = pairs + ((int64_t)blockIdx.y * m + q) * 2;
+      p[0] = s;
+      p[1] = x;
+    }
+  }
+}
+
+// pos[q] from the bf16 rows, in fp32 (the products exact): a wave per query, lane l the 16-byte piece l of a row
+// (8 elements), four answer rows in flight
+__global__ __launch_bounds__(256) void k_kv_pos_bf16(const uint16_t *__restrict__ Q, int64_t ldQ, int64_t m,
+                                                     const uint16_t *__restrict__ E, int64_t ldE, int H,
+                                                     const int64_t *__restrict__ ptr, const int32_t *__restrict__ idx,
+                                                     float *__restrict__ pos) {
+  using u32x4a = __attribute__((ext_vector_type(4))) uint32_t;
+  const int lane = threadIdx.x & 63;
+  const int64_t q = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (q >= m) return;  // (wave uniform; no barrier below)
+  const bool on = 8 * lane < H;   // (the piece lies inside [0, Hp): whole, zeros past H)
+  const int f0 = on ? 8 * lane : 0;
+  const u32x4a qv = *reinterpret_cast<const u32x4a *>(Q + q * ldQ + f0);
+  const int64_t beg = ptr[q], end = ptr[q + 1];
+  float acc = 0.f;
+  for (int64_t k = beg; k < end; k += 4) {
+    u32x4a ev[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int64_t c = idx[k + u < end ? k + u : end - 1];
+      ev[u] = *reinterpret_cast<const u32x4a *>(E + c * ldE + f0);
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      if (k + u < end) {  // wave uniform
+        float p[8];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          p[2 * i] = __uint_as_float(qv[i] << 16) * __uint_as_float(ev[u][i] << 16);
+          p[2 * i + 1] = __uint_as_float(qv[i] & 0xffff0000u) * __uint_as_float(ev[u][i] & 0xffff0000u);
+        }
+        acc += ((p[0] + p[1]) + (p[2] + p[3])) + ((p[4] + p[5]) + (p[6] + p[7]));
+      }
+    }
+  }
+  acc = wave_sum64(on ? acc : 0.f);
+  if (lane == 0) pos[q] = acc;
+}
+
+template <int NK>
+__global__ __launch_bounds__(256) void k_kv_bwd_bf16(const uint16_t *__restrict__ R, int64_t ldR, int64_t nR,
+                                                     const uint16_t *__restrict__ S, int64_t ldS, int64_t nS, int H,
+                                                     const int64_t *__restrict__ ptr, const int32_t *__restrict__ idx,
+                                                     float eps_n, float eps_in, const float *__restrict__ gl,
+                                                     double count, float *__restrict__ out, int64_t ldo) {
+  extern __shared__ __align__(16) uint16_t lp_kv_lds16[];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, lm = lane & 15, kq = lane >> 4;
+  const int hq = hp32(H) / 8;
+  uint16_t *Ss = lp_kv_lds16;
+  uint16_t *Gs = lp_kv_lds16 + kAT * tile_ld<NK>() + 16 * wv * kBGP;  // the wave's own 16 rows of the G tile
+  const int64_t r0 = (int64_t)blockIdx.x * kAT + 16 * wv;
+  const int64_t ntiles = (nS + kAT - 1) / kAT;
+  const float sc = (float)((double)gl[0] / count);
+  bf16x8a a[NK], nxt[NK];
+  f32x4a acc2[2 * NK];
+  load_rows_bf16<NK>(R, ldR, r0, nR, H, lm, kq, a);
+  load_tile_bf16<NK>(S, ldS, 0, nS, H, hq, nxt);
+  // lane i < 16 of a wave walks the list of the wave's row i: `cur` is its next listed stream row
+  int64_t lp = 0, le = 0;
+  if (lane < 16 && r0 + lane < nR) {
+    lp = ptr[r0 + lane];
+    le = ptr[r0 + lane + 1];
+  }
+  int64_t cur = lp < le ? (int64_t)idx[lp] : INT64_MAX;
+#pragma unroll
+  for (int nt = 0; nt < 2 * NK; ++nt) acc2[nt] = f32x4a{0.f, 0.f, 0.f, 0.f};
+  for (int64_t t = 0; t < ntiles; ++t) {
+    const int64_t s0 = t * kAT;
+    store_tile_bf16<NK>(Ss, H, hq, nxt);
+    __syncthreads();
+    load_tile_bf16<NK>(S, ldS, t + 1 < ntiles ? s0 + kAT : s0, nS, H, hq, nxt);
+    f32x4a acc[4];
+    score_tile_bf16<NK>(a, Ss, H, lm, kq, acc);
+    unsigned long long mine = 0;
+    while (cur < s0 + kAT) {  // (lanes past 15 and rows without a listed pair in this tile: never entered)
+      if (cur >= s0) mine |= 1ull << (int)(cur - s0);   // (a list that does not ascend marks nothing outside the tile)
+      ++lp;
+      cur = lp < le ? (int64_t)idx[lp] : INT64_MAX;
+    }
+    unsigned long long mk[4];
+#pragma unroll
+    for (int reg = 0; reg < 4; ++reg) mk[reg] = __shfl(mine, 4 * kq + reg, kWave);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const bool live = s0 + 16 * j + lm < nS;
+#pragma unroll
+      for (int reg = 0; reg < 4; ++reg) {
+        // one exponential gives both sigmoids: r = 1 / (1 + e^-|x|) is that of |x|, e r that of -|x|
+        const float x = acc[j][reg], e = expf(-fabsf(x)), r = 1.f / (1.f + e), er = e * r;
+        const float sg = x >= 0.f ? r : er, om = x >= 0.f ? er : r;   // sigmoid(x), sigmoid(-x)
+        const bool listed = (mk[reg] >> (16 * j + lm)) & 1;
+        store_g_bf16(Gs, lm, kq, j, reg, live ? (listed ? eps_in - om : sg - eps_n) * sc : 0.f);
+      }
+    }
+    wave_lds_fence();   // (the list walk above diverges; the lanes have met again before the transposed reads)
+    second_product_bf16<NK>(Gs, Ss, H, lm, kq, acc2);
+    wave_lds_fence();
+    __syncthreads();
+  }
+  // D: lane (lm, kq) holds rows 4 kq + reg, column 16 nt + lm
+#pragma unroll
+  for (int nt = 0; nt < 2 * NK; ++nt)
+#pragma unroll
+    for (int reg = 0; reg < 4; ++reg) {
+      const int64_t r = r0 + 4 * kq + reg;
+      const int n = 16 * nt + lm;
+      if (r < nR && n < H) out[r * ldo + n] = acc2[nt][reg];
+    }
+}
+
+template <int NK>
+int launch_fwd_bf16(const uint16_t *Q, int64_t ldQ, int64_t m, const uint16_t *E, int64_t ldE, int64_t N, int H,
+                    float *pairs, hipStream_t s) {
+  const size_t lds = stream_lds_bf16<NK>();
+  MRGCN_HIP_TRY(raise_lds_limit((const void *)k_kv_fwd_bf16<NK>, lds));
+  const dim3 grid((unsigned)((m + kAT - 1) / kAT), (unsigned)chunks_of(m, N));
+  k_kv_fwd_bf16<NK><<<grid, dim3(256), lds, s>>>(Q, ldQ, m, E, ldE, N, H, chunk_of(m, N), pairs);
+  MRGCN_HIP_TRY(hipGetLastError());
+  return MRGCN_OK;
+}
+
+template <int NK>
+int launch_bwd_bf16(const uint16_t *R, int64_t ldR, int64_t nR, const uint16_t *S, int64_t ldS, int64_t nS, int H,
+                    const int64_t *ptr, const int32_t *idx, float eps_n, float eps_in, const float *gl, double count,
+                    float *out, int64_t ldo, hipStream_t s) {
+  const size_t lds = stream_lds_bf16<NK>() + g_lds_bf16();
+  MRGCN_HIP_TRY(raise_lds_limit((const void *)k_kv_bwd_bf16<NK>, lds));
+  const dim3 grid((unsigned)((nR + kAT - 1) / kAT));
+  k_kv_bwd_bf16<NK><<<grid, dim3(256), lds, s>>>(R, ldR, nR, S, ldS, nS, H, ptr, idx, eps_n, eps_in, gl, count, out,
+                                                  ldo);
+  MRGCN_HIP_TRY(hipGetLastError());
+  return MRGCN_OK;
+}
+
 inline bool eps_ok(double e) { return e >= 0.0 && e < 1.0; }  // (a NaN fails both)
 inline int64_t pairs_bytes(int64_t m, int64_t N) { return align256(chunks_of(m, N) * m * 2 * 4); }
 
@@ -355,6 +538,74 @@ int mrgcn_lp_kvsall_bwd_f32(const float *Q, int64_t ldQ, int64_t m, const float 
 #define LP_KV_DE(NT) launch_bwd<NT>(E, ldE, N, Q, ldQ, m, H, cand_ptr, cand_qry, eps_n, eps_in, gl, count, dE, lddE, s)
     const int rc = LP_ALL_BY_WIDTH(H, LP_KV_DE);
 #undef LP_KV_DE
+    if (rc != MRGCN_OK) return rc;
+  }
+  return MRGCN_OK;
+}
+
+int32_t mrgcn_lp_kvsall_supported_bf16(const uint16_t *Q, int64_t ldQ, int64_t m, const uint16_t *E, int64_t ldE,
+                                       int64_t N, int32_t H) {
+  return Q && E && shape_ok_bf16(Q, ldQ, m, E, ldE, N, H) ? 1 : 0;
+}
+
+int mrgcn_lp_kvsall_fwd_bf16(const uint16_t *Q, int64_t ldQ, int64_t m, const uint16_t *E, int64_t ldE, int64_t N,
+                             int32_t H, const int64_t *ans_ptr, const int32_t *ans_idx, double label_smoothing,
+                             float *per_query, float *loss, void *workspace, int64_t workspace_bytes, void *stream) {
+  MRGCN_REQUIRE(Q && E && ans_ptr && ans_idx && loss, "lp_kvsall_fwd_bf16: NULL");
+  MRGCN_REQUIRE(shape_ok_bf16(Q, ldQ, m, E, ldE, N, H),
+                "lp_kvsall_fwd_bf16: shape (H % 4 == 0, 4 <= H <= 256, 1 <= m, N < 2^31, bf16 rows of ld % 32 == 0, ld "
+                ">= 32 ceil(H / 32), 16-byte aligned)");
+  MRGCN_REQUIRE(eps_ok(label_smoothing), "lp_kvsall_fwd_bf16: label_smoothing in [0, 1)");
+  MRGCN_REQUIRE(workspace && ((uintptr_t)workspace & 15) == 0 && workspace_bytes >= mrgcn_lp_kvsall_workspace(m, N, H),
+                "lp_kvsall_fwd_bf16: workspace (mrgcn_lp_kvsall_workspace bytes, 16-byte aligned)");
+  hipStream_t s = (hipStream_t)stream;
+  const int64_t nchunks = chunks_of(m, N), nparts = (m + kMergeTB - 1) / kMergeTB;
+  float *pairs = (float *)workspace;
+  float *pos = (float *)((char *)workspace + pairs_bytes(m, N));
+  double *parts = (double *)((char *)pos + align256(m * 4));
+#define LP_KV_FWD16(NK) launch_fwd_bf16<NK>(Q, ldQ, m, E, ldE, N, H, pairs, s)
+  const int rc = LP_BF16_BY_WIDTH(H, LP_KV_FWD16);
+#undef LP_KV_FWD16
+  if (rc != MRGCN_OK) return rc;
+  k_kv_pos_bf16<<<dim3((unsigned)((m + 3) / 4)), dim3(256), 0, s>>>(Q, ldQ, m, E, ldE, H, ans_ptr, ans_idx, pos);
+  MRGCN_HIP_TRY(hipGetLastError());
+  k_kv_merge<<<dim3((unsigned)nparts), dim3(kMergeTB), 0, s>>>(pairs, nchunks, m, pos, label_smoothing / (double)N,
+                                                                1.0 - label_smoothing, per_query, parts);
+  MRGCN_HIP_TRY(hipGetLastError());
+  k_kv_loss<<<dim3(1), dim3(kMergeTB), 0, s>>>(parts, nparts, (double)m * (double)N, loss);
+  MRGCN_HIP_TRY(hipGetLastError());
+  return MRGCN_OK;
+}
+
+int mrgcn_lp_kvsall_bwd_bf16(const uint16_t *Q, int64_t ldQ, int64_t m, const uint16_t *E, int64_t ldE, int64_t N,
+                             int32_t H, const int64_t *ans_ptr, const int32_t *ans_idx, const int64_t *cand_ptr,
+                             const int32_t *cand_qry, double label_smoothing, const float *gl, float *dQ, int64_t lddQ,
+                             float *dE, int64_t lddE, void *workspace, int64_t workspace_bytes, void *stream) {
+  (void)workspace;
+  (void)workspace_bytes;  // the backward keeps nothing between its launches
+  MRGCN_REQUIRE(Q && E && gl && (!dQ || (ans_ptr && ans_idx)) && (!dE || (cand_ptr && cand_qry)),
+                "lp_kvsall_bwd_bf16: NULL (dQ needs the answer lists, dE the candidates' query lists)");
+  MRGCN_REQUIRE(shape_ok_bf16(Q, ldQ, m, E, ldE, N, H),
+                "lp_kvsall_bwd_bf16: shape (H % 4 == 0, 4 <= H <= 256, 1 <= m, N < 2^31, bf16 rows of ld % 32 == 0, ld "
+                ">= 32 ceil(H / 32), 16-byte aligned)");
+  MRGCN_REQUIRE(eps_ok(label_smoothing), "lp_kvsall_bwd_bf16: label_smoothing in [0, 1)");
+  MRGCN_REQUIRE((!dQ || lddQ >= H) && (!dE || lddE >= H), "lp_kvsall_bwd_bf16: lddQ, lddE >= H");
+  hipStream_t s = (hipStream_t)stream;
+  const double count = (double)m * (double)N;
+  const float eps_n = (float)(label_smoothing / (double)N);
+  const float eps_in = (float)(label_smoothing * (1.0 - 1.0 / (double)N));
+  if (dQ) {
+#define LP_KV_DQ16(NK) \
+  launch_bwd_bf16<NK>(Q, ldQ, m, E, ldE, N, H, ans_ptr, ans_idx, eps_n, eps_in, gl, count, dQ, lddQ, s)
+    const int rc = LP_BF16_BY_WIDTH(H, LP_KV_DQ16);
+#undef LP_KV_DQ16
+    if (rc != MRGCN_OK) return rc;
+  }
+  if (dE) {
+#define LP_KV_DE16(NK) \
+  launch_bwd_bf16<NK>(E, ldE, N, Q, ldQ, m, H, cand_ptr, cand_qry, eps_n, eps_in, gl, count, dE, lddE, s)
+    const int rc = LP_BF16_BY_WIDTH(H, LP_KV_DE16);
+#undef LP_KV_DE16
     if (rc != MRGCN_OK) return rc;
   }
   return MRGCN_OK;

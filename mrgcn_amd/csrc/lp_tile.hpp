@@ -125,5 +125,132 @@ inline bool shape_ok(const float *Q, int64_t ldQ, int64_t m, const float *E, int
    : (H) <= 192 ? CALL(3)             \
                 : CALL(4))
 
+// ---- the bf16 form of the tile ---------------------------------------------------------------------------------------
+// x[r][s] = R~[r] . S~[s] on v_mfma_f32_16x16x32_bf16: bf16 operands (a product of two is exact in fp32), fp32 sums, K
+// steps of 32.  Lane l holds A[row l & 15][k = 8 (l >> 4) + j] and B[k = 8 (l >> 4) + j][col l & 15], j = 0..7, as one
+// 16-byte fragment; D is at col = l & 15, row = 4 (l >> 4) + reg — the f32 tile's D map, so the epilogues carry over.
+// Both sides arrive as bf16 TABLES (mrgcn_cast_rows_bf16, once per forward): rows of ld % 32 == 0 elements with zeros
+// in [H, Hp), Hp = 32 ceil(H / 32), so every load is whole and straight-line with no column clamp.  NK = K steps the
+// kernel is built for (Hp / 32 <= NK; the steps past Hp are skipped, block uniform).  The LDS row of a stream tile is
+// 32 NK + 8 elements whatever H: 16 NK + 4 dwords, so the 16 rows one ds_read_b128 of the score product touches start
+// 4 banks apart (conflict free) and every address below is a compile-time offset from one lane base.
+using bf16x8a = __attribute__((ext_vector_type(8))) __bf16;
+using s16x4a = __attribute__((ext_vector_type(4))) short;
+typedef s16x4a __attribute__((address_space(3))) lds_s16x4a;
+
+constexpr int kBGP = kAT + 8;      // padded row of the bf16 G tile (144 bytes: 16-byte pieces stay aligned)
+
+__host__ __device__ inline int hp32(int H) { return (H + 31) / 32 * 32; }
+template <int NK> constexpr int tile_ld() { return 32 * NK + 8; }
+template <int NK> constexpr size_t stream_lds_bf16() { return (size_t)kAT * tile_ld<NK>() * sizeof(uint16_t); }
+constexpr size_t g_lds_bf16() { return (size_t)kAT * kBGP * sizeof(uint16_t); }
+
+// the wave's 16 rows as the A operand: lane (lm, kq) keeps T[r0 + lm][32 ks + 8 kq .. + 7] for every K step ks (rows
+// past the table repeat its last row)
+template <int NK>
+__device__ __forceinline__ void load_rows_bf16(const uint16_t *__restrict__ T, int64_t ld, int64_t r0, int64_t nrows,
+                                               int H, int lm, int kq, bf16x8a (&a)[NK]) {
+  const int64_t r = r0 + lm < nrows ? r0 + lm : nrows - 1;
+  const uint16_t *row = T + r * ld + 8 * kq;
+#pragma unroll
+  for (int ks = 0; ks < NK; ++ks) {
+    if (32 * ks < H) a[ks] = *reinterpret_cast<const bf16x8a *>(row + 32 * ks);  // block uniform
+    else a[ks] = bf16x8a{};
+  }
+}
+
+// a stream tile: 64 rows of hq = Hp / 8 16-byte pieces; thread t takes pieces t, t + 256, ... (Hp / 32 <= NK of them)
+template <int NK>
+__device__ __forceinline__ void load_tile_bf16(const uint16_t *__restrict__ T, int64_t ld, int64_t r0, int64_t nrows,
+                                               int H, int hq, bf16x8a (&v)[NK]) {
+#pragma unroll
+  for (int u = 0; u < NK; ++u) {
+    if (32 * u < H) {  // block uniform: piece t + 256 u lies inside the 64 rows
+      const int i = (int)threadIdx.x + 256 * u;
+      const int row = i / hq, k = 8 * (i - row * hq);
+      const int64_t r = r0 + row < nrows ? r0 + row : nrows - 1;
+      v[u] = *reinterpret_cast<const bf16x8a *>(T + r * ld + k);
+    }
+  }
+}
+template <int NK>
+__device__ __forceinline__ void store_tile_bf16(uint16_t *__restrict__ Ts, int H, int hq, const bf16x8a (&v)[NK]) {
+#pragma unroll
+  for (int u = 0; u < NK; ++u) {
+    if (32 * u < H) {
+      const int i = (int)threadIdx.x + 256 * u;
+      const int row = i / hq, k = 8 * (i - row * hq);
+      *reinterpret_cast<bf16x8a *>(Ts + row * tile_ld<NK>() + k) = v[u];
+    }
+  }
+}
+
+// acc[j][reg] = row (4 kq + reg of the wave's 16) . stream row (16 j + lm of the tile): four independent accumulators
+template <int NK>
+__device__ __forceinline__ void score_tile_bf16(const bf16x8a (&a)[NK], const uint16_t *__restrict__ Ts, int H, int lm,
+                                                int kq, f32x4a (&acc)[4]) {
+#pragma unroll
+  for (int j = 0; j < 4; ++j) acc[j] = f32x4a{0.f, 0.f, 0.f, 0.f};
+  const uint16_t *b0 = Ts + lm * tile_ld<NK>() + 8 * kq;
+#pragma unroll
+  for (int ks = 0; ks < NK; ++ks) {
+    if (32 * ks < H) {  // block uniform
+      bf16x8a b[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) b[j] = *reinterpret_cast<const bf16x8a *>(b0 + 16 * j * tile_ld<NK>() + 32 * ks);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[ks], b[j], acc[j], 0, 0, 0);
+    }
+  }
+}
+
+// the wave's 16 x 64 piece of G, fp32 in D layout, rounded to bf16 ONCE as it becomes the second product's operand:
+// lane (lm, kq) writes rows 4 kq + reg, column 16 j + lm of the wave's own LDS rows
+__device__ __forceinline__ void store_g_bf16(uint16_t *__restrict__ Gs, int lm, int kq, int j, int reg, float g) {
+  reinterpret_cast<__bf16 *>(Gs)[(4 * kq + reg) * kBGP + 16 * j + lm] = (__bf16)g;  // (v_cvt_pk_bf16_f32: nearest even)
+}
+
+// the second product: acc2[nt] += G~ (16 x 64, the wave's LDS rows: the A operand read by rows) . S~ (the 64 stream
+// rows in LDS, features 16 nt .. 16 nt + 15).  The sum runs over the STREAM rows, so the B operand wants k along the
+// rows of the image the score product reads by rows: lane l needs S[32 kk + 8 (l >> 4) + j][16 nt + (l & 15)], j =
+// 0..7, which is what two ds_read_b64_tr_b16 deliver from the SAME image — per 16-lane group a block of 4 rows x 16
+// columns, lane 4 q + p of the group giving the address of row q, columns 4 p .. 4 p + 3, lane i receiving column i of
+// the four rows.  Group g = l >> 4 takes rows 32 kk + 8 g .. + 3 and .. + 4 .. + 7: a 32-lane half's two blocks are 8
+// rows apart in the same columns.  All 64 lanes are active here (the ISA requires it) and every address is in bounds.
+template <int NK>
+__device__ __forceinline__ void second_product_bf16(const uint16_t *__restrict__ Gs, uint16_t *__restrict__ Ss, int H,
+                                                    int lm, int kq, f32x4a (&acc2)[2 * NK]) {
+  const uint16_t *tb = Ss + (8 * kq + (lm >> 2)) * tile_ld<NK>() + 4 * (lm & 3);
+#pragma unroll
+  for (int kk = 0; kk < 2; ++kk) {
+    const bf16x8a g = *reinterpret_cast<const bf16x8a *>(Gs + lm * kBGP + 32 * kk + 8 * kq);
+#pragma unroll
+    for (int nt = 0; nt < 2 * NK; ++nt) {
+      if (16 * nt < H) {  // block uniform
+        const uint16_t *p = tb + 32 * kk * tile_ld<NK>() + 16 * nt;
+        const s16x4a lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4a *)p);
+        const s16x4a hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4a *)(p + 4 * tile_ld<NK>()));
+        const bf16x8a b = __builtin_bit_cast(bf16x8a, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
+        acc2[nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(g, b, acc2[nt], 0, 0, 0);
+      }
+    }
+  }
+}
+
+// the shapes the bf16 tile kernels take: bf16 tables of whole K steps, 32-bit row numbers
+inline bool shape_ok_bf16(const uint16_t *Q, int64_t ldQ, int64_t m, const uint16_t *E, int64_t ldE, int64_t N,
+                          int32_t H) {
+  return H % 4 == 0 && H >= 4 && H <= 256 && m >= 1 && N >= 1 && m < ((int64_t)1 << 31) && N < ((int64_t)1 << 31) &&
+         ldQ >= hp32(H) && ldE >= hp32(H) && ldQ % 32 == 0 && ldE % 32 == 0 &&
+         (((uintptr_t)Q | (uintptr_t)E) & 15) == 0;
+}
+
+#define LP_BF16_BY_WIDTH(H, CALL)     \
+  ((H) <= 32    ? CALL(1)             \
+   : (H) <= 64  ? CALL(2)             \
+   : (H) <= 128 ? CALL(4)             \
+   : (H) <= 192 ? CALL(6)             \
+                : CALL(8))
+
 }  // namespace
 }  // namespace mrgcn

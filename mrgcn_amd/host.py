@@ -534,6 +534,55 @@ def kvsall_loss32(Q, E, ptr, idx, label_smoothing=0.0):
     return f(per_query.sum(dtype=f) / f(float(m) * float(N))), per_query
 
 
+# ---- the bf16 score arithmetic of the two decoders (csrc/lp_tile.hpp: the bf16 tile; set_score_dtype("bf16")) -------
+# The kernels round Q and E to bf16, sum the exact products in fp32, keep everything after the scores in fp32 / float64
+# and round the gradient tile G to bf16 once, as the operand of dQ = G~ E~ and dE = G~^T Q~.  The mirrors below are the
+# float64 loss and gradients on the ROUNDED operands with G NOT rounded, plus what G's rounding can move each gradient
+# element by: |G~ - G| <= 2^-9 |G| per element under nearest-even (bf16 keeps 8 significand bits: a unit roundoff of
+# 2^-8, half of it per rounding), but the kernels' G is a float32 value that differs from the float64 G, so a tie can
+# fall the other way: the bound takes the whole unit, 2^-8 |G|, summed with the other operand's magnitudes.
+BF16_UNIT = 2.0 ** -8
+
+
+def round_bf16(a):
+    """float32 array -> the float32 array of its values rounded to bf16, nearest even, on the bit pattern (what
+    `torch.Tensor.bfloat16().float()` gives; a value past the largest bf16 rounds to infinity).  No NaNs."""
+    import numpy as np
+    u = np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
+    r = (u + np.uint32(0x7fff) + ((u >> np.uint32(16)) & np.uint32(1))) & np.uint32(0xffff0000)
+    return r.view(np.float32)
+
+
+def all_loss_bf16_64(Q, E, target, upstream=1.0):
+    """`all_loss64` on the operands rounded to bf16, G not rounded -> (loss, lse [m], xt [m], dQ [m, H], dE [N, H],
+    B_dQ [m, H], B_dE [N, H]): B_dQ = 2^-8 |G| |E~| and B_dE = 2^-8 |G|^T |Q~| bound, per element, what rounding G to
+    bf16 moves the gradients by."""
+    import numpy as np
+    Qr, Er = round_bf16(Q).astype(np.float64), round_bf16(E).astype(np.float64)
+    tg = np.asarray(target, dtype=np.int64)
+    m = Qr.shape[0]
+    loss, lse, dQ, dE = all_loss64(Qr, Er, tg, upstream)
+    x = Qr @ Er.T
+    G = np.exp(x - lse[:, None])
+    G[np.arange(m), tg] -= 1.0
+    G = np.abs(G * (float(upstream) / m))
+    return loss, lse, x[np.arange(m), tg], dQ, dE, BF16_UNIT * (G @ np.abs(Er)), BF16_UNIT * (G.T @ np.abs(Qr))
+
+
+def kvsall_loss_bf16_64(Q, E, ptr, idx, label_smoothing=0.0, upstream=1.0):
+    """`kvsall_loss64` on the operands rounded to bf16, G not rounded -> (loss, per_query [m], dQ, dE, B_dQ, B_dE), the
+    bounds as `all_loss_bf16_64`'s."""
+    import numpy as np
+    Qr, Er = round_bf16(Q).astype(np.float64), round_bf16(E).astype(np.float64)
+    eps = float(label_smoothing)
+    loss, per_query, dQ, dE = kvsall_loss64(Qr, Er, ptr, idx, eps, upstream)
+    m, N = Qr.shape[0], Er.shape[0]
+    _, Ys = _kvsall_dense_labels(m, N, ptr, idx, eps, np.float64)
+    x = Qr @ Er.T
+    G = np.abs((np.exp(np.minimum(x, 0.0)) / (1.0 + np.exp(-np.abs(x))) - Ys) * (float(upstream) / (m * N)))
+    return loss, per_query, dQ, dE, BF16_UNIT * (G @ np.abs(Er)), BF16_UNIT * (G.T @ np.abs(Qr))
+
+
 # ---- block-diagonal relation transform (csrc/block_xform.hip; Schlichtkrull et al. 2018, eq. 4) ----------------------
 # W: (R, NB, ki, fo), W_r = blockdiag(W[r, 0], ..., W[r, NB-1]); a compact column c is the pair (node[c], rel[c]).
 def block_weight_dense64(W):

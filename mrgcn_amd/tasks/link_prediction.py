@@ -574,9 +574,62 @@ def pair_vectors(facts, E, Rel, side="both", scorer="distmult"):
     return torch.cat(q, 0), torch.cat(tg, 0)
 
 
+# Arithmetic of the score product of the two all-candidates decoders (`decoder="all"`, `decoder="kvsall"`): "f32"
+# (v_mfma_f32_16x16x4_f32, exact fp32 — the default) or "bf16" (Q and E rounded to bf16 tables once per forward,
+# v_mfma_f32_16x16x32_bf16 with fp32 sums, the gradient tile rounded to bf16 as the second product's operand; lse,
+# softplus, the merges, the loss and both gradients stay fp32 / float64).  Process-wide, as `dense.set_matmul_dtype`;
+# every entry point takes `mm=` for one call, and a backward runs what its forward ran.
+SCORE_DTYPES = ("f32", "bf16")
+_SCORE_DTYPE = "f32"
+
+
+def set_score_dtype(dtype: str) -> str:
+    """Returns the previous setting."""
+    global _SCORE_DTYPE
+    if dtype not in SCORE_DTYPES:
+        raise _lib.MrgcnError(f"set_score_dtype: the score arithmetic is one of {SCORE_DTYPES}, not {dtype!r}")
+    prev, _SCORE_DTYPE = _SCORE_DTYPE, dtype
+    return prev
+
+
+def score_dtype() -> str:
+    return _SCORE_DTYPE
+
+
+def _mm(mm, who) -> str:
+    if mm is None:
+        return _SCORE_DTYPE
+    if mm not in SCORE_DTYPES:
+        raise _lib.MrgcnError(f"{who}: mm is one of {SCORE_DTYPES} or None (the setting), not {mm!r}")
+    return mm
+
+
+def _bf16_table(X: torch.Tensor) -> torch.Tensor:
+    """The float32 rows of X as a bf16 table [n, Hp], Hp = 32 ceil(H / 32), zeros past H (raw 16-bit rows; one cast
+    kernel, stream ordered)."""
+    n, H = int(X.shape[0]), int(X.shape[1])
+    Hp = (H + 31) // 32 * 32
+    T = torch.empty((n, Hp), dtype=torch.int16, device=X.device)
+    _lib.check(_lib.load().mrgcn_cast_rows_bf16(_ptr(X), X.stride(0), n, H, _ptr(T), Hp, _stream()),
+               "mrgcn_cast_rows_bf16")
+    return T
+
+
+def _bf16_through(X: torch.Tensor) -> torch.Tensor:
+    """X rounded to bf16 with the rounding passed straight through by autograd (the materialised fallback's operands)."""
+    return X + (X.bfloat16().float() - X).detach()
+
+
 def _all_supported(lib, Q, E) -> bool:
     return bool(Q.shape[0] >= 1 and E.shape[0] >= 1 and lib.mrgcn_lp_all_supported(
         _ptr(Q), Q.stride(0), Q.shape[0], _ptr(E), E.stride(0), E.shape[0], E.shape[1]))
+
+
+def _bf16_supported(Q, E) -> bool:
+    """The bf16 kernels' shapes (mrgcn_lp_all_supported_bf16 on the tables `_bf16_table` makes: their strides and
+    alignment always qualify, so the rule is the width's)."""
+    H = int(E.shape[1])
+    return bool(Q.shape[0] >= 1 and E.shape[0] >= 1 and H % 4 == 0 and 4 <= H <= 256)
 
 
 def _all_fwd(lib, Q, E, target):
@@ -587,6 +640,21 @@ def _all_fwd(lib, Q, E, target):
     _lib.check(lib.mrgcn_lp_all_fwd_f32(_ptr(Q), Q.stride(0), m, _ptr(E), E.stride(0), N, H, _ptr(target), _ptr(lse),
                                         _ptr(xt), _ptr(loss), _ptr(ws), ws.numel(), _stream()), "lp_all_fwd")
     return lse, xt, loss
+
+
+def _all_fwd_bf16(lib, Q, E, target):
+    """-> (lse, xt, loss, Qb, Eb): the bf16 tables are made here, once, and handed on to the backward."""
+    m, N, H = Q.shape[0], E.shape[0], E.shape[1]
+    Qb, Eb = _bf16_table(Q), _bf16_table(E)
+    if not lib.mrgcn_lp_all_supported_bf16(_ptr(Qb), Qb.stride(0), m, _ptr(Eb), Eb.stride(0), N, H):
+        raise _lib.MrgcnError("the bf16 1-vs-all kernels do not take this shape")
+    out = torch.empty(3 * m + 1, dtype=torch.float32, device=E.device)
+    lse, xt, loss = out[:2 * m], out[2 * m:3 * m], out[3 * m:].view(())
+    ws = _det_scratch(E.device, "lp_all", int(lib.mrgcn_lp_all_workspace(m, N, H)))
+    _lib.check(lib.mrgcn_lp_all_fwd_bf16(_ptr(Qb), Qb.stride(0), m, _ptr(Eb), Eb.stride(0), N, H, _ptr(target),
+                                         _ptr(lse), _ptr(xt), _ptr(loss), _ptr(ws), ws.numel(), _stream()),
+               "lp_all_fwd_bf16")
+    return lse, xt, loss, Qb, Eb
 
 
 class _AllLoss(torch.autograd.Function):
@@ -608,36 +676,69 @@ class _AllLoss(torch.autograd.Function):
         return dQ, dE, None
 
 
-def all_pairs_loss(Q, E, target):
+class _AllLossBf16(torch.autograd.Function):
+    """`_AllLoss` on the bf16 kernels: the forward's tables are saved, the backward reads them (no second cast)."""
+    @staticmethod
+    def forward(ctx, Q, E, target):
+        lse, _, loss, Qb, Eb = _all_fwd_bf16(_lib.load(), Q, E, target)
+        ctx.save_for_backward(Qb, Eb, target, lse)
+        ctx.width = int(E.shape[1])
+        return loss
+
+    @staticmethod
+    def backward(ctx, gl):
+        Qb, Eb, target, lse = ctx.saved_tensors
+        m, N, H = Qb.shape[0], Eb.shape[0], ctx.width
+        gl = gl.contiguous().float()
+        dQ = torch.empty((m, H), dtype=torch.float32, device=Qb.device) if ctx.needs_input_grad[0] else None
+        dE = torch.empty((N, H), dtype=torch.float32, device=Eb.device) if ctx.needs_input_grad[1] else None
+        _lib.check(_lib.load().mrgcn_lp_all_bwd_bf16(
+            _ptr(Qb), Qb.stride(0), m, _ptr(Eb), Eb.stride(0), N, H, _ptr(target), _ptr(lse), _ptr(gl), _ptr(dQ), H,
+            _ptr(dE), H, None, 0, _stream()), "lp_all_bwd_bf16")
+        return dQ, dE, None
+
+
+def all_pairs_loss(Q, E, target, mm=None):
     """The mean softmax cross-entropy of the scores Q E^T against `target` (float32 [m, H] and [N, H] on the device,
     int64 [m]) as a float32 device scalar carrying autograd to Q and E — `F.cross_entropy(Q @ E.T, target)` without the
     [m, N] matrix (csrc/lp_all.hip); never synchronises.  Shapes the kernels do not take — H % 4 != 0, H > 256, rows
-    not 16-byte aligned — materialise the matrix (`stats()["lp.decoder.all.fallback"]`)."""
+    not 16-byte aligned — materialise the matrix (`stats()["lp.decoder.all.fallback"]`).  `mm`: the score arithmetic,
+    "f32" or "bf16" (None: `score_dtype()`); under "bf16" the fallback materialises the scores of the operands rounded
+    to bf16, the rounding passed straight through."""
     import torch.nn.functional as F
+    mm = _mm(mm, "all_pairs_loss")
     Q, E = _f32_rows(Q, "Q"), _f32_rows(E, "E")
     if Q.shape[1] != E.shape[1] or target.shape[0] != Q.shape[0]:
         raise _lib.MrgcnError("all_pairs_loss: Q [m, H], E [N, H], target [m]")
     target = target.contiguous()
+    if mm == "bf16":
+        if not _bf16_supported(Q, E):
+            bump("lp.decoder.all.fallback")
+            return F.cross_entropy(_bf16_through(Q) @ _bf16_through(E).t(), target)
+        return _AllLossBf16.apply(Q, E, target)
     if not _all_supported(_lib.load(), Q, E):
         bump("lp.decoder.all.fallback")
         return F.cross_entropy(Q @ E.t(), target)
     return _AllLoss.apply(Q, E, target)
 
 
-def all_lse(Q, E, target):
+def all_lse(Q, E, target, mm=None):
     """(lse [m], xt [m]) as the forward kernel writes them — lse[q] = log sum_c exp(Q[q] . E[c]),
     xt[q] = Q[q] . E[target[q]] — without autograd, for tests and tools.  Raises where the kernels do not take the
-    shape."""
+    shape.  `mm`: as `all_pairs_loss`."""
+    mm = _mm(mm, "all_lse")
     Q, E = _f32_rows(Q, "Q"), _f32_rows(E, "E")
     lib = _lib.load()
-    if Q.shape[1] != E.shape[1] or target.shape[0] != Q.shape[0] or not _all_supported(lib, Q, E):
+    if Q.shape[1] != E.shape[1] or target.shape[0] != Q.shape[0] or \
+            not (_bf16_supported(Q, E) if mm == "bf16" else _all_supported(lib, Q, E)):
         raise _lib.MrgcnError("all_lse: the 1-vs-all kernels do not take this shape")
     with torch.no_grad():
-        lse, xt, _ = _all_fwd(lib, Q.detach(), E.detach(), target.contiguous())
+        fwd = _all_fwd_bf16 if mm == "bf16" else _all_fwd
+        lse, xt = fwd(lib, Q.detach(), E.detach(), target.contiguous())[:2]
     return lse[:Q.shape[0]], xt
 
 
-def all_loss(facts, node_embeddings, edge_embeddings, side="both", scorer="distmult"):
+def all_loss(facts, node_embeddings, edge_embeddings, side="both", scorer="distmult", mm=None):
     """The mean 1-vs-all softmax cross-entropy of the facts: every fact scored against ALL rows of `node_embeddings` as
     its missing tail and — `side="both"` — as its missing head (`side`: "both", "tail" or "head"), the fact's own end
     the target.  A float32 device scalar carrying autograd to both embedding tensors; never synchronises, so a hipGraph
@@ -645,9 +746,12 @@ def all_loss(facts, node_embeddings, edge_embeddings, side="both", scorer="distm
     stream captures.  `scorer`: "distmult" or "complex" (`pair_vectors` builds the query vectors; the kernels of
     csrc/lp_all.hip do not know the scorer).  Known answers other than the fact's own stay in the denominator (no
     filtering), there is no label smoothing.  Shapes the kernels do not take go through
-    `F.cross_entropy(Q @ E.T, target)` (`stats()["lp.decoder.all.fallback"]`)."""
+    `F.cross_entropy(Q @ E.T, target)` (`stats()["lp.decoder.all.fallback"]`).  `mm`: the score arithmetic, "f32" or
+    "bf16" (None: `score_dtype()`, which is how the steps and run loops choose it); a bf16 call also counts in
+    `stats()["lp.decoder.all.bf16"]`."""
     _scorer(scorer, "all_loss")
     _all_side(side, "all_loss")
+    mm = _mm(mm, "all_loss")
     E = _f32_rows(node_embeddings, "node_embeddings")
     Rel = _f32_rows(edge_embeddings, "edge_embeddings")
     t = facts if torch.is_tensor(facts) and facts.is_cuda and facts.dtype == torch.int64 and facts.dim() == 2 \
@@ -662,8 +766,10 @@ def all_loss(facts, node_embeddings, edge_embeddings, side="both", scorer="distm
         except AttributeError:
             pass
     bump("lp.decoder.all")
+    if mm == "bf16":
+        bump("lp.decoder.all.bf16")
     Q, target = pair_vectors(t, E, Rel, side, scorer)
-    return all_pairs_loss(Q, E, target)
+    return all_pairs_loss(Q, E, target, mm=mm)
 
 
 def _all_facts(sampler, fallback, who, decoder="all"):
@@ -756,22 +862,60 @@ class _KvsAllLoss(torch.autograd.Function):
         return dQ, dE, None, None
 
 
-def kvsall_pairs_loss(Q, E, queries, label_smoothing=0.0):
+class _KvsAllLossBf16(torch.autograd.Function):
+    """`_KvsAllLoss` on the bf16 kernels: the forward's tables are saved, the backward reads them (no second cast)."""
+    @staticmethod
+    def forward(ctx, Q, E, kq, eps):
+        lib = _lib.load()
+        m, N, H = Q.shape[0], E.shape[0], E.shape[1]
+        Qb, Eb = _bf16_table(Q), _bf16_table(E)
+        if not lib.mrgcn_lp_kvsall_supported_bf16(_ptr(Qb), Qb.stride(0), m, _ptr(Eb), Eb.stride(0), N, H):
+            raise _lib.MrgcnError("the bf16 kvsall kernels do not take this shape")
+        loss = torch.empty((), dtype=torch.float32, device=E.device)
+        ws = _det_scratch(E.device, "lp_kvsall", int(lib.mrgcn_lp_kvsall_workspace(m, N, H)))
+        _lib.check(lib.mrgcn_lp_kvsall_fwd_bf16(_ptr(Qb), Qb.stride(0), m, _ptr(Eb), Eb.stride(0), N, H, _ptr(kq.ptr),
+                                                _ptr(kq.idx), eps, None, _ptr(loss), _ptr(ws), ws.numel(), _stream()),
+                   "lp_kvsall_fwd_bf16")
+        ctx.save_for_backward(Qb, Eb)
+        ctx.kvsall = (kq, eps, int(H))
+        return loss
+
+    @staticmethod
+    def backward(ctx, gl):
+        Qb, Eb = ctx.saved_tensors
+        kq, eps, H = ctx.kvsall
+        m, N = Qb.shape[0], Eb.shape[0]
+        gl = gl.contiguous().float()
+        dQ = torch.empty((m, H), dtype=torch.float32, device=Qb.device) if ctx.needs_input_grad[0] else None
+        dE = torch.empty((N, H), dtype=torch.float32, device=Eb.device) if ctx.needs_input_grad[1] else None
+        _lib.check(_lib.load().mrgcn_lp_kvsall_bwd_bf16(
+            _ptr(Qb), Qb.stride(0), m, _ptr(Eb), Eb.stride(0), N, H, _ptr(kq.ptr), _ptr(kq.idx), _ptr(kq.cptr),
+            _ptr(kq.cqry), eps, _ptr(gl), _ptr(dQ), H, _ptr(dE), H, None, 0, _stream()), "lp_kvsall_bwd_bf16")
+        return dQ, dE, None, None
+
+
+def kvsall_pairs_loss(Q, E, queries, label_smoothing=0.0, mm=None):
     """The mean binary cross-entropy of the scores Q E^T (float32 [m, H] and [N, H] on the device) against the
     label-smoothed multi-hot target of `queries` (a `KvsAllQueries` with m queries over N nodes, on the same device):
     `F.binary_cross_entropy_with_logits(Q @ E.T, (1 - eps) Y + eps / N)` as a float32 device scalar carrying autograd
     to Q and E, without the [m, N] matrices (csrc/lp_kvsall.hip); never synchronises.  Shapes the kernels do not take —
-    H % 4 != 0, H > 256, rows not 16-byte aligned — materialise both (`stats()["lp.decoder.kvsall.fallback"]`)."""
+    H % 4 != 0, H > 256, rows not 16-byte aligned — materialise both (`stats()["lp.decoder.kvsall.fallback"]`).  `mm`:
+    the score arithmetic, as `all_pairs_loss`."""
     import torch.nn.functional as F
     eps = _smoothing(label_smoothing, "kvsall_pairs_loss")
+    mm = _mm(mm, "kvsall_pairs_loss")
     Q, E = _f32_rows(Q, "Q"), _f32_rows(E, "E")
     if not isinstance(queries, KvsAllQueries):
         raise _lib.MrgcnError("kvsall_pairs_loss: queries is a KvsAllQueries")
     if Q.shape[1] != E.shape[1] or Q.shape[0] != queries.m or E.shape[0] != queries.num_nodes \
             or queries.device != E.device:
         raise _lib.MrgcnError("kvsall_pairs_loss: Q [m, H], E [N, H] and the kvsall queries' m, num_nodes and device")
-    if not _kvsall_supported(_lib.load(), Q, E):
+    if mm == "bf16" and _bf16_supported(Q, E):
+        return _KvsAllLossBf16.apply(Q, E, queries, eps)
+    if mm == "bf16" or not _kvsall_supported(_lib.load(), Q, E):
         bump("lp.decoder.kvsall.fallback")
+        if mm == "bf16":
+            Q, E = _bf16_through(Q), _bf16_through(E)
         N = E.shape[0]
         Y = torch.full((queries.m, N), eps / N, dtype=torch.float32, device=E.device)
         Y[queries.rows, queries.idx.long()] = (1.0 - eps) + eps / N
@@ -781,15 +925,18 @@ def kvsall_pairs_loss(Q, E, queries, label_smoothing=0.0):
     return _KvsAllLoss.apply(Q, E, queries, eps)
 
 
-def kvsall_loss(queries, node_embeddings, edge_embeddings, label_smoothing=0.0, scorer="distmult"):
+def kvsall_loss(queries, node_embeddings, edge_embeddings, label_smoothing=0.0, scorer="distmult", mm=None):
     """The KvsAll loss of a fact set's `KvsAllQueries`: every distinct (s, p, ?) query — and (?, p, o) query, by the
     queries' side — scored against ALL rows of `node_embeddings`, all known answers of the query positives, the target
     smoothed to (1 - label_smoothing) Y + label_smoothing / N, the binary cross-entropy averaged over all m N scores
     (`kvsall_pairs_loss`).  A float32 device scalar carrying autograd to both embedding tensors; never synchronises, so
     a hipGraph captures it.  `scorer`: "distmult" or "complex" — the query vectors are `pair_vectors` of the queries'
-    representative facts, the tail queries' then the head queries'; the kernels do not know the scorer."""
+    representative facts, the tail queries' then the head queries'; the kernels do not know the scorer.  `mm`: the score
+    arithmetic, "f32" or "bf16" (None: `score_dtype()`); a bf16 call also counts in
+    `stats()["lp.decoder.kvsall.bf16"]`."""
     _scorer(scorer, "kvsall_loss")
     eps = _smoothing(label_smoothing, "kvsall_loss")
+    mm = _mm(mm, "kvsall_loss")
     if not isinstance(queries, KvsAllQueries):
         raise _lib.MrgcnError("kvsall_loss: queries is a KvsAllQueries (the kvsall decoder scores distinct queries, not "
                               "facts)")
@@ -798,12 +945,14 @@ def kvsall_loss(queries, node_embeddings, edge_embeddings, label_smoothing=0.0, 
     if queries.num_nodes != E.shape[0] or queries.num_relations > Rel.shape[0]:
         raise _lib.MrgcnError("kvsall_loss: the kvsall queries were built for other num_nodes / num_relations")
     bump("lp.decoder.kvsall")
+    if mm == "bf16":
+        bump("lp.decoder.kvsall.bf16")
     mt, q = queries.m_tail, []
     if mt:
         q.append(pair_vectors(queries.reps[:mt], E, Rel, "tail", scorer)[0])
     if mt < queries.m:
         q.append(pair_vectors(queries.reps[mt:], E, Rel, "head", scorer)[0])
-    return kvsall_pairs_loss(q[0] if len(q) == 1 else torch.cat(q, 0), E, queries, eps)
+    return kvsall_pairs_loss(q[0] if len(q) == 1 else torch.cat(q, 0), E, queries, eps, mm=mm)
 
 
 def _kvsall_queries_of(holder, facts, num_nodes, num_relations, device):

@@ -128,6 +128,15 @@ python3 tools/lp_all_probe.py --out $o/lp_all_probe.json > $o/lp_all_probe.txt 2
 # tools/lp_kvsall_probe.py into it and run `python3 tools/lp_kvsall_probe.py --legs epoch_untouched
 # batch_step_untouched --out <this tree>/profiles/lp_kvsall_probe_parent.json` there.
 python3 tools/lp_kvsall_probe.py --out $o/lp_kvsall_probe.json > $o/lp_kvsall_probe.txt 2> $o/lp_kvsall_probe.err
+# (10n'') the bf16 score arithmetic of both all-candidates decoders beside the f32 arithmetic in the same run: the C
+# entries alone (forward, dQ, dE, forward + backward, TFLOP/s) at all 272 115, 32 768 and 4 096 facts and at the median
+# mini-batch's shape, the bf16 tables' bytes and casts, torch's materialised route in fp32 and under bf16 autocast, the
+# replayed fit epoch of both decoders under both settings.  The f32 rows' band is the PARENT commit's on the same box:
+# check the parent out beside this tree, build it, copy tools/lp_bf16_probe.py into it and run `python3
+# tools/lp_bf16_probe.py --f32-only --out <this tree>/profiles/lp_bf16_probe_parent.json` there.  The resource table:
+# `python3 tools/kernel_resources.py mrgcn_amd/csrc/lp_all.hip bf16` and the same for lp_kvsall.hip ->
+# profiles/lp_bf16_kernels.md
+python3 tools/lp_bf16_probe.py --out $o/lp_bf16_probe.json > $o/lp_bf16_probe.txt 2> $o/lp_bf16_probe.err
 # (10o) a block-diagonal hidden layer (200 -> 200, 40 blocks) at the FB15k-237 shape: its five passes alone, the layer on
 # the fused engine against the literal engine on the dense expansion (with peak memory), the replayed two-layer fit epoch
 python3 tools/block_layer_probe.py --out $o/block_layer_probe.json > $o/block_layer_probe.txt 2> $o/block_layer_probe.err
